@@ -4,14 +4,17 @@ BASELINE.json configs[1]: EchoNet-Dynamic 112x112x32 clips, bf16 inference, batc
 
     python bench.py --gpus N --steps K --warmup W        (N>1: one rank per GPU under torch.distributed.run -- either
                                                           the caller's, or bench.py starts it itself as a child process)
+    python bench.py ... --dump-outputs DIR               also write the last timed step's masks to DIR/masks.npy
+    python bench.py ... --full                           also run every leg below after the headline
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+headline: `value` (frames/s), `ms_per_step` and `config`.  With --full the line carries the extra objects as well:
   roofline      the hot path's dominant kernels (gdr_prepm_kernel + gdr_affine_scan_kernel = one gdkvm_scan_fwd), timed
                 live with HIP events on the launch stream; achieved = SURVEY.md §8(d) algorithmic bytes / time
   cpu_baseline  the CPU oracle module (oracle/model_ref.py: PyTorch CPU convs + scalar C memory path) on a
                 bounded sample of the same workload, rank 0, N=1 only
-and a third, `train_step`: BASELINE.json configs[3]'s per-GPU training step (16 clips x 32 frames, bf16 autocast, AdamW; DDP
-over RCCL when N > 1), a few steps measured AFTER the headline's timed region -- it never enters `value`.
+and `train_step`: BASELINE.json configs[3]'s per-GPU training step (16 clips x 32 frames, bf16 autocast, AdamW; DDP
+over RCCL when N > 1), a few steps measured AFTER the headline's timed region -- none of them enters `value`.
 Clips shard over GPUs with no data-path collective (inference): scaling is weak, per-GPU batch fixed.
 """
 from __future__ import annotations
@@ -248,6 +251,23 @@ def time_events(fn, iters, warmup=3, rotate=0):
     return sum(ms) / len(ms), ms[len(ms) // 2]
 
 
+DUMP_BYTES_MAX = 60 * 10 ** 6     # below the 64 MB that a dump may take, .npy header included
+
+
+def dump_outputs(dirname, mask):
+    """--dump-outputs: what a caller of the timed step receives -- segment()'s masks, uint8 class indices [B, T, H, W] (its Dice counts are
+    None without a target) -- as DIR/masks.npy in float32 (exact for class indices).  Inputs and weights are seeded, so two builds given the
+    same arguments can be compared mask for mask.  Above DUMP_BYTES_MAX (non-default shapes) a fixed strided sample of the flattened masks is
+    written instead, as a 1-D array."""
+    import numpy as np
+    m = mask.cpu().numpy().astype(np.float32)
+    stride = -(-m.nbytes // DUMP_BYTES_MAX)
+    if stride > 1:
+        m = np.ascontiguousarray(m.reshape(-1)[::stride])
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "masks.npy"), m)
+
+
 def run_train(args, world, rank, dev, steps, warmup):
     """BASELINE configs[3]: EchoNet-Dynamic training, DDP over the GPUs of one node, 16 clips x 32 frames per GPU,
     bf16 autocast with fp32 master weights, AdamW lr 1e-4 (the reference guide's learning rate).  A step = forward,
@@ -439,6 +459,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the roofline kernel timings, the host-fed, step-mode and latency legs, the other "
+                         "BASELINE shapes, the CPU baseline and Dice checks, and the training leg (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the masks of the last timed step (rank 0) to DIR/masks.npy as float32 (inference mode)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the scan timings at the other BASELINE shapes")
     ap.add_argument("--batch", type=int, default=16, help="clips per GPU")
     ap.add_argument("--frames", type=int, default=32)
@@ -449,12 +474,14 @@ def main():
                     help="infer = BASELINE configs[1] (the headline metric); train = configs[3]: DDP training step")
     ap.add_argument("--kernel-iters", type=int, default=50)
     ap.add_argument("--train-steps", type=int, default=5,
-                    help="infer mode: timed steps of the configs[3] training leg reported as `train_step` (0 = skip the leg)")
+                    help="infer mode with --full: timed steps of the configs[3] training leg reported as `train_step` (0 = skip the leg)")
     ap.add_argument("--train-warmup", type=int, default=2)
     ap.add_argument("--train-leg-timeout", type=float, default=240.0, help="seconds before the training leg is given up (N > 1)")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU/gloo ranks, no kernels: exercises the --gpus N launch path only (tests)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "infer":
+        ap.error("--dump-outputs writes the inference step's masks: use it with --mode infer")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                                   # never returns
@@ -500,8 +527,8 @@ def main():
         model.decoder.head.bias.copy_(model.decoder.head.bias.bfloat16().float())   # exactly representable in the bf16 build
         model.invalidate_packed_weights()
         model = model.cpu()
-    if rank == 0 and world == 1:
-        ref_state = {k_: v_.clone() for k_, v_ in model.state_dict().items()}     # fp32, BatchNorm unfolded
+    if rank == 0 and world == 1 and args.full:
+        ref_state = {k_: v_.clone() for k_, v_ in model.state_dict().items()}     # fp32, BatchNorm unfolded (the CPU baseline's weights)
     # inference build: BatchNorm folded into the convs, conv weights held in bf16 (no per-step autocast casts);
     # the KPFF weights and the recurrent state stay fp32
     model = model.fuse_for_inference().to(dev).to(torch.bfloat16).to(memory_format=torch.channels_last)
@@ -572,21 +599,25 @@ def main():
     prewarm = int(os.environ.get("GDKVM_BENCH_PREWARM", "40"))
 
     def timed_region():
+        """(seconds of the K timed steps, the last step's masks: complete after the closing barrier)"""
         for i in range(args.warmup):
             step(i)
         barrier()
         t_ = time.perf_counter()
+        last = None
         for i in range(args.steps):
-            step(args.warmup + i)
+            last = step(args.warmup + i)
         barrier()
-        return time.perf_counter() - t_
+        return time.perf_counter() - t_, last
 
-    # the pre-warm's effect, stated once (round 6): the contract's region -- W warm-up steps, K timed steps -- is run FIRST straight after the
-    # set-up (what the line would read without the pre-warm), then again after the untimed forwards; `value` is the second
-    dt_cold = timed_region() if prewarm > 0 else None
+    # the pre-warm's effect, stated once (round 6; --full): the contract's region -- W warm-up steps, K timed steps -- is run FIRST straight after
+    # the set-up (what the line would read without the pre-warm), then again after the untimed forwards; `value` is the second
+    dt_cold = timed_region()[0] if prewarm > 0 and args.full else None
     for i in range(prewarm):
         step(i)
-    dt = timed_region()
+    dt, last_mask = timed_region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_mask)
     ranks_seen = 1
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -607,14 +638,15 @@ def main():
                       "input": "frames resident in HBM as bf16 before the timed region (host-to-device copy and cast untimed)",
                       "launch": launch,
                       "prewarm": f"{prewarm} untimed forwards before the {args.warmup} warm-up steps (clock ramp after the set-up's idle gaps)",
-                      "ms_per_step_without_prewarm": None if dt_cold is None else round(1e3 * dt_cold / args.steps, 3),
                       "input_rotation": f"{n_rot} distinct resident batches ({n_rot * frames.numel() * 2 / 1e6:.0f} MB of frames), one per step in turn: "
                                         "the inputs are not re-read from the 256 MB Infinity Cache",
                       "sharding": f"clips over {world} GPU(s), no data-path collective",
                       "world_size": (dist.get_world_size() if world > 1 else 1), "ranks_seen": ranks_seen,
                       "collective_backend": ("nccl (RCCL)" if world > 1 else None)}}
+    if args.full:
+        out["config"]["ms_per_step_without_prewarm"] = None if dt_cold is None else round(1e3 * dt_cold / args.steps, 3)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the hot path's dominant kernels, live HIP-event timing on the launch stream -------
         N, Hh, Dk, Dv = (S // 16) ** 2, cfg.heads, cfg.key_dim, cfg.value_dim
         gq = torch.Generator(device=dev).manual_seed(1)
@@ -976,14 +1008,14 @@ def main():
             except Exception as e:                              # noqa: BLE001 -- informational leg
                 out["dice_fitted_model"] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    # ---- BASELINE configs[3] beside the headline: a few training steps at the per-GPU shape, AFTER the timed region and the
+    # ---- (--full) BASELINE configs[3] beside the headline: a few training steps at the per-GPU shape, AFTER the timed region and the
     # kernel timings above (every rank; DDP + RCCL all-reduce when N > 1).  It can only add a `train_step` object: a failure is
     # reported inside it, and a hung collective is cut off by the watchdog with the line printed as it stands.
     def emit():
         if rank == 0:
             print(json.dumps(out), flush=True)
 
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         del model, frames
         torch.cuda.empty_cache()
 

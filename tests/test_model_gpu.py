@@ -360,6 +360,35 @@ def test_train_and_eval_entry_points(hip, tmp_path):
     assert os.listdir(os.path.join(tmp_path, "vis"))
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_masks(hip, tmp_path):
+    """bench.py without --full: ONE JSON line carrying the headline alone, --steps timed steps, `ms_per_step` consistent with `value`;
+    --dump-outputs writes the last timed step's masks (float32 class indices of a balanced head: both classes present), and a second run
+    with the same arguments writes the same masks (seeded inputs and weights)."""
+    import json
+    import subprocess
+    import sys
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    masks = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "frames/s" and out["dtype"] == "bf16"
+        assert out["ms_per_step"] > 0 and abs(16 * 32 / (out["ms_per_step"] * 1e-3) / out["value"] - 1) < 0.01, out
+        assert not {"roofline", "cpu_baseline", "train_step", "pipeline", "step_mode"} & set(out), sorted(out)
+        assert sorted(os.listdir(d)) == ["masks.npy"]
+        masks.append(np.load(d / "masks.npy"))
+    m = masks[0]
+    assert m.dtype == np.float32 and m.shape == (16, 32, 112, 112) and m.nbytes <= 64e6
+    assert set(np.unique(m).tolist()) == {0.0, 1.0} and 0.05 < m.mean() < 0.95, m.mean()
+    assert np.array_equal(masks[0], masks[1])
+
+
 def test_dice_parity_on_a_fitted_model(hip):
     """BASELINE.json's second figure of merit, "Dice vs reference", on a model whose head separates the classes by real margins: a short fit
     on the synthetic echo clips (the training step itself: HIP forward / backward kernels, fused loss, AdamW), then on held-out clips
