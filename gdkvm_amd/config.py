@@ -28,6 +28,7 @@ class DataCfg:
 @dataclass
 class ModelCfg:
     heads: int = 1
+    key_dim: int = 64                # Dk per head: 64 runs the measured kernels; 72 .. 256 (multiples of 8) the wide-key coverage path
     value_dim: int = 256
     rule: str = "delta_sequential"
     scan_segments: int = 1           # evaluation of long clips: GDKVMConfig.scan_segments (1 = serial scan, bit-identical under chunking)

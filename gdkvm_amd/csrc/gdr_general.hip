@@ -7,11 +7,13 @@
 // frame's tokens in raster order -- rule 0: S += b k v^T; rule 2: e = v - S^T k against the state as updated so far, S += b k e^T; rule 1:
 // the same with e taken against the decayed state of the frame's start (kept in a second LDS slice).  Everything is fp32 FMAs in a fixed
 // order (deterministic; bit-identical when a clip is cut into calls with the state carried); q / k normalisation and the gate sigmoids as
-// in the fast path's prologue (flags).  Inference only (no s_hist).  It is serial over tokens by construction -- two workgroup barriers per
-// token -- and is NOT the measured path: cfg2-sized problems run ~40x slower than the Dk = 64 kernels; it exists so that a model with wider
+// in the fast path's prologue (flags).  With HIST (training: gdkvm_scan_train_fwd) the kernel also writes the state before every frame
+// into s_hist -- its backward is gdr_general_bwd.hip; without it the code is that of the inference kernel.  It is serial over tokens by
+// construction -- two workgroup barriers per token -- and is NOT the measured path: cfg2-sized problems run ~40x slower than the Dk = 64 kernels; it exists so that a model with wider
 // keys gets the same results from the same entry point instead of an error.
 #include "gdkvm_common.hpp"
 #include "gdr_ws.hpp"
+#include "gdr_general.hpp"
 
 namespace {
 
@@ -20,10 +22,11 @@ constexpr int GG_CHUNK = 64;             // tokens whose inverse key norms are s
 
 struct GeneralArgs {
     const void* q; const void* k; const void* v; const float* alpha; const float* beta; const float* s_in; void* r; float* s_out;
+    float* s_hist;                                        // HIST: [B,T,Hh,Dk,Dv] fp32, the state before every frame
     int B, T, Hh, N, Dk, Dv, rule, flags;
 };
 
-template <int IO>
+template <int IO, bool HIST>
 __global__ __launch_bounds__(256) void gdr_general_scan_kernel(GeneralArgs a)
 {
     __shared__ float s_S[GG_MAXDK][16];                   // this slice of the state
@@ -45,6 +48,12 @@ __global__ __launch_bounds__(256) void gdr_general_scan_kernel(GeneralArgs a)
 
     for (int t = 0; t < a.T; ++t) {
         const size_t bt = (size_t)b * a.T + t;
+        if constexpr (HIST) {                              // (s_S is stable here: behind the previous frame's last barrier)
+            for (int j = 0; j < nj; ++j) {
+                const int d = dg + 16 * j;
+                if (d < Dk) a.s_hist[((bt * Hh + h) * Dk + d) * Dv + c0 + c] = s_S[d][c];
+            }
+        }
         // ---- read: token n = 16 pass + dg, column c; a thread walks the whole key axis of its token (q rows are L1 hits across the 16 columns)
         for (int n0 = 0; a.r && n0 < N; n0 += 16) {
             const int n = n0 + dg;
@@ -126,6 +135,20 @@ __global__ __launch_bounds__(256) void gdr_general_scan_kernel(GeneralArgs a)
     }
 }
 
+static int general_launch(const GeneralArgs& a, int io_dtype, hipStream_t st)
+{
+    const dim3 grid((unsigned)(a.Dv / 16), (unsigned)(a.B * a.Hh));
+    if (a.s_hist) {
+        if (io_dtype == GDKVM_F32) hipLaunchKernelGGL((gdr_general_scan_kernel<GDKVM_F32, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((gdr_general_scan_kernel<GDKVM_BF16, true>), grid, dim3(256), 0, st, a);
+    } else {
+        if (io_dtype == GDKVM_F32) hipLaunchKernelGGL((gdr_general_scan_kernel<GDKVM_F32, false>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((gdr_general_scan_kernel<GDKVM_BF16, false>), grid, dim3(256), 0, st, a);
+    }
+    GDKVM_LAUNCH_CHECK("gdr_general_scan_kernel");
+    return GDKVM_OK;
+}
+
 }  // namespace
 
 bool gdr_wide_keys(int Dk) { return Dk > GDKVM_DK && Dk <= GG_MAXDK && Dk % 8 == 0; }
@@ -143,10 +166,14 @@ int gdr_general_scan_fwd(const void* q, const void* k, const void* v, const floa
     if (!r_out && !s_out) return GDKVM_OK;
     if (T > 0 && N > 0 && (!q || !k || !v || !alpha || !beta)) return gdkvm_fail(GDKVM_ERR_ARG, "scan_fwd: null pointer");
     if (int rc = gdkvm_check_device()) return rc;
-    GeneralArgs a{q, k, v, alpha, beta, s_in, r_out, s_out, B, T, Hh, N, Dk, Dv, rule, flags};
-    const dim3 grid((unsigned)(Dv / 16), (unsigned)(B * Hh));
-    if (io_dtype == GDKVM_F32) hipLaunchKernelGGL((gdr_general_scan_kernel<GDKVM_F32>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gdr_general_scan_kernel<GDKVM_BF16>), grid, dim3(256), 0, st, a);
-    GDKVM_LAUNCH_CHECK("gdr_general_scan_kernel");
-    return GDKVM_OK;
+    return general_launch(GeneralArgs{q, k, v, alpha, beta, s_in, r_out, s_out, nullptr, B, T, Hh, N, Dk, Dv, rule, flags}, io_dtype, st);
+}
+
+// the training forward (gdkvm_scan_train_fwd at wide keys; shapes checked by the caller): the same kernel, plus the history
+int gdr_general_scan_fwd_hist(const void* q, const void* k, const void* v, const float* alpha, const float* beta, const float* s_in,
+                              void* r_out, float* s_out, float* s_hist, int B, int T, int Hh, int N, int Dk, int Dv, int io_dtype, int rule,
+                              int flags, hipStream_t st)
+{
+    if (int rc = gdkvm_check_device()) return rc;
+    return general_launch(GeneralArgs{q, k, v, alpha, beta, s_in, r_out, s_out, s_hist, B, T, Hh, N, Dk, Dv, rule, flags}, io_dtype, st);
 }

@@ -7,8 +7,12 @@
 // saved history, whose state gradients enter the reverse recurrence as its additive term).  Until round 2 only gdkvm_amd/ops.py
 // composed these calls, with framework padding ops in between; here the padded operands are built by two copy kernels into ONE
 // workspace that carries everything from the forward to the backward call.
+//
+// Key widths 72 .. 256 (gdr_wide_keys) train on their own pair instead, for every N: gdr_general.hip's recurrence with the state history
+// written beside it, and its backward in gdr_general_bwd.hip (one workspace as well: gdr_general.hpp).
 #include "gdkvm_common.hpp"
 #include "gdr_ws.hpp"
+#include "gdr_general.hpp"
 
 namespace {
 
@@ -100,13 +104,21 @@ TrainView train_carve(void* base, int B, int T, int Hh, int N, int Dk, int Dv, i
 int train_check(const char* fn, void* ws, size_t ws_bytes, int B, int T, int Hh, int N, int Dk, int Dv, int io_dtype, int rule, int flags,
                 TrainView* out)
 {
-    if (int rc = check_common(fn, B, T, Hh, N, Dk, Dv, io_dtype, flags)) return rc;
+    const bool wide = gdr_wide_keys(Dk);
+    if (int rc = check_common(fn, B, T, Hh, N, wide ? GDKVM_DK : Dk, Dv, io_dtype, flags)) return rc;
     if (rule < 0 || rule > 2) return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: rule=%d", fn, rule);
     if (T <= 0 || N <= 0) return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: T and N must be positive", fn);
     if (N > 64 && rule == GDKVM_RULE_DELTA_PARALLEL)
         return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: training with rule delta_parallel is limited to 64 tokens per frame (its chunks combine additively)", fn);
+    if (wide && (long long)B * Hh > 65535)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: B*Hh=%lld clip-heads (at most 65535 per call with Dk > %d)", fn, (long long)B * Hh, GDKVM_DK);
     if (B == 0) return GDKVM_OK;
     if (!ws || !gdkvm_aligned16(ws)) return gdkvm_fail(GDKVM_ERR_ARG, "%s: workspace null or misaligned", fn);
+    if (wide) {                                       // (the wide-key workspace has a layout of its own: gdr_general.hpp)
+        const size_t need = gdr_general_train_workspace_bytes(B, T, Hh, N, Dk, Dv);
+        if (ws_bytes < need) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+        return GDKVM_OK;
+    }
     *out = train_carve(ws, B, T, Hh, N, Dk, Dv, io_dtype);
     if (ws_bytes < out->total) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, out->total);
     return GDKVM_OK;
@@ -128,6 +140,7 @@ int gdr_block_copy(const void* src, void* dst, size_t nblk, size_t src_q, size_t
 extern "C" size_t gdkvm_scan_train_workspace_bytes(int B, int T, int Hh, int N, int Dk, int Dv, int io_dtype)
 {
     if (B <= 0 || T <= 0 || Hh <= 0 || N <= 0 || Dk <= 0 || Dv <= 0) return 256;
+    if (gdr_wide_keys(Dk)) return gdr_general_train_workspace_bytes(B, T, Hh, N, Dk, Dv) + 256;
     return train_carve(nullptr, B, T, Hh, N, Dk, Dv, io_dtype).total + 256;
 }
 
@@ -139,6 +152,9 @@ extern "C" int gdkvm_scan_train_fwd(const void* q, const void* k, const void* v,
     if (int rc = train_check("scan_train_fwd", train_workspace, train_workspace_bytes, B, T, Hh, N, Dk, Dv, io_dtype, rule, flags, &tv)) return rc;
     if (B == 0) return GDKVM_OK;
     if (int rc = check_ptrs("scan_train_fwd", {q, k, v, alpha, beta, r_out}, {s_in, s_out})) return rc;
+    if (gdr_wide_keys(Dk))
+        return gdr_general_scan_fwd_hist(q, k, v, alpha, beta, s_in, r_out, s_out, gdr_general_train_hist(train_workspace), B, T, Hh, N, Dk, Dv,
+                                         io_dtype, rule, flags, static_cast<hipStream_t>(stream));
     if (tv.C == 1)
         return gdkvm_scan_fwd(q, k, v, alpha, beta, s_in, r_out, s_out, tv.hist, tv.fws, tv.fws_bytes, B, T, Hh, N, Dk, Dv, io_dtype, rule, flags, stream);
     if (int rc = gdkvm_check_device()) return rc;
@@ -172,6 +188,9 @@ extern "C" int gdkvm_scan_train_bwd(const void* q, const void* k, const void* v,
     if (int rc = train_check("scan_train_bwd", train_workspace, train_workspace_bytes, B, T, Hh, N, Dk, Dv, io_dtype, rule, flags, &tv)) return rc;
     if (B == 0) return GDKVM_OK;
     if (int rc = check_ptrs("scan_train_bwd", {q, k, v, alpha, beta, d_r, d_q, d_k, d_v, d_alpha, d_beta}, {d_s_out, d_s_in})) return rc;
+    if (gdr_wide_keys(Dk))
+        return gdr_general_train_bwd(q, k, v, alpha, beta, d_r, d_s_out, d_q, d_k, d_v, d_alpha, d_beta, d_s_in, train_workspace, B, T, Hh, N,
+                                     Dk, Dv, io_dtype, rule, flags, static_cast<hipStream_t>(stream));
     if (tv.C == 1)
         return gdkvm_scan_bwd(q, k, v, alpha, beta, tv.hist, tv.fws, tv.fws_bytes, d_r, d_s_out, d_q, d_k, d_v, d_alpha, d_beta, d_s_in,
                               tv.bws, tv.bws_bytes, B, T, Hh, N, Dk, Dv, io_dtype, rule, flags, stream);

@@ -37,7 +37,7 @@ class GDKVMConfig:
     in_channels: int = 3
     num_classes: int = 2            # EchoNet-Dynamic: background / LV.  CAMUS: 4.
     heads: int = 1                  # Hh
-    key_dim: int = 64               # Dk per head (the HIP kernels are specialised for 64)
+    key_dim: int = 64               # Dk per head (the fast HIP kernels are specialised for 64; 72 .. 256 infer and train on a coverage path)
     value_dim: int = 256            # Dv per head
     pixel_dim: int = 256            # Cp, stride-16 encoder feature
     widths: Tuple[int, int, int] = (64, 128, 256)

@@ -184,7 +184,7 @@ def _stream(dev) -> int:
 
 
 KERNEL_DK = 64                # per-head key dim the fast kernels are built for (include/gdkvm.h; narrower keys run on them through zero
-                              # channels, wider ones -- up to 256 -- on the general kernel of csrc/gdr_general.hip, inference only)
+                              # channels, wider ones -- up to 256 -- on the general kernel of csrc/gdr_general.hip, trained through gdr_general_bwd.hip)
 
 
 def _pad_keys(q, k, state):
@@ -502,7 +502,7 @@ def scan(q, k, v, alpha, beta, state=None, rule: int = RULE_DELTA_SEQUENTIAL, fl
         qp, kp, sp = _pad_keys(q, k, state)
         r, s = scan(qp, kp, v, alpha, beta, sp, rule, flags)
         return r, s[:, :, :q.shape[-1]]
-    if q.shape[2] > 64:
+    if q.shape[2] > 64 or q.shape[-1] > KERNEL_DK:        # (wider keys train on gdkvm_scan_train_fwd / _bwd at every N)
         return _ScanTrainFunction.apply(q, k, v, alpha, beta, state, rule, flags)
     return _ScanFunction.apply(q, k, v, alpha, beta, state, rule, flags)
 

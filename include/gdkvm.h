@@ -87,7 +87,8 @@ size_t gdkvm_scan_workspace_bytes(int B, int T, int Hh, int N, int Dk, int Dv);
  * Supported: Dk == 64 (the measured kernels); 8 <= Dk < 64 in multiples of 8 (gdkvm_scan_fwd only, not with s_hist: the call zero-extends
  * q, k and the state to 64 channels inside the workspace, which is exact); 64 < Dk <= 256 in multiples of 8 (gdkvm_scan_fwd only,
  * inference: the definitional recurrence in fp32 on one workgroup per 16-column slice of the state, csrc/gdr_general.hip -- same
- * results, same chunk bit-identity, no workspace, far slower than the Dk = 64 path; gdkvm_scan_status has nothing to report for it);
+ * results, same chunk bit-identity, no workspace, far slower than the Dk = 64 path; gdkvm_scan_status has nothing to report for it;
+ * training at these widths: gdkvm_scan_train_fwd / gdkvm_scan_train_bwd, not s_hist);
  * Dv % 16 == 0; 0 <= N <= 4096 (a 1024x1024 frame at stride 16).
  * s_hist (training): if non-NULL, [B,T,Hh,Dk,Dv] fp32 receives the state BEFORE every frame; gdkvm_scan_bwd needs
  * it together with the untouched workspace of this call. */
@@ -209,7 +210,12 @@ int gdkvm_scan_bwd(const void* q, const void* k, const void* v, const float* alp
  * the same inputs, that workspace untouched, d_r and d_s_out (may be NULL = 0), and returns the gradients of gdkvm_scan_bwd.
  * N <= 64 is exactly gdkvm_scan_fwd (s_hist inside the workspace) + gdkvm_scan_bwd; N > 64 composes gdkvm_scan_fwd without a
  * read-out, gdkvm_readout_fwd / _bwd and gdkvm_scan_state_bwd below.  GDKVM_RULE_DELTA_PARALLEL: N <= 64 only (its chunks
- * combine additively, not in sequence).  Supported: Dk == 64, Dv % 16 == 0, 1 <= N <= 4096. */
+ * combine additively, not in sequence).  Supported: Dk == 64, or 72 <= Dk <= 256 in multiples of 8; Dv % 16 == 0, 1 <= N <= 4096.
+ * Wide keys (Dk > 64; B * Hh <= 65535) train on their own pair at every N: the forward is gdkvm_scan_fwd's wide-key kernel (its R and
+ * S_T bit for bit) writing the state before every frame beside, the backward the exact gradient of that fp32 recurrence
+ * (csrc/gdr_general_bwd.hip: a reverse walk per 16-column state slice, per-slice partials summed in a fixed order -- deterministic).
+ * Its workspace, every term rounded up to 256 bytes, with FH = B*T*Hh frame-heads and NS = Dv/16 slices:
+ *     4 * (FH*Dk*Dv  +  B*Hh*Dv*N  +  2*NS*FH*N*Dk  +  NS*FH*N  +  NS*FH)  +  256 bytes. */
 size_t gdkvm_scan_train_workspace_bytes(int B, int T, int Hh, int N, int Dk, int Dv, int io_dtype);
 int gdkvm_scan_train_fwd(const void* q, const void* k, const void* v, const float* alpha, const float* beta, const float* s_in,
                          void* r_out, float* s_out, void* train_workspace, size_t train_workspace_bytes,

@@ -44,7 +44,8 @@ def main(argv=None):
     torch.cuda.set_device(dev)
     torch.manual_seed(cfg.seed)                                   # identical initial weights on every rank
 
-    mcfg = GDKVMConfig(num_classes=cfg.data.num_classes, heads=cfg.model.heads, value_dim=cfg.model.value_dim, rule=cfg.model.rule)
+    mcfg = GDKVMConfig(num_classes=cfg.data.num_classes, heads=cfg.model.heads, key_dim=cfg.model.key_dim,
+                       value_dim=cfg.model.value_dim, rule=cfg.model.rule)
     model = GDKVM(mcfg).train().to(dev).to(memory_format=torch.channels_last)
     step0, epoch0, opt_state = 0, None, None
     if args.resume:
