@@ -2,7 +2,6 @@
 // integer Dice counts.  HBM-bound: every logit is read once with 8/16-byte loads, the mask is written
 // once; counts are reduced wave-wide with ballots, per block in LDS, then one integer atomic per
 // (block, class, kind) -- integer adds commute, so the result is bit-reproducible.
-#include <stdlib.h>
 
 #include "gdkvm_common.hpp"
 
@@ -150,11 +149,8 @@ __global__ __launch_bounds__(256) void upsample_argmax_dice_kernel(UpArgs a)
     // wrong values).  The host computes lr_cap with THIS arithmetic for every block of the launch (up_src_host: the same fp32
     // operations) and refuses the call with GDKVM_ERR_SHAPE when a band does not fit the LDS tile, so the condition cannot hold here;
     // a block that met it anyway fails LOUDLY in its output: every mask byte of its range becomes 255 (no class has that index, so the
-    // mask is visibly wrong and its Dice counts stay zero) instead of whatever torch.empty held (GDKVM_DEBUG_TRAPS builds: it faults).
+    // mask is visibly wrong and its Dice counts stay zero) instead of whatever torch.empty held.
     if (a.hw_ && !staged) {
-#ifdef GDKVM_DEBUG_TRAPS
-        __builtin_trap();
-#endif
         for (int p = q_lo * PX + (int)threadIdx.x; p < q_hi * PX; p += 256) a.mask[(size_t)f * HW + p] = 255;
         return;
     }
@@ -374,13 +370,12 @@ static int upsample_launch(const char* who, const void* src, const float* head_w
     if (target) if (int rc = zero_counts(counts, (size_t)BT * ncls * 3, st)) return rc;
     const int nq = (W % 4 == 0) ? H * W / 4 : H * W;       // work items per frame (pixel quads when rows allow)
     int gx = (nq + 255) / 256;
-    static const int cap_env = [] { const char* e = getenv("GDKVM_ARGMAX_BLOCKS"); return e ? atoi(e) : 0; }();   // (A/B runs)
     // enough blocks to fill the chip, few enough that launch and the per-block count reduction do not dominate.  256 .. 1023 frames: THREE
     // (round 5, 512 frames of 112 x 112: 20.7 us against 23.8 with four, 22.0 with two; the ranges are multiples of 256 quads, so three
     // blocks own 1280 / 1280 / 576 of a frame's 3136 -- four owned 1024 / 1024 / 1024 / 64, the last staging a band for 64 quads -- and
     // blocks of unequal length fall out of step: one's memory-bound band phase overlaps another's arithmetic; evenly split ranges
     // measured 21.3 - 22.3)
-    const int cap = cap_env > 0 ? cap_env : BT >= 1024 ? 2 : (BT >= 256 ? 3 : 16);
+    const int cap = BT >= 1024 ? 2 : (BT >= 256 ? 3 : 16);
     if (gx > cap) gx = cap;
     // low-resolution rows a block's contiguous output range touches: the kernel's own arithmetic (band of block bx = rows
     // up_src(q_lo) .. up_src(q_hi - 1) + 1), evaluated here for every block of the launch -- lr_cap is the largest band, exactly

@@ -29,15 +29,6 @@ constexpr int CV_PIX = 160;              // bytes between LDS pixels: 8 data chu
 
 __device__ const uint4 g_conv_zero16 = {0, 0, 0, 0};          // source of the zero padding
 
-#ifdef CV_DIAG
-// diagnostic builds (tools/abl_conv_tile.py c64stamps): s_memtime per wave of workgroup 0 at the phase boundaries of its first tiles
-__device__ unsigned long long* g_cv_diag = nullptr;
-#define CV_STAMP(slot) do { if (blockIdx.x == 0 && lane == 0 && nt_done < 8) { unsigned long long t__; \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory"); g_cv_diag[(nt_done * 4 + w) * 8 + (slot)] = t__; } } while (0)
-#else
-#define CV_STAMP(slot) do {} while (0)
-#endif
-
 struct Conv64Args {
     const bf16_t* x; const bf16_t* w; const float* bias; const bf16_t* res; bf16_t* y;
     int N, H, W, tiles_x, tiles_y, relu;
@@ -53,9 +44,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), wm = w >> 1, wn = w & 1;
     const int ntiles = a.N * a.tiles_y * a.tiles_x;
-    int nt_done = 0;
-    (void)nt_done;
-    CV_STAMP(6);
 
     // band fetch by LDS-DMA: piece j = w + 4u (64 consecutive 16-byte LDS slots) is issued by wave w; slot d = 10 pix + c holds
     // channel chunk c of band pixel pix (c = 8, 9: padding).  The slot geometry does not depend on the tile: kept in registers.
@@ -134,7 +122,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
     if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x, 1);
     for (; tile < ntiles; tile += gridDim.x, cur ^= 1) {
         const unsigned char* band = band2 + cur * BAND_BYTES;
-        CV_STAMP(0);
 
         f32x4 acc[4][2];
 #pragma unroll
@@ -171,11 +158,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         if (wm == 0 || NM1 == 4) compute(std::integral_constant<int, (NMT < 4 ? NMT : 4)>{});
         else if constexpr (NM1 > 0 && NM1 < 4) compute(std::integral_constant<int, (NM1 > 0 ? NM1 : 1)>{});
 
-        CV_STAMP(1);
         __syncthreads();                                   // everyone is done with this band; the next one has landed
-        CV_STAMP(2);
-
-        CV_STAMP(3);
 
         // epilogue: lane (li, g) holds channels 32wn + 8g .. +7 of pixel 16(4wm+m) + li (tile nt: the four channels 4nt ..)
         const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
@@ -209,18 +192,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         // LDS-DMA against register loads and waits with vmcnt(0) for the residual -- ahead of the epilogue that wait also covered
         // the band just requested from HBM (+9 us per residual layer); the band still has a whole tile of MFMAs to land.
         if (tile + 2 * (int)gridDim.x < ntiles) fetch(tile + 2 * gridDim.x, cur);
-        CV_STAMP(4);
-#ifdef CV_DIAG
-        ++nt_done;
-#endif
     }
 }
 
 }  // namespace
-
-#ifdef CV_DIAG
-extern "C" void gdkvm_cv_diag_buffer(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_cv_diag), &p, sizeof(p)); }
-#endif
 
 // internal entry used by gdkvm_conv_bias_act (conv_dispatch.hip): returns 0 on launch
 int gdkvm_conv3x3_c64_launch(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H, int W,

@@ -18,7 +18,6 @@
 //     ct_channel (16-byte stores / residual loads);
 //   * the same kernel computes the training-mode data gradient (weights packed flipped and transposed).
 // Arithmetic: fp32 accumulation over the same 9 C products as a library convolution, one rounding after the epilogue.
-#include <stdlib.h>
 #include <atomic>
 #include <type_traits>
 
@@ -27,10 +26,7 @@
 namespace {
 
 constexpr int CT_CK = 64;                // input channels per LDS chunk
-#ifndef CT_PIX_BYTES
-#define CT_PIX_BYTES 160
-#endif
-constexpr int CT_PIX = CT_PIX_BYTES;              // bytes between LDS pixels: 8 data chunks + 2 padding chunks of 16 B (144 B is NOT
+constexpr int CT_PIX = 160;              // bytes between LDS pixels: 8 data chunks + 2 padding chunks of 16 B (144 B is NOT
                                          // conflict-free for ds_read_b128: its 16-lane groups mix two lane quarters)
 constexpr int CT_SLOTS = CT_PIX / 16;    // 16-byte LDS slots per pixel
 constexpr int CT_MAXMT = 13;             // 16-pixel tiles per workgroup tile (208 pixels)
@@ -41,15 +37,6 @@ constexpr int CT_MAXMT = 13;             // 16-pixel tiles per workgroup tile (2
 constexpr int CT_VARIANT_128 = 4, CT_VARIANT_64 = 3;
 
 __device__ const uint4 g_ct_zero16 = {0, 0, 0, 0};
-
-#ifdef CT_DIAG
-// diagnostic builds (tools/abl_conv_tile.py stamps): s_memtime per wave of workgroup 0 around the barrier and the trips of a chunk
-__device__ unsigned long long* g_ct_diag = nullptr;
-#define CT_STAMP(slot) do { if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && gc < 8) { unsigned long long t__; \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory"); g_ct_diag[(gc * 8 + w) * 8 + (slot)] = t__; } } while (0)
-#else
-#define CT_STAMP(slot) do {} while (0)
-#endif
 
 template <int I, int E, class F>
 __device__ __forceinline__ void static_for_ct(F&& f)
@@ -100,9 +87,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     extern __shared__ __attribute__((aligned(16))) unsigned char ct_band[];    // [2][npieces * 1024] | 1 KiB dump slot
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), wn = w % NWN, wm = w / NWN;
-#ifdef CT_DIAG
-    { const int gc = 0; CT_STAMP(6); }                      // kernel entry (slot 6 of chunk 0)
-#endif
     const int H = a.H, W = a.W, C = a.C, K = a.K, BW = a.bw;
     const int band_bytes = a.npieces * 1024, nchunk = C / CT_CK;
     const int tpix = a.fpt * a.th * W;                     // output pixels of a full tile
@@ -150,9 +134,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
         const bf16_t* origin = (second ? q.b2 : q.b1) + chunk * CT_CK;
         // straight-line on purpose (always PP pieces: surplus ones land in a dump slot): a branch would make the compiler's vmcnt
         // counting conservative for the weight fragments in flight around it
-#ifdef CT_ABL_NODMA
-        if (chunk > 0 || tile != (int)blockIdx.x) return;
-#endif
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
             const int j = w + NWV * u;
@@ -197,13 +178,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     // The hardware returns them in issue order, so "at most N younger operations outstanding" is exact.
     struct WF { bf16x8 f[NTW]; };
     auto wload = [&](WF& o, int ks) __attribute__((always_inline)) {    // (wraps: a tile's last loads fetch the next tile's first k-steps)
-#ifdef CT_ABL_NOWLOAD
-        if (ks >= 3) return;                               // (only the prologue's loads)
-#endif
         ks = ks >= nks ? ks - nks : ks;
-#ifdef CT_ABL_NOW
-        ks = 0;                                            // (every weight fragment from one address: L1 hits)
-#endif
         size_t off;
         if constexpr (PK) off = (size_t)ks * 512;
         else {
@@ -239,11 +214,8 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
             // this chunk's band (DMA issued a chunk ago) has landed once only the WD NTW weight loads of the last WD k-steps --
             // all younger than it -- are outstanding; past the barrier the other buffer is free.  (Not __syncthreads: its vmcnt(0)
             // would drain the weight fragments in flight.)
-            CT_STAMP(0);
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WD * NTW) : "memory");
-            CT_STAMP(1);
             asm volatile("s_barrier" ::: "memory");
-            CT_STAMP(2);
             // the next band streams in behind this chunk's MFMAs: the tile's next chunk, or chunk 0 of the workgroup's next tile
             // (past the last tile: one more band of the last tile, into the buffer nobody reads again)
             {
@@ -259,9 +231,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                 const unsigned off = (unsigned)((dy * BW + dx) * CT_PIX + kh * 64);
 #pragma unroll
                 for (int m = 0; m < MTW; ++m) {
-#ifdef CT_ABL_NOLDS
-                    if (r > 1) { xb[m] = __builtin_bit_cast(bf16x8, make_uint4(off, r, m, off)); continue; }
-#endif
                     xb[m] = *reinterpret_cast<const bf16x8*>(band + pbase[m] + off);
                 }
             };
@@ -270,11 +239,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                 for (int m = 0; m < MTW; ++m)
 #pragma unroll
                     for (int nt = 0; nt < NTW; ++nt) {
-#ifdef CT_ABL_NOMFMA
-                        acc[m][nt] += __builtin_bit_cast(f32x4, wfr.f[nt]) * __builtin_bit_cast(f32x4, xb[m]);
-#else
                         acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfr.f[nt], xb[m], acc[m][nt], 0, 0, 0);
-#endif
                     }
             };
             const int ksb = chunk * 18;
@@ -294,15 +259,11 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                     __builtin_amdgcn_sched_barrier(0);
                 });
             };
-            CT_STAMP(3);
             trip(0, std::true_type{});
-            CT_STAMP(4);
 #pragma unroll 1
             for (int r0 = KU; r0 < 18; r0 += KU) trip(r0, std::false_type{});
-            CT_STAMP(5);
         }
         // epilogue: lane (li, g) holds rows 4g .. 4g+3 of each of the wave's output tiles for pixel 16 (wm + MW m) + li
-#ifndef CT_ABL_NOEPI
         {
             const int ty = tile % a.tiles_y, fg = tile / a.tiles_y;
             auto bf4 = [](uint2 rr) { return f32x4{__uint_as_float(rr.x << 16), __uint_as_float(rr.x & 0xffff0000u), __uint_as_float(rr.y << 16), __uint_as_float(rr.y & 0xffff0000u)}; };
@@ -392,10 +353,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                 }
             }
         }
-#endif
-#ifdef CT_DIAG
-        { const int gcs = gc; { const int gc = gcs - 1; CT_STAMP(7); } }   // end of the tile's epilogue (slot 7 of its last chunk)
-#endif
         cur = nxt;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // nothing may land in LDS after the workgroup is gone
@@ -545,23 +502,17 @@ bool setattr_tile()
 }
 }  // namespace
 
-#ifdef CT_DIAG
-extern "C" void gdkvm_ct_diag_buffer(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ct_diag), &p, sizeof(p)); }
-#endif
-
 int gdkvm_conv3x3_tile_launch(const void* x, const void* x2, int C1, const void* w, const float* bias, const void* residual, void* y,
                               int N, int C, int H, int W, int K, int relu, int variant, int packed, hipStream_t st)
 {
-    static const bool half_default = [] { const char* e = getenv("GDKVM_CONV_TILE128"); return !(e && e[0] == '2'); }();     // ("2": A/B switch, the eight-wave form)
-    if (variant == 0 && K % 128 == 0 && CT_VARIANT_128 == 4 && half_default) {
+    if (variant == 0 && K % 128 == 0 && CT_VARIANT_128 == 4) {
         // by shape: the two-workgroups-per-CU form where the tile's band fits its 32 DMA pieces, else the eight-wave form
         if (gdkvm_conv3x3_tile_launch(x, x2, C1, w, bias, residual, y, N, C, H, W, K, relu, 4, packed, st) == 0) return 0;
         variant = 2;
     }
-    static const bool half64 = [] { const char* e = getenv("GDKVM_CONV_TILE64"); return !(e && e[0] == '3'); }();   // ("3": A/B switch, the eight-wave form)
     // (a half tile must still hold two rows of the map: on 64-pixel rows it would be ONE row under a three-row band -- at 256x256 inputs the
     //  192 -> 64 layer took 273 us that way and the forward 1.573 ms against 1.515 ms with the eight-wave form, same box, round 4)
-    if (variant == 0 && K % 128 != 0 && half64 && (H * W <= 16 * 7 || 2 * W <= 16 * 7)) {
+    if (variant == 0 && K % 128 != 0 && (H * W <= 16 * 7 || 2 * W <= 16 * 7)) {
         if (gdkvm_conv3x3_tile_launch(x, x2, C1, w, bias, residual, y, N, C, H, W, K, relu, 5, packed, st) == 0) return 0;
         variant = 3;
     }

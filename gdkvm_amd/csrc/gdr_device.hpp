@@ -1,35 +1,9 @@
-// gdr_device.hpp -- device helpers shared by the GDR kernels (gdr_prep.hip, gdr_scan.hip): in-kernel diagnostic stamps,
-// compile-time loops, the three-term bf16 operand format (split3) and its MFMA image layout.  Not part of the C ABI.
+// gdr_device.hpp -- device helpers shared by the GDR kernels (gdr_prep.hip, gdr_scan.hip): compile-time loops,
+// the three-term bf16 operand format (split3) and its MFMA image layout.  Not part of the C ABI.
 #pragma once
 #include <type_traits>
 
 #include "gdkvm_common.hpp"
-
-#ifdef GDKVM_DIAG
-// Diagnostic build only (libgdkvm_hip_diag.so, built by tools/diag_scan.py): wave 0 of block 0 stamps s_memtime at
-// five points per frame into a buffer of its own.  Never compiled into the product library.
-extern unsigned long long* g_gdkvm_diag_buf;     // defined in gdr_scan.hip (gdkvm_diag_set_buffer)
-#define DIAG_STAMP(slot)                                                                      \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t__;                                                               \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");            \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.diag && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && tid == 0) a.diag[(size_t)t * 8 + (slot)] = t__;      \
-    } while (0)
-// a second row of stamps (row T - 1) for points inside a phase
-#define DIAG_STAMP2(slot)                                                                     \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t__;                                                               \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");            \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.diag && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && tid == 0) a.diag[(size_t)(t - 1) * 8 + (slot)] = t__; \
-    } while (0)
-#else
-#define DIAG_STAMP(slot) do {} while (0)
-#define DIAG_STAMP2(slot) do {} while (0)
-#endif
 
 template <int I, int E, class F>
 static __device__ __forceinline__ void static_for(F&& f)

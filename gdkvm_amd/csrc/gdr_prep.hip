@@ -384,9 +384,6 @@ struct PrepMArgs {
     int T, Hh, N, Dv, rule, flags, np_total;            // N = tokens of the frame, np_total = its padded count (qinv row length)
     int nchunk;                                         // FUSE: 64-token chunks per frame, walked by ONE workgroup (else gridDim.y)
     int grid3;                                          // launched as (8, T, B / 8): frame = (x + 8 z) T + y, no division (one chunk, one head)
-#ifdef GDKVM_DIAG
-    unsigned long long* diag;
-#endif
 };
 
 __host__ __device__ constexpr bool prepm_split(int NB, int IO) { return NB == 4 && IO == GDKVM_BF16; }
@@ -484,21 +481,10 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
     f32x4 X[FUSE ? 4 : 1][XJ];
     float xsplit_max = 0.f;                               // FUSE: largest |running map entry| this wave re-split into fp16 pairs
     const int tid_k = tid;
-#if defined(GDKVM_DIAG) && defined(GDKVM_DIAG_TWICE)
-    // diagnostic: the whole body twice over the same frame (trip count opaque: one copy of the code), second pass stamped into row T - 1 --
-    // what the first pass pays for instructions and data met for the first time
-    int npass__ = 2;
-    asm volatile("" : "+s"(npass__));
-    for (int pass__ = 0; pass__ < npass__; ++pass__)
-#endif
     for (int chunk = (FUSE || a.grid3) ? 0 : (int)blockIdx.y, chunk_end = FUSE ? nchunk : chunk + 1; chunk < chunk_end; ++chunk) {
     // FUSE: the lane ids are re-derived per chunk from an opaque copy -- otherwise every lane-dependent address of the body is
     // hoisted out of the chunk loop as an invariant and held (then spilled) across it: ~100 registers the running map needs
     int tid_o = tid_k;
-#if defined(GDKVM_DIAG) && defined(GDKVM_DIAG_TWICE)
-    asm volatile("" : "+v"(tid_o));
-    __syncthreads();
-#endif
     if constexpr (FUSE) asm volatile("" : "+v"(tid_o));
     const int tid = tid_o, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int tok0 = chunk * NP;
@@ -508,22 +494,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
     const bool p_identity = a.rule == GDKVM_RULE_GATED_LINEAR;
     // the frame's final G goes to the scan in the scan's scale (it carries S * STATE); chunk maps headed for the composition stay raw
     const float gscale = nchunk == 1 ? OpFmt<FMT>::STATE : 1.0f, gscale_inv = nchunk == 1 ? OpFmt<FMT>::STATE_INV : 1.0f;
-#if defined(GDKVM_DIAG) && defined(GDKVM_DIAG_TWICE)
-    const int t = a.T - pass__;
-#else
-    const int t = a.T;                                    // diagnostic builds: stamps go to row T of the buffer
-#endif
-    (void)t;
-    DIAG_STAMP(0);
-#if defined(GDKVM_DIAG) && defined(GDKVM_DIAG_SPAN)
-    // diagnostic: every workgroup's entry and exit time (a chip-wide counter) behind the stamp rows -- when the workgroups of one launch
-    // start, how long each lives, what the launch adds around them
-    if (a.diag && tid == 0) {
-        unsigned long long t__;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");
-        a.diag[(size_t)(a.T + 1) * 8 + 2 * (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z))] = t__;
-    }
-#endif
 
     // this wave's first V tile, raw, in the accumulator layout: x[I][r] = V[token 16I+4g+r][16cV+li]
     float xk[NB][4], xv[SPLIT ? 1 : 2][SPLIT ? 1 : NB][4];
@@ -547,12 +517,8 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
     // (a uniform base and two 32-bit lane offsets: as 64-bit lane addresses they cost four registers across the G loop, which the
     // three-workgroups-per-CU build of this kernel does not have)
     const bf16_t* vrow = static_cast<const bf16_t*>(a.v) + (bt * Hh + h) * Dv;
-#ifdef GDKVM_ABL_PREP_VSAME                                 // (tools/abl_scan.py prep: every lane pair reads token 0's piece -- one row segment per load)
-    const unsigned voff0 = 8u * (lane & 1), voff1 = 8u * (lane & 1);
-#else
     const unsigned voff0 = (unsigned)min(lane >> 1, N - 1) * (unsigned)(Hh * Dv) + 8u * (lane & 1);
     const unsigned voff1 = (unsigned)min(32 + (lane >> 1), N - 1) * (unsigned)(Hh * Dv) + 8u * (lane & 1);
-#endif
     auto load_vraw = [&](int cV, uint4& d0, uint4& d1) __attribute__((always_inline)) {
         cV = min(cV, nsl - 1);
         const bf16_t* vp = vrow + 16 * cV;
@@ -607,7 +573,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
                 load_vraw(w + 12, vD0, vD1);
             }
         }
-        DIAG_STAMP2(0);                                    // every load of the phase requested
         if constexpr (IO == GDKVM_BF16) {
             // the raw rows are all the later phases read (rows past N: the clamped duplicates, as fetched -- finite, and gated out by
             // kinv = beta = 0); widened to fp32 only for the norms, and only when they did not come with the projections
@@ -633,7 +598,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
                 sq += y[0] * y[0] + y[1] * y[1] + y[2] * y[2] + y[3] * y[3];
             }
         }
-        DIAG_STAMP2(1);                                    // key rows arrived, converted, staged
         if (!given) {
             sk += __shfl_xor(sk, 1); sq += __shfl_xor(sq, 1);
             sk += __shfl_xor(sk, 2); sq += __shfl_xor(sq, 2);
@@ -660,9 +624,7 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
             a.qinv[(size_t)fh * a.np_total + tok0 + n] = qinv;
         }
     }
-    DIAG_STAMP2(2);                                        // norms and gates done
     __syncthreads();
-    DIAG_STAMP(1);
     if constexpr (IO == GDKVM_BF16) {
 #pragma unroll
         for (int X = 0; X < NB; ++X)
@@ -727,7 +689,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
         }
     }
 
-    DIAG_STAMP2(3);                                        // Kn^T images built
     constexpr bool WAVE_BLOCKS = IO == GDKVM_BF16 && NB == 4;
     f32x4* s_T = WAVE_BLOCKS ? s_Ld : s_TmT;              // where phase 3 finds the T^T images
     if (seq && WAVE_BLOCKS) {
@@ -800,7 +761,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
             s_T[I * 64 + q * 16 + j] = tq;
         });
         }
-        DIAG_STAMP(2);
         __syncthreads();
     } else if (seq) {
         // ---- phase 1
@@ -871,7 +831,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
             }
         }
         __syncthreads();
-        DIAG_STAMP(2);
         // ---- phase 2: T_II by forward substitution (16 threads per block, one column each), stored transposed
         {
             const int I = tid >> 4, j = tid & 15;
@@ -897,7 +856,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
         }
         __syncthreads();
     }
-    DIAG_STAMP(3);
 
     // ---- phase 3: back substitution on Kn column tile w
     if (!seq) __syncthreads();                            // every wave has taken its Kn tile out of the staging tile (kni aliases it)
@@ -954,7 +912,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
         }
     }
     __syncthreads();
-    DIAG_STAMP(4);
 
     // ---- phase 4: P images and G tiles
     const int nlast = N - 16 * (NB - 1);                  // real tokens in the last block (<= 0: none)
@@ -1061,7 +1018,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
             else pp[(m * NT + sp) * SPLIT_IMG + e] = tt[sp];
         }
     }
-    DIAG_STAMP(5);
     // FUSE, chunk c >= 1: column tile j of the running map as B images (this wave's private tile), then row tile m of
     // P_c X[:, j] (+ the chunk's own G tile) -- gdr_compose_kernel's step, without leaving the workgroup
     auto col_images = [&](auto jc, uint4 (&xb)[NT][2]) __attribute__((always_inline)) {
@@ -1294,15 +1250,6 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
             g_tiles(cV + 4, xv[1]);
         }
     }
-    DIAG_STAMP(6);
-#if defined(GDKVM_DIAG) && defined(GDKVM_DIAG_SPAN)
-    __syncthreads();
-    if (a.diag && tid == 0) {
-        unsigned long long t__;
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");
-        a.diag[(size_t)(a.T + 1) * 8 + 2 * (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) + 1] = t__;
-    }
-#endif
     if constexpr (FUSE) __syncthreads();                  // the next chunk's staging tile overwrites what this one's phase 4 read
     }   // chunks
     if constexpr (FUSE) {
@@ -1345,12 +1292,7 @@ __attribute__((amdgpu_waves_per_eu(1, (W3 ? 3 : 2)))) void gdr_prepm_kernel(Prep
 template <int NB, int IO, int FMT, bool FUSE = false, bool W3 = false>
 int launch_prepm_fmt(const PrepMArgs& pa, int FH, int nchunk, hipStream_t st)
 {
-    size_t lds = prepm_lds_bytes(NB, IO, FUSE);
-    // diagnostics (tools/n4_bench.py fold): extra KiB of LDS per workgroup, to measure what a design that keeps more per frame
-    // resident -- the projections folded into this kernel need the frame's feature and value tiles: 104 KiB, one workgroup per CU --
-    // would pay in occupancy before any of its own work
-    static const int lds_pad_kb = [] { const char* e = getenv("GDKVM_PREP_LDS_PAD_KB"); return e ? atoi(e) : 0; }();
-    if (lds_pad_kb > 0 && lds + (size_t)lds_pad_kb * 1024 <= 160 * 1024) lds += (size_t)lds_pad_kb * 1024;
+    const size_t lds = prepm_lds_bytes(NB, IO, FUSE);
     if (lds > 64 * 1024) {
         // > 64 KiB of dynamic LDS needs the opt-in once per kernel and device; lock-free cache as in gdr_scan.hip
         static std::atomic<unsigned long long> done_mask{0};
@@ -1386,9 +1328,7 @@ int launch_prepm(const PrepMArgs& pa, int FH, int nchunk, bool wide, bool fuse, 
             int n = 0;
             if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
         }
-        bool w3 = (long)FH * nchunk > 2L * cus;
-        if (const char* e = getenv("GDKVM_PREP_W3")) w3 = e[0] == '1';           // "0" / "1": overrides the choice (A/B runs; same results)
-        if (w3)
+        if ((long)FH * nchunk > 2L * cus)
             return wide ? launch_prepm_fmt<NB, IO, FMT_SPLIT3, false, true>(pa, FH, nchunk, st) : launch_prepm_fmt<NB, IO, FMT_PAIR16, false, true>(pa, FH, nchunk, st);
     }
     return wide ? launch_prepm_fmt<NB, IO, FMT_SPLIT3>(pa, FH, nchunk, st) : launch_prepm_fmt<NB, IO, FMT_PAIR16>(pa, FH, nchunk, st);
@@ -1531,9 +1471,6 @@ static int scan_prep_impl(const void* q, const void* k, const void* v, const flo
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!(flags & GDKVM_FLAG_TRAIN) || ws.nchunk > 1) {  // P and G directly (frames of > 64 tokens: per 64-token chunk, then composed)
         PrepMArgs pm{q, k, v, beta, ws.qinv, ws.pp, ws.gg, ws.gmax, norms, ws.x0, ws.ppc, ws.ggc, T, Hh, N, Dv, rule, flags, 16 * ws.nb, ws.nchunk};
-#ifdef GDKVM_DIAG
-        pm.diag = g_gdkvm_diag_buf;
-#endif
         const bool wide = flags & GDKVM_FLAG_WIDE_RANGE;
         // Frames of more than 64 tokens: with enough frames to fill the device on their own, ONE workgroup walks a frame's chunks and
         // composes its map in registers (no chunk maps through HBM, no compose kernel); with few frames the chunks run as separate

@@ -22,11 +22,6 @@
 #include "gdr_device.hpp"
 #include "gdr_ws.hpp"
 
-#ifdef GDKVM_DIAG
-unsigned long long* g_gdkvm_diag_buf = nullptr;
-extern "C" void gdkvm_diag_set_buffer(unsigned long long* p) { g_gdkvm_diag_buf = p; }
-#endif
-
 namespace {
 
 // gdr_affine_scan_kernel: the serial recurrence on the folded operands.  8 waves per workgroup in two fixed roles:
@@ -61,13 +56,8 @@ __host__ __device__ constexpr size_t aff_lds_bytes(int IO, int NT)
 {
     return (size_t)(aff_s_f4(NT) + (IO == GDKVM_F32 && NT == 3 ? 2 * 4 * 64 : 0)) * 16;
 }
-#ifndef AFF_PD_FRAMES
-#define AFF_PD_FRAMES 2
-#endif
-#ifndef AFF_NBUF
-#define AFF_NBUF 4
-#endif
-constexpr int AFF_PD = AFF_PD_FRAMES;                // operand prefetch distance of the state waves, in frames (read waves: AFF_NBUF - 1)
+constexpr int AFF_NBUF = 4;
+constexpr int AFF_PD = 2;                // operand prefetch distance of the state waves, in frames (read waves: AFF_NBUF - 1)
 constexpr int AFF_THREADS = 512;
 
 __device__ __forceinline__ void aff_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -539,11 +529,7 @@ __global__ __launch_bounds__(256, 2) void gdr_readout_kernel(ReadoutArgs a)     
             }
             const f32x4 accR = (acc0 + acc1) * (rscale * sinv[c]);
             const int nr = 16 * tt + li;
-#ifdef GDKVM_ABL_RO_NOSTORE                                 // (tools/abl_scan.py: stores only where a value is NaN -- never, but not provably)
-            if (nr < N && (c == 0 || two) && accR[0] != accR[0]) {
-#else
             if (nr < N && (c == 0 || two)) {
-#endif
                 char* p = rbase + (size_t)nr * rowr + c * 16 * ESZ;
                 if constexpr (IO == GDKVM_F32) *reinterpret_cast<f32x4*>(p) = accR;
                 else *reinterpret_cast<uint2*>(p) = make_uint2(cvt_pk_bf16(accR[0], accR[1]), cvt_pk_bf16(accR[2], accR[3]));
@@ -552,24 +538,16 @@ __global__ __launch_bounds__(256, 2) void gdr_readout_kernel(ReadoutArgs a)     
     };
     QT qa, qb;
     load_q(tt0, qa);
-#ifdef GDKVM_ABL_RO_NOQ                                     // (tools/abl_scan.py: the first two token tiles' q rows for every tile)
-    load_q(tt0 + 1, qb);
-    for (int tt = tt0; tt < ntt; tt += 2) {
-        tile(tt, qa);
-        if (tt + 1 < ntt) tile(tt + 1, qb);
-    }
-#else
     for (int tt = tt0; tt < ntt; tt += 2) {
         load_q(tt + 1, qb);
         tile(tt, qa);
         load_q(tt + 2, qa);
         if (tt + 1 < ntt) tile(tt + 1, qb);
     }
-#endif
 }
 
 // gdr_readout_rows_kernel -- the same read-out for bf16 I/O with every global access a run of whole rows (round 6).  Ablation of the
-// kernel above at cfg5 (tools/abl_scan.py ro, profiles/r06_ad_readout_ablation.txt): 82 us of which the R stores cost ~80 and the q loads
+// kernel above at cfg5 (profiles/r06_ad_readout_ablation.txt): 82 us of which the R stores cost ~80 and the q loads
 // ~25-45 -- not their bytes (134 + 33 MB) but their SHAPE: a wave's store is 16 rows x 32 bytes, its q load 16 rows x 64 bytes, every
 // wave of the frame's workgroups loads the same q rows, and the memory pipeline is paid per row segment.  Here the workgroup moves both
 // through LDS: q rows of TWO token tiles (32 tokens x 128 bytes) arrive as one 16-byte load per thread (a contiguous 4 KB when Hh = 1),

@@ -9,7 +9,6 @@
 //                                                   order (deterministic: no atomics).  Row-major slabs are staged in LDS and read
 //                                                   back transposed (ds_read_b64_tr_b16) as MFMA fragments.
 // bf16 operands run on v_mfma_f32_16x16x32_bf16, fp32 operands on the exact v_mfma_f32_16x16x4_f32.
-#include <stdlib.h>
 
 #include "gdkvm_common.hpp"
 
@@ -397,10 +396,10 @@ extern "C" int gdkvm_gemm_tn_colsum(const void* a, const void* b, float* c, floa
 // Row splits: enough workgroups to keep every CU several deep (the kernel is a chain of staged 32-row slabs: latency-bound per workgroup, so
 // what fills the chip is the NUMBER of resident workgroups) without drowning the reduction in partial tiles: ~1024 workgroups in all, at
 // least 256 rows each.  (A 1x1 / stride-2 branch has ONE column tile: at 2048 rows per split it ran on 49 workgroups and took as long as
-// its block's 3x3 layer with nine times the work.)  GDKVM_CW_WGS overrides the target (A/B runs).
+// its block's 3x3 layer with nine times the work.)
 static int cw_splits(long long M, int K, int taps, int C)
 {
-    static const int target = [] { const char* e = getenv("GDKVM_CW_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }();
+    constexpr int target = 1024;
     const long long tiles = (long long)((K + 127) / 128) * (taps * C / 64);
     long long s = (target + tiles - 1) / tiles;
     const long long smax = (M + 255) / 256;

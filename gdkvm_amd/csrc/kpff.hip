@@ -198,23 +198,6 @@ __global__ __launch_bounds__(256) void kpff_kernel(KpffArgs a)
 // fragment = 8 consecutive k of one output channel = one 16-byte load, a wave's 64 fragments contiguous).  Lane l = 16g + i:
 //   A = X[row i][k 8g..8g+7],  B = W[col i][k 8g..8g+7],  C/D reg r = D[row 4g + r][col i].
 
-#ifdef KPFF_STAMPS
-// Diagnostic build only (tools/stamp_kpff.py): lane 0 of every wave of the first 64 workgroups stamps s_memtime at the phase
-// boundaries of kpff_bf16_kernel into a buffer of its own ([block][wave][16]).  Never compiled into the product library.
-__device__ unsigned long long* g_kpff_stamps = nullptr;
-extern "C" void gdkvm_kpff_diag_set_buffer(unsigned long long* p) { hipMemcpyToSymbol(HIP_SYMBOL(g_kpff_stamps), &p, sizeof(p)); }
-#define KPFF_STAMP(slot)                                                                                           \
-    do {                                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                          \
-        unsigned long long t__;                                                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");                                \
-        __builtin_amdgcn_sched_barrier(0);                                                                          \
-        if (g_kpff_stamps && blockIdx.x < 64 && (threadIdx.x & 63) == 0) g_kpff_stamps[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 16 + (slot)] = t__; \
-    } while (0)
-#else
-#define KPFF_STAMP(slot) do {} while (0)
-#endif
-
 struct KpffBf16Args {
     const bf16_t* L; const bf16_t* G; const bf16_t* P;
     const bf16_t* wa; const float* ba; const bf16_t* wl; const bf16_t* wg;
@@ -271,10 +254,7 @@ __device__ __forceinline__ f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c)
 // loaded set made the compiler wait for the newest fetch every k-step: s_waitcnt vmcnt(0) / vmcnt(1) inside the loop.)
 // OT output tiles at once: a token fragment read from LDS feeds NS*OT MFMAs (the kernel is LDS-read-bound at OT = 1: every
 // 32-deep k-step re-reads MT KiB of tokens for MT*NS MFMAs); ot_stride = elements between consecutive output tiles' packs.
-#ifndef KPFF_WD_STEPS
-#define KPFF_WD_STEPS 4
-#endif
-constexpr int KPFF_WD = KPFF_WD_STEPS;               // ring depth = k-steps per unrolled trip
+constexpr int KPFF_WD = 4;               // ring depth = k-steps per unrolled trip
 
 // The ring of weight register sets of one pass.  A caller may own it and PRIME it (kpff_prime: the pass's first KPFF_WD k-steps
 // requested) long before the pass runs -- at kernel entry, or right behind the previous output tile's pass of the same kind -- so that
@@ -282,15 +262,10 @@ constexpr int KPFF_WD = KPFF_WD_STEPS;               // ring depth = k-steps per
 // tile took 4.9 k cycles against an MFMA floor of 2.6 k, the long one ~1 k over its floor: one exposed prologue each).
 template <int NS, int OT> struct KRing { bf16x8 b0[KPFF_WD][OT]; bf16x8 b1[KPFF_WD][OT]; };
 
-#ifdef KPFF_ABL_WSAME                                       // ablation: every weight fragment from one L1-resident KiB
-#define KPFF_WOFF(x) ((size_t)0 * (x))
-#else
-#define KPFF_WOFF(x) (x)
-#endif
 template <int NS, int OT>
 __device__ __forceinline__ void kpff_wload(const bf16_t* w0, const bf16_t* w1, size_t ot_stride, int slot_ks, int n, bf16x8 (&d0)[OT], bf16x8 (&d1)[OT])
 {
-    const size_t off = KPFF_WOFF((size_t)min(slot_ks, n - 1) * 512);
+    const size_t off = (size_t)min(slot_ks, n - 1) * 512;
 #pragma unroll
     for (int o = 0; o < OT; ++o) {
         d0[o] = *reinterpret_cast<const bf16x8*>(w0 + o * ot_stride + off);
@@ -338,7 +313,6 @@ __device__ __forceinline__ void kpff_stream(const bf16_t* xb, int ld, int ks0, i
             xa[mt] = *reinterpret_cast<const bf16x8*>(xb + (size_t)mt * 16 * ld + 32 * ksn);
         }
         wload(i + KPFF_WD, b0[j], b1[j]);                  // refill the weight set just used
-#ifndef KPFF_NO_SCHED_GROUPS
         // Pin the order written above.  Left alone, the machine scheduler clusters: all of the k-step's MFMAs first, then the MT
         // LDS reads in one batch -- and the next k-step opens with s_waitcnt lgkmcnt(MT - 1) on a read issued a few cycles earlier:
         // a full LDS round trip exposed per k-step (round 3 disassembly; the MFMA pipe was 40 % busy inside this loop).  One group
@@ -349,7 +323,6 @@ __device__ __forceinline__ void kpff_stream(const bf16_t* xb, int ld, int ks0, i
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             // DS read
         }
         __builtin_amdgcn_sched_group_barrier(0x020, NS * OT, 0);           // VMEM read
-#endif
         __builtin_amdgcn_sched_barrier(0);
     };
     int i = 0;
@@ -373,9 +346,7 @@ __device__ __forceinline__ void kpff_stream(const bf16_t* xb, int ld, int ks0, i
 // workgroup the kernel sits at the L2 balance point (0.75 MB of weights per 64 tokens ~ 64 flop per L2 byte).
 // OT = output tiles a wave accumulates at once; the workgroup has 4*NT/OT waves (NT = 2, OT = 2: four waves with up to 512
 // registers each, 64 accumulator tiles per wave).
-#ifndef KPFF_OT
-#define KPFF_OT 1
-#endif
+constexpr int KPFF_OT = 1;
 // SB = rows a sub-tile occupies in the workgroup's tile: 64, or 56 when both sub-tiles hold at most 56 tokens (two 7x7 frames:
 // 98 tokens in SEVEN 16-row token tiles instead of eight -- an eighth off the MFMA passes, the fragment reads and the epilogues).
 template <int NT, int OT, int SB = KPFF_TM>
@@ -410,9 +381,6 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
 #pragma unroll
     for (int sb = 0; sb < NT; ++sb) inv_tw[sb] = 1.0f / (float)max(t_w[sb], 1);
     auto gtok = [&](int sb, int tok) {
-#ifdef KPFF_ABL_INTDIV                                          // ablation: the integer divisions of rounds 1-2
-        { const int ty = tok / t_w[sb]; return t_n0[sb] + ty * a.w + (tok - ty * t_w[sb]); }
-#endif
         if (full_w) return t_n0[sb] + tok;
         const int ty = (int)(((float)tok + 0.5f) * inv_tw[sb]);
         return t_n0[sb] + ty * a.w + (tok - ty * t_w[sb]);
@@ -426,10 +394,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
     auto wl_g = [&](int ob) { return a.wl + ((size_t)(ob / 16) * ksL * 64 + lane) * 8; };
     auto wg_g = [&](int ob) { return a.wg + ((size_t)(ob / 16) * ksG * 64 + lane) * 8; };
     KRing<2, OT> ring_g;
-#ifndef KPFF_SKIP_GEMM
     if (16 * OT * w_id < Cp) kpff_prime<2, OT>(ring_g, wa_g(16 * OT * w_id), wa_g(Cp + 16 * OT * w_id), (size_t)KSa * 512, KSa);
-#endif
-    KPFF_STAMP(0);
     // ---- stage the [P ; L] rows as they are (8 channels = 16 bytes per thread, 4 loads in flight) -----------
     {
         const int q8 = (Cp + Ck) / 8, total = TMW * q8;
@@ -440,11 +405,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int idx = base + u * NTHR;
-#ifdef KPFF_ABL_INTDIV
-                const int trow = idx / q8, c = (idx - trow * q8) * 8;
-#else
                 const int trow = (int)(((float)idx + 0.5f) * inv_q8), c = (idx - trow * q8) * 8;
-#endif
                 const int sb = trow >= SB ? 1 : 0, tok = trow - SB * sb;
                 dst[u] = idx < total ? trow * ld + c : -1;
                 x[u] = make_uint4(0u, 0u, 0u, 0u);
@@ -459,8 +420,6 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
                 if (dst[u] >= 0) *reinterpret_cast<uint4*>(s_xb + dst[u]) = x[u];
         }
     }
-    KPFF_STAMP(1);
-#ifndef KPFF_SKIP_POOL
     // ---- G: pooled (multi-scale) straight from global memory: one thread per (4x4 cell, group of four channels), the cell's 16 tokens
     //      as 16 independent 8-byte loads, fp32 math (per channel the sums run over the cell's tokens in raster order), one 8-byte store
     //      per token into the tile.  Both sub-tiles share one index space, so at 7x7 tokens and 256 channels every thread has exactly
@@ -538,10 +497,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
         pool_issue(pi, u, ok);
         pool_finish(pi, u, ok);
     }
-#endif
-    KPFF_STAMP(2);
     __syncthreads();
-    KPFF_STAMP(3);
     if (a.sv.gms) {                                            // training: keep the pooled feature for the backward
         bf16_t* gms = static_cast<bf16_t*>(a.sv.gms);
 #pragma unroll
@@ -560,7 +516,6 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) gl[o][mt] = gg[o][mt] = lp[o][mt] = gp[o][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
         const bf16_t* xb = s_xb + (size_t)li * ld + 8 * g;             // B fragment: token 16mt+li, k 8g..8g+7
-#ifndef KPFF_SKIP_GEMM
         // fragment-order packs: k-step ks of output tile ot lives at ((ot*KS + ks)*64 + lane)*8.  Every pass runs on a ring primed
         // earlier (kernel entry for the first output tile); behind each pass its ring is primed for the wave's NEXT output tile.
         const int obn = ob0 + OB_STEP;                             // the wave's next output tile (uniform)
@@ -571,13 +526,8 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
         kpff_prime<1, OT>(ring_p, wg_g(ob0), nullptr, (size_t)ksG * 512, ksG);
         kpff_stream<2, MT, OT, true>(xb, ld, 0, KSa, wa_g(ob0), wa_g(Cp + ob0), (size_t)KSa * 512, gl, gg, ring_g);                       // gates
         if (obn < Cp) kpff_prime<2, OT>(ring_g, wa_g(obn), wa_g(Cp + obn), (size_t)KSa * 512, KSa);
-        KPFF_STAMP(ob0 < 16 * OT * (NTHR / 64) ? 4 : 8);
         kpff_stream<1, MT, OT, true>(xb, ld, ksP, ksL, wl_g(ob0), nullptr, (size_t)ksL * 512, lp, lp, ring_l);                             // L Wl^T
         kpff_stream<1, MT, OT, true>(xb, ld, ksP + ksL, ksG, wg_g(ob0), nullptr, (size_t)ksG * 512, gp, gp, ring_p);
-#else
-        gl[0][0][0] = xb[0]; (void)ksP; (void)ksL; (void)KSa;
-#endif
-        KPFF_STAMP(ob0 < 16 * OT * (NTHR / 64) ? 5 : 9);
 #pragma unroll
         for (int o = 0; o < OT; ++o) {
         const int ob = ob0 + 16 * o;
@@ -588,11 +538,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int trow = 16 * mt + li, sb = (NT > 1 && trow >= SB) ? 1 : 0, tok = trow - SB * sb;
-#ifdef KPFF_SKIP_EPI
-            if (tok < t_ntok[sb] && gl[o][mt][0] == 123.f) {
-#else
             if (tok < t_ntok[sb]) {
-#endif
                 const uint2 pu = *reinterpret_cast<const uint2*>(s_xb + (size_t)trow * ld + oc);
                 const float pv[4] = {__uint_as_float(pu.x << 16), __uint_as_float(pu.x & 0xffff0000u),
                                      __uint_as_float(pu.y << 16), __uint_as_float(pu.y & 0xffff0000u)};
@@ -620,7 +566,6 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
             }
         }
         }
-        KPFF_STAMP(ob0 < 16 * OT * (NTHR / 64) ? 6 : 10);
     }
 }
 
@@ -909,9 +854,7 @@ __global__ __launch_bounds__(256) void kpff_bwd_post_kernel(const void* dF, cons
 // order as the A operand (kpff_stream) -- so the same machinery serves: a workgroup stages 128 token rows, its 8 waves walk the
 // 16-channel output tiles of all three projections, and the epilogue adds the bias and writes each tile into the tensor it
 // belongs to (contiguous [tokens, width] rows: exactly what gdkvm_scan_prep and gdkvm_kpff_fwd read).
-#ifndef PROJ_TM_SWITCH
-#define PROJ_TM_SWITCH (128 * 512)
-#endif
+constexpr int PROJ_TM_SWITCH = 128 * 512;
 struct ProjArgs {
     const bf16_t* x; const bf16_t* wpack; const float* bias;
     bf16_t* out[3];
@@ -1029,7 +972,6 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
     }
     float* s_part = reinterpret_cast<float*>(s_px + (size_t)TM * ld);
     const size_t row0 = (size_t)blockIdx.x * TM;
-    KPFF_STAMP(0);
     for (int base = tid; base < TM * q8; base += 4 * 512) {            // stage the token rows (zero beyond M), 4 loads in flight
         uint4 x[4];
 #pragma unroll
@@ -1043,9 +985,7 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
             if (idx < TM * q8) *reinterpret_cast<uint4*>(s_px + (size_t)r * ld + c) = x[u];
         }
     }
-    KPFF_STAMP(1);
     __syncthreads();
-    KPFF_STAMP(2);
     {   // ---- write-gate logits from the staged rows: 512 / TM threads per token, 16-byte pieces interleaved over them
         constexpr int TPT = 512 / TM;
         const int tok = tid / TPT, part = tid % TPT;
@@ -1065,7 +1005,6 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
             if (part == 0 && row0 + tok < (size_t)a.M) ga.beta[(row0 + tok) * Hh + h] = d + ga.b_gate[h];
         }
     }
-    KPFF_STAMP(3);
     const bf16_t* xb = s_px + (size_t)li * ld + 8 * g;
     const int ntile_norm = (a.width[0] + a.width[1]) / 16;               // the key and query tiles
     for (int ot = w_id; ot < a.ntile_out; ot += 8) {
@@ -1095,9 +1034,7 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
             }
         }
     }
-    KPFF_STAMP(4);
     __syncthreads();
-    KPFF_STAMP(5);
     // inverse norms per (token, head): the Dk / 16 tile sums of a head in tile order; norms[row][head][0 = key, 1 = query]
     const int tph = ga.Dk / 16;
     for (int idx = tid; idx < TM * 2 * Hh; idx += 512) {
@@ -1107,7 +1044,6 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
         for (int t = 0; t < tph; ++t) ss += s_part[(t0 + t) * TM + tok];
         if (row0 + tok < (size_t)a.M) ga.norms[((row0 + tok) * Hh + h) * 2 + which] = 1.0f / sqrtf(ss + GDKVM_EPS_NORM);
     }
-    KPFF_STAMP(6);
 }
 
 }  // namespace
@@ -1179,21 +1115,15 @@ extern "C" int gdkvm_kpff_fwd_train(const void* local, const void* global, const
         const size_t lds1 = (size_t)KPFF_TM * (Cin + KPFF_PAD16) * sizeof(bf16_t);
         if (lds1 > 160 * 1024) return gdkvm_fail(GDKVM_ERR_SHAPE, "kpff_fwd: Cp+Ck+Cv=%d exceeds the LDS tile", Cin);
         const int total_tiles = BT * tiles;
-#ifdef KPFF_FORCE_NT1                                           // ablation (tools/abl_kpff.py): one 64-token tile per four-wave workgroup, two workgroups per CU
-        const bool pair = false;
-#else
         // Up to one tile per CU (the per-frame step mode runs KPFF on ONE frame per clip; a group of clips of a forward split over streams): the
         // kernel's time is one workgroup's latency, and a four-wave workgroup with ONE tile is done sooner than an eight-wave one with two --
         // 24.3 against 25.7 us at 16 frames, 26.8 against 29.2 at 256, 34.1 against 30.2 at 320 (round 6; same bits).
-        // GDKVM_KPFF_SINGLE_BELOW=n: single-tile workgroups for fewer than n tiles (0 = never).
         static const int single_below = [] {
-            if (const char* e = getenv("GDKVM_KPFF_SINGLE_BELOW")) return atoi(e);
             int dev = 0, n = 0;
             if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) return n + 1;
             return 257;
         }();
         const bool pair = 2 * lds1 <= 160 * 1024 && total_tiles >= 2 && total_tiles >= single_below;     // two 64-token tiles per 8-wave workgroup
-#endif
         bf16_t* wab = static_cast<bf16_t*>(workspace);
         const size_t na = (size_t)2 * Cp * Cin, nl = (size_t)Cp * Ck;
         if (!g_kpff_skip_pack) {
@@ -1203,11 +1133,7 @@ extern "C" int gdkvm_kpff_fwd_train(const void* local, const void* global, const
         KpffBf16Args b{static_cast<const bf16_t*>(local), static_cast<const bf16_t*>(global), static_cast<const bf16_t*>(pixel),
                        wab, ba, wab + na, wab + na + nl, static_cast<bf16_t*>(out), Ck, Cv, Cp, h, w, rows, tiles, sv, cols, col_tiles};
         // two sub-tiles of at most 56 tokens each (two 7x7 frames): packed at 56 rows apiece, seven token tiles instead of eight
-#ifdef KPFF_ABL_NOPACK56                                        // ablation: eight token tiles as in rounds 1-2
-        const bool packed56 = false;
-#else
         const bool packed56 = pair && rows * cols <= 56;
-#endif
         const size_t lds = packed56 ? (size_t)112 * (Cin + KPFF_PAD16) * sizeof(bf16_t) : (pair ? 2 * lds1 : lds1);
         const void* fn = packed56 ? reinterpret_cast<const void*>(kpff_bf16_kernel<2, KPFF_OT, 56>)
                        : pair ? reinterpret_cast<const void*>(kpff_bf16_kernel<2, KPFF_OT>) : reinterpret_cast<const void*>(kpff_bf16_kernel<1, 1>);

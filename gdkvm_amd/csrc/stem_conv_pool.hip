@@ -126,12 +126,10 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
     __syncthreads();
     for (; tile < ntiles; tile += gridDim.x, cur ^= 1) {
         const bool more = tile + (int)gridDim.x < ntiles;
-#ifndef STEM_ABL_NODMA
         if (more) {                                                                      // lands behind this tile's MFMAs
             if constexpr (NCHW) fetch_nchw(tile + gridDim.x);
             else fetch(tile + gridDim.x, cur ^ 1);
         }
-#endif
         const unsigned char* band = band2 + cur * SP_BAND_BYTES;
         const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
         const int cy0 = POOL ? 2 * SP_TPY * ty - 1 : SP_CR * ty, cx0 = POOL ? 2 * SP_TPX * tx - 1 : (SP_CC - 7) * tx;   // convolution row / column of tile position (0, 0)
@@ -157,12 +155,8 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
                 const int ky = ks >> 1, half = ks & 1;
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
-#ifdef STEM_ABL_NOMFMA                                      // (tools/abl_stem.py: timing ablations, wrong results by design)
-                    acc[r][0][0] += __builtin_bit_cast(f32x4, xf[r + ky][half])[0];
-#else
                     acc[r][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][ks], xf[r + ky][half], acc[r][0], 0, 0, 0);
                     acc[r][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1][ks], xf[r + ky][half], acc[r][1], 0, 0, 0);
-#endif
                 }
             }
             if constexpr (!POOL) {                          // the raw convolution, straight to memory
@@ -200,7 +194,6 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
         __syncthreads();                                   // the convolution tile is complete (and the next band has landed)
 
         // ---- 3x3 / stride 2 max-pool out of LDS: item = (pooled row q, pooled column px, 8-channel group) ------------------
-#ifndef STEM_ABL_NOPOOL
         for (int it = tid; POOL && it < SP_TPY * SP_TPX * 8; it += 512) {
             const int cg = it & 7, pp = it >> 3, q = pp / SP_TPX, px = pp - q * SP_TPX;
             const int py_g = SP_TPY * ty + q, px_g = SP_TPX * tx + px;
@@ -224,7 +217,6 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
                 *reinterpret_cast<uint4*>(a.y + (((size_t)n * a.Hp + py_g) * a.Wp + px_g) * 64 + cg * 8) = o;
             }
         }
-#endif
         if constexpr (POOL) __syncthreads();               // the tile may be overwritten
     }
 }
@@ -423,9 +415,7 @@ static int stem_conv_pool_impl(const char* who, const void* xs, const void* xf, 
             done_mask.fetch_or(bit, std::memory_order_relaxed);
         }
     }
-#ifndef STEM_GRID
-#define STEM_GRID 256                                      // persistent, one workgroup per CU
-#endif
+    constexpr int STEM_GRID = 256;                     // persistent, one workgroup per CU
     const int grid = (int)(ntiles < STEM_GRID ? ntiles : STEM_GRID);
     if (!pool) hipLaunchKernelGGL((stem_conv_pool_kernel<true, false>), dim3(grid), dim3(512), lds, static_cast<hipStream_t>(stream), a);
     else if (xf) hipLaunchKernelGGL(stem_conv_pool_kernel<true>, dim3(grid), dim3(512), lds, static_cast<hipStream_t>(stream), a);

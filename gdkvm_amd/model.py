@@ -126,30 +126,10 @@ def _describe(conv: nn.Conv2d, x: torch.Tensor) -> str:
 
 
 _BN_COUNTED_BY_MODEL = [False]
-# The strided 3x3 layers of the inference build: gdkvm_conv_bias_act's general implicit-GEMM kernel with the epilogue inside
-# (default), or the library convolution + one epilogue pass (GDKVM_CONV_IGEMM=0).  Measured equal on the EchoNet shapes -- 1.013 /
-# 1.020 ms against 1.021 ms per cfg2 forward -- so the hand-written path is taken: no solver search, one launch.
-_IGEMM_STRIDED = os.environ.get("GDKVM_CONV_IGEMM", "1") != "0"
-# SURVEY.md §8f row n4 in the inference build: key / query / value projections, both gate logits and the key / query norms in ONE
-# launch over the pixel feature (ops.proj_gates), the scan taking the norms as given -- or (GDKVM_PROJ_GATES=0, the A/B switch
-# behind DESIGN.md §8 n4's numbers) the three-launch form: ops.proj_rows, ops.gate_logits, norms inside gdkvm_scan_prep.
-_PROJ_GATES = os.environ.get("GDKVM_PROJ_GATES", "1") != "0"
-# The inference stem reading the NCHW frames itself (round 4: ops.stem_conv_pool_nchw), or (GDKVM_STEM_NCHW=0, the A/B switch) the
-# space-to-depth pass followed by the stem kernel; bit-identical.
-_STEM_NCHW = os.environ.get("GDKVM_STEM_NCHW", "1") != "0"
-# training stem: BatchNorm + ReLU + max-pool as one op in both directions (ops.bn_relu_pool); "0" = bn_act then maxpool3x3s2 (A/B switch)
-_STEM_BN_POOL = os.environ.get("GDKVM_STEM_BN_POOL", "1") != "0"
-# training: the decoder's 1x1 head on gdkvm_head_logits / gdkvm_head_bwd (deterministic gradients); "0" = the library convolution (A/B switch)
-_TRAIN_HEAD_HIP = os.environ.get("GDKVM_TRAIN_HEAD_HIP", "1") != "0"
-# training: a residual block's input as two outputs of its first convolution's node (ops.conv3x3_fork); "0" = the framework adds the gradients
-_TRAIN_CONV_FORK = os.environ.get("GDKVM_TRAIN_CONV_FORK", "1") != "0"
-# training: a strided block's 3x3 / stride-2 convolution + 1x1 branch on csrc/conv_s2_train.hip (deterministic); "0" = the library convolutions (A/B switch)
-_TRAIN_CONV_S2 = os.environ.get("GDKVM_TRAIN_CONV_S2", "1") != "0"
-# segment_clip(graph=True): the next chunk's encoder + projections beside the current chunk's memory path and decoder (PipelinedClip); "0" = one
-# whole-forward graph per chunk, chunks strictly one after the other (A/B switch; same bits)
-_CLIP_PIPELINE = os.environ.get("GDKVM_CLIP_PIPELINE", "1") != "0"
-# training: key / query / value / gate projections as one stacked product (ops.token_projections); "0" = one product each (A/B switch)
-_TRAIN_PROJ_STACKED = os.environ.get("GDKVM_TRAIN_PROJ_STACKED", "1") != "0"
+# segment_clip(graph=True): the next chunk's encoder + projections beside the current chunk's memory path and decoder (PipelinedClip).
+# Tests set it False to get the reference they compare against: one whole-forward graph per chunk, chunks strictly one after the other
+# (same bits).
+_CLIP_PIPELINE = True
 
 
 def _bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -207,7 +187,7 @@ class BasicBlock(nn.Module):
                 return self.conv2(pair[0], pair[1])
             skip = x if self.down is None else self.down(x)
             return self.conv2(self.conv1(x), skip.contiguous(memory_format=torch.channels_last) if skip.is_cuda else skip)
-        if (self.down is None and _TRAIN_CONV_FORK and torch.is_grad_enabled() and x.requires_grad and self.conv1.bias is None
+        if (self.down is None and torch.is_grad_enabled() and x.requires_grad and self.conv1.bias is None
                 and self.conv1.padding_mode == "zeros"
                 and ops.conv3x3_train_served(x, self.conv1.weight, self.conv1.stride, self.conv1.padding, self.conv1.dilation, self.conv1.groups)):
             # the block's input feeds the first convolution AND the skip: as two outputs of one node (ops.conv3x3_fork), so that the
@@ -215,7 +195,7 @@ class BasicBlock(nn.Module):
             y1, xs = ops.conv3x3_fork(x, self.conv1.weight)
             y = _bn_act(self.bn1, y1, True)
             return _bn_act(self.bn2, _conv(self.conv2, y), True, xs)
-        if (self.down is not None and _TRAIN_CONV_S2 and torch.is_grad_enabled() and isinstance(self.conv1, nn.Conv2d)
+        if (self.down is not None and torch.is_grad_enabled() and isinstance(self.conv1, nn.Conv2d)
                 and isinstance(self.down[0], nn.Conv2d) and ops.conv_s2_block_served(x, self.conv1, self.down[0])):
             # the strided convolution and the downsample branch as one node on the hand-written kernels (ops.conv_s2_block): one forward launch,
             # one data-gradient launch for both branches, deterministic weight gradients
@@ -250,7 +230,7 @@ class Encoder(nn.Module):
                 x = s[0](x)
             p, bn = s[3], s[1]
             pool_ok = isinstance(p, nn.MaxPool2d) and (p.kernel_size, p.stride, p.padding, p.dilation, p.ceil_mode) == (3, 2, 1, 1, False)
-            if (_STEM_BN_POOL and pool_ok and bn.training and bn.affine and bn.weight.dtype == torch.float32 and ops.bn_relu_pool_served(x)):
+            if (pool_ok and bn.training and bn.affine and bn.weight.dtype == torch.float32 and ops.bn_relu_pool_served(x)):
                 # BatchNorm + ReLU + max-pool as one op both ways: the full-resolution activation and its gradient are never written
                 momentum = bn.momentum
                 if bn.track_running_stats:
@@ -353,7 +333,7 @@ class Decoder(nn.Module):
             if head_fused and size is None:
                 return HeadFeature(y, cache[1], cache[2])
             x = ops.head_logits(y, cache[1], cache[2])
-        elif _TRAIN_HEAD_HIP and torch.is_grad_enabled() and ops.head_served(y, hd):
+        elif torch.is_grad_enabled() and ops.head_served(y, hd):
             # training: gdkvm_head_logits forward, gdkvm_head_bwd backward (one pass, fixed summation order) -- the library's bf16 weight
             # gradient for this layer accumulates atomically and differed by several bf16 ulps from run to run
             x = ops.head(y, hd.weight, hd.bias)
@@ -414,7 +394,7 @@ class FusedConv(nn.Module):
         `down` the block's folded 1x1 convolution of the same stride whose bias already sits in the consumer's epilogue; else None."""
         cv = self.conv
         d = down[0] if isinstance(down, nn.Sequential) and len(down) == 1 else None
-        if not (_IGEMM_STRIDED and isinstance(d, FusedConv) and getattr(d, "bias_folded_downstream", False) and not d.relu
+        if not (isinstance(d, FusedConv) and getattr(d, "bias_folded_downstream", False) and not d.relu
                 and not getattr(self, "bias_folded_downstream", False) and x.is_cuda and x.dtype == torch.bfloat16
                 and cv.kernel_size == (3, 3) and cv.padding == (1, 1) and cv.dilation == (1, 1) and cv.groups == 1
                 and cv.stride[0] == cv.stride[1] and d.conv.kernel_size == (1, 1) and d.conv.stride == cv.stride
@@ -453,9 +433,10 @@ class FusedConv(nn.Module):
                 packed = self._packed(x.device) if tile in (4, 5) else None
                 return ops.conv_bias_act(x.contiguous(memory_format=torch.channels_last), cv.weight, self.epi.bias, residual,
                                          cv.stride[0], 1, self.relu, tile, packed)
-            if _IGEMM_STRIDED and cv.in_channels % 32 == 0 and cv.out_channels % 128 == 0:
+            if cv.in_channels % 32 == 0 and cv.out_channels % 128 == 0:
                 # what the two 3x3 / 1 / 1 kernels do not take -- the strided layers, rows wider than 64 pixels -- on the general
-                # implicit-GEMM kernel, epilogue included (A/B switch: see _IGEMM_STRIDED)
+                # implicit-GEMM kernel, epilogue included.  Measured equal to the library convolution + one epilogue pass on the EchoNet
+                # shapes (1.013 / 1.020 ms against 1.021 ms per cfg2 forward): no solver search, one launch.
                 return ops.conv_bias_act(x.contiguous(memory_format=torch.channels_last), cv.weight, self.epi.bias, residual,
                                          cv.stride[0], 1, self.relu, ops.CONV_KERNEL_IGEMM, self._packed(x.device, igemm=True))
         _library_fallback(x, _describe(cv, x), "inference build: the hand-written kernels take bf16 channels_last 3x3 / pad 1 layers with channel counts "
@@ -501,14 +482,11 @@ class FusedConvPool(FusedConv):
 
     def forward(self, x, residual=None):
         if x.is_cuda and getattr(self, "w_s2d", None) is not None and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0:
-            if (_STEM_NCHW and x.dtype == torch.bfloat16 and x.shape[1] <= 4 and self.w_s2d.dtype == torch.bfloat16
+            if (x.dtype == torch.bfloat16 and x.shape[1] <= 4 and self.w_s2d.dtype == torch.bfloat16
                     and tuple(self.w_s2d.shape) == (64, 16, 4, 4) and self.w_s2d.is_contiguous(memory_format=torch.channels_last)):
-                # the stem kernel builds its space-to-depth band from the NCHW frames itself: one kernel, no 16-channel copy of the input
+                # convolution + bias + ReLU + max-pool in one kernel, which builds its space-to-depth band from the NCHW frames itself
                 return ops.stem_conv_pool_nchw(x.contiguous(), self.w_s2d, self.epi.bias)
             xs = ops.stem_s2d(x.contiguous(), self.S2D_CH)                       # NCHW frames -> NHWC space-to-depth, one pass
-            if (xs.dtype == torch.bfloat16 and self.w_s2d.dtype == torch.bfloat16 and tuple(self.w_s2d.shape) == (64, 16, 4, 4)
-                    and self.w_s2d.is_contiguous(memory_format=torch.channels_last)):
-                return ops.stem_conv_pool(xs, self.w_s2d, self.epi.bias)         # convolution + bias + ReLU + max-pool: one kernel
             y = F.conv2d(xs, self.w_s2d, None, 1, 2)                             # [N, Cout, H/2 + 1, W/2 + 1]: last row/col unused
             return ops.bias_relu_maxpool(y.contiguous(memory_format=torch.channels_last)[:, :, :x.shape[2] // 2, :x.shape[3] // 2],
                                          self.epi.bias)
@@ -887,7 +865,7 @@ class GDKVM(nn.Module):
         cp8 = tok2d.shape[1] // 8
         infer_bf16 = (tok2d.is_cuda and not train_gpu and not torch.is_grad_enabled() and tok2d.dtype == torch.bfloat16
                       and tok2d.shape[1] % 32 == 0 and tok2d.shape[1] <= 512 and wk % 16 == 0 and wv % 16 == 0)
-        if infer_bf16 and _PROJ_GATES and Dk == ops.KERNEL_DK and cp8 & (cp8 - 1) == 0:
+        if infer_bf16 and Dk == ops.KERNEL_DK and cp8 & (cp8 - 1) == 0:
             # ONE launch for everything derived from the pixel feature: K / Q / V, both gate logits, the key / query norms
             projs = (self.key_proj, self.query_proj, self.value_proj)
             gp, dp = self.gate_proj, self.decay_proj
@@ -915,7 +893,7 @@ class GDKVM(nn.Module):
                 self._qkv_pack = cache
             k2d, q2d, v2d = ops.proj_rows(tok2d, cache[1], cache[2], (wk, wq, wv))
             k_tok, q, v = k2d.reshape(B * T, N, wk), q2d.reshape(B, T, N, Hh, Dk), v2d.reshape(B, T, N, wv)
-        elif train_gpu and tok2d.dtype == torch.bfloat16 and _TRAIN_PROJ_STACKED:
+        elif train_gpu and tok2d.dtype == torch.bfloat16:
             # training: the four projections of the feature as ONE stacked product forward and two backward (ops.token_projections)
             # -- and the decay logit with them: W_d mean_n(x) + b_d = mean_n(W_d x + b_d), so the per-frame decay is the token mean of one
             # more stacked column (the mean taken in fp32 over bf16 per-token values; the separate path rounded the mean itself to bf16)
@@ -1154,7 +1132,7 @@ class GraphedSegment:
         bits; what changes is the schedule: every kernel of a forward fills the chip, drains with a tail and runs its phases in lockstep,
         and a second, independent stream fills those gaps -- cfg2: 0.898 against 0.940 ms per 16 x 32 frames with two groups of eight,
         although each half-batch kernel alone is less efficient (the halves one after the other: 1.085 ms); three or four groups and
-        unequal ones lose (profiles/r05_n_two_streams_in_one_graph.txt).  None = 2 for batches of at least 8 clips that halve, else 1 (GDKVM_SEGMENT_STREAMS overrides where it divides the batch).
+        unequal ones lose (profiles/r05_n_two_streams_in_one_graph.txt).  None = 2 for batches of at least 8 clips that halve, else 1.
         pool: another GraphedSegment's ``graph.pool()`` -- graphs of one pool share their activation memory (never replay two of them
         concurrently; a graph's outputs are valid until another graph of the pool replays): several captures over DIFFERENT input buffers
         cost one set of activations (bench.py rotates eight input batches this way)."""
@@ -1169,8 +1147,7 @@ class GraphedSegment:
             return n == 1 or ((per_ * frames.shape[1] * frames.shape[3] * frames.shape[4]) % 16 == 0
                               and (target is None or (per_ * frames.shape[1] * model.cfg.num_classes * 12) % 16 == 0))
         if streams is None:
-            env = os.environ.get("GDKVM_SEGMENT_STREAMS", "")
-            streams = int(env) if env.isdigit() and int(env) >= 1 and B % int(env) == 0 else (2 if (B >= 8 and B % 2 == 0) else 1)
+            streams = 2 if (B >= 8 and B % 2 == 0) else 1
             if not aligned(streams):
                 streams = 1                                 # (e.g. 10 clips x 3 frames x 2 classes: 360-byte count slabs)
         if streams < 1 or B % streams:
@@ -1251,8 +1228,8 @@ class PipelinedClip:
     chunk's encoder and projections running BESIDE the current chunk's memory path, KPFF, decoder and mask kernel (round 6).  Only the second
     half depends on the state, and a chunk of a long clip is few frames of few clips -- kernels that leave most of the chip idle -- so the two
     halves of consecutive chunks overlap: configs[4] (2 clips x 512 frames of 256 x 256 in 16 chunks) 12.3 -> 11.2 ms, one 112 x 112 clip of 256
-    frames 2.68 -> 2.07 ms, four 3.45 -> 2.80 (tools/clip_pipeline_probe.py, profiles/r06_at_clip_pipeline.txt; GDKVM_CLIP_PIPELINE=0 = one
-    whole-forward graph per chunk).  Two captured "front" graphs (encoder + projections, double-buffered outputs, a stream of their own) and two
+    frames 2.68 -> 2.07 ms, four 3.45 -> 2.80 (tools/clip_pipeline_probe.py, profiles/r06_at_clip_pipeline.txt; with _CLIP_PIPELINE
+    False: one whole-forward graph per chunk).  Two captured "front" graphs (encoder + projections, double-buffered outputs, a stream of their own) and two
     "back" graphs (scan with the state carried, KPFF, decoder, masks + Dice counts; the caller's stream), tied by events:
         front(i + 1) waits for back(i - 1) (which read the buffers front(i + 1) overwrites);  back(i) waits for front(i).
     The same kernels on the same operands in the same order per chunk: masks, counts and the final state are segment_clip's, bit for bit."""

@@ -1131,9 +1131,8 @@ class _Conv3x3Function(torch.autograd.Function):
     def _fwd(ctx, lib, x, xb, weight, k, c):
         packs = _train_packs_of(weight)                    # (conv3x3_train_packs ran for this version of the weight: nothing to cast or pack here)
         ctx.kc, ctx.wdtype, ctx.xdtype = (k, c), weight.dtype, x.dtype
-        ctx.w_cl = (weight.is_contiguous(memory_format=torch.channels_last) and not weight.is_contiguous()
-                    and os.environ.get("GDKVM_WGRAD_KRSC", "1") != "0")          # ("0": A/B switch for tools)
-        if packs is not None and os.environ.get("GDKVM_CONV_WGRAD") != "framework":
+        ctx.w_cl = weight.is_contiguous(memory_format=torch.channels_last) and not weight.is_contiguous()
+        if packs is not None:
             # the data-gradient pack belongs to THIS version of the weight: a copy would cost what the pre-pack saves, so the backward
             # checks that the weight has not been written since (an optimiser step between forward and backward is not a thing)
             ctx.dgrad_pack, ctx.pack_key = packs[1], (weight._version, weight.data_ptr())
@@ -1170,10 +1169,7 @@ class _Conv3x3Function(torch.autograd.Function):
         elif res is not None:
             dx = res.to(ctx.xdtype)
         if ctx.needs_input_grad[1]:
-            if os.environ.get("GDKVM_CONV_WGRAD") == "framework":          # (A/B switch for tools: the framework's weight gradient)
-                dw = torch.ops.aten.convolution_backward(dyb, xb, wb, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False))[1].to(ctx.wdtype)
-            else:
-                dw = conv3x3_wgrad(xb, dyb, channels_last=ctx.w_cl).to(ctx.wdtype)  # (fp32 sums over all pixels, deterministic; in the weight's own memory order)
+            dw = conv3x3_wgrad(xb, dyb, channels_last=ctx.w_cl).to(ctx.wdtype)  # (fp32 sums over all pixels, deterministic; in the weight's own memory order)
         return dx, dw, None
 
 

@@ -9,7 +9,6 @@ path lives here; the one computation is the uint8 -> [0, 1] cast of frames a loa
 the float32 bytes cross PCIe)."""
 from __future__ import annotations
 
-import os
 import sys
 import warnings
 from typing import Iterable, Iterator, Optional, Tuple
@@ -45,7 +44,7 @@ class DevicePrefetcher:
         # the casts run on a stream of their OWN (round 6): behind the copy on the copy stream, every batch made the DMA engine wait for a
         # small kernel that itself waits for room beside the forward's kernels -- copy, cast, copy in one queue ran at 0.53 ms per 19 MB batch
         # with nothing else on the GPU and ~0.75 ms beside the forward, against 0.36 ms for the copies alone
-        self.cast_stream = torch.cuda.Stream(device=device) if os.environ.get("GDKVM_PREFETCH_CAST_STREAM", "1") != "0" else self.stream
+        self.cast_stream = torch.cuda.Stream(device=device)
         self._pinned = [None] * slots           # per slot: the page-locked (frames, target) its copy in flight reads (kept alive)
         self._stage_buf = [None] * slots        # per slot: this class's own pinned staging buffers, re-used while the shape holds
         self._dev = [None] * slots
@@ -77,17 +76,16 @@ class DevicePrefetcher:
         with torch.cuda.stream(self.stream):
             if self._free[slot] is not None:
                 self.stream.wait_event(self._free[slot])
-            if self._cast_done[slot] is not None and self.cast_stream is not self.stream:
+            if self._cast_done[slot] is not None:
                 self.stream.wait_event(self._cast_done[slot])          # (the slot's raw buffers were last read by its previous cast)
             dev[0].copy_(pin[0], non_blocking=True)
             dev[1].copy_(pin[1], non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(self.stream)            # (the pinned buffers are free again once this has passed)
         with torch.cuda.stream(self.cast_stream):
-            if self.cast_stream is not self.stream:
-                self.cast_stream.wait_event(copied)
-                if self._free[slot] is not None:
-                    self.cast_stream.wait_event(self._free[slot])      # (the cast buffers of the slot are the consumer's inputs)
+            self.cast_stream.wait_event(copied)
+            if self._free[slot] is not None:
+                self.cast_stream.wait_event(self._free[slot])          # (the cast buffers of the slot are the consumer's inputs)
             out_f, out_t = self._convert(slot, dev[0], dev[1])
             ev = torch.cuda.Event()
             ev.record(self.cast_stream)

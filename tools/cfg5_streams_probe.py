@@ -13,4 +13,4 @@ def rate(fn, it=3):
     b.record(); torch.cuda.synchronize()
     return a.elapsed_time(b) / it
 m = model.segment_clip(f5, 32, graph=True)
-print("streams env", os.environ.get("GDKVM_SEGMENT_STREAMS"), f"{rate(lambda: model.segment_clip(f5, 32, graph=True)):.3f} ms per 1024 frames", int(m[0].sum()))
+print(f"{rate(lambda: model.segment_clip(f5, 32, graph=True)):.3f} ms per 1024 frames", int(m[0].sum()))

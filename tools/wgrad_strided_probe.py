@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times ops.conv_wgrad_strided on the four strided layers of the training step (512 frames): us per call.
-    [GDKVM_CW_WGS=<target workgroups>] python tools/wgrad_strided_probe.py"""
+    python tools/wgrad_strided_probe.py"""
 import os
 import sys
 
@@ -24,4 +24,4 @@ for (n, c, k, h, r, st, pad) in ((512, 64, 128, 28, 3, 2, 1), (512, 64, 128, 28,
         a.record(); ops.conv_wgrad_strided(x, dy, like, st, pad); b.record()
     torch.cuda.synchronize()
     ms = sorted(a.elapsed_time(b) for a, b in ev)
-    print(f"{c:4d} -> {k:4d} {r}x{r}/{st} @ {h:2d}: {1e3 * ms[len(ms) // 2]:7.1f} us  (GDKVM_CW_WGS={os.environ.get('GDKVM_CW_WGS', 'default')})", flush=True)
+    print(f"{c:4d} -> {k:4d} {r}x{r}/{st} @ {h:2d}: {1e3 * ms[len(ms) // 2]:7.1f} us", flush=True)
