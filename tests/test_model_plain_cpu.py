@@ -63,7 +63,11 @@ def test_the_plain_restatement_notices_a_rewired_skip():
 
 
 @pytest.mark.parametrize("case", [dict(widths=(16, 32, 64), pixel_dim=64, value_dim=32, rule="delta_sequential", num_classes=2),
-                                  dict(widths=(16, 16, 32), pixel_dim=32, value_dim=16, heads=2, rule="gated_linear", num_classes=3)])
+                                  dict(widths=(16, 16, 32), pixel_dim=32, value_dim=16, heads=2, rule="gated_linear", num_classes=3),
+                                  # the default model (GDKVMConfig()) at a batch whose BatchNorm is stable.  Its stem weight gradient sums
+                                  # 6 x 56 x 56 products of positive pixels with mixed-sign gradients per element in the reference's
+                                  # float32 CPU convolution: 6.2e-3 of its max measured (1.4e-3 rel-L2), every other tensor <= 3e-5
+                                  dict(clip=(2, 3, 112, 112), loose={"encoder.stem.0.weight": 1e-2})])
 def test_reference_gradients_equal_the_plain_restatement(case):
     """The gradient oracle is independent too: one training step's loss and gradients from the reference module (the product's wiring,
     torch autograd, train-mode BatchNorm, gdkvm_amd.train.segmentation_loss) against oracle.model_plain.plain_loss_and_grads (the
@@ -73,11 +77,14 @@ def test_reference_gradients_equal_the_plain_restatement(case):
     from gdkvm_amd.model import GDKVMConfig
     from gdkvm_amd.train import segmentation_loss
     from oracle.model_plain import plain_loss_and_grads
+    case = dict(case)
+    B, T, H, W = case.pop("clip", (2, 2, 64, 64))
+    loose = case.pop("loose", {})
     cfg = GDKVMConfig(**case)
     ref = _ref(cfg, seed=7).train()
     g = torch.Generator().manual_seed(11)
-    frames = torch.rand(2, 2, 3, 64, 64, generator=g)
-    target = torch.randint(0, cfg.num_classes, (2, 2, 64, 64), generator=g)
+    frames = torch.rand(B, T, 3, H, W, generator=g)
+    target = torch.randint(0, cfg.num_classes, (B, T, H, W), generator=g)
     target[:, 1, :20] = 255                                                    # unlabelled rows of the second frame
     loss = segmentation_loss(ref(frames), target)
     loss.backward()
@@ -89,6 +96,6 @@ def test_reference_gradients_equal_the_plain_restatement(case):
             assert (p.grad is None or p.grad.abs().max() == 0) and (n not in gp or gp[n].abs().max() == 0), n
             continue
         scale = max(gp[n].abs().max().item(), 1e-7)
-        assert (p.grad.double() - gp[n]).abs().max().item() <= 2e-3 * scale, (n, (p.grad.double() - gp[n]).abs().max().item(), scale)
+        assert (p.grad.double() - gp[n]).abs().max().item() <= loose.get(n, 2e-3) * scale, (n, (p.grad.double() - gp[n]).abs().max().item(), scale)
         seen += 1
     assert seen >= 60                                                          # every layer of the model took part
