@@ -38,7 +38,7 @@ def main(argv=None):
     torch.manual_seed(cfg.seed)
     mcfg = GDKVMConfig(num_classes=cfg.data.num_classes, heads=cfg.model.heads, key_dim=cfg.model.key_dim,
                        value_dim=cfg.model.value_dim, rule=cfg.model.rule,
-                       scan_segments=cfg.model.scan_segments)
+                       scan_segments=cfg.model.scan_segments, mask_feedback=cfg.model.mask_feedback)
     model = GDKVM(mcfg).eval()
     if args.weights:
         model.load_state_dict(torch.load(args.weights, map_location="cpu")["model"])

@@ -32,6 +32,7 @@ class ModelCfg:
     value_dim: int = 256
     rule: str = "delta_sequential"
     scan_segments: int = 1           # evaluation of long clips: GDKVMConfig.scan_segments (1 = serial scan, bit-identical under chunking)
+    mask_feedback: bool = False      # GDKVMConfig.mask_feedback: train and evaluate in the per-frame step mode (predicted masks fed back)
 
 
 @dataclass

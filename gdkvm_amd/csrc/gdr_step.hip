@@ -115,7 +115,159 @@ __global__ __launch_bounds__(64) void mask_embed_add_kernel(EmbedArgs a)
     }
 }
 
+// The weight gradient of mask_embed_add: d_w[c] = sum over (f, n) of m(f, n) * d_v[f, n, c], m the pooled indicator above (same cells,
+// same integer count, same fp32 division).  Deterministic, no float atomics: block b takes the rows [b RB, (b + 1) RB) of the F*N token
+// rows (wgrad_split), 64 rows at a time -- their m from the mask into LDS, then every thread owns one 16-byte piece of a row (8 bf16 or 4
+// fp32 columns) and walks the chunk's rows with a stride of 256 / (C / V) -- and writes the column sums of its rows to partial[b][C] after
+// a fixed-order sum over its row lanes.  mask_embed_wgrad_final_kernel adds the partials of all blocks in a fixed order.  d_v is read
+// once, in 16-byte pieces; the mask bytes once per cell (a pixel of a ragged grid can sit in two cells).
+constexpr int WG_THREADS = 256, WG_ROWS = 64, WG_TARGET_BLOCKS = 512;
+
+static inline void wgrad_split(long long M, long long& G, long long& RB)
+{
+    RB = (M + WG_TARGET_BLOCKS - 1) / WG_TARGET_BLOCKS;
+    if (RB < 1) RB = 1;
+    G = (M + RB - 1) / RB;
+}
+
+struct WgradArgs { const uint8_t* mask; const void* dv; float* partial; long long M, RB; int H, W, h, wd, C, chmax; };
+
+template <int IO>
+__global__ __launch_bounds__(WG_THREADS) void mask_embed_wgrad_kernel(WgradArgs a)
+{
+    constexpr int V = IO == GDKVM_F32 ? 4 : 8;                       // columns per 16-byte piece
+    __shared__ int s_cnt[WG_ROWS];
+    __shared__ float s_avg[WG_ROWS];
+    __shared__ float s_red[WG_THREADS * V];
+    const int tid = threadIdx.x, N = a.h * a.wd, L = a.C / V, R = WG_THREADS / L;
+    const int rl = tid / L, jv = tid - rl * L;                        // row lane, 16-byte column piece
+    const long long r_begin = (long long)blockIdx.x * a.RB;
+    const long long r_end = r_begin + a.RB < a.M ? r_begin + a.RB : a.M;
+    float acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
+    for (long long r0 = r_begin; r0 < r_end; r0 += WG_ROWS) {
+        const int rows = r_end - r0 < WG_ROWS ? (int)(r_end - r0) : WG_ROWS;
+        if (tid < WG_ROWS) s_cnt[tid] = 0;
+        __syncthreads();                                               // (also: the previous chunk's reads of s_avg are done)
+        for (int it = tid; it < rows * a.chmax; it += WG_THREADS) {     // one (row, pixel row of its cell) per item
+            const int rr = it / a.chmax, k = it - rr * a.chmax;
+            const long long row = r0 + rr, f = row / N;
+            const int n = (int)(row - f * N), i = n / a.wd, j = n - i * a.wd;
+            const int y0 = (i * a.H) / a.h, y1 = ((i + 1) * a.H + a.h - 1) / a.h;
+            if (y0 + k >= y1) continue;
+            const int x0 = (j * a.W) / a.wd, x1 = ((j + 1) * a.W + a.wd - 1) / a.wd;
+            const uint8_t* m = a.mask + ((size_t)f * a.H + y0 + k) * a.W;
+            int sum = 0;
+            for (int xx = x0; xx < x1; ++xx) sum += (m[xx] != 0 && m[xx] != 255) ? 1 : 0;
+            if (sum) atomicAdd(&s_cnt[rr], sum);                         // (integer adds: exact in any order)
+        }
+        __syncthreads();
+        if (tid < rows) {
+            const long long row = r0 + tid, f = row / N;
+            const int n = (int)(row - f * N), i = n / a.wd, j = n - i * a.wd;
+            const int cnt = (((i + 1) * a.H + a.h - 1) / a.h - (i * a.H) / a.h) * (((j + 1) * a.W + a.wd - 1) / a.wd - (j * a.W) / a.wd);
+            s_avg[tid] = (float)s_cnt[tid] / (float)cnt;
+        }
+        __syncthreads();
+        if (rl < R) {
+#pragma unroll 4
+            for (int rr = rl; rr < rows; rr += R) {
+                const float av = s_avg[rr];
+                const size_t o = (size_t)(r0 + rr) * a.C + (size_t)jv * V;
+                const uint4 u = *reinterpret_cast<const uint4*>(static_cast<const char*>(a.dv) + o * (IO == GDKVM_F32 ? 4 : 2));
+                const unsigned w4[4] = {u.x, u.y, u.z, u.w};
+                if constexpr (IO == GDKVM_F32) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[k] = fmaf(av, __uint_as_float(w4[k]), acc[k]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        acc[2 * k] = fmaf(av, __uint_as_float(w4[k] << 16), acc[2 * k]);
+                        acc[2 * k + 1] = fmaf(av, __uint_as_float(w4[k] & 0xffff0000u), acc[2 * k + 1]);
+                    }
+                }
+            }
+        }
+    }
+    if (rl < R) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) s_red[rl * a.C + jv * V + k] = acc[k];
+    }
+    __syncthreads();
+    for (int c = tid; c < a.C; c += WG_THREADS) {
+        float s = 0.f;
+        for (int q = 0; q < R; ++q) s += s_red[q * a.C + c];           // row lanes in order
+        a.partial[(size_t)blockIdx.x * a.C + c] = s;
+    }
+}
+
+// d_w[c] = the sum of partial[b][c] over the G blocks: a block per 16 columns, 64 lanes of 4 columns each summing b = g, g + 64, ...
+// in order, then a fixed pairwise tree over the 64 lanes.  G == 0 writes zeros.
+__global__ __launch_bounds__(WG_THREADS) void mask_embed_wgrad_final_kernel(const float* partial, float* dw, int G, int C)
+{
+    __shared__ f32x4 s[WG_THREADS];
+    const int tid = threadIdx.x, g = tid >> 2, c4 = blockIdx.x * 4 + (tid & 3);
+    const bool live = 4 * c4 < C;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+#pragma unroll 4
+        for (int b = g; b < G; b += WG_THREADS / 4) acc += *reinterpret_cast<const f32x4*>(partial + (size_t)b * C + 4 * c4);
+    }
+    s[tid] = acc;
+    __syncthreads();
+    for (int half = WG_THREADS / 8; half >= 1; half >>= 1) {             // lanes g and g + half, 4 threads per lane
+        if (g < half) s[tid] += s[tid + 4 * half];
+        __syncthreads();
+    }
+    if (g == 0 && live) *reinterpret_cast<f32x4*>(dw + 4 * c4) = s[tid];
+}
+
 }  // namespace
+
+extern "C" size_t gdkvm_mask_embed_wgrad_workspace_bytes(int F, int h, int w, int C)
+{
+    if (F <= 0 || h <= 0 || w <= 0 || C <= 0) return 0;
+    long long G, RB;
+    wgrad_split((long long)F * h * w, G, RB);
+    return (size_t)G * (size_t)C * sizeof(float);
+}
+
+extern "C" int gdkvm_mask_embed_wgrad(const uint8_t* mask, const void* d_v, float* d_w, void* workspace, size_t workspace_bytes,
+                                      int F, int H, int W, int h, int w, int C, int io_dtype, void* stream)
+{
+    if (F < 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0 || C <= 0 || h > H || w > W)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_embed_wgrad: F=%d mask %dx%d tokens %dx%d C=%d", F, H, W, h, w, C);
+    if (io_dtype != GDKVM_F32 && io_dtype != GDKVM_BF16) return gdkvm_fail(GDKVM_ERR_DTYPE, "mask_embed_wgrad: io_dtype=%d", io_dtype);
+    const int V = io_dtype == GDKVM_F32 ? 4 : 8;
+    if (C % V || C / V > WG_THREADS)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_embed_wgrad: C=%d must be a multiple of %d and at most %d", C, V, V * WG_THREADS);
+    if ((long long)H * h > 0x7fffffffLL || (long long)W * w > 0x7fffffffLL)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_embed_wgrad: mask %dx%d with tokens %dx%d overflows the cell arithmetic", H, W, h, w);
+    if (int rc = check_ptrs("mask_embed_wgrad", {d_w}, {})) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long M = (long long)F * h * w;
+    long long G = 0, RB = 1;
+    if (M > 0) {
+        if (!mask) return gdkvm_fail(GDKVM_ERR_ARG, "mask_embed_wgrad: null mask");     // (bytes: any alignment)
+        if (int rc = check_ptrs("mask_embed_wgrad", {d_v, workspace}, {})) return rc;
+        wgrad_split(M, G, RB);
+        if (G > 0x7fffffffLL) return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_embed_wgrad: too many tokens");
+        const size_t need = gdkvm_mask_embed_wgrad_workspace_bytes(F, h, w, C);
+        if (workspace_bytes < need) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "mask_embed_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
+    }
+    if (int rc = gdkvm_check_device()) return rc;
+    if (M > 0) {
+        WgradArgs a{mask, d_v, static_cast<float*>(workspace), M, RB, H, W, h, w, C, (H + h - 1) / h + 1};
+        if (io_dtype == GDKVM_F32) hipLaunchKernelGGL(mask_embed_wgrad_kernel<GDKVM_F32>, dim3((unsigned)G), dim3(WG_THREADS), 0, st, a);
+        else hipLaunchKernelGGL(mask_embed_wgrad_kernel<GDKVM_BF16>, dim3((unsigned)G), dim3(WG_THREADS), 0, st, a);
+        GDKVM_LAUNCH_CHECK("mask_embed_wgrad");
+    }
+    hipLaunchKernelGGL(mask_embed_wgrad_final_kernel, dim3((unsigned)((C + 15) / 16)), dim3(WG_THREADS), 0, st,
+                       static_cast<const float*>(workspace), d_w, (int)G, C);
+    GDKVM_LAUNCH_CHECK("mask_embed_wgrad_final");
+    return GDKVM_OK;
+}
 
 extern "C" int gdkvm_lkva_read(const void* q, const float* norms, const float* s, void* r_out,
                                int B, int N, int Hh, int Dk, int Dv, int io_dtype, int flags, void* stream)

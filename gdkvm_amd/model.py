@@ -56,8 +56,9 @@ class GDKVMConfig:
     normalizer_eps: float = 1e-6
     # per-frame `step` mode -- the value written for frame t carries the embedding (mask_embed) of the mask
     # PREDICTED for frame t (of mask0 for frame 0 when it is given), XMem-style: read -> KPFF -> decoder -> mask -> write, frame by frame.
-    # Inference only; the time loop is then ~12 launches per frame instead of one scan launch per chunk (GDKVM.segment captures it in
-    # one hipGraph all the same: GraphedSegment).
+    # Inference: the time loop is then ~12 launches per frame instead of one scan launch per chunk (GDKVM.segment captures it in
+    # one hipGraph all the same: GraphedSegment).  Training (GDKVM._feedback_train): that loop without autograd gives the masks, then the
+    # ordinary whole-clip forward on the values v + embed(mask) -- the exact gradient, as the masks are piecewise constant in every weight.
     mask_feedback: bool = False
 
 
@@ -126,6 +127,9 @@ def _describe(conv: nn.Conv2d, x: torch.Tensor) -> str:
 
 
 _BN_COUNTED_BY_MODEL = [False]
+# The feedback pass of a step-mode training forward (GDKVM._feedback_pass, under no_grad): BatchNorm layers normalise with the batch
+# statistics of what they see and write no buffer (running statistics, step counters), and convolutions run the training kernels.
+_FEEDBACK_PASS = [False]
 # segment_clip(graph=True): the next chunk's encoder + projections beside the current chunk's memory path and decoder (PipelinedClip).
 # Tests set it False to get the reference they compare against: one whole-forward graph per chunk, chunks strictly one after the other
 # (same bits).
@@ -137,20 +141,24 @@ def _bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, residual: Optional[
     (ops.bn_act: statistics, normalise + add + ReLU; the library BatchNorm kernels were 38 % of a training step); eval mode of
     the un-folded model and the CPU reference module use torch."""
     v = 8 if x.dtype == torch.bfloat16 else 4
+    track = bn.track_running_stats and not _FEEDBACK_PASS[0]
     if (x.is_cuda and bn.training and bn.affine and x.dtype in (torch.bfloat16, torch.float32) and bn.weight.dtype == torch.float32
             and x.shape[1] % v == 0 and x.shape[1] // v <= 256):
         momentum = bn.momentum
-        if bn.track_running_stats:
+        if track:
             if not _BN_COUNTED_BY_MODEL[0]:                 # GDKVM.forward bumps all counters in one foreach launch
                 bn.num_batches_tracked.add_(1)
             if momentum is None:
                 momentum = 1.0 / float(bn.num_batches_tracked)
         res = None if residual is None else residual.to(x.dtype)
-        return ops.bn_act(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
-                          bn.running_var if bn.track_running_stats else None, res, momentum or 0.0, bn.eps, relu)
-    if _BN_COUNTED_BY_MODEL[0] and bn.training and bn.track_running_stats:
-        bn.num_batches_tracked.sub_(1)                      # torch's own layer counts this step itself
-    y = bn(x)
+        return ops.bn_act(x, bn.weight, bn.bias, bn.running_mean if track else None,
+                          bn.running_var if track else None, res, momentum or 0.0, bn.eps, relu)
+    if _FEEDBACK_PASS[0] and bn.training:
+        y = F.batch_norm(x, None, None, bn.weight, bn.bias, True, 0.0, bn.eps)
+    else:
+        if _BN_COUNTED_BY_MODEL[0] and bn.training and bn.track_running_stats:
+            bn.num_batches_tracked.sub_(1)                  # torch's own layer counts this step itself
+        y = bn(x)
     if residual is not None:
         y = y + residual
     return F.relu(y, inplace=True) if relu else y
@@ -159,11 +167,12 @@ def _bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, residual: Optional[
 def _conv(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """A training-build convolution: the stride-1 3x3 layers with channel counts in multiples of 64 run forward, data gradient
     and weight gradient on the hand-written kernels (ops.conv3x3: csrc/conv3x3_tile.hip, conv3x3_wgrad.hip), everything else is
-    conv(x) (MIOpen)."""
-    if (torch.is_grad_enabled() and isinstance(conv, nn.Conv2d) and conv.bias is None and conv.padding_mode == "zeros"
+    conv(x) (MIOpen).  The feedback pass of a step-mode training forward (_FEEDBACK_PASS, no autograd) runs the same kernels."""
+    train = torch.is_grad_enabled() or _FEEDBACK_PASS[0]
+    if (train and isinstance(conv, nn.Conv2d) and conv.bias is None and conv.padding_mode == "zeros"
             and ops.conv3x3_train_served(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
         return ops.conv3x3(x, conv.weight)
-    if torch.is_grad_enabled():
+    if train:
         _library_fallback(x, _describe(conv, x), "training build: only stride-1 3x3 layers with channel counts in multiples of 64, "
                           "the stem and the strided blocks of the default widths are hand-written")
     return conv(x)
@@ -669,15 +678,21 @@ class GDKVM(nn.Module):
         return x.permute(0, 2, 3, 1).reshape(x.shape[0], x.shape[2] * x.shape[3], x.shape[1]).contiguous()
 
     def forward(self, frames: torch.Tensor, mask0: Optional[torch.Tensor] = None,
-                state: Optional[torch.Tensor] = None, return_state: bool = False, _lowres: bool = False, _head_fused: bool = False):
+                state: Optional[torch.Tensor] = None, return_state: bool = False, _lowres: bool = False, _head_fused: bool = False,
+                return_masks: bool = False):
+        """frames [B,T,C,H,W] -> logits [B,T,ncls,H,W] (stride-4 logits with _lowres), then the state after the last frame (return_state)
+        and, in the step mode (cfg.mask_feedback), the fed-back masks uint8 [B,T,H,W] (return_masks)."""
         if frames.dim() != 5:
             raise ValueError("frames must be [B,T,C,H,W]")
         cfg = self.cfg
         B, T, C, H, W = frames.shape
         Hh, Dk, Dv = cfg.heads, cfg.key_dim, cfg.value_dim
-        if cfg.mask_feedback:
-            logits, _, _, s_out = self._forward_feedback(frames, mask0, state, lowres=_lowres)
-            return (logits, s_out) if return_state else logits
+        if return_masks and not cfg.mask_feedback:
+            raise ValueError("return_masks: only the step mode (GDKVMConfig(mask_feedback=True)) feeds masks back")
+        feedback_train = cfg.mask_feedback and self.training and torch.is_grad_enabled()
+        if cfg.mask_feedback and not feedback_train:
+            logits, mask, _, s_out = self._forward_feedback(frames, mask0, state, lowres=_lowres)
+            return _outputs(logits, s_out, mask, return_state, return_masks)
         x = frames.reshape(B * T, C, H, W)
         dt = self.key_proj.weight.dtype
         if torch.is_autocast_enabled():
@@ -706,6 +721,9 @@ class GDKVM(nn.Module):
         _BN_COUNTED_BY_MODEL[0] = counted
         try:
             f4, f8, f16 = self.encoder(x)
+            if feedback_train:
+                logits, s_out, mask = self._feedback_train(f4, f8, f16, mask0, state, _lowres, (B, T, H, W))
+                return _outputs(logits, s_out, mask, return_state, return_masks)
             return self._after_encoder(f4, f8, f16, mask0, state, return_state, _lowres, (B, T, H, W), _head_fused)
         finally:
             _BN_COUNTED_BY_MODEL[0] = False
@@ -719,12 +737,10 @@ class GDKVM(nn.Module):
             v_t = value_proj(f_t) + mask_embed(pool(mask_t != 0))      (mask0 instead of mask_0 when given)
             S_t = GDR(S_{t-1}, K_t, v_t)               (_memory_scan with T = 1, no read-out)
         The batch is laid out TIME-MAJOR ([T*B, ...]: one transposed copy of the frames) so that every per-frame operand is a contiguous
-        block.  Returns (logits [B,T,ncls,.,.] | None when masks_only, mask uint8 [B,T,H,W], Dice counts [B,T,ncls,3] | None, S_T)."""
-        cfg = self.cfg
-        if torch.is_grad_enabled() and self.training:
-            raise NotImplementedError("GDKVMConfig(mask_feedback=True) is an inference mode (the predicted mask is an argmax): eval() / torch.no_grad()")
+        block.  Returns (logits [B,T,ncls,.,.] | None when masks_only, mask uint8 [B,T,H,W], Dice counts [B,T,ncls,3] | None, S_T).
+        Training mode under no_grad: the BatchNorm layers normalise with the statistics of what they see (the encoder all B*T frames, the
+        decoder frame t of the B clips) and update their buffers; GDKVM._feedback_pass is this loop without the buffer updates."""
         B, T, C, H, W = frames.shape
-        Hh, Dk, Dv = cfg.heads, cfg.key_dim, cfg.value_dim
         with torch.no_grad():
             x = frames.transpose(0, 1).reshape(T * B, C, H, W)                   # time-major copy
             dt = self.key_proj.weight.dtype
@@ -734,19 +750,32 @@ class GDKVM(nn.Module):
             else:
                 x = x.to(dtype=dt, memory_format=torch.channels_last)
             f4, f8, f16 = self.encoder(x)
-            h, w = f16.shape[-2:]
+            projected = self._project(f16, T, B, None)                          # q [T,B,N,Hh,Dk], alpha [T,B,Hh], ...
+            return self._feedback_loop(f4, f8, f16.shape[-2:], projected, (B, T, H, W), mask0, state, lowres, target, masks_only,
+                                       mask_out, counts_out)
+
+    def _feedback_loop(self, f4, f8, hw, projected, dims, mask0=None, state=None, lowres=False, target=None, masks_only=False,
+                       mask_out=None, counts_out=None, embedded0=False):
+        """The frame loop of _forward_feedback on TIME-MAJOR encoder outputs f4, f8 [T*B, ...] and projections (_project(f16, T, B)).
+        embedded0: frame 0's values already carry mask0's embedding (the training forward's projections)."""
+        cfg = self.cfg
+        B, T, H, W = dims
+        Hh, Dk, Dv = cfg.heads, cfg.key_dim, cfg.value_dim
+        dev = f4.device
+        with torch.no_grad():
+            h, w = hw
             N = h * w
-            p_tok, k_tok, q, v, alpha, beta, norms = self._project(f16, T, B, None)      # q [T,B,N,Hh,Dk], alpha [T,B,Hh], ...
+            p_tok, k_tok, q, v, alpha, beta, norms = projected
             v = v.reshape(T, B, N, Hh * Dv)
             k5 = k_tok.reshape(T, B, N, Hh, Dk)
             nrm = None if norms is None else norms.reshape(T, B * N, Hh, 2)
-            if frames.is_cuda:                   # (the kernels want 16-byte aligned operands: frame t's gate / norm rows must start on one)
+            if f4.is_cuda:                   # (the kernels want 16-byte aligned operands: frame t's gate / norm rows must start on one)
                 alpha, beta = _rows_aligned16(alpha), _rows_aligned16(beta)
                 nrm = None if nrm is None else _rows_aligned16(nrm)
-            S = torch.zeros((B, Hh, Dk, Dv), dtype=torch.float32, device=frames.device) if state is None else state.to(torch.float32)
+            S = torch.zeros((B, Hh, Dk, Dv), dtype=torch.float32, device=dev) if state is None else state.to(torch.float32)
             tgt = None if target is None else target.transpose(0, 1).contiguous()          # [T,B,H,W]
-            mask_tm = torch.empty((T, B, H, W), dtype=torch.uint8, device=frames.device)
-            counts_tm = None if target is None else torch.empty((T, B, cfg.num_classes, 3), dtype=torch.int32, device=frames.device)
+            mask_tm = torch.empty((T, B, H, W), dtype=torch.uint8, device=dev)
+            counts_tm = None if target is None else torch.empty((T, B, cfg.num_classes, 3), dtype=torch.int32, device=dev)
             lows = []
             for t in range(T):
                 sl = slice(t * B, (t + 1) * B)
@@ -776,7 +805,7 @@ class GDKVM(nn.Module):
                 if t == 0 and mask0 is not None:
                     m0 = F.adaptive_avg_pool2d(mask0.to(v_t.dtype), (h, w))
                     v_t = v_t + self._tokens(self.mask_embed(m0))
-                else:
+                elif not (t == 0 and embedded0):
                     v_t = self._embed_mask_(v_t, mask_tm[t], h, w)
                 kw = {} if nrm is None else {"norms": nrm[t]}
                 _, S = self._memory_scan(q[t].unsqueeze(1), k5[t].unsqueeze(1), v_t.reshape(B, 1, N, Hh, Dv), alpha[t].unsqueeze(1),
@@ -801,6 +830,59 @@ class GDKVM(nn.Module):
                 logits = low if lowres else F.interpolate(low.reshape(B * T, *low.shape[2:]), size=(H, W), mode="bilinear",
                                                            align_corners=False).reshape(B, T, -1, H, W)
             return logits, mask, counts, S
+
+    def _feedback_pass(self, f4, f8, hw, projected, dims, mask0, state):
+        """Pass 1 of the step-mode training forward: the fed-back masks uint8 [B,T,H,W] from _feedback_loop on THIS forward's encoder
+        outputs and projections (clip-major, with autograd), detached and copied time-major into buffers of its own (the loop adds the
+        embeddings to its values in place) -- the encoder does not run twice.  No autograd; BatchNorm layers use the statistics of what they
+        see and write no buffer (_FEEDBACK_PASS).  The inference weight packs the loop reads (KPFF, head, mask embedding) are rebuilt here
+        from the current weights: their keys cannot see a fused optimiser's step unless weights_changed() was called."""
+        B, T = dims[:2]
+
+        def tm(x):                                     # [B*T, ...] clip-major -> [T*B, ...] time-major, always a new buffer (channels_last stays so)
+            x = x.detach()
+            if x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last):
+                return tm(x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+            out = torch.empty((T, B) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+            out.copy_(x.unflatten(0, (B, T)).transpose(0, 1))
+            return out.flatten(0, 1)
+
+        p_tok, k_tok, q, v, alpha, beta, norms = projected
+        assert norms is None                           # (only the inference projections, ops.proj_gates, come with norms)
+        proj_tm = (tm(p_tok), tm(k_tok), tm(q.flatten(0, 1)).unflatten(0, (T, B)), tm(v.flatten(0, 1)).unflatten(0, (T, B)),
+                   tm(alpha.flatten(0, 1)).unflatten(0, (T, B)), tm(beta.flatten(0, 1)).unflatten(0, (T, B)), None)
+        for name in ("_kpff_pack", "_mask_w32"):
+            self.__dict__.pop(name, None)
+        self.decoder.__dict__.pop("_head_w32", None)
+        _FEEDBACK_PASS[0] = True
+        try:
+            _, mask, _, _ = self._feedback_loop(tm(f4), tm(f8), hw, proj_tm, dims, None, None if state is None else state.detach(),
+                                                masks_only=True, embedded0=mask0 is not None)
+        finally:
+            _FEEDBACK_PASS[0] = False
+        return mask
+
+    def _feedback_train(self, f4, f8, f16, mask0, state, lowres, dims):
+        """The training forward of the step mode (cfg.mask_feedback, training mode, grad enabled) after the encoder: (logits, S_T, masks).
+        The mask fed back for frame t is an argmax, piecewise constant in every weight, so the exact gradient is the one with the masks
+        held fixed -- and with the masks fixed the recurrence IS the whole-clip scan on the values v + e (the scan reads before it writes):
+          pass 1 (_feedback_pass, no autograd): the per-frame loop gives the masks m [B,T,H,W];
+          pass 2: the ordinary training forward on v' = v + pool(m != 0) (x) mask_embed (ops.mask_embed: mask_embed.weight gets its true
+                  gradient through it; frame 0 keeps mask0's embedding instead when mask0 is given).
+        The returned logits are pass 2's.  They differ from pass 1's by the read-out kernel (the scan's against gdkvm_lkva_read) and by the
+        decoder's BatchNorm statistics (the whole batch against one frame of every clip)."""
+        cfg = self.cfg
+        B, T, H, W = dims
+        Hh, Dv = cfg.heads, cfg.value_dim
+        h, w = f16.shape[-2:]
+        projected = self._project(f16, B, T, mask0)
+        mask = self._feedback_pass(f4, f8, (h, w), projected, dims, mask0, state)
+        p_tok, k_tok, q, v, alpha, beta, norms = projected
+        fed = mask if mask0 is None else torch.cat([torch.zeros_like(mask[:, :1]), mask[:, 1:]], 1)
+        v = ops.mask_embed(v.reshape(B * T, h * w, Hh * Dv), fed.reshape(B * T, H, W), self.mask_embed.weight, h, w)
+        logits, s_out = self._after_projection(f4, f8, f16, (p_tok, k_tok, q, v.reshape(B, T, h * w, Hh, Dv), alpha, beta, norms), state,
+                                               True, lowres, dims)
+        return logits, s_out, mask
 
     def _after_encoder(self, f4, f8, f16, mask0, state, return_state, _lowres, dims, _head_fused=False):
         cfg = self.cfg
@@ -909,7 +991,8 @@ class GDKVM(nn.Module):
             m = F.adaptive_avg_pool2d(mask0.to(v.dtype), (h, w))
             me = self._tokens(self.mask_embed(m))                                # [B,N,Hh*Dv]
             v = torch.cat([v[:, :1] + me.unsqueeze(1), v[:, 1:]], 1)
-        keep_mask_embed = mask0 is None and torch.is_grad_enabled() and self.mask_embed.weight.requires_grad
+        # (the step mode's training forward adds mask_embed to every frame's values itself: _feedback_train)
+        keep_mask_embed = mask0 is None and torch.is_grad_enabled() and self.mask_embed.weight.requires_grad and not cfg.mask_feedback
         v = v.reshape(B, T, N, Hh, Dv)
         v8 = 8 if p_tok.dtype == torch.bfloat16 else 4
         g_lanes = p_tok.shape[-1] // v8
@@ -1100,6 +1183,12 @@ class GDKVM(nn.Module):
             remapped[key] = val
         self.invalidate_packed_weights()
         return super().load_state_dict(remapped, strict=strict, **kw)
+
+
+def _outputs(logits, s_out, mask, return_state: bool, return_masks: bool):
+    """GDKVM.forward's result: logits, then the state (return_state), then the fed-back masks (return_masks)."""
+    out = (logits,) + ((s_out,) if return_state else ()) + ((mask,) if return_masks else ())
+    return out if len(out) > 1 else logits
 
 
 def _packs_held(model: "GDKVM"):

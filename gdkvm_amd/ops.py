@@ -50,6 +50,8 @@ SIGNATURES = {
     "gdkvm_scan_fwd_normalizer": (_i, [_vp] * 11 + [_sz] + [_i] * 9 + [ctypes.c_float, _vp]),
     "gdkvm_lkva_read": (_i, [_vp] * 4 + [_i] * 7 + [_vp]),
     "gdkvm_mask_embed_add": (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
+    "gdkvm_mask_embed_wgrad_workspace_bytes": (_sz, [_i] * 4),
+    "gdkvm_mask_embed_wgrad": (_i, [_vp] * 4 + [_sz] + [_i] * 7 + [_vp]),
     "gdkvm_scan_train_workspace_bytes": (_sz, [_i] * 7),
     "gdkvm_scan_train_fwd": (_i, [_vp] * 9 + [_sz] + [_i] * 9 + [_vp]),
     "gdkvm_scan_train_bwd": (_i, [_vp] * 14 + [_sz] + [_i] * 9 + [_vp]),
@@ -330,6 +332,52 @@ def mask_embed_add_(v: torch.Tensor, mask: torch.Tensor, w_embed: torch.Tensor, 
                                       _io_dtype(v), _stream(dev))
     _check(rc, "gdkvm_mask_embed_add")
     return v
+
+
+def mask_embed_wgrad(mask: torch.Tensor, d_v: torch.Tensor, h: int, w: int, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gdkvm_mask_embed_wgrad: d_w fp32 [C] = sum over the token rows of adaptive_avg_pool(mask != 0) * d_v -- the weight gradient of
+    mask_embed_add_.  mask uint8 [F,H,W], d_v [F, h*w, C] f32|bf16; workspace: uint8 of at least
+    gdkvm_mask_embed_wgrad_workspace_bytes(F, h, w, C) bytes (allocated here when None)."""
+    lib = load()
+    if d_v.dim() != 3 or mask.dim() != 3 or mask.dtype != torch.uint8 or mask.shape[0] != d_v.shape[0] or d_v.shape[1] != h * w:
+        raise GdkvmError(f"mask_embed_wgrad: bad shapes d_v{tuple(d_v.shape)} mask{tuple(mask.shape)} {mask.dtype} tokens {h}x{w}")
+    F_, C = d_v.shape[0], d_v.shape[2]
+    dev = _dev(d_v, mask, workspace)
+    if workspace is None:
+        workspace = torch.empty(max(16, int(lib.gdkvm_mask_embed_wgrad_workspace_bytes(F_, h, w, C))), dtype=torch.uint8, device=dev)
+    dw = torch.empty(C, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.gdkvm_mask_embed_wgrad(_ptr(mask), _ptr(d_v), _ptr(dw), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                        F_, mask.shape[1], mask.shape[2], h, w, C, _io_dtype(d_v), _stream(dev))
+    _check(rc, "gdkvm_mask_embed_wgrad")
+    return dw
+
+
+class _MaskEmbedFunction(torch.autograd.Function):
+    """v' = v + adaptive_avg_pool(mask != 0) (x) w_embed, differentiable in v and w_embed (training in the step mode): forward
+    gdkvm_mask_embed_add on a copy of v, backward d_v = d_v' and d_w from gdkvm_mask_embed_wgrad.  The mask is a constant."""
+
+    @staticmethod
+    def forward(ctx, v, mask, weight, h, w):
+        out = v.clone(memory_format=torch.contiguous_format)
+        mask_embed_add_(out, mask, weight.detach().reshape(-1).float().contiguous(), h, w)
+        ctx.save_for_backward(mask)
+        ctx.meta = (h, w, weight.dtype, tuple(weight.shape), out.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (mask,) = ctx.saved_tensors
+        h, w, wdt, wshape, odt = ctx.meta
+        d_out = d_out.to(odt).contiguous()
+        dw = mask_embed_wgrad(mask, d_out, h, w) if ctx.needs_input_grad[2] else None
+        return d_out, None, (None if dw is None else dw.reshape(wshape).to(wdt)), None, None
+
+
+def mask_embed(v: torch.Tensor, mask: torch.Tensor, weight: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """v [F, h*w, C] + w_embed[c] * adaptive_avg_pool(mask != 0) per token, as a new tensor, differentiable in v and weight (C elements,
+    e.g. the mask_embed 1x1 convolution's [C,1,1,1] weight): _MaskEmbedFunction.  mask uint8 [F,H,W] (255 = unlabelled = background)."""
+    return _MaskEmbedFunction.apply(v, mask, weight, h, w)
 
 
 def scan_status(workspace: torch.Tensor, B: int, T: int, Hh: int, N: int, Dk: int, Dv: int, flags: int = 0) -> None:

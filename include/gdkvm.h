@@ -183,11 +183,20 @@ int gdkvm_scan_fwd_normalizer(const void* q, const void* k, const void* v, const
  *   gdkvm_mask_embed_add  v [BT, h*w, C] (io_dtype) += w_embed[c] * m, m = the mean over the token's adaptive-average-pool cell
  *                         (PyTorch's adaptive_avg_pool2d cells) of the foreground indicator of mask [BT, H, W] (uint8: class != 0;
  *                         255 = unlabelled counts as background): the first-frame-mask embedding of the module applied to a predicted
- *                         mask.  The write itself is gdkvm_scan_fwd with T == 1. */
+ *                         mask.  The write itself is gdkvm_scan_fwd with T == 1.
+ *   gdkvm_mask_embed_wgrad  the weight gradient of gdkvm_mask_embed_add (training in the step mode): d_w[c] (fp32 [C]) = the sum over
+ *                         the F*h*w token rows of m(f, n) * d_v[f, n, c], m the pooled indicator of mask [F, H, W] exactly as
+ *                         gdkvm_mask_embed_add computes it, d_v [F, h*w, C] (io_dtype; C a multiple of 8 for bf16, of 4 for f32, at most
+ *                         256 16-byte pieces).  fp32 accumulation; per-block partials in `workspace`
+ *                         (gdkvm_mask_embed_wgrad_workspace_bytes) added in a fixed order: deterministic, no float atomics.
+ *                         F == 0 writes zeros. */
 int gdkvm_lkva_read(const void* q, const float* norms, const float* s, void* r_out,
                     int B, int N, int Hh, int Dk, int Dv, int io_dtype, int flags, void* stream);
 int gdkvm_mask_embed_add(const uint8_t* mask, const float* w_embed, void* v, int BT, int H, int W, int h, int w, int C,
                          int io_dtype, void* stream);
+size_t gdkvm_mask_embed_wgrad_workspace_bytes(int F, int h, int w, int C);
+int gdkvm_mask_embed_wgrad(const uint8_t* mask, const void* d_v, float* d_w, void* workspace, size_t workspace_bytes,
+                           int F, int H, int W, int h, int w, int C, int io_dtype, void* stream);
 
 /* Row a7: backward of gdkvm_scan_fwd.  Inputs: the forward's inputs, its s_hist, its workspace exactly as the
  * forward left it, the gradients d_r [B,T,N,Hh,Dv] (io_dtype) and d_s_out [B,Hh,Dk,Dv] (fp32, may be NULL = 0).

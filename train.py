@@ -45,7 +45,7 @@ def main(argv=None):
     torch.manual_seed(cfg.seed)                                   # identical initial weights on every rank
 
     mcfg = GDKVMConfig(num_classes=cfg.data.num_classes, heads=cfg.model.heads, key_dim=cfg.model.key_dim,
-                       value_dim=cfg.model.value_dim, rule=cfg.model.rule)
+                       value_dim=cfg.model.value_dim, rule=cfg.model.rule, mask_feedback=cfg.model.mask_feedback)
     model = GDKVM(mcfg).train().to(dev).to(memory_format=torch.channels_last)
     step0, epoch0, opt_state = 0, None, None
     if args.resume:
