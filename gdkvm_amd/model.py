@@ -79,26 +79,75 @@ def weights_changed(model: Optional[nn.Module] = None) -> None:
     packs and its captured GraphedSegment (train_step / GraphedTrainStep pass the model they stepped); without an argument every model
     in the process is told (the process-wide epoch)."""
     inner = getattr(model, "module", model)
-    cell = None if inner is None else inner.__dict__.get("_epoch_cell")
-    if cell is None:
+    packs = None if inner is None else inner.__dict__.get("_packs")
+    if packs is None:
         _WEIGHTS_EPOCH[0] += 1
     else:
-        cell[0] += 1
+        packs.epoch += 1
 
 
-def _epoch_of(owner) -> Tuple[int, int]:
-    """(process-wide epoch, the owning model's epoch): GDKVM hands its ``_epoch_cell`` to the sub-modules that cache packs."""
-    cell = None if owner is None else owner.__dict__.get("_epoch_cell")
-    return (_WEIGHTS_EPOCH[0], 0 if cell is None else cell[0])
+class _Packs:
+    """Everything one model derives from its weights and keeps between calls -- the K/Q/V fragment pack, the fp32 gate, mask-embedding and
+    head weights, the KPFF bf16 pack, every FusedConv's fragment-ordered copy, segment_clip's captured graphs -- and the one rule by which
+    they are keyed, dropped and kept alive.  One instance per GDKVM, shared with the sub-modules that cache (`adopt`); a Decoder or FusedConv
+    outside a GDKVM makes its own (`_packs_of`).  A slot is a name (the model's own packs) or the caching sub-module itself.
+    A deep copy of the model gets an empty cache of its own, shared by the copy's sub-modules."""
+
+    def __init__(self):
+        self.epoch = 0              # this model's weights epoch: weights_changed(model)
+        self.drops = 0              # how often drop_all() ran
+        self.slots = {}             # slot -> (key, value)
+        self.graphs = {}            # GDKVM.segment_clip: what chose the kernels -> GraphedSegment | PipelinedClip (each with its .stamp)
+
+    def __deepcopy__(self, memo):
+        return _Packs()
+
+    def adopt(self, root: nn.Module) -> None:
+        """Hand this cache to `root` and to every sub-module of it that caches packs."""
+        root.__dict__["_packs"] = self
+        for m in root.modules():
+            if isinstance(m, (Decoder, FusedConv)):
+                m.__dict__["_packs"] = self
+
+    def stamp(self) -> Tuple[int, int, int]:
+        """What a captured graph remembers and compares before every replay: it reads the packs of capture time by address, so it is
+        valid while no weights epoch moved (weights_changed) and nothing was dropped."""
+        return (_WEIGHTS_EPOCH[0], self.epoch, self.drops)
+
+    def get(self, slot, tensors, extras, build):
+        """The value cached in `slot`, from build() when the key changed.  The key: the weights epochs (weights_changed: process-wide and
+        this model's), version counter AND storage address of EVERY source tensor, then the caller's `extras` (device, dtype, kernel choice).
+        In-place writes through ``.data`` (``p.data.copy_()``: EMA swaps, weight surgery) and fused optimiser steps bump no counter -- after
+        such a write call ``weights_changed(model)`` or ``GDKVM.invalidate_packed_weights()`` (load_state_dict / .to() / a train() / eval()
+        mode CHANGE / fuse_for_inference() do the latter themselves; train_step / GraphedTrainStep the former).
+        A build() that raises leaves the slot as it was."""
+        key = (_WEIGHTS_EPOCH[0], self.epoch) + tuple((t._version, t.data_ptr()) for t in tensors) + tuple(extras)
+        ent = self.slots.get(slot)
+        if ent is None or ent[0] != key:
+            ent = self.slots[slot] = (key, build())
+        return ent[1]
+
+    def drop(self, *slots) -> None:
+        for slot in slots:
+            self.slots.pop(slot, None)
+
+    def drop_all(self) -> None:
+        """Graphs captured over the model hold the packs they read (`held`) and compare `stamp`: a replay after this raises instead of
+        computing with the weights of capture time."""
+        self.slots.clear()
+        self.graphs.clear()
+        self.drops += 1
+
+    def held(self) -> list:
+        """Every cached value right now (what a captured graph reads by address and must keep alive)."""
+        return [value for _, value in self.slots.values()]
 
 
-def _wkey(owner, *tensors):
-    """Cache key of a weight pack: the weights epochs (weights_changed: process-wide and the owning model's), and version counter AND
-    storage address of EVERY source tensor.
-    In-place writes through ``.data`` (``p.data.copy_()``: EMA swaps, weight surgery) and fused optimiser steps bump no counter -- after
-    such a write call ``weights_changed(model)`` or ``GDKVM.invalidate_packed_weights()`` (load_state_dict / .to() / a train() / eval()
-    mode CHANGE / fuse_for_inference() do the latter themselves; train_step / GraphedTrainStep the former)."""
-    return _epoch_of(owner) + tuple((t._version, t.data_ptr()) for t in tensors)
+def _packs_of(module: nn.Module) -> _Packs:
+    packs = module.__dict__.get("_packs")
+    if packs is None:
+        packs = module.__dict__["_packs"] = _Packs()
+    return packs
 
 
 # Convolutions the hand-written kernels do not serve (other `widths`, odd sizes, fp32 inference) run on the framework's library: allowed
@@ -334,14 +383,11 @@ class Decoder(nn.Module):
                 and hd.stride == (1, 1) and hd.padding == (0, 0) and hd.groups == 1 and hd.bias is not None and y.shape[1] % v == 0
                 and g <= 64 and g & (g - 1) == 0 and hd.out_channels <= g and y.is_contiguous(memory_format=torch.channels_last)):
             # 1x1 convolution + bias straight into the NCHW planes the argmax / loss kernels read (ops.head_logits): one pass
-            key = _wkey(self, hd.weight, hd.bias) + (y.device,)
-            cache = getattr(self, "_head_w32", None)
-            if cache is None or cache[0] != key:
-                cache = (key, hd.weight.detach().reshape(hd.out_channels, -1).float().contiguous(), hd.bias.detach().float().contiguous())
-                self._head_w32 = cache
+            w32, b32 = _packs_of(self).get(self, (hd.weight, hd.bias), (y.device,), lambda: (
+                hd.weight.detach().reshape(hd.out_channels, -1).float().contiguous(), hd.bias.detach().float().contiguous()))
             if head_fused and size is None:
-                return HeadFeature(y, cache[1], cache[2])
-            x = ops.head_logits(y, cache[1], cache[2])
+                return HeadFeature(y, w32, b32)
+            x = ops.head_logits(y, w32, b32)
         elif torch.is_grad_enabled() and ops.head_served(y, hd):
             # training: gdkvm_head_logits forward, gdkvm_head_bwd backward (one pass, fixed summation order) -- the library's bf16 weight
             # gradient for this layer accumulates atomically and differed by several bf16 ulps from run to run
@@ -390,13 +436,9 @@ class FusedConv(nn.Module):
 
     def _packed(self, device, igemm: bool = False):
         """The fragment-ordered copy of the weights (ops.conv3x3_pack_weights, or ops.conv_igemm_pack_weights for the general
-        kernel), kept until the weights change (_wkey)."""
-        key = _wkey(self, self.conv.weight) + (device, igemm)
-        ent = self.__dict__.get("_wpack")
-        if ent is None or ent[0] != key:
-            ent = (key, (ops.conv_igemm_pack_weights if igemm else ops.conv3x3_pack_weights)(self.conv.weight))
-            self.__dict__["_wpack"] = ent
-        return ent[1]
+        kernel), kept until the weights change (_Packs.get)."""
+        pack = ops.conv_igemm_pack_weights if igemm else ops.conv3x3_pack_weights
+        return _packs_of(self).get(self, (self.conv.weight,), (device, igemm), lambda: pack(self.conv.weight))
 
     def with_down(self, x, down):
         """(self(x), down(x)) from one launch of the general kernel (ops.conv_down_bias_act) when this is a strided 3x3 layer and
@@ -574,37 +616,20 @@ class GDKVM(nn.Module):
         nn.init.constant_(self.decay_proj.bias, 2.0)                     # sigmoid(2) ~ 0.88: remember by default
         self.kpff = KPFFParams(Hh * Dk, Hh * Dv, Cp)
         self.decoder = Decoder(Cp, cfg.widths, cfg.num_classes)
-        # this model's weights epoch (weights_changed(model)), shared with every sub-module that caches a weight pack
-        self.__dict__["_epoch_cell"] = [0]
-        self._share_epoch_cell()
-
-    def _share_epoch_cell(self):
-        cell = self.__dict__["_epoch_cell"]
-        for m in self.modules():
-            if isinstance(m, (Decoder, FusedConv)):
-                m.__dict__["_epoch_cell"] = cell
+        _Packs().adopt(self)                                             # one pack cache for this model and its caching sub-modules
 
     # ------------------------------------------------------------------ packed-weight caches of the inference build
     def invalidate_packed_weights(self):
         """Drop the weight packs the inference forward keeps between calls (K/Q/V fragment pack, fp32 gate and head weights,
-        KPFF bf16 pack, every FusedConv's fragment-ordered weight copy).  They are keyed on every source tensor's version counter and address (`_wkey`), which catches
+        KPFF bf16 pack, every FusedConv's fragment-ordered weight copy) and segment_clip's captured graphs.  They are keyed on every source
+        tensor's version counter and address (`_Packs.get`), which catches
         optimiser steps, ``load_state_dict`` and re-binding; an in-place write through ``.data`` changes neither, so code that
         does one must call this.  Called by load_state_dict(), _apply() (.to / .cuda / .half ...), train() and
         fuse_for_inference()."""
-        for name in ("_qkv_pack", "_gate_w32", "_kpff_pack", "_clip_graphs", "_mask_w32"):
-            self.__dict__.pop(name, None)
-        # graphs captured over this module (GraphedSegment, GraphedTrainStep) hold the packs they read and compare this counter: a replay
-        # after the packs were dropped raises instead of convolving with the weights of capture time
-        self.__dict__["_pack_epoch"] = self.__dict__.get("_pack_epoch", 0) + 1
+        packs = self.__dict__.get("_packs")                 # (None while __init__ is still running)
+        if packs is not None:
+            packs.drop_all()
         ops.drop_train_packs(self.__dict__.pop("_train_pack_weights", None) or ())     # (the training step's per-weight packs, ops.conv3x3_train_packs)
-        if "_modules" not in self.__dict__:
-            return
-        dec = self._modules.get("decoder")
-        if dec is not None:
-            dec.__dict__.pop("_head_w32", None)
-        for m in self.modules():                            # the fragment-ordered weight copies of the fused convolutions
-            if isinstance(m, FusedConv):
-                m.__dict__.pop("_wpack", None)
 
     def _apply(self, fn, recurse=True):
         self.invalidate_packed_weights()
@@ -650,32 +675,43 @@ class GDKVM(nn.Module):
 
     def _embed_mask_(self, v, mask, h, w):
         """v [B,N,Hh*Dv] += mask_embed(adaptive_avg_pool(mask != 0)) in place; mask uint8 [B,H,W] (a predicted mask)."""
-        key = _wkey(self, self.mask_embed.weight) + (v.device,)
-        cache = self.__dict__.get("_mask_w32")
-        if cache is None or cache[0] != key:
-            cache = (key, self.mask_embed.weight.detach().reshape(-1).float().contiguous())
-            self.__dict__["_mask_w32"] = cache
-        return ops.mask_embed_add_(v, mask, cache[1], h, w)
+        w32 = self._packs.get("mask_embed", (self.mask_embed.weight,), (v.device,),
+                              lambda: self.mask_embed.weight.detach().reshape(-1).float().contiguous())
+        return ops.mask_embed_add_(v, mask, w32, h, w)
 
     def _fuse(self, local, glob, pixel, h, w):
         p = self.kpff
         if torch.is_grad_enabled() and (pixel.requires_grad or p.wa.requires_grad):
             return ops.kpff(local, glob, pixel, p.wa, p.ba, p.wl, p.wg, h, w)
-        # inference: keep the bf16 weight pack of the previous call while the weight tensors are unchanged
-        key = _wkey(self, p.wa, p.ba, p.wl, p.wg) + (local.dtype, local.device)
-        cache = getattr(self, "_kpff_pack", None)
-        hit = cache is not None and cache[0] == key
-        ws = cache[1] if hit else torch.empty(ops.load().gdkvm_kpff_workspace_bytes(local.shape[-1], glob.shape[-1], pixel.shape[-1],
-                                                                             ops._io_dtype(local)), dtype=torch.uint8, device=local.device)
-        out = ops.kpff_fwd(local, glob, pixel, p.wa, p.ba, p.wl, p.wg, h, w, workspace=ws, packed=hit)
-        self._kpff_pack = (key, ws)
-        return out
+        # inference: keep the bf16 weight pack of the previous call while the weight tensors are unchanged.  A miss packs into a new
+        # workspace and computes in ONE launch (packed=False), and the workspace is cached only once that launch was made
+        missed = []
+
+        def pack_and_run():
+            ws = torch.empty(ops.load().gdkvm_kpff_workspace_bytes(local.shape[-1], glob.shape[-1], pixel.shape[-1], ops._io_dtype(local)),
+                             dtype=torch.uint8, device=local.device)
+            missed.append(ops.kpff_fwd(local, glob, pixel, p.wa, p.ba, p.wl, p.wg, h, w, workspace=ws, packed=False))
+            return ws
+
+        ws = self._packs.get("kpff", (p.wa, p.ba, p.wl, p.wg), (local.dtype, local.device), pack_and_run)
+        return missed[0] if missed else ops.kpff_fwd(local, glob, pixel, p.wa, p.ba, p.wl, p.wg, h, w, workspace=ws, packed=True)
 
     # ------------------------------------------------------------------------------------------ forward
     @staticmethod
     def _tokens(x):
         """[BT,C,h,w] conv output -> [BT, h*w, C] token-major view (free when x is channels_last)."""
         return x.permute(0, 2, 3, 1).reshape(x.shape[0], x.shape[2] * x.shape[3], x.shape[1]).contiguous()
+
+    def _cast_frames(self, x, dt=None, train_stem: bool = False):
+        """Frames [N,C,H,W] in the dtype the encoder runs in (dt; the weights' when None): NCHW as they are where the stem kernel reads NCHW
+        frames itself -- the inference build's, or with train_stem (forward() alone) the training build's under grad -- else channels_last."""
+        dt = self.key_proj.weight.dtype if dt is None else dt
+        stem0 = self.encoder.stem[0]
+        if x.is_cuda and ((isinstance(stem0, FusedConvPool) and getattr(stem0, "w_s2d", None) is not None)
+                          or (train_stem and torch.is_grad_enabled() and isinstance(stem0, nn.Conv2d) and dt == torch.bfloat16
+                              and ops.stem_conv_served(x, stem0))):
+            return x.to(dt)
+        return x.to(dtype=dt, memory_format=torch.channels_last)                 # cast + NHWC in one pass
 
     def forward(self, frames: torch.Tensor, mask0: Optional[torch.Tensor] = None,
                 state: Optional[torch.Tensor] = None, return_state: bool = False, _lowres: bool = False, _head_fused: bool = False,
@@ -697,12 +733,7 @@ class GDKVM(nn.Module):
         dt = self.key_proj.weight.dtype
         if torch.is_autocast_enabled():
             dt = torch.get_autocast_dtype(x.device.type) if x.is_cuda else x.dtype
-        stem0 = self.encoder.stem[0]
-        if x.is_cuda and ((isinstance(stem0, FusedConvPool) and getattr(stem0, "w_s2d", None) is not None)
-                          or (torch.is_grad_enabled() and isinstance(stem0, nn.Conv2d) and dt == torch.bfloat16 and ops.stem_conv_served(x, stem0))):
-            x = x.to(dt)                                                         # (the stem kernels read NCHW frames themselves)
-        else:
-            x = x.to(dtype=dt, memory_format=torch.channels_last)                # cast + NHWC in one pass
+        x = self._cast_frames(x, dt, train_stem=True)
         if self.training and x.is_cuda and torch.is_grad_enabled() and dt == torch.bfloat16:
             # the forward and data-gradient packs of every stride-1 3x3 layer's weights, ONE launch for the step (ops.conv3x3 finds them;
             # per layer it was a cast, a pack and, in the backward, a second pack)
@@ -743,13 +774,7 @@ class GDKVM(nn.Module):
         B, T, C, H, W = frames.shape
         with torch.no_grad():
             x = frames.transpose(0, 1).reshape(T * B, C, H, W)                   # time-major copy
-            dt = self.key_proj.weight.dtype
-            stem0 = self.encoder.stem[0]
-            if x.is_cuda and isinstance(stem0, FusedConvPool) and getattr(stem0, "w_s2d", None) is not None:
-                x = x.to(dt)
-            else:
-                x = x.to(dtype=dt, memory_format=torch.channels_last)
-            f4, f8, f16 = self.encoder(x)
+            f4, f8, f16 = self.encoder(self._cast_frames(x))
             projected = self._project(f16, T, B, None)                          # q [T,B,N,Hh,Dk], alpha [T,B,Hh], ...
             return self._feedback_loop(f4, f8, f16.shape[-2:], projected, (B, T, H, W), mask0, state, lowres, target, masks_only,
                                        mask_out, counts_out)
@@ -851,9 +876,7 @@ class GDKVM(nn.Module):
         assert norms is None                           # (only the inference projections, ops.proj_gates, come with norms)
         proj_tm = (tm(p_tok), tm(k_tok), tm(q.flatten(0, 1)).unflatten(0, (T, B)), tm(v.flatten(0, 1)).unflatten(0, (T, B)),
                    tm(alpha.flatten(0, 1)).unflatten(0, (T, B)), tm(beta.flatten(0, 1)).unflatten(0, (T, B)), None)
-        for name in ("_kpff_pack", "_mask_w32"):
-            self.__dict__.pop(name, None)
-        self.decoder.__dict__.pop("_head_w32", None)
+        self._packs.drop("kpff", "mask_embed", self.decoder)
         _FEEDBACK_PASS[0] = True
         try:
             _, mask, _, _ = self._feedback_loop(tm(f4), tm(f8), hw, proj_tm, dims, None, None if state is None else state.detach(),
@@ -885,11 +908,7 @@ class GDKVM(nn.Module):
         return logits, s_out, mask
 
     def _after_encoder(self, f4, f8, f16, mask0, state, return_state, _lowres, dims, _head_fused=False):
-        cfg = self.cfg
-        B, T, H, W = dims
-        Hh, Dk, Dv = cfg.heads, cfg.key_dim, cfg.value_dim
-        h, w = f16.shape[-2:]
-        N = h * w
+        B, T = dims[:2]
         return self._after_projection(f4, f8, f16, self._project(f16, B, T, mask0), state, return_state, _lowres, dims, _head_fused)
 
     def _after_projection(self, f4, f8, f16, projected, state, return_state, _lowres, dims, _head_fused=False):
@@ -901,10 +920,8 @@ class GDKVM(nn.Module):
         h, w = f16.shape[-2:]
         N = h * w
         p_tok, k_tok, q, v, alpha, beta, norms = projected
-        if norms is not None and not cfg.normalizer:
-            r, s_out = self._memory_scan(q, k_tok.reshape(B, T, N, Hh, Dk), v, alpha, beta, state, norms=norms)
-        else:
-            r, s_out = self._memory_scan(q, k_tok.reshape(B, T, N, Hh, Dk), v, alpha, beta, state)
+        kw = {"norms": norms} if norms is not None and not cfg.normalizer else {}     # (_memory_scan is an overridable hook)
+        r, s_out = self._memory_scan(q, k_tok.reshape(B, T, N, Hh, Dk), v, alpha, beta, state, **kw)
         fused = self._fuse(k_tok, r.reshape(B * T, N, Hh * Dv), p_tok, h, w)       # [BT,N,Cp]
         fmap = fused.reshape(B * T, h, w, -1).permute(0, 3, 1, 2)                  # channels_last view, no copy
         logits = self.decoder(fmap, f8, f4, None if _lowres else (H, W), head_fused=_head_fused and _lowres)
@@ -942,6 +959,20 @@ class GDKVM(nn.Module):
                 return ops.token_linear(tok2d, wp, bp)[:, :conv.out_channels]
             return F.linear(tok2d, w2, conv.bias)
 
+        # what the inference packs are built from (self._packs): the K / Q / V fragment pack with its fp32 bias, the fp32 gate weights
+        projs = (self.key_proj, self.query_proj, self.value_proj)
+        gp, dp = self.gate_proj, self.decay_proj
+        qkv_src = tuple(t for c in projs for t in (c.weight, c.bias))
+        gate_src = (gp.weight, gp.bias, dp.weight, dp.bias)
+
+        def qkv_pack():
+            w_all = torch.cat([c.weight.detach().reshape(c.out_channels, -1).float() for c in projs], 0)
+            b_all = torch.cat([c.bias.detach().float() for c in projs], 0).contiguous()
+            return ops.pack_rows_weight(w_all), b_all
+
+        def gates32():
+            return tuple(t.detach().float().contiguous() for t in (gp.weight.reshape(Hh, -1), gp.bias, dp.weight, dp.bias))
+
         wk, wq, wv = Hh * Dk, Hh * Dk, Hh * Dv
         norms = beta = alpha = beta_stacked = alpha_stacked = None
         cp8 = tok2d.shape[1] // 8
@@ -949,31 +980,15 @@ class GDKVM(nn.Module):
                       and tok2d.shape[1] % 32 == 0 and tok2d.shape[1] <= 512 and wk % 16 == 0 and wv % 16 == 0)
         if infer_bf16 and Dk == ops.KERNEL_DK and cp8 & (cp8 - 1) == 0:
             # ONE launch for everything derived from the pixel feature: K / Q / V, both gate logits, the key / query norms
-            projs = (self.key_proj, self.query_proj, self.value_proj)
-            gp, dp = self.gate_proj, self.decay_proj
-            key = _wkey(self, *(t for c in projs for t in (c.weight, c.bias)), gp.weight, gp.bias, dp.weight, dp.bias) + (tok2d.device,)
-            cache = getattr(self, "_qkv_pack", None)
-            if cache is None or cache[0] != key:
-                w_all = torch.cat([c.weight.detach().reshape(c.out_channels, -1).float() for c in projs], 0)
-                b_all = torch.cat([c.bias.detach().float() for c in projs], 0).contiguous()
-                gw = tuple(t.detach().float().contiguous() for t in (gp.weight.reshape(Hh, -1), gp.bias, dp.weight, dp.bias))
-                cache = (key, ops.pack_rows_weight(w_all), b_all, gw)
-                self._qkv_pack = cache
-            (k2d, q2d, v2d), (beta, alpha), norms = ops.proj_gates(p_tok, cache[1], cache[2], *cache[3], Hh, Dk, Dv)
+            w_pack, b_all, gw = self._packs.get("qkv", qkv_src + gate_src, (tok2d.device,), lambda: qkv_pack() + (gates32(),))
+            (k2d, q2d, v2d), (beta, alpha), norms = ops.proj_gates(p_tok, w_pack, b_all, *gw, Hh, Dk, Dv)
             beta, alpha = beta.reshape(B, T, N, Hh), alpha.reshape(B, T, Hh)
             k_tok, q, v = k2d.reshape(B * T, N, wk), q2d.reshape(B, T, N, Hh, Dk), v2d.reshape(B, T, N, wv)
         elif infer_bf16:
             # the three projections in ONE pass over the tokens (ops.proj_rows: token tile in LDS, weights streamed in MFMA
             # fragment order); the packed weight is rebuilt only when a projection's parameters change
-            projs = (self.key_proj, self.query_proj, self.value_proj)
-            key = _wkey(self, *(t for c in projs for t in (c.weight, c.bias))) + (tok2d.device,)
-            cache = getattr(self, "_qkv_pack", None)
-            if cache is None or cache[0] != key:
-                w_all = torch.cat([c.weight.detach().reshape(c.out_channels, -1).float() for c in projs], 0)
-                b_all = torch.cat([c.bias.detach().float() for c in projs], 0).contiguous()
-                cache = (key, ops.pack_rows_weight(w_all), b_all)
-                self._qkv_pack = cache
-            k2d, q2d, v2d = ops.proj_rows(tok2d, cache[1], cache[2], (wk, wq, wv))
+            w_pack, b_all = self._packs.get("qkv", qkv_src, (tok2d.device,), qkv_pack)
+            k2d, q2d, v2d = ops.proj_rows(tok2d, w_pack, b_all, (wk, wq, wv))
             k_tok, q, v = k2d.reshape(B * T, N, wk), q2d.reshape(B, T, N, Hh, Dk), v2d.reshape(B, T, N, wv)
         elif train_gpu and tok2d.dtype == torch.bfloat16:
             # training: the four projections of the feature as ONE stacked product forward and two backward (ops.token_projections)
@@ -1001,13 +1016,7 @@ class GDKVM(nn.Module):
         elif (p_tok.is_cuda and not train_gpu and not torch.is_grad_enabled() and p_tok.dtype in (torch.bfloat16, torch.float32)
                 and p_tok.shape[-1] % v8 == 0 and g_lanes <= 64 and g_lanes & (g_lanes - 1) == 0):
             # both gate logits in one pass over the feature (token mean + two N = 1 projections + casts as framework ops: 6 launches)
-            gp, dp = self.gate_proj, self.decay_proj
-            key = _wkey(self, gp.weight, gp.bias, dp.weight, dp.bias) + (p_tok.device,)
-            cache = getattr(self, "_gate_w32", None)
-            if cache is None or cache[0] != key:
-                cache = (key, tuple(t.detach().float().contiguous() for t in (gp.weight.reshape(Hh, -1), gp.bias, dp.weight, dp.bias)))
-                self._gate_w32 = cache
-            beta, alpha = ops.gate_logits(p_tok, *cache[1])
+            beta, alpha = ops.gate_logits(p_tok, *self._packs.get("gates", gate_src, (p_tok.device,), gates32))
             beta, alpha = beta.reshape(B, T, N, Hh), alpha.reshape(B, T, Hh)
         else:
             beta = beta_stacked if beta_stacked is not None else proj(self.gate_proj).float().reshape(B, T, N, Hh)
@@ -1058,7 +1067,7 @@ class GDKVM(nn.Module):
             fused.conv, fused.epi, fused.relu = stem[0].conv, stem[0].epi, True
             stem = nn.Sequential(fused.enable_s2d())
         self.encoder.stem = stem
-        self._share_epoch_cell()
+        self._packs.adopt(self)
         return self
 
     @torch.no_grad()
@@ -1099,14 +1108,7 @@ class GDKVM(nn.Module):
         if self.training or self.cfg.mask_feedback:
             raise RuntimeError("_encode_project serves the inference forward in scan mode")
         B, T, C, H, W = frames.shape
-        x = frames.reshape(B * T, C, H, W)
-        dt = self.key_proj.weight.dtype
-        stem0 = self.encoder.stem[0]
-        if x.is_cuda and isinstance(stem0, FusedConvPool) and getattr(stem0, "w_s2d", None) is not None:
-            x = x.to(dt)                                                         # (as forward(): the stem kernels read NCHW frames themselves)
-        else:
-            x = x.to(dtype=dt, memory_format=torch.channels_last)
-        f4, f8, f16 = self.encoder(x)
+        f4, f8, f16 = self.encoder(self._cast_frames(frames.reshape(B * T, C, H, W)))
         return f4, f8, f16, self._project(f16, B, T, None)
 
     def _segment_from_features(self, feats, state, dims, target=None):
@@ -1133,23 +1135,21 @@ class GDKVM(nn.Module):
             # module): the same kernels and the same bits as the loop below, without the host's launch calls between them -- a long clip is
             # many short forwards, which is where a slow host shows (round 4: 17.5 against 12.0 ms per 1024 frames between two boxes)
             cfg = self.cfg
-            # (keyed on everything the captured kernels were chosen by: the shape, the recurrence and its segmenting, and the weight /
-            # pack epochs -- a graph reads the weight packs of capture time; invalidate_packed_weights() drops the whole cache)
-            key = (B, chunk_frames) + tuple(frames.shape[2:]) + (frames.dtype, target is not None, frames.device, cfg.rule, cfg.scan_segments,
-                                                                   _epoch_of(self), self.__dict__.get("_pack_epoch", 0))
-            cache = self.__dict__.setdefault("_clip_graphs", {})
-            for old in [k_ for k_ in cache if k_[:-3] == key[:-2] and k_[:-1] != key]:
-                del cache[old]                              # the same shape under older weights: never replayed again
             pipelined = (_CLIP_PIPELINE and not cfg.mask_feedback and T // chunk_frames >= 2
                          and (state is None or state.shape[-1] == cfg.value_dim + int(cfg.normalizer)))
-            key = key + (pipelined,)
-            if key not in cache:
+            # (keyed on everything the captured kernels were chosen by: the shape, the recurrence and its segmenting; a graph reads the
+            # weight packs of capture time, so one captured under an older stamp is replaced; invalidate_packed_weights() drops them all)
+            key = (B, chunk_frames) + tuple(frames.shape[2:]) + (frames.dtype, target is not None, frames.device, cfg.rule, cfg.scan_segments,
+                                                                   pipelined)
+            g = self._packs.graphs.get(key)
+            if g is None or g.stamp != self._packs.stamp():
+                f0, tg0 = frames[:, :chunk_frames].clone(), None if target is None else target[:, :chunk_frames].clone()
                 if pipelined:
-                    cache[key] = PipelinedClip(self, frames[:, :chunk_frames].clone(), None if target is None else target[:, :chunk_frames].clone())
+                    g = PipelinedClip(self, f0, tg0)
                 else:
                     s0 = torch.zeros((B, cfg.heads, cfg.key_dim, cfg.value_dim), dtype=torch.float32, device=frames.device)
-                    cache[key] = GraphedSegment(self, frames[:, :chunk_frames].clone(), None if target is None else target[:, :chunk_frames].clone(), state=s0)
-            g = cache[key]
+                    g = GraphedSegment(self, f0, tg0, state=s0)
+                self._packs.graphs[key] = g
             if pipelined:
                 return g(frames, target, state)
             cur = torch.zeros_like(g.state) if state is None else state
@@ -1192,17 +1192,31 @@ def _outputs(logits, s_out, mask, return_state: bool, return_masks: bool):
 
 
 def _packs_held(model: "GDKVM"):
-    """Every packed-weight tensor the module caches hold right now (what a captured graph reads by address)."""
-    held = [model.__dict__.get(n) for n in ("_qkv_pack", "_gate_w32", "_kpff_pack", "_mask_w32")]
-    dec = model._modules.get("decoder")
-    if dec is not None:
-        held.append(dec.__dict__.get("_head_w32"))
-    for m in model.modules():
-        if isinstance(m, FusedConv):
-            held.append(m.__dict__.get("_wpack"))
-    for p in model.parameters():
-        held.append(p.__dict__.get("_gdkvm_train_packs"))
-    return [h for h in held if h is not None]
+    """Every packed-weight tensor kept for the model right now (what a captured graph reads by address): the inference packs of its cache and
+    the training step's per-parameter packs (ops.conv3x3_train_packs)."""
+    train = [p.__dict__.get("_gdkvm_train_packs") for p in model.parameters()]
+    return model._packs.held() + [t for t in train if t is not None]
+
+
+def _warm_up(device, warmup: int, step) -> None:
+    """`warmup` (at least one) eager calls of step() on a side stream, joined and synchronised: what a capture must not meet -- weight packs
+    and workspaces being built, kernel attributes set, solvers chosen, optimiser state created -- happens here."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(max(1, warmup)):
+            step()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+
+
+def _capture_mode(thread_local: bool = False, **kw) -> dict:
+    """Keyword arguments of torch.cuda.graph (`kw`: the caller's own, e.g. pool).  With a process group alive its watchdog THREAD may poll
+    events of earlier collectives while this thread captures: under the default "global" capture mode its hipEventQuery aborts the process with
+    "operation not permitted when stream is capturing" (measured round 5 in train.GraphedTrainStep) -- so only this thread is policed."""
+    if thread_local or (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        kw["capture_error_mode"] = "thread_local"
+    return kw
 
 
 class GraphedSegment:
@@ -1246,23 +1260,16 @@ class GraphedSegment:
                              f"boundary for {B} clips x {frames.shape[1]} frames ({model.cfg.num_classes} classes); use streams=1")
         self.streams = streams
         kw = {} if state is None else {"state": state, "return_state": True}
+        def eager():
+            model.segment(self.frames, self.target, **kw)
+            if streams > 1:                                # (the groups' shapes too: nothing may be built or sized inside the capture)
+                kw_w = {} if state is None else {"state": state[: B // streams], "return_state": True}
+                model.segment(self.frames[: B // streams], None if target is None else self.target[: B // streams], **kw_w)
+
         with torch.no_grad():
-            side = torch.cuda.Stream(device=frames.device)
-            side.wait_stream(torch.cuda.current_stream(frames.device))
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup)):
-                    model.segment(self.frames, self.target, **kw)
-                    if streams > 1:                        # (the groups' shapes too: nothing may be built or sized inside the capture)
-                        kw_w = {} if state is None else {"state": state[: B // streams], "return_state": True}
-                        model.segment(self.frames[: B // streams], None if target is None else self.target[: B // streams], **kw_w)
-            torch.cuda.current_stream(frames.device).wait_stream(side)
-            torch.cuda.synchronize(frames.device)
+            _warm_up(frames.device, warmup, eager)
             self.graph = torch.cuda.CUDAGraph()
-            # (with a process group alive its watchdog THREAD may poll events of earlier collectives while this thread captures: under the
-            # default "global" capture mode that aborts the process -- train.GraphedTrainStep met it -- so only this thread is policed)
-            mode = {} if pool is None else {"pool": pool}
-            if torch.distributed.is_available() and torch.distributed.is_initialized():
-                mode["capture_error_mode"] = "thread_local"
+            mode = _capture_mode(pool=pool)
             if streams == 1:
                 with torch.cuda.graph(self.graph, **mode):
                     self.out = model.segment(self.frames, self.target, **kw)
@@ -1289,17 +1296,16 @@ class GraphedSegment:
                         cur.wait_stream(s_)
                     self.out = (mask, counts) if state is None else (mask, counts, torch.cat(states, 0))     # (the groups' final states: one small copy)
         # The graph holds raw addresses of the weight packs the warm-up calls built OUTSIDE its memory pool: keep them alive here (a replay
-        # must never read freed memory), and remember the epochs they belong to -- a replay after the weights or packs changed would segment
+        # must never read freed memory), and remember the stamp they belong to -- a replay after the weights or packs changed would segment
         # with the weights of capture time, so __call__ raises instead.
-        self._held = _packs_held(model)
-        self._epochs = (_epoch_of(model), model.__dict__.get("_pack_epoch", 0))
+        self._held, self.stamp = _packs_held(model), model._packs.stamp()
 
     def __call__(self, frames: torch.Tensor, target: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None):
         if (frames.shape != self.frames.shape or frames.dtype != self.frames.dtype or (target is None) != (self.target is None)
                 or (state is None) != (self.state is None)):
             raise RuntimeError(f"GraphedSegment was captured for frames {tuple(self.frames.shape)} {self.frames.dtype}"
                                f"{'' if self.target is None else ' with a target'}{'' if self.state is None else ' with a state'}")
-        if self._epochs != (_epoch_of(self.model), self.model.__dict__.get("_pack_epoch", 0)):
+        if self.stamp != self.model._packs.stamp():
             raise RuntimeError("GraphedSegment: the model's weights or weight packs changed since the capture (optimiser step, load_state_dict, "
                                ".to(), train() / eval()): the graph reads the packs of capture time -- capture a new one")
         if frames.data_ptr() != self.frames.data_ptr():
@@ -1334,17 +1340,9 @@ class PipelinedClip:
         self.fin = [frames.clone(), frames.clone()]
         self.tgt = [None, None] if target is None else [target.clone(), target.clone()]
         self.front_stream = torch.cuda.Stream(device=dev)
-        mode = {}
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            mode["capture_error_mode"] = "thread_local"
+        mode = _capture_mode()
         with torch.no_grad():
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup)):          # (weight packs, kernel attributes, workspaces: nothing may be built inside a capture)
-                    model._segment_from_features(model._encode_project(self.fin[0]), self.state, self.dims, self.tgt[0])
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
+            _warm_up(dev, warmup, lambda: model._segment_from_features(model._encode_project(self.fin[0]), self.state, self.dims, self.tgt[0]))
             self.gfront, self.feats, self.gback, self.out = [], [], [], []
             for j in range(2):                           # front graphs: a pool EACH -- in a shared pool the second capture places its outputs where
                 g = torch.cuda.CUDAGraph()               # the first keeps scratch, and front(i + 2) would write over what back(i + 1) still reads
@@ -1358,8 +1356,7 @@ class PipelinedClip:
                     o = model._segment_from_features(self.feats[j], self.state, self.dims, self.tgt[j])
                 self.gback.append(g)
                 self.out.append(o)
-        self._held = _packs_held(model)
-        self._epochs = (_epoch_of(model), model.__dict__.get("_pack_epoch", 0))
+        self._held, self.stamp = _packs_held(model), model._packs.stamp()
 
     @torch.no_grad()
     def __call__(self, frames: torch.Tensor, target: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None):
@@ -1368,7 +1365,7 @@ class PipelinedClip:
         if (frames.shape[0] != B or tuple(frames.shape[2:]) != self.shape[2:] or frames.dtype != self.dtype or frames.shape[1] % Tc
                 or (target is None) != (not self.has_target)):
             raise RuntimeError(f"PipelinedClip was captured for chunks of {self.shape} {self.dtype}{' with a target' if self.has_target else ''}")
-        if self._epochs != (_epoch_of(self.model), self.model.__dict__.get("_pack_epoch", 0)):
+        if self.stamp != self.model._packs.stamp():
             raise RuntimeError("PipelinedClip: the model's weights or weight packs changed since the capture -- capture a new one")
         dev = frames.device
         cur, fs = torch.cuda.current_stream(dev), self.front_stream

@@ -199,26 +199,18 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep takes the bare module; several ranks: pass grad_sync=FlatGradSync(model) (one captured all-reduce)")
         self.model, self.opt, self.autocast_dtype, self.grad_sync = model, opt, autocast_dtype, grad_sync
         self.frames, self.target = frames.clone(), target.clone()
-        side = torch.cuda.Stream(device=frames.device)
-        side.wait_stream(torch.cuda.current_stream(frames.device))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self.loss = train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync)
-        torch.cuda.current_stream(frames.device).wait_stream(side)
-        torch.cuda.synchronize(frames.device)
+        from .model import _capture_mode, _packs_held, _warm_up
+        # (library convolutions pick their solvers, the optimiser creates its state; nothing of that may happen inside the capture)
+        _warm_up(frames.device, warmup, lambda: train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync))
         self.graph = torch.cuda.CUDAGraph()
-        # (with a collective in the step the process group's watchdog THREAD polls the events of the warm-up steps' all-reduces while this
-        # thread captures; under the default "global" capture mode its hipEventQuery aborts the process with "operation not permitted when
-        # stream is capturing" -- measured round 5 -- so only this thread's calls are policed)
-        import torch.distributed as dist
-        mode = {"capture_error_mode": "thread_local"} if (grad_sync is not None or (dist.is_available() and dist.is_initialized())) else {}
+        # (a collective in the step is reason enough for the thread-local capture mode, whether or not a process group is up yet)
+        mode = _capture_mode(thread_local=grad_sync is not None)
         with torch.cuda.graph(self.graph, **mode):
             self.loss = train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync)
         self.eager_steps = max(1, warmup)       # optimiser steps taken before the first replay (the capture itself runs no kernel)
         # the captured kernels address the per-weight packs (re-packed by the graph itself every replay) and other buffers the warm-up steps
         # allocated outside the graph's pool: held here, so that GDKVM.invalidate_packed_weights() (an eval() / train() toggle between steps)
         # cannot free what a replay writes
-        from .model import _packs_held
         inner = getattr(model, "module", model)
         self._held = _packs_held(inner) if hasattr(inner, "invalidate_packed_weights") else []
 

@@ -301,7 +301,7 @@ def test_cfg5_module_long_clip_in_chunks_with_the_state_carried(hip):
     # (round 6) that form runs the NEXT chunk's encoder and projections beside the current chunk's memory path and decoder (PipelinedClip);
     # the strictly sequential form (one whole-forward graph per chunk) gives the same bits, and so does a clip continued from a carried state
     import gdkvm_amd.model as M
-    assert any(isinstance(v_, M.PipelinedClip) for v_ in fused.__dict__["_clip_graphs"].values())
+    assert any(isinstance(v_, M.PipelinedClip) for v_ in fused._packs.graphs.values())
     M._CLIP_PIPELINE = False
     try:
         mq, cq, sq = fused.segment_clip(fr, 32, target=tgt, graph=True)

@@ -16,27 +16,95 @@ def test_eval_on_an_eval_model_keeps_graphs_valid_and_epochs_are_per_model():
     from gdkvm_amd import model as M
     a = M.GDKVM(M.GDKVMConfig(widths=(16, 32, 64), pixel_dim=64, value_dim=32)).eval()
     b = M.GDKVM(M.GDKVMConfig(widths=(16, 32, 64), pixel_dim=64, value_dim=32)).eval()
-    ea, eb = a.__dict__["_pack_epoch"], b.__dict__["_pack_epoch"]
+    pa, pb = a._packs, b._packs
+    ea, eb, sa = pa.drops, pb.drops, pa.stamp()
     a.eval()                                                     # a defensive eval(): no mode change, nothing invalidated
-    assert a.__dict__["_pack_epoch"] == ea
+    assert pa.drops == ea and pa.stamp() == sa
     a.train()
-    assert a.__dict__["_pack_epoch"] == ea + 1                  # a real mode change drops the packs
+    assert pa.drops == ea + 1 and pa.stamp() != sa               # a real mode change drops the packs ...
+    assert pa.epoch == 0                                         # ... and is no weights epoch
     a.eval()
-    ka, kb = M._epoch_of(a), M._epoch_of(b)
+    ka, kb, wa, wb = pa.stamp(), pb.stamp(), pa.epoch, pb.epoch
     M.weights_changed(a)                                         # an optimiser step on `a` ...
-    assert M._epoch_of(a) != ka and M._epoch_of(b) == kb         # ... leaves a frozen model `b` (teacher / EMA copy) alone
-    assert b.__dict__["_pack_epoch"] == eb
+    assert pa.stamp() != ka and pa.epoch == wa + 1               # ... moves its stamp, by its weights epoch ...
+    assert pb.stamp() == kb and pb.epoch == wb                   # ... and leaves a frozen model `b` (teacher / EMA copy) alone
+    assert pb.drops == eb
     M.weights_changed()                                          # the process-wide form tells everyone
-    assert M._epoch_of(b) != kb
-    # the sub-modules that cache packs share their model's cell, before and after folding
-    assert a.decoder.__dict__["_epoch_cell"] is a.__dict__["_epoch_cell"]
+    assert pb.stamp() != kb and pb.epoch == wb and pb.drops == eb
+    # the sub-modules that cache packs share their model's cache, before and after folding
+    assert a.decoder.__dict__["_packs"] is pa
     a.fuse_for_inference()
     convs = [m for m in a.modules() if isinstance(m, M.FusedConv)]
-    assert convs and all(m.__dict__["_epoch_cell"] is a.__dict__["_epoch_cell"] for m in convs)
+    assert convs and all(m.__dict__["_packs"] is pa for m in convs) and a._packs is pa
     wrapped = types.SimpleNamespace(module=a)                    # DistributedDataParallel-style wrapper
-    k2 = M._epoch_of(a)
+    k2 = pa.stamp()
     M.weights_changed(wrapped)
-    assert M._epoch_of(a) != k2
+    assert pa.stamp() != k2
+
+
+def test_pack_cache_key_rule_drops_and_deep_copy():
+    """The pack cache alone (model._Packs) on CPU tensors with a counting builder: what rebuilds a pack, what does not, what a drop reaches,
+    what is held for captured graphs, and that a deep copy of a module tree gets one new, empty cache of its own."""
+    import copy
+    from gdkvm_amd import model as M
+    root = torch.nn.Module()
+    root.decoder = M.Decoder(64, (16, 32, 64), 2)
+    packs = M._Packs()
+    packs.adopt(root)
+    assert M._packs_of(root.decoder) is packs and "_packs" not in root.state_dict()
+    w, w2 = torch.ones(4), torch.ones(3)
+    builds = {"a": 0, root.decoder: 0}
+
+    def get(slot, src, extras=("cpu",)):
+        def build():
+            builds[slot] += 1
+            return src * 2.0
+        return packs.get(slot, (src,), extras, build)
+
+    v = get("a", w)
+    assert get("a", w) is v and builds["a"] == 1                 # same sources: one build
+    w.add_(1)                                                    # an in-place write bumps the version counter: rebuilt
+    v = get("a", w)
+    assert builds["a"] == 2 and torch.equal(v, w * 2.0)
+    w.data.mul_(0)                                               # a write through .data is invisible to the key ...
+    assert get("a", w) is v and builds["a"] == 2 and not torch.equal(v, w * 2.0)
+    M.weights_changed(root)                                      # ... until the model says so
+    v = get("a", w)
+    assert builds["a"] == 3 and torch.equal(v, w * 2.0)
+    assert get("a", w, ("cpu", True)) is not v and builds["a"] == 4      # the caller's extras are part of the key
+    v = get("a", w)
+    assert builds["a"] == 5
+    d = get(root.decoder, w2)                                    # a sub-module's slot is the module itself
+    assert builds[root.decoder] == 1 and get(root.decoder, w2) is d
+    held = packs.held()
+    assert len(held) == 2 and any(h is v for h in held) and any(h is d for h in held)     # exactly the live values
+    packs.drop(root.decoder)                                     # a named drop rebuilds that slot only
+    assert len(packs.held()) == 1 and packs.held()[0] is v
+    get("a", w); d = get(root.decoder, w2)
+    assert builds["a"] == 5 and builds[root.decoder] == 2
+    stamp = packs.stamp()
+    packs.graphs["shape"] = object()
+    packs.drop_all()                                             # drop-all: every slot rebuilds, the graphs go, the stamp moves
+    assert packs.held() == [] and not packs.graphs and packs.stamp() != stamp
+    v = get("a", w); d = get(root.decoder, w2)
+    assert builds["a"] == 6 and builds[root.decoder] == 3
+
+    def failing():
+        raise RuntimeError("no pack")
+    w.add_(1)
+    with pytest.raises(RuntimeError, match="no pack"):           # a builder that raises leaves the slot as it was
+        packs.get("a", (w,), ("cpu",), failing)
+    assert any(h is v for h in packs.held())
+    get("a", w)
+    assert builds["a"] == 7
+
+    twin = copy.deepcopy(root)                                   # the copy: ONE new cache, shared by its sub-modules, empty
+    assert twin._packs is not packs and twin.decoder.__dict__["_packs"] is twin._packs and twin._packs.held() == []
+    stamp = packs.stamp()
+    M.weights_changed(twin)
+    assert packs.stamp() == stamp and twin._packs.epoch == 1
+    lone = M.Decoder(64, (16, 32, 64), 2)                        # outside a model: a cache of its own on first use
+    assert M._packs_of(lone) is M._packs_of(lone) is not packs
 
 
 def test_library_fallbacks_are_loud(monkeypatch):

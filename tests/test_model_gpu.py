@@ -252,12 +252,12 @@ def test_invalidate_packed_weights_reaches_the_fused_convolutions(hip):
         model = model.fuse_for_inference().to(torch.bfloat16)
         before = model(frames, _lowres=True).float()
         conv = model.encoder.layer2[1].conv1                       # a 128 -> 128 layer on the packed-weight kernel
-        assert isinstance(conv, FusedConv) and "_wpack" in conv.__dict__
+        assert isinstance(conv, FusedConv) and conv in model._packs.slots
         conv.conv.weight.data.mul_(0)
         stale = model(frames, _lowres=True).float()
         assert torch.equal(stale, before)                          # (the hazard: the pack is still the old weights)
         model.invalidate_packed_weights()
-        assert "_wpack" not in conv.__dict__
+        assert conv not in model._packs.slots and conv.__dict__["_packs"] is model._packs
         after = model(frames, _lowres=True).float()
     assert not torch.equal(after, before)
 
