@@ -13,8 +13,11 @@
 //   * per k-step a wave reads one 16-pixel B fragment per m-tile (4 reads) and issues 8 v_mfma_f32_16x16x32_bf16; with the
 //     weights as the A operand a lane ends with 4 consecutive output channels of one pixel -> 8-byte stores;
 //   * the next tile's band streams into the other LDS buffer by LDS-DMA (global_load_lds, no registers: the 144 weight
-//     registers leave none to stage through) while the current tile computes; pixels outside the image are fetched from a
-//     16-byte zero constant (the DMA writes lane-linear, so the padding slots are fetched from there too).
+//     registers leave none to stage through) while the current tile computes.  With one tile per row of the map (tiles_x == 1:
+//     every map of the model) the DMA goes through a buffer descriptor over the tile's frame: its range check zero-fills the
+//     rows above and below the frame, and the padding slots and the left / right halo columns (the DMA writes lane-linear, so
+//     they are fetched too) carry an offset that is always out of range.  Wider maps keep per-lane pointers and fetch those
+//     slots from a 16-byte zero constant.
 // HBM traffic: input once (+ halo rows from L2), output once.  Arithmetic: fp32 accumulation over the same 576 products as the
 // library kernel, one rounding after the epilogue.
 #include <type_traits>
@@ -35,7 +38,8 @@ struct Conv64Args {
     int packed;                          // w is the gdkvm_conv3x3_pack_weights copy: fragment (kt, ks) = 1 KiB contiguous, rows in this kernel's channel order
 };
 
-template <int TW>
+// DESC: one tile per row (tiles_x == 1), band fetched through a buffer descriptor; else per-lane pointers, any tiles_x
+template <int TW, bool DESC>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
 {
     constexpr int BW = TW + 2, NPIX = CV_TH * TW, BAND_PIX = (CV_TH + 2) * BW;
@@ -47,31 +51,65 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
 
     // band fetch by LDS-DMA: piece j = w + 4u (64 consecutive 16-byte LDS slots) is issued by wave w; slot d = 10 pix + c holds
     // channel chunk c of band pixel pix (c = 8, 9: padding).  The slot geometry does not depend on the tile: kept in registers.
+    // DESC: g_rel is the slot's BYTE offset from the frame's first byte for the tile at row 0 (band row 0 is row -1: negative, huge as
+    // unsigned); a tile adds its first row as a scalar.  The descriptor spans exactly the frame, so the rows above and below it read as
+    // zeros; the slots that are zero in every tile -- padding, the halo columns, past the band -- carry CV_DEAD, out of range with any
+    // such scalar added (the launcher keeps a frame below 2^31 bytes).
     constexpr int PP = (NPIECES + 3) / 4;
-    int g_rel[PP], g_yx[PP];                               // element offset from the band's (0, 0) pixel; (by << 8 | bx), -1 = no data
+    constexpr unsigned CV_DEAD = 0x80000000u;
+    int g_rel[PP], g_yx[DESC ? 1 : PP];                    // !DESC: element offset from the band's (0, 0) pixel; (by << 8 | bx), -1 = no data
 #pragma unroll
     for (int u = 0; u < PP; ++u) {
         const int j = w + 4 * u, d = 64 * j + lane, pix = d / 10, c = d - 10 * pix;
         const int by = pix / BW, bx = pix - by * BW;
-        g_rel[u] = (by * a.W + bx) * CV_C + c * 8;
-        bool live = j < NPIECES && c < 8 && pix < BAND_PIX;
-        if (a.tiles_x == 1) live = live && bx >= 1 && bx <= a.W;     // one tile per row: the column test does not depend on the tile
-        g_yx[u] = live ? (by << 8 | bx) : -1;
+        if constexpr (DESC) {
+            const bool live = j < NPIECES && c < 8 && pix < BAND_PIX && bx >= 1 && bx <= a.W;
+            g_rel[u] = live ? (((by - 1) * a.W + bx - 1) * CV_C + c * 8) * 2 : (int)CV_DEAD;
+        } else {
+            g_rel[u] = (by * a.W + bx) * CV_C + c * 8;
+            bool live = j < NPIECES && c < 8 && pix < BAND_PIX;
+            if (a.tiles_x == 1) live = live && bx >= 1 && bx <= a.W;     // one tile per row: the column test does not depend on the tile
+            g_yx[u] = live ? (by << 8 | bx) : -1;
+        }
     }
-    const bool one_col = a.tiles_x == 1;
-    auto fetch = [&](int tile, int buf) __attribute__((always_inline)) {
-        const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
-        const int y0 = ty * CV_TH - 1, x0 = tx * TW - 1;
-        const bf16_t* origin = a.x + (((long long)n * a.H + y0) * a.W + x0) * CV_C;
+    // DESC: a tile is (frame n, row tile ty); the workgroup's tiles are gridDim.x apart, so the pair advances by a fixed step with one
+    // carry (the split of the tile index by two run-time divisions was ~60 scalar instructions per tile, twice)
+    struct TilePos { int n, ty; };
+    const int step_n = DESC ? (int)gridDim.x / a.tiles_y : 0, step_ty = DESC ? (int)gridDim.x % a.tiles_y : 0;
+    auto advance = [&](TilePos& p) __attribute__((always_inline)) {
+        if constexpr (DESC) {
+            p.n += step_n; p.ty += step_ty;
+            if (p.ty >= a.tiles_y) { p.ty -= a.tiles_y; ++p.n; }
+        }
+    };
+    auto fetch = [&](int tile, TilePos pos, int buf) __attribute__((always_inline)) {
+        if constexpr (DESC) {
+            // wave-uniform values only: the descriptor lives in SGPRs, no waterfall loop
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x + (long long)pos.n * a.H * a.W * CV_C), 0,
+                                                                                  a.H * a.W * CV_C * 2, 0x00020000);
+            const unsigned ts = (unsigned)(pos.ty * CV_TH * a.W * CV_C * 2);
 #pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            const int j = w + 4 * u;
-            if (j >= NPIECES) break;                       // (wave-uniform)
-            const int yy = y0 + (g_yx[u] >> 8), xx = x0 + (g_yx[u] & 255);
-            const bool ok = g_yx[u] >= 0 && (unsigned)yy < (unsigned)a.H && (one_col || (unsigned)xx < (unsigned)a.W);
-            const bf16_t* src = ok ? origin + g_rel[u] : reinterpret_cast<const bf16_t*>(&g_conv_zero16);
-            __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(
-                reinterpret_cast<uintptr_t>(band2 + buf * BAND_BYTES + 1024 * j)), 16, 0, 0);
+            for (int u = 0; u < PP; ++u) {
+                const int j = w + 4 * u;
+                if (j >= NPIECES) break;                   // (wave-uniform)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, reinterpret_cast<__attribute__((address_space(3))) void*>(
+                    reinterpret_cast<uintptr_t>(band2 + buf * BAND_BYTES + 1024 * j)), 16, (int)((unsigned)g_rel[u] + ts), 0, 0, 0);
+            }
+        } else {
+            const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
+            const int y0 = ty * CV_TH - 1, x0 = tx * TW - 1;
+            const bf16_t* origin = a.x + (((long long)n * a.H + y0) * a.W + x0) * CV_C;
+            const bool one_col = a.tiles_x == 1;
+#pragma unroll
+            for (int u = 0; u < PP; ++u) {
+                const int j = w + 4 * u;
+                if (j >= NPIECES) break;                   // (wave-uniform)
+                const int yy = y0 + (g_yx[u] >> 8), xx = x0 + (g_yx[u] & 255);
+                const bool ok = g_yx[u] >= 0 && (unsigned)yy < (unsigned)a.H && (one_col || (unsigned)xx < (unsigned)a.W);
+                const bf16_t* src = ok ? origin + g_rel[u] : reinterpret_cast<const bf16_t*>(&g_conv_zero16);
+                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(
+                    reinterpret_cast<uintptr_t>(band2 + buf * BAND_BYTES + 1024 * j)), 16, 0, 0);
+            }
         }
     };
 
@@ -88,7 +126,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
     // | this tile's epilogue | DMA of the tile after next into `cur`.  The stores and the DMA are never waited for right
     // after being issued: the next wait is a tile of MFMAs later.
     int tile = blockIdx.x, cur = 0;
-    if (tile < ntiles) fetch(tile, 0);                     // (the first band is on its way while the weights load)
+    TilePos tpos{DESC ? tile / a.tiles_y : 0, DESC ? tile % a.tiles_y : 0}, fpos = tpos;      // (DESC) this tile; the next tile to fetch
+    if (tile < ntiles) fetch(tile, fpos, 0);               // (the first band is on its way while the weights load)
+    advance(fpos);
 
     // weights of this wave's 32 output channels, all 18 k-steps, as A-operand fragments.  Which channel an MFMA row stands for is
     // free: row rho = 4 g' + r of n-tile nt is channel 32wn + 8g' + 4nt + r, so that a lane's two accumulator tiles hold EIGHT
@@ -119,7 +159,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
     }
 
     __syncthreads();                                       // (vmcnt(0) + barrier: the first band has landed)
-    if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x, 1);
+    if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x, fpos, 1);
+    advance(fpos);
     for (; tile < ntiles; tile += gridDim.x, cur ^= 1) {
         const unsigned char* band = band2 + cur * BAND_BYTES;
 
@@ -161,7 +202,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         __syncthreads();                                   // everyone is done with this band; the next one has landed
 
         // epilogue: lane (li, g) holds channels 32wn + 8g .. +7 of pixel 16(4wm+m) + li (tile nt: the four channels 4nt ..)
-        const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
+        const int t2 = DESC ? 0 : tile / a.tiles_x, tx = DESC ? 0 : tile % a.tiles_x, ty = DESC ? tpos.ty : t2 % a.tiles_y, n = DESC ? tpos.n : t2 / a.tiles_y;
+        advance(tpos);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int p = 16 * (4 * wm + m) + li;
@@ -191,7 +233,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         // the band of the tile after next, into the buffer just consumed.  Issued BEHIND the epilogue: the compiler cannot order
         // LDS-DMA against register loads and waits with vmcnt(0) for the residual -- ahead of the epilogue that wait also covered
         // the band just requested from HBM (+9 us per residual layer); the band still has a whole tile of MFMAs to land.
-        if (tile + 2 * (int)gridDim.x < ntiles) fetch(tile + 2 * gridDim.x, cur);
+        if (tile + 2 * (int)gridDim.x < ntiles) fetch(tile + 2 * gridDim.x, fpos, cur);
+        advance(fpos);
     }
 }
 
@@ -213,8 +256,17 @@ int gdkvm_conv3x3_c64_launch(const void* x, const void* w, const float* bias, co
     const long long ntiles = (long long)N * a.tiles_x * a.tiles_y;
     if (ntiles <= 0 || ntiles > 0x7fffffffLL) return 1;
     const int grid = (int)(ntiles < 512 ? ntiles : 512);   // persistent: two workgroups per CU, weights loaded once each
-    if (TW == 28) hipLaunchKernelGGL(conv3x3_c64_kernel<28>, dim3(grid), dim3(256), 0, st, a);
-    else if (TW == 16) hipLaunchKernelGGL(conv3x3_c64_kernel<16>, dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(conv3x3_c64_kernel<32>, dim3(grid), dim3(256), 0, st, a);
+    // one tile per row, and a frame (with the band rows below it) below 2^31 bytes -- offsets from there on stand for "zeros" --:
+    // the band goes through a buffer descriptor; else the per-lane pointer form
+    const bool desc = a.tiles_x == 1 && (long long)(H + CV_TH + 2) * W * CV_C * 2 < 0x7fffffffLL;
+    if (desc) {
+        if (TW == 28) hipLaunchKernelGGL((conv3x3_c64_kernel<28, true>), dim3(grid), dim3(256), 0, st, a);
+        else if (TW == 16) hipLaunchKernelGGL((conv3x3_c64_kernel<16, true>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((conv3x3_c64_kernel<32, true>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+        if (TW == 28) hipLaunchKernelGGL((conv3x3_c64_kernel<28, false>), dim3(grid), dim3(256), 0, st, a);
+        else if (TW == 16) hipLaunchKernelGGL((conv3x3_c64_kernel<16, false>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((conv3x3_c64_kernel<32, false>), dim3(grid), dim3(256), 0, st, a);
+    }
     return 0;
 }

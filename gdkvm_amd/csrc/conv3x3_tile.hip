@@ -9,7 +9,8 @@
 //     channels + padding per pixel: a ds_read_b128 of 16 consecutive pixels is conflict-free and every operand
 //     address is base + immediate -- 128 B + 32 B in fact: CT_PIX = 160) is staged in LDS by LDS-DMA, double-buffered: chunk c+1
 //     streams in while chunk c computes; the input may be the channel concatenation of TWO tensors (x2 / C1), fetched in place;
-//     pixels outside the frame and the padding slots are fetched from a 16-byte zero constant;
+//     the DMA goes through a buffer descriptor over the tile's frames, whose range check zero-fills the pixels above and below the
+//     frame; the padding slots and the left / right halo columns carry an offset that is always out of range;
 //   * the nine taps are nine SHIFTED READS of that image; the weights never touch LDS: a wave owns one or two 16-channel output
 //     tiles and streams their weight fragments (one 16-byte load each per k-step, three k-steps ahead, straight from L2) -- each
 //     is used for all the wave's pixel tiles (7 MFMAs per load);
@@ -35,8 +36,6 @@ constexpr int CT_MAXMT = 13;             // 16-pixel tiles per workgroup tile (2
 // (64 channels per workgroup); the defaults are the measured picks (tools/conv_probe.py; K = 64: <2, 2> since the
 // weights are packed -- 121 against 129 us on the 192 -> 64 layer: half the LDS operand reads per MFMA, and the fourfold weight fetch is cheap now)
 constexpr int CT_VARIANT_128 = 4, CT_VARIANT_64 = 3;
-
-__device__ const uint4 g_ct_zero16 = {0, 0, 0, 0};
 
 template <int I, int E, class F>
 __device__ __forceinline__ void static_for_ct(F&& f)
@@ -103,45 +102,55 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
         asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(bias4[nt]) : "v"(bp) : "memory");
     }
 
-    // DMA piece geometry (tile-invariant): piece j = w + NWV u, slot d = 64 j + lane = CT_SLOTS pix + c; c >= 8 is padding
+    // DMA piece geometry (tile-invariant): piece j = w + NWV u, slot d = 64 j + lane = CT_SLOTS pix + c; c >= 8 is padding.
+    // A piece is fetched through a raw buffer descriptor that spans exactly the tile's frame group (nfr H W pixels of the tensor the chunk
+    // lies in): a lane's source is ONE 32-bit byte offset from the group's first byte, g_off + a per-chunk scalar (the tile's first row and
+    // the chunk's channels), and a lane whose offset is out of the descriptor's range gets zeros from the hardware -- the row above the
+    // frame (a negative offset: huge as unsigned), the rows below it and the frames a ragged last group lacks (>= num_records).  Slots that
+    // hold zeros in EVERY tile carry CT_DEAD, out of range whatever the scalar (the launcher keeps a group below 2^31 bytes): padding, the
+    // left / right halo columns, slots past the band, surplus pieces -- and, with several whole frames per tile (tiles_y == 1), each frame's
+    // halo rows, which in memory are the neighbouring frame's rows.  One offset set per pixel pitch (a concatenated input has two).
     constexpr int PP = NWV == 8 ? 7 : 8;                   // pieces per wave: npieces <= 56 (eight waves) / 32 (four)
-    int g_pix[PP], g_meta[PP];                             // source pixel offset from the band's (0, 0); band row << 16 | 8c << 8 | frame, or -1
+    constexpr unsigned CT_DEAD = 0x80000000u;
+    const int cs1 = a.C1, cs2 = a.x2 ? C - a.C1 : C;       // pixel pitch of x (the whole input when there is no x2) and of x2
+    unsigned g_off1[PP], g_off2[PP];
 #pragma unroll
     for (int u = 0; u < PP; ++u) {
         const int j = w + NWV * u, d = 64 * j + lane, pix = d / CT_SLOTS, c = d - CT_SLOTS * pix;
         const int f = ct_div(pix, a.inv_band), r = pix - f * (a.bh * BW), by = ct_div(r, a.inv_bw), bx = r - by * BW;
-        g_pix[u] = (f * H + by) * W + bx;
-        const bool live = j < a.npieces && c < 8 && pix < a.band_px && bx >= 1 && bx <= W;
-        g_meta[u] = live ? (by << 16 | (c * 8) << 8 | f) : -1;
+        const int sp = (f * H + by - 1) * W + bx - 1;      // source pixel, from the group's first, of a tile that starts at row 0
+        const bool live = j < a.npieces && c < 8 && pix < a.band_px && bx >= 1 && bx <= W && (a.tiles_y > 1 || (by >= 1 && by <= a.th));
+        g_off1[u] = live ? (unsigned)(sp * cs1 * 2 + c * 16) : CT_DEAD;
+        g_off2[u] = live ? (unsigned)(sp * cs2 * 2 + c * 16) : CT_DEAD;
     }
-    // what a tile's band fetches need of the tile, computed ONCE per tile (scalar: the row / frame-group split of the tile index and two
-    // 64-bit origins; recomputed per chunk it was ~85 scalar instructions of the ~2 000 cycles a wave spent issuing a chunk's fetch)
-    struct Geo { const bf16_t* b1; const bf16_t* b2; int y0, nfr; };
+    const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>(ct_band);
+    const int nlive = max(0, (a.npieces - w + NWV - 1) / NWV);         // this wave's pieces u < nlive exist (j = w + NWV u < npieces)
+    // what a tile's band fetches need of the tile, computed ONCE per tile (scalar): the frame group's first pixel, its pixel count and the
+    // tile's first row, in pixels -- the descriptor and the offset scalar of a chunk are a few scalar instructions from these
+    struct Geo { int px0, npx, row0; };
     auto geo_of = [&](int tile) __attribute__((always_inline)) {
         const int ty = tile % a.tiles_y, fg = tile / a.tiles_y;          // row tile, frame group
         Geo q;
-        q.y0 = ty * a.th - 1;
-        q.nfr = min(a.fpt, a.N - fg * a.fpt);                           // frames that exist in the last group
-        const long long px0 = ((long long)fg * a.fpt * H + q.y0) * W - 1;       // band pixel (0, 0) of frame 0
-        q.b1 = a.x + px0 * (a.x2 ? a.C1 : C);
-        q.b2 = a.x2 ? a.x2 + px0 * (C - a.C1) - a.C1 : a.x;             // (indexed by the channel of the concatenated input)
+        q.px0 = fg * a.fpt * H * W;
+        q.npx = min(a.fpt, a.N - fg * a.fpt) * H * W;                   // (the frames that exist in the last group)
+        q.row0 = ty * a.th * W;
         return q;
     };
     auto fetch = [&](const Geo q, int chunk, int buf) __attribute__((always_inline)) {
-        const int y0 = q.y0, nfr = q.nfr;
         const bool second = a.x2 != nullptr && chunk * CT_CK >= a.C1;   // which tensor of a concatenated input holds this chunk
-        const int cs = a.x2 ? (second ? C - a.C1 : a.C1) : C;           // its channel count = pixel pitch
-        const bf16_t* origin = (second ? q.b2 : q.b1) + chunk * CT_CK;
-        // straight-line on purpose (always PP pieces: surplus ones land in a dump slot): a branch would make the compiler's vmcnt
-        // counting conservative for the weight fragments in flight around it
+        const int cs = second ? cs2 : cs1;                              // its channel count = pixel pitch
+        // wave-uniform values only (kernel arguments and scalars of the tile loop): the descriptor lives in SGPRs, no waterfall loop
+        const bf16_t* base = (second ? a.x2 : a.x) + (long long)q.px0 * cs;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, q.npx * cs * 2, 0x00020000);
+        const unsigned ts = (unsigned)((q.row0 * cs + chunk * CT_CK - (second ? a.C1 : 0)) * 2);
+        const unsigned dst0 = lds0 + buf * band_bytes + 1024 * w;       // LDS address of this wave's piece 0
+        // straight-line on purpose (always PP pieces: surplus ones land in a dump slot): the hand-written vmcnt counts of the chunk loop
+        // assume exactly PP DMA operations per fetch
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
-            const int j = w + NWV * u;
-            const int yy = y0 + (g_meta[u] >> 16);
-            const bool ok = g_meta[u] >= 0 && (unsigned)yy < (unsigned)H && (g_meta[u] & 255) < nfr;
-            const bf16_t* src = ok ? origin + g_pix[u] * cs + ((g_meta[u] >> 8) & 255) : reinterpret_cast<const bf16_t*>(&g_ct_zero16);
-            unsigned char* dst = j < a.npieces ? ct_band + buf * band_bytes + 1024 * j : ct_band + 2 * band_bytes;
-            __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(reinterpret_cast<uintptr_t>(dst)), 16, 0, 0);
+            const unsigned dst = u < nlive ? dst0 + 1024 * NWV * u : lds0 + 2 * band_bytes;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, reinterpret_cast<__attribute__((address_space(3))) void*>(static_cast<uintptr_t>(dst)), 16,
+                                                     (int)((second ? g_off2[u] : g_off1[u]) + ts), 0, 0, 0);
         }
     };
 
@@ -221,7 +230,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
             {
                 const bool more = chunk + 1 < nchunk;
                 Geo q;                                     // (field by field: a select between the two structs would put them in scratch)
-                q.b1 = more ? cur.b1 : nxt.b1; q.b2 = more ? cur.b2 : nxt.b2; q.y0 = more ? cur.y0 : nxt.y0; q.nfr = more ? cur.nfr : nxt.nfr;
+                q.px0 = more ? cur.px0 : nxt.px0; q.npx = more ? cur.npx : nxt.npx; q.row0 = more ? cur.row0 : nxt.row0;
                 fetch(q, more ? chunk + 1 : 0, buf ^ 1);
             }
             const unsigned char* band = ct_band + buf * band_bytes;
@@ -536,6 +545,9 @@ int gdkvm_conv3x3_tile_launch(const void* x, const void* x2, int C1, const void*
     while (pieces() > maxpieces && a.th > 1) { --a.th; a.bh = a.th + 2; a.tiles_y = (H + a.th - 1) / a.th; }
     a.npieces = pieces();
     if (a.npieces > maxpieces) return 1;
+    // a band piece is addressed by a 32-bit byte offset from its frame group's first byte, and offsets from 2^31 on stand for "zeros":
+    // a group, the band row below it included, stays below that
+    if ((long long)(a.fpt * H + 2) * W * (x2 ? (C1 > C - C1 ? C1 : C - C1) : C) * 2 >= 0x7fffffffLL) return 1;
     a.inv_band = 1.0f / (float)(a.bh * a.bw); a.inv_bw = 1.0f / (float)a.bw;
     a.inv_tw = 1.0f / (float)(a.th * W); a.inv_w = 1.0f / (float)W;
     a.perm = K % 32 == 0;
