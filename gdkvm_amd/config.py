@@ -6,7 +6,7 @@ launcher environment variables are torchrun's (``MASTER_PORT`` etc., index.astro
 from __future__ import annotations
 
 from dataclasses import asdict, dataclass, field, fields, is_dataclass
-from typing import Any, Dict
+from typing import Any, Dict, List
 
 import yaml
 
@@ -36,6 +36,20 @@ class ModelCfg:
 
 
 @dataclass
+class AugmentCfg:
+    """Training-clip augmentation on the GPU (data.ClipAugment -> gdkvm_augment_clips inside the prefetcher's cast pass).  Off by default;
+    every range defaults to a no-op.  eval.py never augments."""
+    enabled: bool = False
+    rotate_deg: float = 0.0                                        # rotation in +-degrees about the frame centre
+    scale: List[float] = field(default_factory=lambda: [1.0, 1.0])  # (lo, hi) zoom
+    translate: float = 0.0                                         # shift as a +-fraction of the frame size
+    hflip: float = 0.0                                             # probability of a left-right mirror
+    gain: List[float] = field(default_factory=lambda: [1.0, 1.0])  # (lo, hi) intensity gain
+    bias: float = 0.0                                              # +-intensity offset
+    gamma: List[float] = field(default_factory=lambda: [1.0, 1.0])  # (lo, hi), log-uniform
+
+
+@dataclass
 class RunConfig:
     data_path: str = ""
     batch_size: int = 8
@@ -44,6 +58,7 @@ class RunConfig:
     eval_stage: EvalStage = field(default_factory=EvalStage)
     data: DataCfg = field(default_factory=DataCfg)
     model: ModelCfg = field(default_factory=ModelCfg)
+    augment: AugmentCfg = field(default_factory=AugmentCfg)
     run_dir: str = "outputs"
     save_every: int = 1000
     log_every: int = 20

@@ -62,6 +62,82 @@ class SyntheticEchoClips(Dataset):
 IGNORE_LABEL = 255             # an unlabelled pixel / frame: outside [0, num_classes), so the loss and the Dice counts skip it
 
 
+IDENTITY_ROW = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+
+
+class ClipAugment:
+    """Samples the per-clip parameter rows of ops.augment_clips (gdkvm_augment_clips): one affine warp and one intensity curve per clip, the
+    same for every frame of it.  The kernel warps while it casts the bytes to [0, 1] on the device (pipeline.DevicePrefetcher(augment=...));
+    nothing is warped on the host -- this class only draws 8 numbers per clip and composes a 2 x 3 matrix.
+
+      rotate_deg   rotation about the frame centre, uniform in [-rotate_deg, +rotate_deg] degrees
+      scale        (lo, hi): isotropic zoom about the frame centre, uniform (> 1 enlarges the content)
+      translate    shift, uniform in [-translate, +translate] as a fraction of the frame's width (x) and height (y)
+      hflip        probability of a left-right mirror about the frame centre
+      gain, gamma  (lo, hi): out = gain * in ** gamma + bias on intensities in [0, 1], clamped; gain uniform, gamma log-uniform
+      bias         uniform in [-bias, +bias]
+
+    Forward map of a source pixel index p = (x, y) (x to the right, y down, pixel centres at integers), c = ((W-1)/2, (H-1)/2):
+        p' = A (p - c) + c + (tx W, ty H),   A = scale * [[cos a, -sin a], [sin a, cos a]] * diag(-1 if mirrored else 1, 1)
+    A row holds the INVERSE of it (destination -> source: what a gather needs), inverted in float64 and stored as fp32, then gain, bias,
+    gamma and three zeros.  The defaults are all no-ops: the rows are then exactly IDENTITY_ROW.
+    params() draws from np.random.default_rng([seed, rank, epoch, index]): the same arguments give the same rows, ranks and batches differ,
+    and a run resumed at an epoch repeats that epoch's sequence (the granularity at which train.py resumes the shuffle)."""
+
+    def __init__(self, rotate_deg: float = 0.0, scale=(1.0, 1.0), translate: float = 0.0, hflip: float = 0.0, gain=(1.0, 1.0),
+                 bias: float = 0.0, gamma=(1.0, 1.0), seed: int = 0, rank: int = 0):
+        pair = lambda v: (float(v[0]), float(v[1]))
+        self.rotate_deg, self.translate, self.hflip, self.bias = float(rotate_deg), float(translate), float(hflip), float(bias)
+        self.scale, self.gain, self.gamma = pair(scale), pair(gain), pair(gamma)
+        self.seed, self.rank = int(seed), int(rank)
+        for name, (lo, hi) in (("scale", self.scale), ("gain", self.gain), ("gamma", self.gamma)):
+            if not lo <= hi:
+                raise ValueError(f"ClipAugment: {name} range ({lo}, {hi}) is not (lo, hi)")
+        if self.scale[0] <= 0 or self.gamma[0] <= 0:
+            raise ValueError("ClipAugment: scale and gamma must be positive")
+        if self.rotate_deg < 0 or self.translate < 0 or self.bias < 0 or not 0.0 <= self.hflip <= 1.0:
+            raise ValueError("ClipAugment: rotate_deg, translate and bias are magnitudes (>= 0), hflip a probability")
+        if self.seed < 0 or self.rank < 0:
+            raise ValueError("ClipAugment: seed and rank must be non-negative")
+
+    def draw(self, epoch: int, index: int, B: int) -> dict:
+        """The raw draws of batch `index` of `epoch`, float64 arrays of length B (always all eight, in this order, whatever the ranges)."""
+        rng = np.random.default_rng([self.seed, self.rank, int(epoch), int(index)])
+        return {"angle_deg": rng.uniform(-self.rotate_deg, self.rotate_deg, B),
+                "scale": rng.uniform(self.scale[0], self.scale[1], B),
+                "tx": rng.uniform(-self.translate, self.translate, B),
+                "ty": rng.uniform(-self.translate, self.translate, B),
+                "flip": rng.random(B) < self.hflip,
+                "gain": rng.uniform(self.gain[0], self.gain[1], B),
+                "bias": rng.uniform(-self.bias, self.bias, B),
+                "gamma": np.exp(rng.uniform(np.log(self.gamma[0]), np.log(self.gamma[1]), B))}
+
+    def params(self, epoch: int, index: int, B: int, H: int, W: int) -> torch.Tensor:
+        """fp32 [B, 12] host tensor: the rows of batch `index` of `epoch` for frames of H x W pixels."""
+        d = self.draw(epoch, index, B)
+        c = np.array([(W - 1) / 2.0, (H - 1) / 2.0])
+        a = np.deg2rad(d["angle_deg"])
+        cos, sin, mirror = np.cos(a), np.sin(a), np.where(d["flip"], -1.0, 1.0)
+        fwd = np.zeros((B, 3, 3))
+        fwd[:, 0, 0], fwd[:, 0, 1], fwd[:, 1, 0], fwd[:, 1, 1] = cos * mirror, -sin, sin * mirror, cos
+        fwd[:, :2, :2] *= d["scale"][:, None, None]
+        fwd[:, :2, 2] = c + np.stack([d["tx"] * W, d["ty"] * H], 1) - fwd[:, :2, :2] @ c
+        fwd[:, 2, 2] = 1.0
+        rows = np.zeros((B, 12), np.float64)
+        rows[:, :6] = np.linalg.inv(fwd)[:, :2].reshape(B, 6)
+        rows[:, 6], rows[:, 7], rows[:, 8] = d["gain"], d["bias"], d["gamma"]
+        return torch.from_numpy((rows + 0.0).astype(np.float32))
+
+
+def build_augment(cfg, rank: int = 0):
+    """The ClipAugment of a run configuration (config.AugmentCfg), or None when augmentation is off."""
+    a = cfg.augment
+    if not a.enabled:
+        return None
+    return ClipAugment(rotate_deg=a.rotate_deg, scale=a.scale, translate=a.translate, hflip=a.hflip, gain=a.gain, bias=a.bias,
+                       gamma=a.gamma, seed=cfg.seed, rank=rank)
+
+
 def polygon_mask(xs, ys, height: int, width: int) -> np.ndarray:
     """uint8 [height, width] mask of the closed polygon (xs[i], ys[i]) -- even-odd scanline fill at pixel centres, vertices in pixel
     coordinates (x to the right, y down), as the EchoNet tracings are given.  Pure numpy: the converter runs without skimage / cv2."""

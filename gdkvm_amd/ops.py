@@ -113,6 +113,7 @@ SIGNATURES = {
     "gdkvm_bn_bwd": (_i, [_vp] * 10 + [_sz, ctypes.c_longlong, _i, _i, _i, _vp]),
     "gdkvm_bn_pool_fwd_train": (_i, [_vp] * 9 + [_sz] + [_i] * 4 + [ctypes.c_float] * 2 + [_i, _vp]),
     "gdkvm_bn_pool_bwd": (_i, [_vp] * 9 + [_sz] + [_i] * 5 + [_vp]),
+    "gdkvm_augment_clips": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
 }
 
 
@@ -827,6 +828,39 @@ def head_upsample_argmax_dice(x: torch.Tensor, weight: torch.Tensor, bias: torch
                                                  BT, C, ncls, hl, wl, H, W, _io_dtype(x), _stream(dev))
     _check(rc, "gdkvm_head_upsample_argmax_dice")
     return mask, counts
+
+
+def augment_clips(frames: torch.Tensor, target: Optional[torch.Tensor], params: torch.Tensor, frames_dtype: torch.dtype,
+                  fill_label: int = 255, out: Optional[torch.Tensor] = None, target_out: Optional[torch.Tensor] = None):
+    """gdkvm_augment_clips: the uint8 -> [0, 1] cast of a batch of clips with one affine warp and one intensity table per clip, and the
+    labels warped alike (nearest neighbour, `fill_label` where the source lies outside the frame).  frames uint8 [B,T,C,H,W], target uint8 |
+    int64 [B,T,H,W] or None, params fp32 [B,12] on the device (data.ClipAugment.params: m00 m01 m02 m10 m11 m12 gain bias gamma 0 0 0, the
+    matrix mapping destination to source pixel indices), frames_dtype float32 | bfloat16.  Returns (frames_out, target_out | None); with
+    the identity row the frames are torch.mul(frames, 1/255) bit for bit."""
+    lib = load()
+    if frames.dtype != torch.uint8 or frames.dim() != 5:
+        raise GdkvmError(f"augment_clips: frames must be uint8 [B,T,C,H,W], got {frames.dtype} {tuple(frames.shape)} (float frames are not augmented)")
+    B, T, C, H, W = frames.shape
+    if target is not None and (tuple(target.shape) != (B, T, H, W) or target.dtype not in (torch.uint8, torch.int64)):
+        raise GdkvmError(f"augment_clips: target must be uint8 or int64 {(B, T, H, W)}, got {target.dtype} {tuple(target.shape)}")
+    if params.dtype != torch.float32 or tuple(params.shape) != (B, 12):
+        raise GdkvmError(f"augment_clips: params must be float32 [{B}, 12], got {params.dtype} {tuple(params.shape)}")
+    if frames_dtype not in (torch.float32, torch.bfloat16):
+        raise GdkvmError(f"augment_clips: frames_dtype {frames_dtype} (float32 or bfloat16)")
+    if not 0 <= int(fill_label) <= 255:
+        raise GdkvmError(f"augment_clips: fill_label {fill_label} outside [0, 255]")
+    if target is None and target_out is not None:
+        raise GdkvmError("augment_clips: target_out given without a target")
+    dev = _dev(frames, target, params, out, target_out)
+    f_out = _out_like(out, frames.shape, frames_dtype, dev, "augment_clips: out")
+    t_out = None if target is None else _out_like(target_out, target.shape, target.dtype, dev, "augment_clips: target_out")
+    if B * T > 0 and (f_out.data_ptr() == frames.data_ptr() or (target is not None and t_out.data_ptr() == target.data_ptr())):
+        raise GdkvmError("augment_clips: the outputs must not alias the inputs (a gather)")
+    with torch.cuda.device(dev):
+        rc = lib.gdkvm_augment_clips(_ptr(frames), _ptr(target), _ptr(params), _ptr(f_out), _ptr(t_out), B, T, C, H, W, _io_dtype(f_out),
+                                     1 if target is None else target.element_size(), int(fill_label), _stream(dev))
+    _check(rc, "gdkvm_augment_clips")
+    return f_out, t_out
 
 
 def bias_act_(x: torch.Tensor, bias: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = True) -> torch.Tensor:

@@ -32,13 +32,19 @@ class DevicePrefetcher:
     for the next batch; an exception in the loader or the staging is re-raised in the consumer).  Off by default: measured at the EchoNet
     shape it is SLOWER (1.23 against 1.05 ms per batch, profiles/r06_v_pipeline_probe.txt) -- the loop is not bound by host work (a graph
     launch is 0.17 ms, the staging calls ~0.1 ms) but by the host-to-device copies themselves, which take 2-3x their stand-alone time
-    beside the forward's kernels; a second thread only adds hand-offs.  Useful when the LOADER is slow (decoding in the main process)."""
+    beside the forward's kernels; a second thread only adds hand-offs.  Useful when the LOADER is slow (decoding in the main process).
+    augment (a data.ClipAugment; training): uint8 clips are warped WHILE they are cast -- the batch's parameter rows
+    (augment.params(epoch, batch index, ...)) cross on the copy stream behind the batch, and one ops.augment_clips call on the cast stream
+    takes the place of the cast and the target copy, same events, same per-slot buffers; labels keep their dtype, pixels whose source lies
+    outside the frame get data.IGNORE_LABEL.  None (default): the code below runs exactly as without the argument."""
 
     def __init__(self, loader: Iterable, device: torch.device, slots: int = 3, frames_dtype: Optional[torch.dtype] = None,
-                 target_dtype: Optional[torch.dtype] = None, threaded: bool = False):
+                 target_dtype: Optional[torch.dtype] = None, threaded: bool = False, augment=None, epoch: int = 0):
         if slots < 2:
             raise ValueError("DevicePrefetcher needs at least two slots")
         self.loader, self.device, self.slots, self.threaded = loader, device, slots, threaded
+        self.augment, self.epoch, self._staged = augment, epoch, 0
+        self._par = [None] * slots              # per slot (augment): the pinned and the device copy of the batch's parameter rows
         self.frames_dtype, self.target_dtype = frames_dtype, target_dtype
         self.stream = torch.cuda.Stream(device=device)
         # the casts run on a stream of their OWN (round 6): behind the copy on the copy stream, every batch made the DMA engine wait for a
@@ -56,6 +62,14 @@ class DevicePrefetcher:
 
     def _stage(self, slot: int, batch) -> Tuple[torch.Tensor, torch.Tensor, torch.cuda.Event]:
         frames, target = batch
+        if self.augment is not None:
+            if frames.dtype != torch.uint8 or frames.dim() != 5:
+                raise ValueError(f"DevicePrefetcher(augment=...): clips are augmented as uint8 [B,T,C,H,W] batches, the loader gave {frames.dtype} "
+                                 f"{tuple(frames.shape)}")
+            if self.target_dtype not in (None, target.dtype):
+                raise ValueError(f"DevicePrefetcher(augment=...): labels are warped in their own dtype ({target.dtype}), target_dtype={self.target_dtype}")
+            rows = self.augment.params(self.epoch, self._staged, frames.shape[0], frames.shape[3], frames.shape[4])
+        self._staged += 1
         dev = self._dev[slot]
         if dev is None or dev[0].shape != frames.shape or dev[0].dtype != frames.dtype or dev[1].shape != target.shape or dev[1].dtype != target.dtype:
             dev = self._dev[slot] = (torch.empty(frames.shape, dtype=frames.dtype, device=self.device),
@@ -73,6 +87,12 @@ class DevicePrefetcher:
             pin[0].copy_(frames)                # (host memcpy into page-locked memory: what makes the H2D copy asynchronous)
             pin[1].copy_(target)
         self._pinned[slot] = pin
+        if self.augment is not None:
+            par = self._par[slot]
+            if par is None or par[0].shape != rows.shape:
+                par = self._par[slot] = (torch.empty(rows.shape, dtype=torch.float32, pin_memory=True),
+                                         torch.empty(rows.shape, dtype=torch.float32, device=self.device))
+            par[0].copy_(rows)                  # (its previous copy has left it: `copied` above covers the rows too)
         with torch.cuda.stream(self.stream):
             if self._free[slot] is not None:
                 self.stream.wait_event(self._free[slot])
@@ -80,13 +100,15 @@ class DevicePrefetcher:
                 self.stream.wait_event(self._cast_done[slot])          # (the slot's raw buffers were last read by its previous cast)
             dev[0].copy_(pin[0], non_blocking=True)
             dev[1].copy_(pin[1], non_blocking=True)
+            if self.augment is not None:
+                par[1].copy_(par[0], non_blocking=True)                # (read by the slot's cast: _cast_done above guards it like the raw buffers)
             copied = torch.cuda.Event()
             copied.record(self.stream)            # (the pinned buffers are free again once this has passed)
         with torch.cuda.stream(self.cast_stream):
             self.cast_stream.wait_event(copied)
             if self._free[slot] is not None:
                 self.cast_stream.wait_event(self._free[slot])          # (the cast buffers of the slot are the consumer's inputs)
-            out_f, out_t = self._convert(slot, dev[0], dev[1])
+            out_f, out_t = self._convert(slot, dev[0], dev[1]) if self.augment is None else self._augment(slot, dev[0], dev[1], par[1])
             ev = torch.cuda.Event()
             ev.record(self.cast_stream)
             self._cast_done[slot] = ev
@@ -116,6 +138,17 @@ class DevicePrefetcher:
             conv[1].copy_(target)
             out_t = conv[1]
         return out_f, out_t
+
+    def _augment(self, slot: int, frames: torch.Tensor, target: torch.Tensor, rows: torch.Tensor):
+        """The batch warped and cast by ONE gdkvm_augment_clips launch into this slot's own buffers (called under the cast stream)."""
+        from . import ops
+        from .data import IGNORE_LABEL
+        fdt = self.frames_dtype or torch.float32
+        conv = self._conv[slot]
+        if conv is None or conv[0].shape != frames.shape or conv[0].dtype != fdt or conv[1].shape != target.shape or conv[1].dtype != target.dtype:
+            conv = self._conv[slot] = (torch.empty(frames.shape, dtype=fdt, device=self.device),
+                                       torch.empty(target.shape, dtype=target.dtype, device=self.device))
+        return ops.augment_clips(frames, target, rows, fdt, fill_label=IGNORE_LABEL, out=conv[0], target_out=conv[1])
 
     def _hand_out(self, queue):
         s, f, t, ev = queue.pop(0)

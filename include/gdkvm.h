@@ -569,6 +569,27 @@ int gdkvm_seg_loss_fwd(const void* z, const void* target, float* out, void* ws, 
 int gdkvm_seg_loss_bwd(const void* z, const void* target, const void* ws, size_t ws_bytes, const float* grad_out, void* dz,
                        int images, int C, int h, int w, int H, int W, int io_dtype, int target_bytes, void* stream);
 
+/* Training-clip augmentation folded into the uint8 -> [0, 1] cast of a batch (gdkvm_amd.pipeline.DevicePrefetcher): one pass, one launch.
+ * frames uint8 [B,T,C,H,W]; target [B,T,H,W] (target_bytes = 1: uint8, 8: int64; target and target_out alike, both may be NULL together);
+ * params fp32 [B,12] on the device, one row per clip -- every frame of a clip gets the same warp (the memory path needs temporally
+ * consistent geometry):  m00 m01 m02 m10 m11 m12 gain bias gamma 0 0 0.  frames_out [B,T,C,H,W] in io_dtype.
+ *   coordinates  destination pixel index (x, y) reads source index sx = m00 x + m01 y + m02, sy = m10 x + m11 y + m12; pixel centres sit
+ *                at integers.  The matrix is the INVERSE (destination -> source) map, composed on the host: the kernel does no trigonometry.
+ *   intensity    per clip a 256-entry table: u = float(b) * (1.0f/255.0f);  LUT[b] = clamp(fmaf(gain, gamma == 1 ? u : powf(u, gamma), bias), 0, 1)
+ *                (built once per workgroup in LDS; a workgroup never spans two clips).
+ *   frames       bilinear sampling of LUT[byte]: with x0 = floor(sx), fx = sx - x0 (likewise y) and the taps a = (x0, y0), b = (x0+1, y0),
+ *                c = (x0, y0+1), d = (x0+1, y0+1):  out = (1-fy) ((1-fx) a + fx b) + fy ((1-fx) c + fx d).  A tap whose index lies outside the
+ *                frame is 0 and is not loaded.  Rounded once to io_dtype.
+ *   target       nearest neighbour: ix = floor(sx + 0.5), iy = floor(sy + 0.5); the label is copied unchanged when the index lies inside
+ *                the frame, otherwise it is fill_label (in [0, 255]; gdkvm_amd.data.IGNORE_LABEL makes the loss and the Dice counts skip
+ *                the invented corners).
+ *   identity     with the row 1 0 0 0 1 0 1 0 1 the frames are fp32(byte) * fp32(1/255) rounded once to io_dtype -- bit for bit the plain
+ *                cast -- and the target is copied unchanged.
+ * 16-byte stores when H*W is a multiple of the 16-byte vector (8 pixels bf16, 4 fp32) and the output bases are 16-byte aligned, element
+ * stores otherwise; B*T <= 65535 (one grid row per frame); B*T == 0 is GDKVM_OK without a launch. */
+int gdkvm_augment_clips(const uint8_t* frames, const void* target, const float* params, void* frames_out, void* target_out,
+                        int B, int T, int C, int H, int W, int io_dtype, int target_bytes, int fill_label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

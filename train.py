@@ -31,7 +31,7 @@ def main(argv=None):
 
     from gdkvm_amd import ops
     from gdkvm_amd.config import load_config
-    from gdkvm_amd.data import build_dataset
+    from gdkvm_amd.data import build_augment, build_dataset
     from gdkvm_amd.distributed import init_from_env
     from gdkvm_amd.model import GDKVM, GDKVMConfig
     from gdkvm_amd.pipeline import DevicePrefetcher, make_train_step
@@ -59,6 +59,8 @@ def main(argv=None):
                                      num_workers=2, persistent_workers=True, pin_memory=True)
     run = OfflineRun(cfg.run_dir, cfg.to_dict(), cfg.eval_stage.wandb_mode, enabled=rank == 0)
     amp = torch.bfloat16 if cfg.precision == "bf16" else None
+    # augment.enabled: clips are warped on the GPU inside the prefetcher's cast pass (one affine map and intensity curve per clip)
+    augment = build_augment(cfg, rank)
 
     if len(dl) == 0:
         raise SystemExit(f"train.py: {len(ds)} clips give no full batch of {cfg.batch_size} on each of {world} rank(s) (drop_last): "
@@ -73,7 +75,7 @@ def main(argv=None):
         if sampler is not None:
             sampler.set_epoch(epoch)
         # host batches staged through pinned memory and copied on a side stream while the previous step computes (DevicePrefetcher)
-        for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=torch.float32):
+        for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=torch.float32, augment=augment, epoch=epoch):
             if train_one is None:
                 # the step in the form bench.py measures: one hipGraph replay (forward + backward + gradient all-reduce node + fused AdamW);
                 # a capture that fails falls back to the eager DistributedDataParallel step, loudly
