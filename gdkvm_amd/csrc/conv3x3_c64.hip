@@ -121,10 +121,25 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         const int ty = p / TW, tx = p - ty * TW;
         pbase[m] = (unsigned)((ty * BW + tx) * CV_PIX + g * 16);
     }
+    // DESC: the same pixel's BYTE offset in the output (and the residual) from the first byte of the frame for the tile at row 0, channels
+    // 32wn + 8g ..; pixels the tile does not have carry CV_DEAD.  Output and residual go through descriptors over the tile's frame like the
+    // band, so a row past the frame is out of range: its residual reads as zeros and its store is dropped -- every m-tile issues exactly one
+    // load and one store whatever its pixels, which is what makes the epilogue's wait counts exact.
+    unsigned o_rel[DESC ? 4 : 1];
+    if constexpr (DESC) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int p = 16 * (4 * wm + m) + li, py = p / TW, px = p - py * TW;
+            o_rel[m] = (p < NPIX && px < a.W) ? (unsigned)(((py * a.W + px) * CV_C + 32 * wn + 8 * g) * 2) : CV_DEAD;
+        }
+    }
 
-    // Per tile: MFMAs from buffer `cur` | barrier (+ vmcnt(0): the other buffer's band, issued a whole tile ago, has landed)
-    // | this tile's epilogue | DMA of the tile after next into `cur`.  The stores and the DMA are never waited for right
-    // after being issued: the next wait is a tile of MFMAs later.
+    // Per tile: MFMAs from buffer `cur`, with no wait on memory (the weights were completed before the loop) | barrier + vmcnt(0):
+    // outstanding then are the other buffer's band, requested a whole MFMA phase ago, and the previous epilogue's stores, older still
+    // | this tile's epilogue: (descriptor form) the residual vectors requested together and consumed under counted waits that leave
+    // the younger loads and the stores outstanding | DMA of the tile after next into `cur`.  Neither the stores nor the DMA are
+    // waited for before the next barrier.  The per-lane pointer form keeps the compiler's epilogue (a vmcnt(0) behind each residual
+    // load, which also covers the previous m-tile's store).
     int tile = blockIdx.x, cur = 0;
     TilePos tpos{DESC ? tile / a.tiles_y : 0, DESC ? tile % a.tiles_y : 0}, fpos = tpos;      // (DESC) this tile; the next tile to fetch
     if (tile < ntiles) fetch(tile, fpos, 0);               // (the first band is on its way while the weights load)
@@ -157,6 +172,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias + 32 * wn + 8 * g + 4 * nt);
         bia[nt][0] = b4[0]; bia[nt][1] = b4[1]; bia[nt][2] = b4[2]; bia[nt][3] = b4[3];
     }
+    // The weights and the bias are complete HERE, once: as operands of an (empty) asm statement they have to be in their registers in
+    // front of it, so the compiler's one wait for them stands here and no pending load of theirs is carried into the tile loop.  Left
+    // to its own placement it waited at their first uses, inside the loop's MFMA phase (vmcnt(29), then 11 down to 2): right on the
+    // first tile, and on every later tile a wait for most of the band requested an epilogue earlier, which has until the barrier.
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+        asm volatile("" : "+v"(wf[nt][0]), "+v"(wf[nt][1]), "+v"(wf[nt][2]), "+v"(wf[nt][3]), "+v"(wf[nt][4]), "+v"(wf[nt][5]), "+v"(wf[nt][6]), "+v"(wf[nt][7]),
+                          "+v"(wf[nt][8]), "+v"(wf[nt][9]), "+v"(wf[nt][10]), "+v"(wf[nt][11]), "+v"(wf[nt][12]), "+v"(wf[nt][13]), "+v"(wf[nt][14]),
+                          "+v"(wf[nt][15]), "+v"(wf[nt][16]), "+v"(wf[nt][17]));
+    asm volatile("" : "+v"(bia[0][0]), "+v"(bia[0][1]), "+v"(bia[0][2]), "+v"(bia[0][3]), "+v"(bia[1][0]), "+v"(bia[1][1]), "+v"(bia[1][2]), "+v"(bia[1][3]));
 
     __syncthreads();                                       // (vmcnt(0) + barrier: the first band has landed)
     if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x, fpos, 1);
@@ -202,15 +227,62 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         __syncthreads();                                   // everyone is done with this band; the next one has landed
 
         // epilogue: lane (li, g) holds channels 32wn + 8g .. +7 of pixel 16(4wm+m) + li (tile nt: the four channels 4nt ..)
-        const int t2 = DESC ? 0 : tile / a.tiles_x, tx = DESC ? 0 : tile % a.tiles_x, ty = DESC ? tpos.ty : t2 % a.tiles_y, n = DESC ? tpos.n : t2 / a.tiles_y;
-        advance(tpos);
+        typedef float f32x2 __attribute__((ext_vector_type(2)));           // packed fp32 pairs: v_pk_add_f32 / v_pk_max_f32
+        if constexpr (DESC) {
+            // The residual vectors of ALL the wave's m-tiles are requested together, right behind the barrier, and consumed one by one
+            // under a counted wait.  The loads are asm, so the compiler neither counts them nor answers their uses with vmcnt(0) (which
+            // covered the previous m-tile's store: four serial chains of load round trip + store acknowledgement per tile); operations
+            // retire from the counter in issue order, and behind residual m stand the NM - 1 - m younger loads and the m stores of the
+            // m-tiles before it: NM - 1 younger operations for every m, none of which is waited for.
+            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            const long long fo = (long long)tpos.n * a.H * a.W * CV_C;
+            const unsigned fbytes = (unsigned)(a.H * a.W * CV_C * 2), ts = (unsigned)(tpos.ty * CV_TH * a.W * CV_C * 2);
+            advance(tpos);
+            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(a.y + fo, 0, (int)fbytes, 0x00020000);
+            const unsigned long long ra = reinterpret_cast<unsigned long long>(a.res + fo);
+            const u32x4 rrs = {(unsigned)ra, (unsigned)(ra >> 32) & 0xffffu, fbytes, 0x00020000u};
+            auto epilogue = [&](auto nm_c) __attribute__((always_inline)) {
+                constexpr int NM = decltype(nm_c)::value;
+                unsigned vo[NM];
+                u32x4 rr[NM];
+#pragma unroll
+                for (int m = 0; m < NM; ++m) vo[m] = o_rel[m] + ts;
+                if (a.res) {
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(rr[m]) : "v"(vo[m]), "s"(rrs) : "memory");
+                }
+#pragma unroll
+                for (int m = 0; m < NM; ++m) {
+                    f32x2 v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        v[q] = f32x2{acc[m][q >> 1][2 * (q & 1)], acc[m][q >> 1][2 * (q & 1) + 1]} + f32x2{bia[q >> 1][2 * (q & 1)], bia[q >> 1][2 * (q & 1) + 1]};
+                    if (a.res) {
+                        asm volatile("s_waitcnt vmcnt(%1)" : "+v"(rr[m]) : "n"(NM - 1) : "memory");
+                        const unsigned rw[4] = {rr[m][0], rr[m][1], rr[m][2], rr[m][3]};
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) v[q] += f32x2{__uint_as_float(rw[q] << 16), __uint_as_float(rw[q] & 0xffff0000u)};
+                    }
+                    const float lo = a.relu ? 0.f : -INFINITY;
+                    u32x4 ow;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        v[q] = __builtin_elementwise_max(v[q], f32x2{lo, lo});
+                        ow[q] = (unsigned)f32_to_bf16(v[q][0]) | ((unsigned)f32_to_bf16(v[q][1]) << 16);
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b128(ow, yrs, (int)vo[m], 0, 0);
+                }
+            };
+            if (wm == 0 || NM1 == 4) epilogue(std::integral_constant<int, (NMT < 4 ? NMT : 4)>{});
+            else if constexpr (NM1 > 0 && NM1 < 4) epilogue(std::integral_constant<int, (NM1 > 0 ? NM1 : 1)>{});
+        } else {
+        const int t2 = tile / a.tiles_x, tx = tile % a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int p = 16 * (4 * wm + m) + li;
             const int py = p / TW, px = p - py * TW, yy = ty * CV_TH + py, xx = tx * TW + px;
             if (p >= NPIX || yy >= a.H || xx >= a.W) continue;
             const size_t o = (((size_t)n * a.H + yy) * a.W + xx) * CV_C + 32 * wn + 8 * g;
-            typedef float f32x2 __attribute__((ext_vector_type(2)));       // packed fp32 pairs: v_pk_add_f32 / v_pk_max_f32
             f32x2 v[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -230,9 +302,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
             }
             *reinterpret_cast<uint4*>(a.y + o) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
         }
-        // the band of the tile after next, into the buffer just consumed.  Issued BEHIND the epilogue: the compiler cannot order
-        // LDS-DMA against register loads and waits with vmcnt(0) for the residual -- ahead of the epilogue that wait also covered
-        // the band just requested from HBM (+9 us per residual layer); the band still has a whole tile of MFMAs to land.
+        }
+        // the band of the tile after next, into the buffer just consumed.  Issued BEHIND the epilogue, where it has a whole tile of MFMAs
+        // to land: in front of it the residual waits would cover it (the counter retires in issue order), in the pointer form as
+        // vmcnt(0) (+9 us per residual layer, round 5), in the descriptor form unless the counts allowed for the wave's 7 or 8 pieces
+        // (not built: DESIGN.md section 6, "After round 6: prefetch waits").
         if (tile + 2 * (int)gridDim.x < ntiles) fetch(tile + 2 * gridDim.x, fpos, cur);
         advance(fpos);
     }

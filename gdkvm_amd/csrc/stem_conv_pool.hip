@@ -41,6 +41,8 @@ struct StemArgs {
 // 4-byte column pairs (channel c, row parity p: x[c][2Y + p][2X .. 2X + 1]) -- so the space-to-depth pass (gdkvm_stem_s2d: 38 MB read,
 // 51 MB written and read back, 20 us of a 1 ms forward) disappears.  The pieces the LDS-DMA fetched are fetched into registers a tile
 // ahead (16 dwords per lane) and written to the other band buffer behind the tile's MFMAs; same bytes in LDS, hence the same results.
+// (Round 9: the loads are buffer loads with tile-invariant per-lane offsets and nothing in the loop waits for them in front of the MFMAs;
+// as flat loads under branches behind two index divisions, each tile drained them -- one exposed memory round trip per tile.)
 // POOL = false (round 4, the TRAINING stem's forward): the raw convolution -- no bias, no ReLU, no pooling -- written to memory as bf16
 // [N, Hs, Ws, 64], in non-overlapping tiles of 9 x 57 outputs (BatchNorm needs the full-resolution activation; the library's implicit
 // GEMM took 183 us for it behind a 46 us zero-fill of its output).
@@ -64,14 +66,34 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
             const int co = 32 * wn + 8 * (li >> 2) + 4 * nt + (li & 3);
             wf[nt][ks] = *reinterpret_cast<const bf16x8*>(a.w + (size_t)co * 256 + 32 * ks + 8 * g);
         }
-    float bia[8];
-    {
+    float bia[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (POOL) {                                   // (the convolution-only form has no bias: the pointer is null there)
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + 32 * wn + 8 * g), b1 = *reinterpret_cast<const f32x4*>(a.bias + 32 * wn + 8 * g + 4);
         bia[0] = b0[0]; bia[1] = b0[1]; bia[2] = b0[2]; bia[3] = b0[3]; bia[4] = b1[0]; bia[5] = b1[1]; bia[6] = b1[2]; bia[7] = b1[3];
     }
+    // The weights and the bias are complete HERE, once: as operands of an (empty) asm statement they have to be in their registers in
+    // front of it, so the compiler puts its one wait for them here and carries no pending load of theirs into the tile loop -- left to
+    // its own placement the wait stood in front of the tile's first MFMA, where on every later tile it drained the look-ahead loads.
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+        asm volatile("" : "+v"(wf[nt][0]), "+v"(wf[nt][1]), "+v"(wf[nt][2]), "+v"(wf[nt][3]), "+v"(wf[nt][4]), "+v"(wf[nt][5]), "+v"(wf[nt][6]), "+v"(wf[nt][7]));
+    if constexpr (POOL) asm volatile("" : "+v"(bia[0]), "+v"(bia[1]), "+v"(bia[2]), "+v"(bia[3]), "+v"(bia[4]), "+v"(bia[5]), "+v"(bia[6]), "+v"(bia[7]));
+
+    // A tile is (frame n, row tile ty, column tile tx); the workgroup's tiles are gridDim.x apart, so the triple advances by a fixed step
+    // with two carries (conv3x3_c64.hip's advance()): the tile index is split by divisions once, here, not twice per tile.
+    struct TilePos { int n, ty, tx; };
+    const int step_tx = (int)gridDim.x % a.tiles_x, step_q = (int)gridDim.x / a.tiles_x, step_ty = step_q % a.tiles_y, step_n = step_q / a.tiles_y;
+    auto advance = [&](TilePos& p) __attribute__((always_inline)) {
+        p.tx += step_tx;
+        if (p.tx >= a.tiles_x) { p.tx -= a.tiles_x; ++p.ty; }
+        p.ty += step_ty;
+        if (p.ty >= a.tiles_y) { p.ty -= a.tiles_y; ++p.n; }
+        p.n += step_n;
+    };
 
     // band fetch by LDS-DMA: slot d = 2 pix + c (c = 16-byte half of the pixel's 16 channels), piece j = w + 8u
     constexpr int PP = (SP_PIECES + 7) / 8;
+    static_assert(PP == 4, "put_nchw names the sixteen look-ahead registers");
     auto fetch = [&](int tile, int buf) __attribute__((always_inline)) {
         const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
         const int y0 = (POOL ? 2 * SP_TPY * ty - 1 : SP_CR * ty) - 2, x0 = (POOL ? 2 * SP_TPX * tx - 1 : (SP_CC - 7) * tx) - 2;       // input row / column of band pixel (0, 0)
@@ -88,50 +110,83 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
         }
     };
 
-    // NCHW: the same slots from the frames: slot d = 2 pix + half holds channel pairs (2 half, 2 half + 1) x row parity (0, 1)
+    // NCHW: the same slots from the frames: slot d = 2 pix + half holds channel pairs (2 half, 2 half + 1) x row parity (0, 1).
+    // The 16 loads of a tile are unconditional buffer loads through a descriptor over the tile's frame (all its channels).  What does not
+    // depend on the tile is computed once, here, as per-lane 32-bit values: the slot's band position (by << 8 | bx, -1 = no such slot) and
+    // its BYTE offset from the band's (0, 0) pixel inside a channel plane, and per load the plane / row-parity offset.  A tile adds a
+    // scalar (its band origin) and the row / column test; a slot outside the image gets SP_DEAD, which is out of the descriptor's range
+    // with any plane offset added (the launcher keeps four planes below 2^31 bytes), and so do the planes of channels >= Cf: the range
+    // check supplies the zeros, no load stands under a branch, and no address outside the frame is formed.
+    constexpr unsigned SP_DEAD = 0x80000000u;
     unsigned stage[PP][4];
-    auto fetch_nchw = [&](int tile) __attribute__((always_inline)) {
-        const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
-        const int y0 = (POOL ? 2 * SP_TPY * ty - 1 : SP_CR * ty) - 2, x0 = (POOL ? 2 * SP_TPX * tx - 1 : (SP_CC - 7) * tx) - 2;
+    int s_byx[NCHW ? PP : 1];
+    unsigned s_rel[NCHW ? PP : 1], s_ce[4];
+    if constexpr (NCHW) {
         const int H = 2 * a.Hs, W = 2 * a.Ws;
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
-            const int j = w + 8 * u, d = 64 * j + lane, pix = d >> 1, half = d & 1;
-            const int by = pix / SP_BC, bx = pix - by * SP_BC, yy = y0 + by, xx = x0 + bx;
-            const bool ok = j < SP_PIECES && pix < SP_BR * SP_BC && yy >= 0 && yy < a.Hs && xx >= 0 && xx < a.Ws;
+            const int j = w + 8 * u, d = 64 * j + lane, pix = d >> 1;
+            const int by = pix / SP_BC, bx = pix - by * SP_BC;
+            s_byx[u] = (j < SP_PIECES && pix < SP_BR * SP_BC) ? (by << 8 | bx) : -1;
+            s_rel[u] = (unsigned)((2 * by * W + 2 * bx) * 2);
+        }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {                   // e = 2 (channel within the half) + row parity
-                const int c = 2 * half + (e >> 1);
-                const bool live = ok && c < a.Cf;
-                const bf16_t* src = live ? a.xf + ((((size_t)n * a.Cf + c) * H + 2 * yy + (e & 1)) * W + 2 * xx) : reinterpret_cast<const bf16_t*>(&g_stem_zero16);
-                stage[u][e] = *reinterpret_cast<const unsigned*>(src);
-            }
+        for (int e = 0; e < 4; ++e)                         // e = 2 (channel within the half) + row parity
+            s_ce[e] = (unsigned)(((2 * (lane & 1) + (e >> 1)) * H + (e & 1)) * W * 2);
+    }
+    auto fetch_nchw = [&](TilePos p, bool on) __attribute__((always_inline)) {          // !on: every slot dead (nothing is read)
+        const int y0 = (POOL ? 2 * SP_TPY * p.ty - 1 : SP_CR * p.ty) - 2, x0 = (POOL ? 2 * SP_TPX * p.tx - 1 : (SP_CC - 7) * p.tx) - 2;
+        const int H = 2 * a.Hs, W = 2 * a.Ws;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.xf + (long long)(on ? p.n : 0) * a.Cf * H * W), 0,
+                                                                              a.Cf * H * W * 2, 0x00020000);
+        const unsigned ts = (unsigned)((2 * y0 * W + 2 * x0) * 2);
+#pragma unroll
+        for (int u = 0; u < PP; ++u) {
+            const int yy = y0 + (s_byx[u] >> 8), xx = x0 + (s_byx[u] & 255);
+            const bool ok = on & (s_byx[u] >= 0) & ((unsigned)yy < (unsigned)a.Hs) & ((unsigned)xx < (unsigned)a.Ws);      // (no short circuit: no branch)
+            const unsigned b = ok ? s_rel[u] + ts : SP_DEAD;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                stage[u][e] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(b + s_ce[e]), 0, 0);
         }
     };
     auto put_nchw = [&](int buf) __attribute__((always_inline)) {
+        // the ONE wait for the look-ahead registers: all sixteen are operands of this (empty) statement, so the compiler completes them
+        // here, counted against whatever is younger, and carries no pending load past it (else it re-waits wherever it reuses a register)
+        asm volatile("" : "+v"(stage[0][0]), "+v"(stage[0][1]), "+v"(stage[0][2]), "+v"(stage[0][3]), "+v"(stage[1][0]), "+v"(stage[1][1]), "+v"(stage[1][2]), "+v"(stage[1][3]),
+                          "+v"(stage[2][0]), "+v"(stage[2][1]), "+v"(stage[2][2]), "+v"(stage[2][3]), "+v"(stage[3][0]), "+v"(stage[3][1]), "+v"(stage[3][2]), "+v"(stage[3][3]));
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
             const int j = w + 8 * u;
-            if (j < SP_PIECES)
+            if (8 * u + 7 < SP_PIECES || j < SP_PIECES)    // (only the last piece row depends on the wave)
                 *reinterpret_cast<uint4*>(band2 + buf * SP_BAND_BYTES + 1024 * j + 16 * lane) = make_uint4(stage[u][0], stage[u][1], stage[u][2], stage[u][3]);
         }
     };
 
     const unsigned xoff = (unsigned)((16 * wm + li) * 32 + g * 16);          // this lane's pixel column / K group inside a band row
     int tile = blockIdx.x, cur = 0;
+    TilePos tpos;                                                                        // this tile (divisions: once per workgroup)
+    { const int t2 = tile / a.tiles_x; tpos.tx = tile - t2 * a.tiles_x; tpos.n = t2 / a.tiles_y; tpos.ty = t2 - tpos.n * a.tiles_y; }
     if (tile < ntiles) {
-        if constexpr (NCHW) { fetch_nchw(tile); put_nchw(0); }
+        if constexpr (NCHW) { fetch_nchw(tpos, true); put_nchw(0); }
         else fetch(tile, 0);
     }
     __syncthreads();
+    // NCHW, per tile: the next tile's 16 loads are issued | this tile's MFMAs and LDS tile | the one wait for those loads, in front of
+    // put_nchw (they are the youngest memory operations then: nothing younger is waited for) | barrier | pooling and the pooled stores,
+    // which are not waited for until the next tile's put_nchw, a whole MFMA phase later.  The last tile issues the loads with every slot
+    // dead and writes the zeros: the loop body has no branch around its loads.
     for (; tile < ntiles; tile += gridDim.x, cur ^= 1) {
         const bool more = tile + (int)gridDim.x < ntiles;
-        if (more) {                                                                      // lands behind this tile's MFMAs
-            if constexpr (NCHW) fetch_nchw(tile + gridDim.x);
-            else fetch(tile + gridDim.x, cur ^ 1);
-        }
+        TilePos npos = tpos;
+        advance(npos);
+        if constexpr (NCHW) {
+            fetch_nchw(npos, more);
+            __builtin_amdgcn_sched_barrier(0);                                           // (the loads stay in front of the MFMAs)
+        } else if (more) fetch(tile + gridDim.x, cur ^ 1);                               // lands behind this tile's MFMAs
         const unsigned char* band = band2 + cur * SP_BAND_BYTES;
-        const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
+        const int tx = tpos.tx, ty = tpos.ty, n = tpos.n;
+        tpos = npos;
         const int cy0 = POOL ? 2 * SP_TPY * ty - 1 : SP_CR * ty, cx0 = POOL ? 2 * SP_TPX * tx - 1 : (SP_CC - 7) * tx;   // convolution row / column of tile position (0, 0)
         const int cx = cx0 + 16 * wm + li;                                                // this lane's convolution column
         const bool col_ok = cx >= 0 && cx < a.Ws && (POOL || 16 * wm + li < SP_CC - 7);   // (conv only: 57 columns per tile, no overlap)
@@ -190,7 +245,7 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
                 *reinterpret_cast<uint4*>(ctile + (cr * SP_CC + 16 * wm + li) * SP_CPIX + (32 * wn + 8 * g) * 2) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
             }
         }
-        if constexpr (NCHW) { if (more) put_nchw(cur ^ 1); }   // (the other buffer was last read a tile ago, two barriers back)
+        if constexpr (NCHW) put_nchw(cur ^ 1);              // (the other buffer was last read a tile ago, two barriers back)
         __syncthreads();                                   // the convolution tile is complete (and the next band has landed)
 
         // ---- 3x3 / stride 2 max-pool out of LDS: item = (pooled row q, pooled column px, 8-channel group) ------------------
@@ -401,6 +456,8 @@ static int stem_conv_pool_impl(const char* who, const void* xs, const void* xf, 
     if (!pool) { a.tiles_x = (Ws + SP_CC - 8) / (SP_CC - 7); a.tiles_y = (Hs + SP_CR - 1) / SP_CR; }       // 9 x 57 convolution outputs per tile
     const long long ntiles = (long long)N * a.tiles_x * a.tiles_y;
     if (ntiles > 0x7fffffffLL) return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: too many tiles", who);
+    // NCHW: the band's loads go through a buffer descriptor over a frame, with 32-bit offsets of which 2^31 and above stand for "zeros"
+    if (xf && (long long)(8 * Hs + 2) * (2 * Ws) * 2 >= 0x7fffffffLL) return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: frame of %d x %d too large", who, 2 * Hs, 2 * Ws);
     const size_t lds = 2 * (size_t)SP_BAND_BYTES + SP_CONV_BYTES;
     {   // > 64 KiB of dynamic LDS needs the opt-in once per kernel and device; lock-free cache as in gdr_scan.hip
         static std::atomic<unsigned long long> done_mask{0};
