@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Evaluation entry point: per-class Dice of the argmax masks over a dataset split, clips sharded over the GPUs of one
-node (no data-path collective; only the integer Dice counts are summed at the end).
+"""Evaluation entry point: per-class Dice / IoU of the argmax masks over a dataset split and, for class `data.lv_class`, the left-ventricular
+volumes and ejection fraction measured from the masks on the device (ops.lv_measure / lv_ef: pixel^3 of the network's input grid, isotropic
+pixels assumed; EF is a ratio); clips sharded over the GPUs of one node (no data-path collective; only the integer Dice counts and the eight
+EF sums are summed at the end).
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [key=value ...]"""
 from __future__ import annotations
@@ -51,6 +53,8 @@ def main(argv=None):
     ds = build_dataset(cfg, args.split, as_uint8=True)            # bytes across PCIe; cast and scaled on the GPU
     lo, hi = shard_range(len(ds), world, rank)
     counts = torch.zeros(cfg.data.num_classes, 3, dtype=torch.int64, device=dev)
+    lv_cls = cfg.data.lv_class
+    ef_sums = torch.zeros(8, dtype=torch.float64, device=dev)     # ops.ef_summary, accumulated on the device and read once at the end
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -60,18 +64,32 @@ def main(argv=None):
     i = lo
 
     def batches():
-        """(mask, counts) per batch, one batch behind the submissions: the host queues batch i + 1 (copy, cast, replay) before it reads
-        batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time)"""
+        """(mask, counts, target's LV measurement) per batch, one batch behind the submissions: the host queues batch i + 1 (copy, cast, replay)
+        before it reads batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time).
+        The TARGET is measured right behind the submission, on the stream where the prefetcher handed it out: its slot is recycled once the
+        consumer asks for the next batch, so nothing may read it later."""
         pending = None
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
             nxt = runner.submit(frames, target)
+            if lv_cls >= 0:
+                t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
+                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous())
+            else:
+                nxt = (nxt, None, None)
             if pending is not None:
-                yield pending.get()
+                yield pending[0].get() + pending[1:]
             pending = nxt
         if pending is not None:
-            yield pending.get()
+            yield pending[0].get() + pending[1:]
 
-    for mask, c in batches():
+    for mask, c, t_vol, t_npix in batches():
+        if lv_cls >= 0:
+            # the prediction's volumes at the TARGET's end-diastolic / end-systolic frames (EchoNet-Dynamic: the two traced frames; unlabelled
+            # frames hold no pixel of the class and are no candidates); a clip counts when its target has two such frames and a volume
+            p_stats, _, p_geom = ops.lv_measure(mask, cls=lv_cls)
+            r_idx, r_val = ops.lv_ef(t_vol, t_npix)
+            _, p_val = ops.lv_ef(p_geom[..., 1], p_stats[..., 0], pick_vol=t_vol, pick_npix=t_npix)
+            ef_sums += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
         # only frames that carry labels count (EchoNet-Dynamic: the two traced frames of a clip -- gdkvm_amd.data.IGNORE_LABEL everywhere
         # else, where a predicted pixel must not enter |A|): a labelled frame has a non-empty target in some class
         labelled = (c[..., 2].sum(-1, keepdim=True) > 0).unsqueeze(-1)
@@ -84,12 +102,20 @@ def main(argv=None):
             vis_left -= 1
         i += mask.shape[0]
     if world > 1:
-        torch.distributed.all_reduce(counts)                      # the only exchange: 3 integers per class
+        torch.distributed.all_reduce(counts)                      # the only exchanges: 3 integers per class ...
+        if lv_cls >= 0:
+            torch.distributed.all_reduce(ef_sums)                 # ... and the eight EF sums
     if rank == 0:
         dice = ops.dice_from_counts(counts).tolist()
-        print(json.dumps({"split": args.split, "clips": len(ds), "forward": {"graph_replays": runner.replays, "eager_calls": runner.eager_calls},
-                          "dice_per_class": [round(d, 5) for d in dice],
-                          "mean_foreground_dice": round(sum(dice[1:]) / max(len(dice) - 1, 1), 5)}), flush=True)
+        iou = ops.iou_from_counts(counts).tolist()
+        res = {"split": args.split, "clips": len(ds), "forward": {"graph_replays": runner.replays, "eager_calls": runner.eager_calls},
+               "dice_per_class": [round(d, 5) for d in dice],
+               "mean_foreground_dice": round(sum(dice[1:]) / max(len(dice) - 1, 1), 5),
+               "iou_per_class": [round(d, 5) for d in iou],
+               "mean_foreground_iou": round(sum(iou[1:]) / max(len(iou) - 1, 1), 5)}
+        if lv_cls >= 0:
+            res["lv"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.ef_stats(ef_sums.cpu()).items()}
+        print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -23,6 +23,7 @@ class DataCfg:
     frames: int = 10
     size: int = 256
     num_classes: int = 4
+    lv_class: int = 1                # eval.py: the class whose volumes and ejection fraction are measured (ops.lv_measure / lv_ef); -1 = off
 
 
 @dataclass

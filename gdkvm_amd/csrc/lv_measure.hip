@@ -1,0 +1,315 @@
+// lv_measure.hip -- left-ventricular geometry of label masks on the device (the evaluation's epilogue beside the Dice counts): per frame the
+// pixel moments of one class, its long axis, the overlap-weighted disk areas along that axis and the single-plane method-of-disks volume
+// (lv_measure_kernel); per clip the end-diastolic / end-systolic frames and the ejection fraction (lv_ef_kernel).  include/gdkvm.h holds the
+// definition.  Everything up to the disk areas W_j is integer arithmetic: sums are reduced wave-wide by shuffles and per block through LDS, the
+// disk areas are added with 64-bit integer LDS atomics -- integer adds commute, so the result is bit-reproducible.  The one floating-point step
+// in front of integers (the axis, fp64) is evaluated by every lane from the same totals with explicitly un-fused multiplies and adds.
+// ONE 256-lane workgroup per frame: no cross-workgroup reduction, no global atomics, no fences.
+
+#include "gdkvm_common.hpp"
+
+// No fused multiply-add in this file's own arithmetic: the fp64 steps are the definition's operations, one rounding each.  The pragma is what
+// does it -- HIP's own _rn intrinsics are inline functions compiled with contraction allowed, and a product from one still fuses into a sum
+// from the other (v_mul_f64 + v_fmac_f64 in the gfx950 code), so the steps are written with the operators below instead.
+#pragma clang fp contract(off)
+
+namespace {
+
+typedef long long i64;
+typedef unsigned long long u64;
+
+__device__ __forceinline__ double mul_rn(double a, double b) { return a * b; }
+__device__ __forceinline__ double add_rn(double a, double b) { return a + b; }
+__device__ __forceinline__ double sub_rn(double a, double b) { return a - b; }
+
+constexpr int LV_Q = 1 << 16;        // fixed-point scale of the axis
+constexpr int LV_MAX_D = 64;         // disks
+constexpr int LV_RES = 16;           // 16-byte vectors a lane keeps across the passes: 16 x 256 lanes x 16 bytes = a 256 x 256 frame
+
+struct LvArgs {
+    const uint8_t* mask; i64* stats; i64* disks; double* geom;
+    int HW, W, cls, D;
+};
+
+__device__ __forceinline__ i64 wave_sum(i64 v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ i64 wave_min(i64 v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const i64 w = __shfl_xor(v, o); v = w < v ? w : v; }
+    return v;
+}
+__device__ __forceinline__ i64 wave_max(i64 v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const i64 w = __shfl_xor(v, o); v = w > v ? w : v; }
+    return v;
+}
+
+// bit e = byte e of the vector equals cls
+__device__ __forceinline__ unsigned match16(const uint4& v, unsigned cls)
+{
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    unsigned m = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m |= (((w[q] >> (8 * e)) & 0xffu) == cls ? 1u : 0u) << (4 * q + e);
+    return m;
+}
+
+// f(x, y) for every set bit of m; bit e is pixel p + e of the frame (row-major, rows of W)
+template <class F>
+__device__ __forceinline__ void visit(unsigned m, int p, int W, F&& f)
+{
+    if (!m) return;
+    int y = p / W, x = p - y * W, prev = 0;
+    while (m) {
+        const int e = __builtin_ctz(m);
+        m &= m - 1;
+        x += e - prev;
+        prev = e;
+        while (x >= W) { x -= W; ++y; }
+        f(x, y);
+    }
+}
+
+// One pass over the frame's pixels of the class.  RES: the match bits of the lane's vectors are in registers (mk, filled by the first pass);
+// otherwise the vectors are read again (the frame is L2-hot).  edge: bit 0 = the lane's head byte matches, bit 1 = its tail byte.
+template <bool RES, class F>
+__device__ __forceinline__ void sweep(const unsigned (&mk)[LV_RES], const uint4* body, int nvec, int head, int W, unsigned cls, unsigned edge, F&& f)
+{
+    const int tid = threadIdx.x;
+    if (edge & 1u) visit(1u, tid, W, f);
+    if constexpr (RES) {
+#pragma unroll
+        for (int k = 0; k < LV_RES; ++k) visit(mk[k], head + 16 * (tid + 256 * k), W, f);
+    } else {
+        for (int v = tid; v < nvec; v += 256) visit(match16(body[v], cls), head + 16 * v, W, f);
+    }
+    if (edge & 2u) visit(1u, head + 16 * nvec + tid, W, f);
+}
+
+template <bool RES>
+__global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
+{
+    __shared__ i64 s_red[4][6];
+    __shared__ i64 s_mm[4][2];
+    __shared__ u64 s_w[LV_MAX_D];
+    const int tid = threadIdx.x, wv = tid >> 6, HW = a.HW, W = a.W, D = a.D;
+    const size_t f = blockIdx.x;
+    const unsigned cls = (unsigned)a.cls;
+    const uint8_t* base = a.mask + f * (size_t)HW;
+    // a frame's base address is arbitrary (H*W need not be a multiple of 16): up to 15 head bytes, 16-byte vectors, up to 15 tail bytes
+    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u);
+    if (head > HW) head = HW;
+    const int nvec = (HW - head) >> 4, tail = HW - head - 16 * nvec;
+    const uint4* body = reinterpret_cast<const uint4*>(base + head);
+    if (tid < LV_MAX_D) s_w[tid] = 0;
+
+    unsigned edge = 0;
+    if (tid < head && base[tid] == cls) edge |= 1u;
+    if (tid < tail && base[head + 16 * nvec + tid] == cls) edge |= 2u;
+    unsigned mk[LV_RES];
+    if constexpr (RES) {
+        uint4 r[LV_RES];
+#pragma unroll
+        for (int k = 0; k < LV_RES; ++k) {
+            const int v = tid + 256 * k;
+            r[k] = v < nvec ? body[v] : make_uint4(~0u, ~0u, ~0u, ~0u);      // 255 is no class (cls <= 254)
+        }
+#pragma unroll
+        for (int k = 0; k < LV_RES; ++k) mk[k] = match16(r[k], cls);
+    }
+
+    // pass 1: moments.  A lane sees at most 4096 + 2 pixels of coordinates below 1024: n, sx, sy fit 32 bits, the second moments need 64
+    unsigned n32 = 0, sx32 = 0, sy32 = 0;
+    u64 sxx = 0, sxy = 0, syy = 0;
+    sweep<RES>(mk, body, nvec, head, W, cls, edge, [&](int x, int y) {
+        ++n32; sx32 += (unsigned)x; sy32 += (unsigned)y;
+        sxx += (unsigned)(x * x); sxy += (unsigned)(x * y); syy += (unsigned)(y * y);
+    });
+    {
+        const i64 part[6] = {(i64)n32, (i64)sx32, (i64)sy32, (i64)sxx, (i64)sxy, (i64)syy};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const i64 s = wave_sum(part[i]);
+            if ((tid & 63) == 0) s_red[wv][i] = s;
+        }
+    }
+    __syncthreads();
+    i64 tot[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) tot[i] = s_red[0][i] + s_red[1][i] + s_red[2][i] + s_red[3][i];
+    const i64 n = tot[0], sx = tot[1], sy = tot[2];
+    i64* st = a.stats + f * 12;
+    i64* dk = a.disks + f * (size_t)D;
+    double* ge = a.geom + f * 4;
+    if (n == 0) {                                          // (uniform) empty frame: every output is 0
+        if (tid < 12) st[tid] = 0;
+        if (tid < D) dk[tid] = 0;
+        if (tid < 4) ge[tid] = 0.0;
+        return;
+    }
+
+    // pass 2: the long axis, the eigenvector of the larger eigenvalue of [[A, B], [B, C]] -- every lane, the same operations on the same totals
+    const i64 A = n * tot[3] - sx * sx, B = n * tot[4] - sx * sy, C = n * tot[5] - sy * sy;
+    const double da = (double)(A - C), db = (double)(2 * B);
+    const double r = sqrt(add_rn(mul_rn(da, da), mul_rn(db, db)));
+    double vx, vy;
+    if (r == 0.0) { vx = 0.0; vy = 1.0; }
+    else if (da >= 0.0) { vx = add_rn(da, r); vy = db; }
+    else { vx = db; vy = sub_rn(r, da); }
+    const double nrm = sqrt(add_rn(mul_rn(vx, vx), mul_rn(vy, vy)));
+    double ux = vx / nrm, uy = vy / nrm;
+    if (uy < 0.0 || (uy == 0.0 && ux < 0.0)) { ux = -ux; uy = -uy; }
+    const int Ux = (int)rint(ux * (double)LV_Q), Uy = (int)rint(uy * (double)LV_Q);
+
+    // pass 3: extent of the projections t_p = (n x - sx) Ux + (n y - sy) Uy; |n x - sx| < 2^30, so two 32 x 32 -> 64 multiply-adds per pixel
+    const int n_i = (int)n, sx_i = (int)sx, sy_i = (int)sy;
+    auto proj = [&](int x, int y) -> i64 { return (i64)(n_i * x - sx_i) * Ux + (i64)(n_i * y - sy_i) * Uy; };
+    i64 tmin = 0x7fffffffffffffffLL, tmax = -0x7fffffffffffffffLL - 1;
+    sweep<RES>(mk, body, nvec, head, W, cls, edge, [&](int x, int y) {
+        const i64 t = proj(x, y);
+        tmin = t < tmin ? t : tmin;
+        tmax = t > tmax ? t : tmax;
+    });
+    tmin = wave_min(tmin);
+    tmax = wave_max(tmax);
+    if ((tid & 63) == 0) { s_mm[wv][0] = tmin; s_mm[wv][1] = tmax; }
+    __syncthreads();                                       // (also orders the zeroing of s_w in front of the atomics below)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        tmin = s_mm[w][0] < tmin ? s_mm[w][0] : tmin;
+        tmax = s_mm[w][1] > tmax ? s_mm[w][1] : tmax;
+    }
+
+    // pass 4: pixel p covers [D (t_p - tmin), + D P1), disk j covers [j Lt, (j + 1) Lt): W_j = sum of the overlaps
+    const i64 P1 = n * LV_Q, Lt = tmax - tmin + P1, DP1 = (i64)D * P1;
+    const double inv_lt = 1.0 / (double)Lt;
+    sweep<RES>(mk, body, nvec, head, W, cls, edge, [&](int x, int y) {
+        const i64 lo = (i64)D * (proj(x, y) - tmin), hi = lo + DP1;
+        int j = (int)((double)lo * inv_lt);                // floor(lo / Lt) up to rounding, made exact below
+        j = j < 0 ? 0 : (j > D - 1 ? D - 1 : j);
+        while (j > 0 && (i64)j * Lt > lo) --j;
+        while (j < D - 1 && (i64)(j + 1) * Lt <= lo) ++j;
+        for (; j < D && (i64)j * Lt < hi; ++j) {
+            const i64 d0 = (i64)j * Lt, d1 = d0 + Lt;
+            const i64 ov = (hi < d1 ? hi : d1) - (lo > d0 ? lo : d0);
+            atomicAdd(&s_w[j], (u64)ov);
+        }
+    });
+    __syncthreads();
+
+    // pass 5: the record
+    if (tid < D) dk[tid] = (i64)s_w[tid];
+    if (tid < 6) st[tid] = tot[tid];
+    if (tid == 6) { st[6] = Ux; st[7] = Uy; st[8] = tmin; st[9] = tmax; st[10] = Lt; st[11] = 0; }
+    if (tid == 64) {
+        const double L = (double)Lt / (double)P1;
+        double s = 0.0;
+        for (int j = 0; j < D; ++j) {
+            const double aj = (double)(i64)s_w[j] / (double)DP1;
+            s = add_rn(s, mul_rn(aj, aj));
+        }
+        ge[0] = L;
+        ge[1] = mul_rn(mul_rn(3.14159265358979323846, (double)D), s) / mul_rn(4.0, L);
+        ge[2] = (double)sx / (double)n;
+        ge[3] = (double)sy / (double)n;
+    }
+}
+
+struct EfArgs {
+    const double* vol; const i64* npix; const double* pick_vol; const i64* pick_npix;
+    int32_t* idx; double* val;
+    int T; i64 min_pixels;
+};
+
+// one wave per clip; ED = the valid frame of the largest pick volume, ES = of the smallest, ties -> the lowest t
+__global__ __launch_bounds__(64) void lv_ef_kernel(EfArgs a)
+{
+    const int lane = threadIdx.x, T = a.T;
+    const size_t b = blockIdx.x;
+    const double* pv = (a.pick_vol ? a.pick_vol : a.vol) + b * (size_t)T;
+    const i64* pn = (a.pick_npix ? a.pick_npix : a.npix) + b * (size_t)T;
+    int cnt = 0, edt = -1, est = -1;
+    double edv = 0.0, esv = 0.0;
+    for (int t = lane; t < T; t += 64) {
+        if (pn[t] < a.min_pixels) continue;
+        const double v = pv[t];
+        ++cnt;
+        if (edt < 0 || v > edv) { edv = v; edt = t; }       // (t ascends within a lane: strict comparisons keep the lowest t)
+        if (est < 0 || v < esv) { esv = v; est = t; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o);
+        const int t1 = __shfl_xor(edt, o), t2 = __shfl_xor(est, o);
+        const double v1 = __shfl_xor(edv, o), v2 = __shfl_xor(esv, o);
+        if (t1 >= 0 && (edt < 0 || v1 > edv || (v1 == edv && t1 < edt))) { edv = v1; edt = t1; }
+        if (t2 >= 0 && (est < 0 || v2 < esv || (v2 == esv && t2 < est))) { esv = v2; est = t2; }
+    }
+    if (lane == 0) {
+        int32_t* idx = a.idx + b * 3;
+        double* val = a.val + b * 3;
+        idx[2] = cnt;
+        if (cnt < 2) {
+            idx[0] = idx[1] = -1;
+            val[0] = val[1] = val[2] = 0.0;
+        } else {
+            const double EDV = a.vol[b * (size_t)T + edt], ESV = a.vol[b * (size_t)T + est];
+            idx[0] = edt; idx[1] = est;
+            val[0] = EDV; val[1] = ESV;
+            val[2] = EDV == 0.0 ? 0.0 : sub_rn(EDV, ESV) / EDV;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int gdkvm_lv_measure(const uint8_t* mask, int64_t* stats, int64_t* disks, double* geom,
+                                int frames, int H, int W, int cls, int D, void* stream)
+{
+    if (frames < 0 || H < 1 || H > 1024 || W < 1 || W > 1024)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "lv_measure: bad shape frames=%d H=%d W=%d (H, W in 1..1024)", frames, H, W);
+    if (D < 1 || D > LV_MAX_D) return gdkvm_fail(GDKVM_ERR_SHAPE, "lv_measure: D=%d outside 1..%d", D, LV_MAX_D);
+    if (cls < 0 || cls > 254) return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure: cls=%d outside 0..254", cls);
+    if (frames == 0) return GDKVM_OK;
+    if (!mask || !stats || !disks || !geom) return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure: null pointer");
+    if (!gdkvm_aligned16(stats) || !gdkvm_aligned16(disks) || !gdkvm_aligned16(geom))
+        return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure: outputs must be 16-byte aligned");
+    if (int rc = gdkvm_check_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LvArgs a{mask, reinterpret_cast<i64*>(stats), reinterpret_cast<i64*>(disks), geom, H * W, W, cls, D};
+    // a frame of up to 15 head bytes + LV_RES * 256 vectors keeps its match bits in registers
+    if (H * W <= LV_RES * 256 * 16) hipLaunchKernelGGL((lv_measure_kernel<true>), dim3((unsigned)frames), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((lv_measure_kernel<false>), dim3((unsigned)frames), dim3(256), 0, st, a);
+    GDKVM_LAUNCH_CHECK("lv_measure_kernel");
+    return GDKVM_OK;
+}
+
+extern "C" int gdkvm_lv_ef(const double* vol, const int64_t* npix, const double* pick_vol, const int64_t* pick_npix,
+                           int32_t* ed_es_nvalid, double* edv_esv_ef, int B, int T, int64_t min_pixels, void* stream)
+{
+    if (B < 0 || T < 1) return gdkvm_fail(GDKVM_ERR_SHAPE, "lv_ef: bad shape B=%d T=%d", B, T);
+    if ((pick_vol == nullptr) != (pick_npix == nullptr))
+        return gdkvm_fail(GDKVM_ERR_ARG, "lv_ef: pick_vol and pick_npix go together (one of them is null)");
+    if (B == 0) return GDKVM_OK;
+    if (!vol || !npix || !ed_es_nvalid || !edv_esv_ef) return gdkvm_fail(GDKVM_ERR_ARG, "lv_ef: null pointer");
+    if (!gdkvm_aligned16(ed_es_nvalid) || !gdkvm_aligned16(edv_esv_ef))
+        return gdkvm_fail(GDKVM_ERR_ARG, "lv_ef: outputs must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(vol) | reinterpret_cast<uintptr_t>(npix) | reinterpret_cast<uintptr_t>(pick_vol) |
+         reinterpret_cast<uintptr_t>(pick_npix)) & 7u)
+        return gdkvm_fail(GDKVM_ERR_ARG, "lv_ef: inputs must be 8-byte aligned");
+    if (int rc = gdkvm_check_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    EfArgs a{vol, reinterpret_cast<const i64*>(npix), pick_vol, reinterpret_cast<const i64*>(pick_npix), ed_es_nvalid, edv_esv_ef, T,
+             (i64)min_pixels};
+    hipLaunchKernelGGL(lv_ef_kernel, dim3((unsigned)B), dim3(64), 0, st, a);
+    GDKVM_LAUNCH_CHECK("lv_ef_kernel");
+    return GDKVM_OK;
+}

@@ -114,6 +114,8 @@ SIGNATURES = {
     "gdkvm_bn_pool_fwd_train": (_i, [_vp] * 9 + [_sz] + [_i] * 4 + [ctypes.c_float] * 2 + [_i, _vp]),
     "gdkvm_bn_pool_bwd": (_i, [_vp] * 9 + [_sz] + [_i] * 5 + [_vp]),
     "gdkvm_augment_clips": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
+    "gdkvm_lv_measure": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
 }
 
 
@@ -2068,3 +2070,88 @@ def dice_from_counts(counts: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     """Dice_c = (2|AnB| + eps) / (|A| + |B| + eps) from the integer counts of argmax_dice."""
     c = counts.to(torch.float64)
     return (2.0 * c[..., 0] + eps) / (c[..., 1] + c[..., 2] + eps)
+
+
+def iou_from_counts(counts: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """IoU_c = (|AnB| + eps) / (|A| + |B| - |AnB| + eps) from the same counts (dice_from_counts' eps convention: an absent class scores 1)."""
+    c = counts.to(torch.float64)
+    return (c[..., 0] + eps) / (c[..., 1] + c[..., 2] - c[..., 0] + eps)
+
+
+LV_MAX_SIDE, LV_MAX_DISKS = 1024, 64
+
+
+def lv_measure(mask: torch.Tensor, cls: int = 1, disks: int = 20):
+    """gdkvm_lv_measure: per frame of mask [..., H, W] uint8 the pixel moments of class `cls`, its long axis, the overlap-weighted areas of
+    `disks` disks along it and the single-plane method-of-disks volume (definition: include/gdkvm.h; integer-exact up to the disk areas).
+    Returns (stats int64 [..., 12] = n sx sy sxx sxy syy Ux Uy tmin tmax Lt 0, disks int64 [..., D], geom float64 [..., 4] = L V cx cy);
+    lengths in pixels of the mask's grid, V in pixel^3.  The mask may start at any byte address."""
+    lib = load()
+    if mask.dtype != torch.uint8 or mask.dim() < 2:
+        raise GdkvmError(f"lv_measure: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
+    H, W = mask.shape[-2:]
+    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
+        raise GdkvmError(f"lv_measure: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
+    if not 1 <= int(disks) <= LV_MAX_DISKS:
+        raise GdkvmError(f"lv_measure: disks = {disks} outside 1..{LV_MAX_DISKS}")
+    if not 0 <= int(cls) <= 254:
+        raise GdkvmError(f"lv_measure: cls = {cls} outside 0..254")
+    dev = _dev(mask)
+    lead = tuple(mask.shape[:-2])
+    frames = 1
+    for s in lead:
+        frames *= s
+    stats = torch.empty(lead + (12,), dtype=torch.int64, device=dev)
+    dk = torch.empty(lead + (int(disks),), dtype=torch.int64, device=dev)
+    geom = torch.empty(lead + (4,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.gdkvm_lv_measure(_ptr(mask), _ptr(stats), _ptr(dk), _ptr(geom), frames, H, W, int(cls), int(disks), _stream(dev))
+    _check(rc, "gdkvm_lv_measure")
+    return stats, dk, geom
+
+
+def lv_ef(vol: torch.Tensor, npix: torch.Tensor, pick_vol: Optional[torch.Tensor] = None, pick_npix: Optional[torch.Tensor] = None,
+          min_pixels: int = 1):
+    """gdkvm_lv_ef: per clip the end-diastolic / end-systolic frames and the ejection fraction from vol float64 [B, T] and npix int64 [B, T]
+    (lv_measure's geom[..., 1] and stats[..., 0]; non-contiguous views are copied).  Frames with fewer than `min_pixels` pixels are not
+    candidates; with pick_vol / pick_npix (both or neither, same shapes) ED / ES are chosen on THOSE -- the prediction's volumes at the
+    target's frames.  Returns (ed_es_nvalid int32 [B, 3], edv_esv_ef float64 [B, 3]); fewer than two valid frames: ed = es = -1, EF = 0."""
+    lib = load()
+    if (pick_vol is None) != (pick_npix is None):
+        raise GdkvmError("lv_ef: pick_vol and pick_npix go together")
+    if vol.dim() != 2 or vol.shape[1] < 1:
+        raise GdkvmError(f"lv_ef: vol must be [B, T] with T >= 1, got {tuple(vol.shape)}")
+    for name, t, dt in (("vol", vol, torch.float64), ("npix", npix, torch.int64), ("pick_vol", pick_vol, torch.float64),
+                        ("pick_npix", pick_npix, torch.int64)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != tuple(vol.shape)):
+            raise GdkvmError(f"lv_ef: {name} must be {dt} {tuple(vol.shape)}, got {t.dtype} {tuple(t.shape)}")
+    vol, npix, pick_vol, pick_npix = (None if t is None else t.contiguous() for t in (vol, npix, pick_vol, pick_npix))
+    dev = _dev(vol, npix, pick_vol, pick_npix)
+    B, T = vol.shape
+    idx = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    val = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.gdkvm_lv_ef(_ptr(vol), _ptr(npix), _ptr(pick_vol), _ptr(pick_npix), _ptr(idx), _ptr(val), B, T, int(min_pixels), _stream(dev))
+    _check(rc, "gdkvm_lv_ef")
+    return idx, val
+
+
+def ef_summary(pred_ef: torch.Tensor, ref_ef: torch.Tensor, ok: torch.Tensor) -> torch.Tensor:
+    """The eight running sums of an EF comparison over the clips where `ok`: count, sum e, sum |e|, sum p, sum g, sum p^2, sum g^2, sum p g
+    (e = p - g; float64 [8], on the inputs' device).  Sums of batches and of ranks add, so a multi-GPU evaluation needs one small
+    all_reduce, like the Dice counts; ef_stats turns them into MAE, bias and Pearson r."""
+    k = ok.to(torch.float64)
+    p, g = pred_ef.to(torch.float64) * k, ref_ef.to(torch.float64) * k
+    e = p - g
+    return torch.stack([k.sum(), e.sum(), e.abs().sum(), p.sum(), g.sum(), (p * p).sum(), (g * g).sum(), (p * g).sum()])
+
+
+def ef_stats(sums) -> dict:
+    """{clips_with_ef, ef_mae, ef_bias, ef_pearson_r, mean_ref_ef, mean_pred_ef} from ef_summary's sums (host numbers; r is 0 when either
+    side has no variance or fewer than two clips count)."""
+    n, se, sae, sp, sg, spp, sgg, spg = (float(v) for v in sums)
+    if n < 1:
+        return {"clips_with_ef": 0, "ef_mae": 0.0, "ef_bias": 0.0, "ef_pearson_r": 0.0, "mean_ref_ef": 0.0, "mean_pred_ef": 0.0}
+    vp, vg, cov = n * spp - sp * sp, n * sgg - sg * sg, n * spg - sp * sg
+    r = cov / (vp * vg) ** 0.5 if n >= 2 and vp > 0 and vg > 0 else 0.0
+    return {"clips_with_ef": int(n), "ef_mae": sae / n, "ef_bias": se / n, "ef_pearson_r": r, "mean_ref_ef": sg / n, "mean_pred_ef": sp / n}

@@ -590,6 +590,36 @@ int gdkvm_seg_loss_bwd(const void* z, const void* target, const void* ws, size_t
 int gdkvm_augment_clips(const uint8_t* frames, const void* target, const float* params, void* frames_out, void* target_out,
                         int B, int T, int C, int H, int W, int io_dtype, int target_bytes, int fill_label, void* stream);
 
+/* Left-ventricular geometry of label masks (the evaluation's epilogue beside the Dice counts; csrc/lv_measure.hip).  Integer-exact up to the
+ * disk areas; volumes are in pixel^3 of the mask's grid (isotropic pixels assumed -- physical spacing is the caller's), EF is a ratio.
+ * Per frame mask [H, W] uint8, class cls (0..254; every other byte, 255 included, is "not cls"), D disks (1..64), H, W in 1..1024, Q = 2^16;
+ * P = the pixels (x, y) with mask[y][x] == cls:
+ *   1. moments (int64)   n = |P|, sx = sum x, sy = sum y, sxx = sum x^2, sxy = sum x y, syy = sum y^2
+ *   2. scaled central    A = n sxx - sx^2,  B = n sxy - sx sy,  C = n syy - sy^2
+ *   3. long axis (fp64, un-fused multiplies and adds)   a = (double)(A - C), b = (double)(2 B), r = sqrt(a a + b b);
+ *        r == 0: u = (0, 1);  a >= 0: u ~ (a + r, b);  else u ~ (b, r - a);  u / |u|, sign such that uy > 0 or (uy == 0 and ux > 0);
+ *        Ux = rint(ux Q), Uy = rint(uy Q)   (the eigenvector of the larger eigenvalue of [[A, B], [B, C]]; the default is the image's vertical)
+ *        (every operation rounded once, IEEE fp64, no fused multiply-add: the library is compiled with contraction off for this file.  A host
+ *        restatement whose sqrt and division are correctly rounded reproduces Ux, Uy; one that fuses a a + b b may move a rint tie, so a
+ *        cross-check should accept |dUx|, |dUy| <= 1 and compare steps 4 - 6 using the axis the device reported, as the tests do)
+ *   4. projection (int64)   t_p = (n x - sx) Ux + (n y - sy) Uy;  tmin, tmax over P;  P1 = n Q (one pixel of extent);  Lt = tmax - tmin + P1
+ *   5. disks by overlap (int64)   pixel p covers [D (t_p - tmin), D (t_p - tmin) + D P1), disk j covers [j Lt, (j + 1) Lt);
+ *        W_j = sum_p overlap(p, j), hence sum_j W_j = n D P1 exactly
+ *   6. geometry (fp64)   L = Lt / P1 (pixels);  a_j = W_j / (D P1) (pixels^2 in disk j);  V = pi D sum_j a_j^2 / (4 L) (single-plane method of
+ *        disks: height L / D, mean width a_j D / L);  cx = sx / n, cy = sy / n.   n == 0: every output of the frame is 0.
+ * mask [frames, H, W] contiguous, ANY byte alignment (frames of H W bytes follow each other).  Outputs (16-byte aligned):
+ *   stats [frames, 12] = n, sx, sy, sxx, sxy, syy, Ux, Uy, tmin, tmax, Lt, 0;   disks [frames, D] = W_j;   geom [frames, 4] = L, V, cx, cy.
+ * One workgroup per frame, integer sums only: bit-reproducible.  frames == 0 is GDKVM_OK without a launch. */
+int gdkvm_lv_measure(const uint8_t* mask, int64_t* stats, int64_t* disks, double* geom,
+                     int frames, int H, int W, int cls, int D, void* stream);
+/* Clip level: vol, npix [B, T] (geom[..., 1] and stats[..., 0] of gdkvm_lv_measure, made contiguous; 8-byte aligned), optional pick_vol /
+ * pick_npix [B, T] (both or neither; e.g. the target's, so that the prediction's volumes are read at the annotated frames).  Frame t is valid
+ * when pick_npix[b][t] >= min_pixels (npix without pick arrays); ED = the valid frame of the largest pick volume, ES = of the smallest, ties ->
+ * the lowest t;  EDV = vol[b][ed], ESV = vol[b][es], EF = (EDV - ESV) / EDV (0 when EDV == 0).  Fewer than two valid frames: ed = es = -1 and
+ * EDV = ESV = EF = 0.  ed_es_nvalid int32 [B, 3], edv_esv_ef fp64 [B, 3] (16-byte aligned).  B == 0 is GDKVM_OK without a launch. */
+int gdkvm_lv_ef(const double* vol, const int64_t* npix, const double* pick_vol, const int64_t* pick_npix,
+                int32_t* ed_es_nvalid, double* edv_esv_ef, int B, int T, int64_t min_pixels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""What the LV measurement costs (profiles/r10_a_lv_probe.txt).  python3 tools/lv_probe.py [--quick] [--no-eval]
+
+(a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
+    gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
+    C symbols on preallocated outputs, CALLS launches back to back between ONE pair of device events (a single launch between two events on an
+    empty queue would time the host's way to the launch, not a kernel of a few microseconds); time per launch = window / CALLS, the forms
+    alternated window by window over four rotating inputs, median and minimum over the windows.  Masks: one rotated ellipse per frame covering
+    about a tenth of it (a ventricle); every pixel of the class (the worst case for the per-pixel passes); no pixel of the class.  The floor is
+    the bytes read (and, for the mask kernel, written) once over the 6.3 TB/s achievable HBM rate.
+(b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1 and -1,
+    alternated, twice each."""
+import math
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gdkvm_amd import ops  # noqa: E402
+
+HBM = 6.3e12          # bytes / s: the achievable rate the kernel tables of this project are quoted against
+
+
+def ellipse_masks(F, S, seed):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
+    out = np.zeros((F, S, S), np.uint8)
+    for f in range(F):
+        th = rng.uniform(-0.5, 0.5)
+        la, sa = S * rng.uniform(0.22, 0.30), S * rng.uniform(0.10, 0.14)
+        dx, dy = xx - S * rng.uniform(0.45, 0.55), yy - S * rng.uniform(0.45, 0.55)
+        al, ac = dx * math.sin(th) + dy * math.cos(th), dx * math.cos(th) - dy * math.sin(th)
+        out[f][(al / la) ** 2 + (ac / sa) ** 2 <= 1.0] = 1
+    return out
+
+
+CALLS = 20            # launches per timed window
+
+
+def part_a(dev, F, S, reps, n_in=4):
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    g = torch.Generator().manual_seed(S)
+    masks = [torch.from_numpy(ellipse_masks(F, S, s)).to(dev) for s in range(n_in)]
+    full = torch.ones((F, S, S), dtype=torch.uint8, device=dev)
+    logits = [torch.randn((F, 2, S // 4, S // 4), generator=g).to(dev).bfloat16() for _ in range(n_in)]
+    m_out = torch.empty((F, S, S), dtype=torch.uint8, device=dev)
+    c_out = torch.empty((F, 2, 3), dtype=torch.int32, device=dev)
+    stats = torch.empty((F, 12), dtype=torch.int64, device=dev)
+    disks = torch.empty((F, 20), dtype=torch.int64, device=dev)
+    geom = torch.empty((F, 4), dtype=torch.float64, device=dev)
+
+    def lv(mask, cls):
+        rc = lib.gdkvm_lv_measure(mask.data_ptr(), stats.data_ptr(), disks.data_ptr(), geom.data_ptr(), F, S, S, cls, 20, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def up(i):
+        rc = lib.gdkvm_upsample_argmax_dice(logits[i].data_ptr(), masks[i].data_ptr(), m_out.data_ptr(), c_out.data_ptr(), F, 2, S // 4, S // 4, S, S,
+                                            ops.BF16, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    frac = float(masks[0].float().mean())
+    forms = {
+        f"lv_measure, ellipse ({100 * frac:.0f} % of the frame)": (lambda i: lv(masks[i], 1), F * S * S),
+        "lv_measure, every pixel of the class": (lambda i: lv(full, 1), F * S * S),
+        "lv_measure, no pixel of the class": (lambda i: lv(full, 2), F * S * S),
+        "upsample_argmax_dice (writes the mask)": (up, F * (2 * 2 * (S // 4) ** 2 + 2 * S * S)),
+    }
+    times = {name: [] for name in forms}
+    for r in range(reps + 3):
+        for name, (fn, _) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(CALLS):
+                fn(r % n_in)
+            e1.record()
+            e1.synchronize()
+            if r >= 3:                           # (three warm-up rounds)
+                times[name].append(e0.elapsed_time(e1) * 1e3 / CALLS)
+    print(f"(a) {F} frames of {S}x{S}: us per launch, {CALLS} launches back to back per window of device events, median / minimum of {reps} windows "
+          f"per form (alternated, {n_in} inputs in rotation)")
+    print(f"{'form':48s} {'median us':>10s} {'min us':>9s} {'MB':>8s} {'floor us':>9s}")
+    for name, (_, nbytes) in forms.items():
+        print(f"{name:48s} {statistics.median(times[name]):10.1f} {min(times[name]):9.1f} {nbytes / 1e6:8.1f} {nbytes / HBM * 1e6:9.2f}")
+    print(flush=True)
+
+
+def part_b(runs, overrides):
+    print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
+    for run in range(runs):
+        for lv in (1, -1):
+            t0 = time.perf_counter()
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "eval.py"), f"data.lv_class={lv}"] + overrides, capture_output=True, text=True,
+                                 timeout=600)
+            dt = time.perf_counter() - t0
+            if out.returncode != 0:
+                print(out.stderr[-2000:])
+                raise SystemExit(f"eval.py failed with data.lv_class={lv}")
+            print(f"  run {run + 1} data.lv_class={lv:2d}: {dt:6.2f} s   {out.stdout.strip().splitlines()[-1]}", flush=True)
+
+
+def main():
+    quick = "--quick" in sys.argv
+    ops.require_native()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for S in (112, 256):
+        part_a(dev, 8 if quick else 512, S, 5 if quick else 40)
+    if "--no-eval" not in sys.argv:
+        part_b(1 if quick else 2, ["data.size=64", "data.frames=4", "batch_size=4", "model.value_dim=64"] if quick else [])
+
+
+if __name__ == "__main__":
+    main()
