@@ -3,7 +3,7 @@
 // once; counts are reduced wave-wide with ballots, per block in LDS, then one integer atomic per
 // (block, class, kind) -- integer adds commute, so the result is bit-reproducible.
 
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_dice_kernel(UpArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if constexpr (IO == GDKVM_F32) v[j] = __uint_as_float(xw[j]);
-                else { v[2 * j] = __uint_as_float(xw[j] << 16); v[2 * j + 1] = __uint_as_float(xw[j] & 0xffff0000u); }
+                else { v[2 * j] = bf16_lo(xw[j]); v[2 * j + 1] = bf16_hi(xw[j]); }
             }
             float mine = 0.f;
             if constexpr (NC > 0) {

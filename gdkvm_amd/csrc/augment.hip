@@ -7,7 +7,7 @@
 // The table (256 powf per workgroup instead of one per pixel and plane) is built by the workgroup's 256 threads; blockIdx.y is the frame,
 // so a workgroup never spans two clips.  16-byte stores need every plane to start aligned: H W a multiple of V and aligned bases,
 // otherwise the same code stores element by element.  Bound: bandwidth (1 byte in, 2 or 4 out per element); the kernel has no reuse to find.
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -105,10 +105,7 @@ __global__ __launch_bounds__(WG) void augment_kernel(AugArgs a)
             *reinterpret_cast<f32x4*>(static_cast<float*>(a.fout) + plane + p0) = f32x4{o[0], o[1], o[2], o[3]};
         } else if constexpr (VEC) {
             uint4 u;
-            u.x = (unsigned)f32_to_bf16(o[0]) | ((unsigned)f32_to_bf16(o[1]) << 16);
-            u.y = (unsigned)f32_to_bf16(o[2]) | ((unsigned)f32_to_bf16(o[3]) << 16);
-            u.z = (unsigned)f32_to_bf16(o[4]) | ((unsigned)f32_to_bf16(o[5]) << 16);
-            u.w = (unsigned)f32_to_bf16(o[6]) | ((unsigned)f32_to_bf16(o[7]) << 16);
+            u = pack_bf16x8(o);
             *reinterpret_cast<uint4*>(static_cast<bf16_t*>(a.fout) + plane + p0) = u;
         } else {
 #pragma unroll

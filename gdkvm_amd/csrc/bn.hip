@@ -9,7 +9,7 @@
 // per-channel parameters and accumulators live in registers), every trip has UNR independent loads in flight.
 // Reductions are deterministic (fixed partial layout, fixed summation order; no atomics).  The variance is accumulated on
 // values shifted by the first row of the tensor, so it does not cancel when |mean| >> std.
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -25,8 +25,7 @@ __device__ __forceinline__ void unpack(const uint4& a, float (&v)[VecOf<IO>::V])
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(w[j]);
     } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[2 * j] = __uint_as_float(w[j] << 16); v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
+        unpack_bf16x8(a, v);
     }
 }
 
@@ -37,10 +36,7 @@ __device__ __forceinline__ uint4 pack(const float (&v)[VecOf<IO>::V])
     if constexpr (IO == GDKVM_F32) {
         o.x = __float_as_uint(v[0]); o.y = __float_as_uint(v[1]); o.z = __float_as_uint(v[2]); o.w = __float_as_uint(v[3]);
     } else {
-        o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-        o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-        o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-        o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
+        o = pack_bf16x8(v);
     }
     return o;
 }
@@ -246,7 +242,7 @@ __device__ __forceinline__ uint4 pool_gather(const PoolGeo& q, size_t v, int G, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const unsigned wt = (tb[j >> 2] >> (8 * (j & 3))) & 0xffu;
-            const float d = (j & 1) ? __uint_as_float(w4[j >> 1] & 0xffff0000u) : __uint_as_float(w4[j >> 1] << 16);
+            const float d = (j & 1) ? bf16_hi(w4[j >> 1]) : bf16_lo(w4[j >> 1]);
             acc[j] += (int)wt == tap[k] ? d : 0.f;
         }
     }

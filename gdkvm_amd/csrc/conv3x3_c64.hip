@@ -20,9 +20,7 @@
 //     slots from a 16-byte zero constant.
 // HBM traffic: input once (+ halo rows from L2), output once.  Arithmetic: fp32 accumulation over the same 576 products as the
 // library kernel, one rounding after the epilogue.
-#include <type_traits>
-
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -53,10 +51,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
     // channel chunk c of band pixel pix (c = 8, 9: padding).  The slot geometry does not depend on the tile: kept in registers.
     // DESC: g_rel is the slot's BYTE offset from the frame's first byte for the tile at row 0 (band row 0 is row -1: negative, huge as
     // unsigned); a tile adds its first row as a scalar.  The descriptor spans exactly the frame, so the rows above and below it read as
-    // zeros; the slots that are zero in every tile -- padding, the halo columns, past the band -- carry CV_DEAD, out of range with any
-    // such scalar added (the launcher keeps a frame below 2^31 bytes).
+    // zeros; the slots that are zero in every tile -- padding, the halo columns, past the band -- carry RSRC_DEAD, out of range with any
+    // such scalar added.
     constexpr int PP = (NPIECES + 3) / 4;
-    constexpr unsigned CV_DEAD = 0x80000000u;
     int g_rel[PP], g_yx[DESC ? 1 : PP];                    // !DESC: element offset from the band's (0, 0) pixel; (by << 8 | bx), -1 = no data
 #pragma unroll
     for (int u = 0; u < PP; ++u) {
@@ -64,7 +61,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         const int by = pix / BW, bx = pix - by * BW;
         if constexpr (DESC) {
             const bool live = j < NPIECES && c < 8 && pix < BAND_PIX && bx >= 1 && bx <= a.W;
-            g_rel[u] = live ? (((by - 1) * a.W + bx - 1) * CV_C + c * 8) * 2 : (int)CV_DEAD;
+            g_rel[u] = live ? (((by - 1) * a.W + bx - 1) * CV_C + c * 8) * 2 : (int)RSRC_DEAD;
         } else {
             g_rel[u] = (by * a.W + bx) * CV_C + c * 8;
             bool live = j < NPIECES && c < 8 && pix < BAND_PIX;
@@ -83,17 +80,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         }
     };
     auto fetch = [&](int tile, TilePos pos, int buf) __attribute__((always_inline)) {
+        unsigned char* const bands = static_cast<unsigned char*>(band2);       // (a plain pointer type for lds_dma_dst: see its comment)
         if constexpr (DESC) {
             // wave-uniform values only: the descriptor lives in SGPRs, no waterfall loop
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x + (long long)pos.n * a.H * a.W * CV_C), 0,
-                                                                                  a.H * a.W * CV_C * 2, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(a.x + (long long)pos.n * a.H * a.W * CV_C, a.H * a.W * CV_C * 2);
             const unsigned ts = (unsigned)(pos.ty * CV_TH * a.W * CV_C * 2);
 #pragma unroll
             for (int u = 0; u < PP; ++u) {
                 const int j = w + 4 * u;
                 if (j >= NPIECES) break;                   // (wave-uniform)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, reinterpret_cast<__attribute__((address_space(3))) void*>(
-                    reinterpret_cast<uintptr_t>(band2 + buf * BAND_BYTES + 1024 * j)), 16, (int)((unsigned)g_rel[u] + ts), 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, lds_dma_dst(bands + buf * BAND_BYTES + 1024 * j), 16, (int)((unsigned)g_rel[u] + ts), 0, 0, 0);
             }
         } else {
             const int tx = tile % a.tiles_x, t2 = tile / a.tiles_x, ty = t2 % a.tiles_y, n = t2 / a.tiles_y;
@@ -107,8 +103,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
                 const int yy = y0 + (g_yx[u] >> 8), xx = x0 + (g_yx[u] & 255);
                 const bool ok = g_yx[u] >= 0 && (unsigned)yy < (unsigned)a.H && (one_col || (unsigned)xx < (unsigned)a.W);
                 const bf16_t* src = ok ? origin + g_rel[u] : reinterpret_cast<const bf16_t*>(&g_conv_zero16);
-                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(
-                    reinterpret_cast<uintptr_t>(band2 + buf * BAND_BYTES + 1024 * j)), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(src, lds_dma_dst(bands + buf * BAND_BYTES + 1024 * j), 16, 0, 0);
             }
         }
     };
@@ -122,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         pbase[m] = (unsigned)((ty * BW + tx) * CV_PIX + g * 16);
     }
     // DESC: the same pixel's BYTE offset in the output (and the residual) from the first byte of the frame for the tile at row 0, channels
-    // 32wn + 8g ..; pixels the tile does not have carry CV_DEAD.  Output and residual go through descriptors over the tile's frame like the
+    // 32wn + 8g ..; pixels the tile does not have carry RSRC_DEAD.  Output and residual go through descriptors over the tile's frame like the
     // band, so a row past the frame is out of range: its residual reads as zeros and its store is dropped -- every m-tile issues exactly one
     // load and one store whatever its pixels, which is what makes the epilogue's wait counts exact.
     unsigned o_rel[DESC ? 4 : 1];
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int p = 16 * (4 * wm + m) + li, py = p / TW, px = p - py * TW;
-            o_rel[m] = (p < NPIX && px < a.W) ? (unsigned)(((py * a.W + px) * CV_C + 32 * wn + 8 * g) * 2) : CV_DEAD;
+            o_rel[m] = (p < NPIX && px < a.W) ? (unsigned)(((py * a.W + px) * CV_C + 32 * wn + 8 * g) * 2) : RSRC_DEAD;
         }
     }
 
@@ -227,20 +222,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
         __syncthreads();                                   // everyone is done with this band; the next one has landed
 
         // epilogue: lane (li, g) holds channels 32wn + 8g .. +7 of pixel 16(4wm+m) + li (tile nt: the four channels 4nt ..)
-        typedef float f32x2 __attribute__((ext_vector_type(2)));           // packed fp32 pairs: v_pk_add_f32 / v_pk_max_f32
         if constexpr (DESC) {
             // The residual vectors of ALL the wave's m-tiles are requested together, right behind the barrier, and consumed one by one
             // under a counted wait.  The loads are asm, so the compiler neither counts them nor answers their uses with vmcnt(0) (which
             // covered the previous m-tile's store: four serial chains of load round trip + store acknowledgement per tile); operations
             // retire from the counter in issue order, and behind residual m stand the NM - 1 - m younger loads and the m stores of the
             // m-tiles before it: NM - 1 younger operations for every m, none of which is waited for.
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             const long long fo = (long long)tpos.n * a.H * a.W * CV_C;
             const unsigned fbytes = (unsigned)(a.H * a.W * CV_C * 2), ts = (unsigned)(tpos.ty * CV_TH * a.W * CV_C * 2);
             advance(tpos);
-            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(a.y + fo, 0, (int)fbytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t yrs = make_rsrc(a.y + fo, (int)fbytes);
             const unsigned long long ra = reinterpret_cast<unsigned long long>(a.res + fo);
-            const u32x4 rrs = {(unsigned)ra, (unsigned)(ra >> 32) & 0xffffu, fbytes, 0x00020000u};
+            const u32x4 rrs = {(unsigned)ra, (unsigned)(ra >> 32) & 0xffffu, fbytes, (unsigned)RSRC_WORD3};
             auto epilogue = [&](auto nm_c) __attribute__((always_inline)) {
                 constexpr int NM = decltype(nm_c)::value;
                 unsigned vo[NM];
@@ -261,14 +254,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
                         asm volatile("s_waitcnt vmcnt(%1)" : "+v"(rr[m]) : "n"(NM - 1) : "memory");
                         const unsigned rw[4] = {rr[m][0], rr[m][1], rr[m][2], rr[m][3]};
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] += f32x2{__uint_as_float(rw[q] << 16), __uint_as_float(rw[q] & 0xffff0000u)};
+                        for (int q = 0; q < 4; ++q) v[q] += unpack_bf16x2(rw[q]);
                     }
                     const float lo = a.relu ? 0.f : -INFINITY;
                     u32x4 ow;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         v[q] = __builtin_elementwise_max(v[q], f32x2{lo, lo});
-                        ow[q] = (unsigned)f32_to_bf16(v[q][0]) | ((unsigned)f32_to_bf16(v[q][1]) << 16);
+                        ow[q] = pack_bf16x2(v[q][0], v[q][1]);
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(ow, yrs, (int)vo[m], 0, 0);
                 }
@@ -291,14 +284,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(Conv64Args a)
                 const uint4 rr = *reinterpret_cast<const uint4*>(a.res + o);
                 const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] += f32x2{__uint_as_float(rw[q] << 16), __uint_as_float(rw[q] & 0xffff0000u)};
+                for (int q = 0; q < 4; ++q) v[q] += unpack_bf16x2(rw[q]);
             }
             const float lo = a.relu ? 0.f : -INFINITY;
             unsigned ow[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 v[q] = __builtin_elementwise_max(v[q], f32x2{lo, lo});
-                ow[q] = (unsigned)f32_to_bf16(v[q][0]) | ((unsigned)f32_to_bf16(v[q][1]) << 16);
+                ow[q] = pack_bf16x2(v[q][0], v[q][1]);
             }
             *reinterpret_cast<uint4*>(a.y + o) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
         }

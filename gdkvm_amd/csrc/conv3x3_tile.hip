@@ -20,9 +20,7 @@
 //   * the same kernel computes the training-mode data gradient (weights packed flipped and transposed).
 // Arithmetic: fp32 accumulation over the same 9 C products as a library convolution, one rounding after the epilogue.
 #include <atomic>
-#include <type_traits>
-
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -37,15 +35,6 @@ constexpr int CT_MAXMT = 13;             // 16-pixel tiles per workgroup tile (2
 // weights are packed -- 121 against 129 us on the 192 -> 64 layer: half the LDS operand reads per MFMA, and the fourfold weight fetch is cheap now)
 constexpr int CT_VARIANT_128 = 4, CT_VARIANT_64 = 3;
 
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for_ct(F&& f)
-{
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        static_for_ct<I + 1, E>(f);
-    }
-}
-
 struct ConvTileArgs {
     const bf16_t* x; const bf16_t* w; const float* bias; const bf16_t* res; bf16_t* y;
     const bf16_t* x2; int C1;            // x2 != NULL: the input is the channel concatenation [x (C1 channels) ; x2 (C - C1)], never
@@ -57,10 +46,6 @@ struct ConvTileArgs {
     float inv_band, inv_bw, inv_tw, inv_w;   // 1 / (bh bw), 1 / bw, 1 / (th W), 1 / W: index arithmetic without integer division
     int perm;                                // K % 32 == 0: output channels permuted within groups of 32 (ct_channel)
 };
-
-// floor(n / d) for the small non-negative indices of this kernel (n < 2^16), inv = 1.0f / d: exact, and 3 instructions where an
-// integer division is ~40 (the prologue and every tile's epilogue do dozens of them per lane: 17 % of a 128 -> 128 layer)
-__device__ __forceinline__ int ct_div(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }
 
 // Row j of the 16-channel output tile kt is output channel ct_channel(kt, j).  With K a multiple of 32 the two tiles of a
 // 32-channel group interleave in fours, so that the accumulator rows 4g .. 4g+3 of BOTH tiles of a wave are 8 consecutive
@@ -107,21 +92,20 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     // lies in): a lane's source is ONE 32-bit byte offset from the group's first byte, g_off + a per-chunk scalar (the tile's first row and
     // the chunk's channels), and a lane whose offset is out of the descriptor's range gets zeros from the hardware -- the row above the
     // frame (a negative offset: huge as unsigned), the rows below it and the frames a ragged last group lacks (>= num_records).  Slots that
-    // hold zeros in EVERY tile carry CT_DEAD, out of range whatever the scalar (the launcher keeps a group below 2^31 bytes): padding, the
+    // hold zeros in EVERY tile carry RSRC_DEAD, out of range whatever the scalar: padding, the
     // left / right halo columns, slots past the band, surplus pieces -- and, with several whole frames per tile (tiles_y == 1), each frame's
     // halo rows, which in memory are the neighbouring frame's rows.  One offset set per pixel pitch (a concatenated input has two).
     constexpr int PP = NWV == 8 ? 7 : 8;                   // pieces per wave: npieces <= 56 (eight waves) / 32 (four)
-    constexpr unsigned CT_DEAD = 0x80000000u;
     const int cs1 = a.C1, cs2 = a.x2 ? C - a.C1 : C;       // pixel pitch of x (the whole input when there is no x2) and of x2
     unsigned g_off1[PP], g_off2[PP];
 #pragma unroll
     for (int u = 0; u < PP; ++u) {
         const int j = w + NWV * u, d = 64 * j + lane, pix = d / CT_SLOTS, c = d - CT_SLOTS * pix;
-        const int f = ct_div(pix, a.inv_band), r = pix - f * (a.bh * BW), by = ct_div(r, a.inv_bw), bx = r - by * BW;
+        const int f = idx_div(pix, a.inv_band), r = pix - f * (a.bh * BW), by = idx_div(r, a.inv_bw), bx = r - by * BW;
         const int sp = (f * H + by - 1) * W + bx - 1;      // source pixel, from the group's first, of a tile that starts at row 0
         const bool live = j < a.npieces && c < 8 && pix < a.band_px && bx >= 1 && bx <= W && (a.tiles_y > 1 || (by >= 1 && by <= a.th));
-        g_off1[u] = live ? (unsigned)(sp * cs1 * 2 + c * 16) : CT_DEAD;
-        g_off2[u] = live ? (unsigned)(sp * cs2 * 2 + c * 16) : CT_DEAD;
+        g_off1[u] = live ? (unsigned)(sp * cs1 * 2 + c * 16) : RSRC_DEAD;
+        g_off2[u] = live ? (unsigned)(sp * cs2 * 2 + c * 16) : RSRC_DEAD;
     }
     const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>(ct_band);
     const int nlive = max(0, (a.npieces - w + NWV - 1) / NWV);         // this wave's pieces u < nlive exist (j = w + NWV u < npieces)
@@ -141,7 +125,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
         const int cs = second ? cs2 : cs1;                              // its channel count = pixel pitch
         // wave-uniform values only (kernel arguments and scalars of the tile loop): the descriptor lives in SGPRs, no waterfall loop
         const bf16_t* base = (second ? a.x2 : a.x) + (long long)q.px0 * cs;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, q.npx * cs * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(base, q.npx * cs * 2);
         const unsigned ts = (unsigned)((q.row0 * cs + chunk * CT_CK - (second ? a.C1 : 0)) * 2);
         const unsigned dst0 = lds0 + buf * band_bytes + 1024 * w;       // LDS address of this wave's piece 0
         // straight-line on purpose (always PP pieces: surplus ones land in a dump slot): the hand-written vmcnt counts of the chunk loop
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
             const unsigned dst = u < nlive ? dst0 + 1024 * NWV * u : lds0 + 2 * band_bytes;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, reinterpret_cast<__attribute__((address_space(3))) void*>(static_cast<uintptr_t>(dst)), 16,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, lds_dma_dst(dst), 16,
                                                      (int)((second ? g_off2[u] : g_off1[u]) + ts), 0, 0, 0);
         }
     };
@@ -165,7 +149,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
         const int p = min(16 * (wm + MW * m) + li, tpix - 1);
-        const int f = ct_div(p, a.inv_tw), r = p - f * (a.th * W), py = ct_div(r, a.inv_w), px = r - py * W;
+        const int f = idx_div(p, a.inv_tw), r = p - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
         pbase[m] = (unsigned)(((f * a.bh + py) * BW + px) * CT_PIX + g * 16);
     }
     const bf16_t* wrow[NTW];                               // weights [K][3][3][C]: A operand rows of output tile nt
@@ -259,7 +243,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
             // first WD k-steps of a chunk, the PP band pieces issued above.
             auto trip = [&](int r0, auto firstc) __attribute__((always_inline)) {
                 constexpr bool FIRST = decltype(firstc)::value;
-                static_for_ct<0, KU>([&](auto jc) {
+                static_for<0, KU>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     wwait(wr[j % WD], std::integral_constant<int, (WD - 1) * NTW + (FIRST && j < WD ? PP : 0)>{});
                     if constexpr (j % 2 == 0) { load_x(xb, r0 + j + 1); mfmas(xa, wr[j % WD]); }
@@ -275,10 +259,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
         // epilogue: lane (li, g) holds rows 4g .. 4g+3 of each of the wave's output tiles for pixel 16 (wm + MW m) + li
         {
             const int ty = tile % a.tiles_y, fg = tile / a.tiles_y;
-            auto bf4 = [](uint2 rr) { return f32x4{__uint_as_float(rr.x << 16), __uint_as_float(rr.x & 0xffff0000u), __uint_as_float(rr.y << 16), __uint_as_float(rr.y & 0xffff0000u)}; };
-            auto pk4 = [](const f32x4& v) { return make_uint2((unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16), (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16)); };
             const float lo = a.relu ? 0.f : -INFINITY;
-            typedef float f32x2 __attribute__((ext_vector_type(2)));       // packed fp32 pairs: v_pk_add_f32 / v_pk_max_f32
             if (NTW == 2 && a.perm) {                      // 8 consecutive channels 32G + 8g .. +7 (co0 and K are multiples of 32)
                 if (co0 < K) {
                     // every pixel tile's output offset first, then ALL the residual loads, then the arithmetic: one wait for the seven
@@ -288,7 +269,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                     for (int m = 0; m < MTW; ++m) {
                         const int p = 16 * (wm + MW * m) + li;
                         const int pc = min(p, tpix - 1);
-                        const int f = ct_div(pc, a.inv_tw), r = pc - f * (a.th * W), py = ct_div(r, a.inv_w), px = r - py * W;
+                        const int f = idx_div(pc, a.inv_tw), r = pc - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
                         const int n = fg * a.fpt + f, yy = ty * a.th + py;
                         o[m] = p < tpix && n < a.N && yy < H ? (unsigned)(((n * H + yy) * W + px) * K + co0 + 8 * g) : ~0u;
                     }
@@ -299,13 +280,12 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                     // nothing is waited for at all; with one, the loads go out in groups of four pixel tiles (all seven spill) and each group
                     // is waited for once (vmcnt(0): a count that relied on how many stores were issued would break when a pixel tile has no
                     // live lane and its store is branched over).
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                     bf16_t* const yout = a.y;
                     const bf16_t* const resp = a.res;
                     const unsigned ofallback = (unsigned)(co0 + 8 * g);
                     auto finish = [&](auto resc) __attribute__((always_inline)) {
                         constexpr bool RES = decltype(resc)::value;
-                        static_for_ct<0, (MTW + 3) / 4>([&](auto bc) {
+                        static_for<0, (MTW + 3) / 4>([&](auto bc) {
                             constexpr int M0 = 4 * decltype(bc)::value, M1 = M0 + 4 < MTW ? M0 + 4 : MTW;
                             u32x4 rr[4] = {};
                             if constexpr (RES) {
@@ -325,13 +305,13 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                                     v[q] = f32x2{acc[m][q >> 1][2 * (q & 1)], acc[m][q >> 1][2 * (q & 1) + 1]} + f32x2{bias4[q >> 1][2 * (q & 1)], bias4[q >> 1][2 * (q & 1) + 1]};
                                 if constexpr (RES) {
 #pragma unroll
-                                    for (int q = 0; q < 4; ++q) v[q] += f32x2{__uint_as_float(rr[m - M0][q] << 16), __uint_as_float(rr[m - M0][q] & 0xffff0000u)};
+                                    for (int q = 0; q < 4; ++q) v[q] += unpack_bf16x2(rr[m - M0][q]);
                                 }
                                 u32x4 ow;
 #pragma unroll
                                 for (int q = 0; q < 4; ++q) {
                                     v[q] = __builtin_elementwise_max(v[q], f32x2{lo, lo});
-                                    ow[q] = (unsigned)f32_to_bf16(v[q][0]) | ((unsigned)f32_to_bf16(v[q][1]) << 16);
+                                    ow[q] = pack_bf16x2(v[q][0], v[q][1]);
                                 }
                                 // (s_nop: the hazard recogniser does not see an asm store's data registers being rewritten right behind it)
                                 bf16_t* const yp = yout + o[m];
@@ -346,7 +326,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                 for (int m = 0; m < MTW; ++m) {
                     const int p = 16 * (wm + MW * m) + li;
                     if (p >= tpix) continue;
-                    const int f = ct_div(p, a.inv_tw), r = p - f * (a.th * W), py = ct_div(r, a.inv_w), px = r - py * W;
+                    const int f = idx_div(p, a.inv_tw), r = p - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
                     const int n = fg * a.fpt + f, yy = ty * a.th + py;
                     if (n >= a.N || yy >= H) continue;
                     const size_t opix = (((size_t)n * H + yy) * W + px) * K;
@@ -355,9 +335,9 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                         if (co0 + 16 * nt >= K) continue;
                         const size_t o = opix + ct_channel(co0 / 16 + nt, 4 * g, a.perm);
                         f32x4 v = acc[m][nt] + bias4[nt];
-                        if (a.res) v += bf4(*reinterpret_cast<const uint2*>(a.res + o));
+                        if (a.res) v += unpack_bf16x4(*reinterpret_cast<const uint2*>(a.res + o));
                         v = __builtin_elementwise_max(v, f32x4{lo, lo, lo, lo});
-                        *reinterpret_cast<uint2*>(a.y + o) = pk4(v);
+                        *reinterpret_cast<uint2*>(a.y + o) = pack_bf16x4(v);
                     }
                 }
             }
@@ -421,7 +401,6 @@ __global__ __launch_bounds__(256) void conv3x3_pack_train_kernel(PackTrainArgs a
     if (!L.w) return;
     const int K = L.K, C = L.C;
     const size_t nf = (size_t)(K / 16) * (C / CT_CK * 18) * 64, nd = (size_t)(C / 16) * (K / CT_CK * 18) * 64;
-    auto bf = [](float x) { return (unsigned)f32_to_bf16(x); };
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nf + nd; i += (size_t)gridDim.x * 256) {
         const bool fwd = i < nf;
         const size_t ii = fwd ? i : i - nf;
@@ -443,7 +422,7 @@ __global__ __launch_bounds__(256) void conv3x3_pack_train_kernel(PackTrainArgs a
 #pragma unroll
             for (int j = 0; j < 8; ++j) e[j] = src[(long long)j * L.sK];
         }
-        const uint4 o = make_uint4(bf(e[0]) | bf(e[1]) << 16, bf(e[2]) | bf(e[3]) << 16, bf(e[4]) | bf(e[5]) << 16, bf(e[6]) | bf(e[7]) << 16);
+        const uint4 o = pack_bf16x8(e);
         (fwd ? L.fwd : L.dgrad)[ii] = o;
     }
 }

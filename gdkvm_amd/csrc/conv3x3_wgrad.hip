@@ -15,9 +15,8 @@
 //   * every workgroup writes its partial block (fp32) to the workspace; a second kernel adds the partials in a fixed order
 //     (deterministic) into dW [K][C][3][3].
 #include <atomic>
-#include <type_traits>
 
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -35,11 +34,9 @@ struct WgradArgs {
     int fpt, th, tiles_y, ntiles;           // frames per tile, rows per tile, row tiles per frame, tiles in all
     int bw, bh, band_px, tpix;              // band geometry, output pixels of a full tile
     int npx, npy;                           // 1 KiB DMA pieces of the band and of the dy tile
-    float inv_band, inv_bw, inv_tw, inv_w;  // reciprocals for index arithmetic (see conv3x3_tile.hip)
+    float inv_band, inv_bw, inv_tw, inv_w;  // reciprocals for index arithmetic (idx_div)
     int cblocks;                            // C / 64: blockIdx.y = kb * cblocks + cb
 };
-
-__device__ __forceinline__ int wg_div(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }
 
 __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_kernel(WgradArgs a)
 {
@@ -71,19 +68,19 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_kernel(WgradArgs a)
         const bf16_t* xo = a.x + (((long long)fg * a.fpt * H + y0) * W - 1) * C + cb * 64;
         for (int j = w; j < a.npx; j += 4) {
             const int d = 64 * j + lane, pix = d / WG_SLOTS, c = d - WG_SLOTS * pix;
-            const int f = wg_div(pix, a.inv_band), r = pix - f * (a.bh * BW), by = wg_div(r, a.inv_bw), bx = r - by * BW;
+            const int f = idx_div(pix, a.inv_band), r = pix - f * (a.bh * BW), by = idx_div(r, a.inv_bw), bx = r - by * BW;
             const int yy = y0 + by;
             const bool ok = c < 8 && pix < a.band_px && bx >= 1 && bx <= W && (unsigned)yy < (unsigned)H && f < nfr;
             const bf16_t* src = ok ? xo + ((f * H + by) * W + bx) * C + c * 8 : reinterpret_cast<const bf16_t*>(&g_wg_zero16);
-            __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(reinterpret_cast<uintptr_t>(s_x + 1024 * j)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src, lds_dma_dst(s_x + 1024 * j), 16, 0, 0);
         }
         const bf16_t* yo = a.dy + (((long long)fg * a.fpt * H + ty * a.th) * W) * K + kb * 64;
         for (int j = w; j < a.npy; j += 4) {
             const int d = 64 * j + lane, pix = d / WG_SLOTS, c = d - WG_SLOTS * pix;
-            const int f = wg_div(pix, a.inv_tw), r = pix - f * (a.th * W), py = wg_div(r, a.inv_w);
+            const int f = idx_div(pix, a.inv_tw), r = pix - f * (a.th * W), py = idx_div(r, a.inv_w);
             const bool ok = c < 8 && pix < a.tpix && f < nfr && ty * a.th + py < H;
             const bf16_t* src = ok ? yo + ((f * H + py) * W + (r - py * W)) * K + c * 8 : reinterpret_cast<const bf16_t*>(&g_wg_zero16);
-            __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(reinterpret_cast<uintptr_t>(s_y + 1024 * j)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src, lds_dma_dst(s_y + 1024 * j), 16, 0, 0);
         }
     };
 
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_kernel(WgradArgs a)
             for (int hf = 0; hf < 2; ++hf) {
                 const int pp = 32 * s + 8 * g + 4 * hf + q, pix = min(pp, a.tpix - 1);
                 ya[hf] = (unsigned)(uintptr_t)(s_y + min(pp, a.npy * 64 / WG_SLOTS - 1) * WG_PIX + p4 * 2);
-                const int f = wg_div(pix, a.inv_tw), r = pix - f * (a.th * W), py = wg_div(r, a.inv_w), px = r - py * W;
+                const int f = idx_div(pix, a.inv_tw), r = pix - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
                 xa[hf] = (unsigned)(uintptr_t)(s_x + ((f * a.bh + py) * BW + px) * WG_PIX + (16 * w + p4) * 2);
             }
             // all 26 transposed reads of the k-step are issued, then ONE wait (LDS returns in order; the fragments are operands of

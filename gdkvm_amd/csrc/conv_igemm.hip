@@ -17,9 +17,8 @@
 //   * weights are the A operand, pixels the B operand: a lane ends with 4 consecutive output channels of one pixel (8-byte stores).
 // Arithmetic: fp32 accumulation over the same R S C products as a library convolution, one rounding after the epilogue.
 #include <atomic>
-#include <type_traits>
 
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -33,7 +32,7 @@ struct IgArgs {
     int M, ksteps, cps;                          // output pixels; Kd / 32; k-steps per tap (C / 32)
     const bf16_t* w2; const float* bias2; bf16_t* y2; int centre;   // optional second output: the 1x1 convolution (same stride, K channels,
                                                  // bias2 may be NULL) of the window's centre pixel -- tap index `centre` -- with pack w2
-    float inv_cps, inv_s;                        // per-k-step index arithmetic without integer division (see conv3x3_tile.hip: ct_div)
+    float inv_cps, inv_s;                        // per-k-step index arithmetic without integer division (idx_div)
     // ---- data-gradient form (template parameter DG; training, stride 2): x = dy [N, H, W, C] is the gradient of the forward's OUTPUT
     // (C = the forward's output channels), y = dx [N, OH, OW, K] the gradient of its input.  Input pixel (2a + ph, 2b + pw) receives
     // the taps whose parity matches: blockIdx.z = 2 ph + pw is that class, a plain stride-1 convolution of dy with (1 + ph)(1 + pw)
@@ -42,17 +41,6 @@ struct IgArgs {
     struct Cls { const bf16_t* w; int S, ksteps_main, ksteps_all, ksteps_row; float inv_s; } cls[4];   // ksteps_row: k-steps per row tile IN THE PACK (>= ksteps_all: a pack made with the branch read without it)
     const bf16_t* x2; int OH, OW;
 };
-
-__device__ __forceinline__ int ig_div(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }
-
-template <int I, int E, class F>
-__device__ __forceinline__ void ig_static_for(F&& f)
-{
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        ig_static_for<I + 1, E>(f);
-    }
-}
 
 // TM = pixels per workgroup (128); SUB = 32-deep MFMA k-steps
 // per barrier: with C a multiple of 64 a step gathers 128-byte channel runs (two MFMA k-steps: half the barriers, LDS round trips
@@ -103,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(IgArgs a)
     auto gather = [&](int st, uint4 (&d)[GP], unsigned& okm) __attribute__((always_inline)) {
         const bool second = DG && st >= main_steps;
         const int stm = second ? st - main_steps : st;
-        const int tap = ig_div(stm, inv_spt), c0 = (stm - tap * spt) * 32 * SUB, r = ig_div(tap, inv_s_), s = tap - r * S_;
+        const int tap = idx_div(stm, inv_spt), c0 = (stm - tap * spt) * 32 * SUB, r = idx_div(tap, inv_s_), s = tap - r * S_;
         const ptrdiff_t src = second ? x2_diff : 0;
         okm = 0;
 #pragma unroll
@@ -174,8 +162,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(IgArgs a)
         };
         int l = 0;
         for (; l + UF <= L; l += UF)
-            ig_static_for<0, UF>([&](auto jc) { step(l + decltype(jc)::value, jc); });
-        ig_static_for<0, UF - 1>([&](auto jc) { if (l + decltype(jc)::value < L) step(l + decltype(jc)::value, jc); });
+            static_for<0, UF>([&](auto jc) { step(l + decltype(jc)::value, jc); });
+        static_for<0, UF - 1>([&](auto jc) { if (l + decltype(jc)::value < L) step(l + decltype(jc)::value, jc); });
 
         // epilogue: lane (g, li) holds channels n + 4g .. +3 of pixel 16 mt + li
         const float lo = relu ? 0.f : -INFINITY;
@@ -197,13 +185,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(IgArgs a)
                 }
                 if (res) {
                     const uint2 rr = *reinterpret_cast<const uint2*>(res + o);
-                    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                    v[0] += bf16_lo(rr.x); v[1] += bf16_hi(rr.x);
+                    v[2] += bf16_lo(rr.y); v[3] += bf16_hi(rr.y);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], lo);
-                *reinterpret_cast<uint2*>(y + o) = make_uint2((unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16),
-                                                              (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16));
+                *reinterpret_cast<uint2*>(y + o) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
             }
         }
     };

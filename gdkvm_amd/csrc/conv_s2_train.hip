@@ -9,7 +9,7 @@
 //                parity classes of input pixels, each a stride-1 convolution of dy with 1 / 2 / 2 / 4 taps (no products with zeros);
 //   weight grad  gdkvm_conv_wgrad_strided (gemm.hip): dy^T im2col(x) without the im2col, fixed-order split sums.
 // Everything is deterministic: same inputs, same bits.
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 int gdkvm_conv_igemm_dgrad_launch(const void* dy, const void* dy2, const void* packs, int with_down, void* dx, int N, int Cf, int H, int W, int Kf, hipStream_t st);
 
@@ -21,8 +21,6 @@ struct S2PackArgs {
     uint4* fwd; uint4* fwd_down; uint4* dgrad;
     int K, C;
 };
-
-__device__ __forceinline__ unsigned pack2(float a, float b) { return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16); }
 
 // One thread = one 16-byte piece (8 consecutive reduction indices of one fragment row) of one of the packs:
 //   forward  [K/16][9C/32][lane][8]:  w[16 nt + li][kd = 32 ks + 8 g ..],  kd = (3 r + s) C + c          (gdkvm_conv_igemm_pack_weights' order)
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(256) void conv_s2_pack_kernel(S2PackArgs a)
             }
             dst = a.dgrad + base + j;
         }
-        *dst = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+        *dst = pack_bf16x8(v);
     }
 }
 

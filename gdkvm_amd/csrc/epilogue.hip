@@ -8,7 +8,7 @@
 #include <type_traits>
 
 #include <stdlib.h>
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -44,8 +44,8 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const void* x, const floa
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                v[2 * j] = __uint_as_float(aw[j] << 16) + (res ? __uint_as_float(rw[j] << 16) : 0.f);
-                v[2 * j + 1] = __uint_as_float(aw[j] & 0xffff0000u) + (res ? __uint_as_float(rw[j] & 0xffff0000u) : 0.f);
+                v[2 * j] = bf16_lo(aw[j]) + (res ? bf16_lo(rw[j]) : 0.f);
+                v[2 * j + 1] = bf16_hi(aw[j]) + (res ? bf16_hi(rw[j]) : 0.f);
             }
         }
         float bb[V];
@@ -69,10 +69,7 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const void* x, const floa
         if constexpr (IO == GDKVM_F32) {
             o.x = __float_as_uint(v[0]); o.y = __float_as_uint(v[1]); o.z = __float_as_uint(v[2]); o.w = __float_as_uint(v[3]);
         } else {
-            o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-            o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-            o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-            o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
+            o = pack_bf16x8(v);
         }
         yv[i] = o;
     };
@@ -126,8 +123,8 @@ __global__ __launch_bounds__(256) void bias_relu_maxpool_kernel(const void* x, c
             for (int j = 0; j < 4; ++j) {
                 if constexpr (IO == GDKVM_F32) m[j] = fmaxf(m[j], __uint_as_float(w4[j]));
                 else {
-                    m[2 * j] = fmaxf(m[2 * j], __uint_as_float(w4[j] << 16));
-                    m[2 * j + 1] = fmaxf(m[2 * j + 1], __uint_as_float(w4[j] & 0xffff0000u));
+                    m[2 * j] = fmaxf(m[2 * j], bf16_lo(w4[j]));
+                    m[2 * j + 1] = fmaxf(m[2 * j + 1], bf16_hi(w4[j]));
                 }
             }
         }
@@ -141,10 +138,7 @@ __global__ __launch_bounds__(256) void bias_relu_maxpool_kernel(const void* x, c
         if constexpr (IO == GDKVM_F32) {
             o.x = __float_as_uint(m[0]); o.y = __float_as_uint(m[1]); o.z = __float_as_uint(m[2]); o.w = __float_as_uint(m[3]);
         } else {
-            o.x = (unsigned)f32_to_bf16(m[0]) | ((unsigned)f32_to_bf16(m[1]) << 16);
-            o.y = (unsigned)f32_to_bf16(m[2]) | ((unsigned)f32_to_bf16(m[3]) << 16);
-            o.z = (unsigned)f32_to_bf16(m[4]) | ((unsigned)f32_to_bf16(m[5]) << 16);
-            o.w = (unsigned)f32_to_bf16(m[6]) | ((unsigned)f32_to_bf16(m[7]) << 16);
+            o = pack_bf16x8(m);
         }
         yv[i] = o;
     }
@@ -223,13 +217,6 @@ extern "C" int gdkvm_bias_act(const void* x, const float* bias, const void* resi
 // blend in fp32.  One thread = 8 channels (16 bytes) of one output pixel.
 namespace {
 
-__device__ __forceinline__ void unpack8(const uint4& a, float (&v)[8])
-{
-    const unsigned w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[2 * j] = __uint_as_float(w[j] << 16); v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-}
-
 // One workgroup per output row (image n, row y), grid-striding over rows: the vertical taps and weights are uniform per row
 // and every index is 32-bit (the first version spent its time in 64-bit div/mod per vector and ran at 48 % of the HBM rate).
 // Per row a thread handles its share of the W*C1/8 interpolated vectors (four independent tap loads each) and of the W*C2/8
@@ -268,7 +255,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bf16_kernel(const bf16_t* lo
                 const uint4 t10 = *reinterpret_cast<const uint4*>(lo1 + x0 * C1 + c), t11 = *reinterpret_cast<const uint4*>(lo1 + x1 * C1 + c);
                 if (u0 + tid >= nu) continue;
                 float a[8], b[8], cc[8], d[8];
-                unpack8(t00, a); unpack8(t01, b); unpack8(t10, cc); unpack8(t11, d);
+                unpack_bf16x8(t00, a); unpack_bf16x8(t01, b); unpack_bf16x8(t10, cc); unpack_bf16x8(t11, d);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const int x = 2 * jp + 1 + e;
@@ -279,7 +266,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bf16_kernel(const bf16_t* lo
                     for (int q = 0; q < 4; ++q) {
                         const float v0 = hy * (hx * a[2 * q] + lx * b[2 * q]) + ly * (hx * cc[2 * q] + lx * d[2 * q]);
                         const float v1 = hy * (hx * a[2 * q + 1] + lx * b[2 * q + 1]) + ly * (hx * cc[2 * q + 1] + lx * d[2 * q + 1]);
-                        r[q] = (unsigned)f32_to_bf16(v0) | ((unsigned)f32_to_bf16(v1) << 16);
+                        r[q] = pack_bf16x2(v0, v1);
                     }
                     *reinterpret_cast<uint4*>(orow + x * C + c) = make_uint4(r[0], r[1], r[2], r[3]);
                 }
@@ -307,13 +294,13 @@ __global__ __launch_bounds__(256) void upsample_cat_bf16_kernel(const bf16_t* lo
                 if (j0 + u * 256 + tid >= n1) continue;
                 const float hx = 1.f - lx[u];
                 float a[8], b[8], cc[8], d[8];
-                unpack8(t[u][0], a); unpack8(t[u][1], b); unpack8(t[u][2], cc); unpack8(t[u][3], d);
+                unpack_bf16x8(t[u][0], a); unpack_bf16x8(t[u][1], b); unpack_bf16x8(t[u][2], cc); unpack_bf16x8(t[u][3], d);
                 unsigned r[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float v0 = hy * (hx * a[2 * q] + lx[u] * b[2 * q]) + ly * (hx * cc[2 * q] + lx[u] * d[2 * q]);
                     const float v1 = hy * (hx * a[2 * q + 1] + lx[u] * b[2 * q + 1]) + ly * (hx * cc[2 * q + 1] + lx[u] * d[2 * q + 1]);
-                    r[q] = (unsigned)f32_to_bf16(v0) | ((unsigned)f32_to_bf16(v1) << 16);
+                    r[q] = pack_bf16x2(v0, v1);
                 }
                 *reinterpret_cast<uint4*>(orow + oidx[u]) = make_uint4(r[0], r[1], r[2], r[3]);
             }
@@ -366,7 +353,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bf16_2x_kernel(const bf16_t*
             const uint4 t10 = *reinterpret_cast<const uint4*>(lo1 + x0 * C1 + c), t11 = *reinterpret_cast<const uint4*>(lo1 + x1 * C1 + c);
             if (u0 + tid >= nu) continue;
             float a[8], b[8], cc[8], d[8];
-            unpack8(t00, a); unpack8(t01, b); unpack8(t10, cc); unpack8(t11, d);
+            unpack_bf16x8(t00, a); unpack_bf16x8(t01, b); unpack_bf16x8(t10, cc); unpack_bf16x8(t11, d);
 #pragma unroll
             for (int ey = 0; ey < 2; ++ey) {
                 const int y = 2 * ip + 1 + ey;
@@ -385,7 +372,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bf16_2x_kernel(const bf16_t*
                     for (int q = 0; q < 4; ++q) {
                         const float v0 = hy * (hx * a[2 * q] + lx * b[2 * q]) + ly * (hx * cc[2 * q] + lx * d[2 * q]);
                         const float v1 = hy * (hx * a[2 * q + 1] + lx * b[2 * q + 1]) + ly * (hx * cc[2 * q + 1] + lx * d[2 * q + 1]);
-                        r[q] = (unsigned)f32_to_bf16(v0) | ((unsigned)f32_to_bf16(v1) << 16);
+                        r[q] = pack_bf16x2(v0, v1);
                     }
                     *reinterpret_cast<uint4*>(orow + x * C + c) = make_uint4(r[0], r[1], r[2], r[3]);
                 }
@@ -456,7 +443,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const void* x, void* y
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if constexpr (IO == GDKVM_F32) v[j] = __uint_as_float(w4[j]);
-                else { v[2 * j] = __uint_as_float(w4[j] << 16); v[2 * j + 1] = __uint_as_float(w4[j] & 0xffff0000u); }
+                else { v[2 * j] = bf16_lo(w4[j]); v[2 * j + 1] = bf16_hi(w4[j]); }
             }
 #pragma unroll
             for (int j = 0; j < V; ++j)
@@ -523,7 +510,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const void* dy, const 
                 const unsigned wt = (bt[q][j >> 2] >> (8 * (j & 3))) & 0xffu;
                 float d;
                 if constexpr (IO == GDKVM_F32) d = __uint_as_float(w4[j]);
-                else d = (j & 1) ? __uint_as_float(w4[j >> 1] & 0xffff0000u) : __uint_as_float(w4[j >> 1] << 16);
+                else d = (j & 1) ? bf16_hi(w4[j >> 1]) : bf16_lo(w4[j >> 1]);
                 acc[j] += (int)wt == tap[q] ? d : 0.f;
             }
         }
@@ -531,10 +518,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const void* dy, const 
         if constexpr (IO == GDKVM_F32) {
             o.x = __float_as_uint(acc[0]); o.y = __float_as_uint(acc[1]); o.z = __float_as_uint(acc[2]); o.w = __float_as_uint(acc[3]);
         } else {
-            o.x = (unsigned)f32_to_bf16(acc[0]) | ((unsigned)f32_to_bf16(acc[1]) << 16);
-            o.y = (unsigned)f32_to_bf16(acc[2]) | ((unsigned)f32_to_bf16(acc[3]) << 16);
-            o.z = (unsigned)f32_to_bf16(acc[4]) | ((unsigned)f32_to_bf16(acc[5]) << 16);
-            o.w = (unsigned)f32_to_bf16(acc[6]) | ((unsigned)f32_to_bf16(acc[7]) << 16);
+            o = pack_bf16x8(acc);
         }
         xv[i] = o;
     }
@@ -588,7 +572,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bwd_bf16_kernel(const bf16_t
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
                         float v[8];
-                        unpack8(t[a][b], v);
+                        unpack_bf16x8(t[a][b], v);
                         const float wgt = wy[a] * wx[b];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc[e] = fmaf(wgt, v[e], acc[e]);
@@ -603,7 +587,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bwd_bf16_kernel(const bf16_t
                         const float wgt = wy * tap_weight(ox, j, sx, wl);
                         if (wgt == 0.f) continue;
                         float v[8];
-                        unpack8(*reinterpret_cast<const uint4*>(dimg + ((size_t)oy * W + ox) * C + c), v);
+                        unpack_bf16x8(*reinterpret_cast<const uint4*>(dimg + ((size_t)oy * W + ox) * C + c), v);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc[e] = fmaf(wgt, v[e], acc[e]);
                     }
@@ -611,7 +595,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bwd_bf16_kernel(const bf16_t
             }
             unsigned r[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) r[q] = (unsigned)f32_to_bf16(acc[2 * q]) | ((unsigned)f32_to_bf16(acc[2 * q + 1]) << 16);
+            for (int q = 0; q < 4; ++q) r[q] = pack_bf16x2(acc[2 * q], acc[2 * q + 1]);
             *reinterpret_cast<uint4*>(dlo + ((size_t)row * wl + j) * C1 + c) = make_uint4(r[0], r[1], r[2], r[3]);
         }
     }

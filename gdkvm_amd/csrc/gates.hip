@@ -4,7 +4,7 @@
 // As framework ops this is a token-mean reduction, two N = 1 GEMMs, two bf16 -> fp32 casts and a bias add: six launches,
 // ~34 us of a 1.4 ms forward, for 6.4 MB of input.  Here a workgroup reads its frame's tokens once (16-byte loads, fp32
 // accumulation, no intermediate rounding) and writes fp32 logits -- the dtype gdkvm_scan_prep reads.
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void gate_logits_kernel(const void* p, const f
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if constexpr (IO == GDKVM_F32) v[j] = __uint_as_float(xw[j]);
-                    else { v[2 * j] = __uint_as_float(xw[j] << 16); v[2 * j + 1] = __uint_as_float(xw[j] & 0xffff0000u); }
+                    else { v[2 * j] = bf16_lo(xw[j]); v[2 * j + 1] = bf16_hi(xw[j]); }
                 }
                 float dg = 0.f, dd = 0.f;
 #pragma unroll
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const void* x, const f
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if constexpr (IO == GDKVM_F32) v[j] = __uint_as_float(xw[j]);
-            else { v[2 * j] = __uint_as_float(xw[j] << 16); v[2 * j + 1] = __uint_as_float(xw[j] & 0xffff0000u); }
+            else { v[2 * j] = bf16_lo(xw[j]); v[2 * j + 1] = bf16_hi(xw[j]); }
         }
         float mine = 0.f;                                    // lane cg keeps class cg's logit (ncls <= G)
         for (int c = 0; c < ncls; ++c) {
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const void* x, const void
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if constexpr (IO == GDKVM_F32) v[j] = __uint_as_float(xw[j]);
-            else { v[2 * j] = __uint_as_float(xw[j] << 16); v[2 * j + 1] = __uint_as_float(xw[j] & 0xffff0000u); }
+            else { v[2 * j] = bf16_lo(xw[j]); v[2 * j + 1] = bf16_hi(xw[j]); }
         }
         const size_t n = pc / HW, r = pc - n * HW;
         float mine = (live && cg < ncls) ? load1<IO>(dz, (n * ncls + cg) * HW + r) : 0.f;       // lane cg fetches class cg's gradient
@@ -172,8 +172,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const void* x, const void
             uint4 q;
             if constexpr (IO == GDKVM_F32) { q.x = __float_as_uint(o[0]); q.y = __float_as_uint(o[1]); q.z = __float_as_uint(o[2]); q.w = __float_as_uint(o[3]); }
             else {
-                q.x = (unsigned)f32_to_bf16(o[0]) | ((unsigned)f32_to_bf16(o[1]) << 16); q.y = (unsigned)f32_to_bf16(o[2]) | ((unsigned)f32_to_bf16(o[3]) << 16);
-                q.z = (unsigned)f32_to_bf16(o[4]) | ((unsigned)f32_to_bf16(o[5]) << 16); q.w = (unsigned)f32_to_bf16(o[6]) | ((unsigned)f32_to_bf16(o[7]) << 16);
+                q = pack_bf16x8(o);
             }
             static_cast<uint4*>(dx)[p * G + cg] = q;
         }

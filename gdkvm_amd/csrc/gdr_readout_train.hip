@@ -10,7 +10,7 @@
 // Both are frame-parallel, exact fp32 (v_mfma_f32_16x16x4_f32) on operands read straight from global memory: the k index of
 // an MFMA step is free to be permuted, and every product here is arranged so that a lane's k values are CONTIGUOUS in memory
 // (lane group g of k step s takes k = g K/4 + s), i.e. plain 16-byte loads, no LDS staging, no transposes.
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 #include "gdr_ws.hpp"
 
 namespace {
@@ -70,8 +70,7 @@ __global__ __launch_bounds__(256) void gdr_readout_hist_kernel(ReadHistArgs a)
         if (16 * tt + li < N) {
             char* p = static_cast<char*>(a.r_out) + (((bt * N + 16 * tt + li) * Hh + h) * (size_t)Dv + 16 * c + 4 * g) * ESZ;
             if constexpr (IO == GDKVM_F32) *reinterpret_cast<f32x4*>(p) = r;
-            else *reinterpret_cast<uint2*>(p) = make_uint2((unsigned)f32_to_bf16(r[0]) | ((unsigned)f32_to_bf16(r[1]) << 16),
-                                                           (unsigned)f32_to_bf16(r[2]) | ((unsigned)f32_to_bf16(r[3]) << 16));
+            else *reinterpret_cast<uint2*>(p) = pack_bf16x4(r);
         }
     }
 }

@@ -8,7 +8,7 @@
 // over the 64 key channels -- plain fp32, deterministic, no operand splitting (a frame is 49 ... 256 tokens: ~3 us, launch-bound).
 // Normalisation (GDKVM_FLAG_NORMALIZE_QK): the inverse norm of the row AS STORED multiplies the finished dot product; `norms`
 // ([rows, Hh, 2] from gdkvm_proj_gates: entry 1 is the query's) is used when given.
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 #include "gdr_ws.hpp"
 
 namespace {
@@ -183,8 +183,8 @@ __global__ __launch_bounds__(WG_THREADS) void mask_embed_wgrad_kernel(WgradArgs 
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        acc[2 * k] = fmaf(av, __uint_as_float(w4[k] << 16), acc[2 * k]);
-                        acc[2 * k + 1] = fmaf(av, __uint_as_float(w4[k] & 0xffff0000u), acc[2 * k + 1]);
+                        acc[2 * k] = fmaf(av, bf16_lo(w4[k]), acc[2 * k]);
+                        acc[2 * k + 1] = fmaf(av, bf16_hi(w4[k]), acc[2 * k + 1]);
                     }
                 }
             }

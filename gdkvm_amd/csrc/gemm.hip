@@ -10,7 +10,7 @@
 //                                                   back transposed (ds_read_b64_tr_b16) as MFMA fragments.
 // bf16 operands run on v_mfma_f32_16x16x32_bf16, fp32 operands on the exact v_mfma_f32_16x16x4_f32.
 
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -103,8 +103,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p)
             if (n + 3 < N && (N & 3) == 0) {
                 if constexpr (IO == GDKVM_F32) *reinterpret_cast<f32x4*>(static_cast<float*>(p.c) + (size_t)m * N + n) = acc[i][j];
                 else *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p.c) + (size_t)m * N + n) =
-                         make_uint2((unsigned)f32_to_bf16(acc[i][j][0]) | ((unsigned)f32_to_bf16(acc[i][j][1]) << 16),
-                                    (unsigned)f32_to_bf16(acc[i][j][2]) | ((unsigned)f32_to_bf16(acc[i][j][3]) << 16));
+                         pack_bf16x4(acc[i][j]);
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (n + r < N) store1<IO>(p.c, (size_t)m * N + n + r, acc[i][j][r]);

@@ -17,8 +17,7 @@
 //                         channel counts, or a caller that hands over no workspace
 // plus the training forward (saves gates / mixes / pooled feature) and the elementwise halves of the backward.
 #include <atomic>
-#include <type_traits>
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -32,15 +31,6 @@ struct KpffArgs {
     KpffSave sv;
     int cols_per_tile, col_tiles;     // grids wider than 16 columns: a tile is a row band x a block of 16 columns
 };
-
-template <int I, int E, class F>
-__device__ __forceinline__ void kpff_static_for(F&& f)
-{
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        kpff_static_for<I + 1, E>(f);
-    }
-}
 
 constexpr int KPFF_TM = 64;       // tokens per workgroup tile
 constexpr int KPFF_PAD = 4;       // row padding in floats: stride % 64 == 4 -> 16 rows cover all 64 banks
@@ -159,9 +149,9 @@ __global__ __launch_bounds__(256) void kpff_kernel(KpffArgs a)
                 wl3(i + WD, rb[j]);
             };
             int i = 0;
-            for (; i + WD <= n; i += WD) kpff_static_for<0, WD>([&](auto jc) { body(i + decltype(jc)::value, jc); });
+            for (; i + WD <= n; i += WD) static_for<0, WD>([&](auto jc) { body(i + decltype(jc)::value, jc); });
             const int rem = n - i;
-            kpff_static_for<0, WD - 1>([&](auto jc) { if (decltype(jc)::value < rem) body(i + decltype(jc)::value, jc); });
+            static_for<0, WD - 1>([&](auto jc) { if (decltype(jc)::value < rem) body(i + decltype(jc)::value, jc); });
         };
         run(0, kbP, nullptr, nullptr, std::false_type{});
         run(kbP, kbL, a.wl + (size_t)o * Ck + 4 * g, lp, std::true_type{});
@@ -327,9 +317,9 @@ __device__ __forceinline__ void kpff_stream(const bf16_t* xb, int ld, int ks0, i
     };
     int i = 0;
     for (; i + KPFF_WD <= n; i += KPFF_WD)                 // (i stays a multiple of KPFF_WD: the set ids are static)
-        kpff_static_for<0, KPFF_WD>([&](auto jc) { body(i + decltype(jc)::value, jc); });
+        static_for<0, KPFF_WD>([&](auto jc) { body(i + decltype(jc)::value, jc); });
     const int rem = n - i;
-    kpff_static_for<0, KPFF_WD - 1>([&](auto jc) {
+    static_for<0, KPFF_WD - 1>([&](auto jc) {
         if (decltype(jc)::value < rem) body(i + decltype(jc)::value, jc);
     });
 }
@@ -465,8 +455,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
             const int q = ((p >> 3) << 1) | ((p >> 1) & 1);
-            const float v[4] = {__uint_as_float(u[p].x << 16), __uint_as_float(u[p].x & 0xffff0000u),
-                                __uint_as_float(u[p].y << 16), __uint_as_float(u[p].y & 0xffff0000u)};
+            const float v[4] = {bf16_lo(u[p].x), bf16_hi(u[p].x), bf16_lo(u[p].y), bf16_hi(u[p].y)};
             const float m = ok[p] ? 1.f : 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { s2[q][j] += v[j]; s4[j] += v[j]; }
@@ -477,14 +466,13 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
         for (int p = 0; p < 16; ++p) {
             const int q = ((p >> 3) << 1) | ((p >> 1) & 1);
             const float i2 = 1.0f / fmaxf(n2[q], 1.f);
-            const float v[4] = {__uint_as_float(u[p].x << 16), __uint_as_float(u[p].x & 0xffff0000u),
-                                __uint_as_float(u[p].y << 16), __uint_as_float(u[p].y & 0xffff0000u)};
+            const float v[4] = {bf16_lo(u[p].x), bf16_hi(u[p].x), bf16_lo(u[p].y), bf16_hi(u[p].y)};
             float r[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) r[j] = (v[j] + s2[q][j] * i2 + s4[j] * i4) * (1.0f / 3.0f);
             const int y = pi.y0 + (p >> 2), x = pi.x0 + (p & 3);
             if (ok[p]) *reinterpret_cast<uint2*>(gx + (size_t)(y * W + x) * ld + pi.c) =
-                make_uint2((unsigned)f32_to_bf16(r[0]) | ((unsigned)f32_to_bf16(r[1]) << 16), (unsigned)f32_to_bf16(r[2]) | ((unsigned)f32_to_bf16(r[3]) << 16));
+                make_uint2(pack_bf16x2(r[0], r[1]), pack_bf16x2(r[2], r[3]));
         }
     };
     // (Measured and withdrawn in round 3: requesting the cell's loads here and doing the arithmetic behind the [P ; L] part of the first
@@ -540,8 +528,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
             const int trow = 16 * mt + li, sb = (NT > 1 && trow >= SB) ? 1 : 0, tok = trow - SB * sb;
             if (tok < t_ntok[sb]) {
                 const uint2 pu = *reinterpret_cast<const uint2*>(s_xb + (size_t)trow * ld + oc);
-                const float pv[4] = {__uint_as_float(pu.x << 16), __uint_as_float(pu.x & 0xffff0000u),
-                                     __uint_as_float(pu.y << 16), __uint_as_float(pu.y & 0xffff0000u)};
+                const float pv[4] = {bf16_lo(pu.x), bf16_hi(pu.x), bf16_lo(pu.y), bf16_hi(pu.y)};
                 float y[4], sl[4], sg[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -550,8 +537,7 @@ __global__ __launch_bounds__(256 * NT / OT, (NT == 1 ? 2 : 1)) void kpff_bf16_ke
                     y[r] = pv[r] + sl[r] * lp[o][mt][r] + sg[r] * gp[o][mt][r];
                 }
                 auto pack4 = [](const float (&v)[4]) {
-                    return make_uint2((unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16),
-                                      (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16));
+                    return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
                 };
                 const size_t grow = (size_t)t_f[sb] * N + gtok(sb, tok);
                 *reinterpret_cast<uint2*>(a.out + grow * Cp + oc) = pack4(y);
@@ -639,9 +625,9 @@ __device__ __forceinline__ void kpff_stream_split(const bf16_t* xh, const bf16_t
         __builtin_amdgcn_sched_barrier(0);
     };
     int i = 0;
-    for (; i + WD <= n; i += WD) kpff_static_for<0, WD>([&](auto jc) { body(i + decltype(jc)::value, jc); });
+    for (; i + WD <= n; i += WD) static_for<0, WD>([&](auto jc) { body(i + decltype(jc)::value, jc); });
     const int rem = n - i;
-    kpff_static_for<0, WD - 1>([&](auto jc) { if (decltype(jc)::value < rem) body(i + decltype(jc)::value, jc); });
+    static_for<0, WD - 1>([&](auto jc) { if (decltype(jc)::value < rem) body(i + decltype(jc)::value, jc); });
 }
 
 __global__ __launch_bounds__(512) void kpff_split_kernel(KpffSplitArgs a)
@@ -958,8 +944,8 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
                         float dd = 0.f;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            dd = fmaf(__uint_as_float(xw[j] << 16), wd[2 * j], dd);
-                            dd = fmaf(__uint_as_float(xw[j] & 0xffff0000u), wd[2 * j + 1], dd);
+                            dd = fmaf(bf16_lo(xw[j]), wd[2 * j], dd);
+                            dd = fmaf(bf16_hi(xw[j]), wd[2 * j + 1], dd);
                         }
                         dsum += (n0 + tpw * u + sub < ga.N) ? dd : 0.f;
                     }
@@ -995,10 +981,10 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
                 const uint4 xv = *reinterpret_cast<const uint4*>(s_px + (size_t)tok * ld + pc * 8);
                 const f32x4 w0 = *reinterpret_cast<const f32x4*>(ga.w_gate + (size_t)h * K + pc * 8);
                 const f32x4 w1 = *reinterpret_cast<const f32x4*>(ga.w_gate + (size_t)h * K + pc * 8 + 4);
-                d = fmaf(__uint_as_float(xv.x << 16), w0[0], d); d = fmaf(__uint_as_float(xv.x & 0xffff0000u), w0[1], d);
-                d = fmaf(__uint_as_float(xv.y << 16), w0[2], d); d = fmaf(__uint_as_float(xv.y & 0xffff0000u), w0[3], d);
-                d = fmaf(__uint_as_float(xv.z << 16), w1[0], d); d = fmaf(__uint_as_float(xv.z & 0xffff0000u), w1[1], d);
-                d = fmaf(__uint_as_float(xv.w << 16), w1[2], d); d = fmaf(__uint_as_float(xv.w & 0xffff0000u), w1[3], d);
+                d = fmaf(bf16_lo(xv.x), w0[0], d); d = fmaf(bf16_hi(xv.x), w0[1], d);
+                d = fmaf(bf16_lo(xv.y), w0[2], d); d = fmaf(bf16_hi(xv.y), w0[3], d);
+                d = fmaf(bf16_lo(xv.z), w1[0], d); d = fmaf(bf16_hi(xv.z), w1[1], d);
+                d = fmaf(bf16_lo(xv.w), w1[2], d); d = fmaf(bf16_hi(xv.w), w1[3], d);
             }
 #pragma unroll
             for (int o = TPT >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o);
@@ -1025,8 +1011,8 @@ __global__ __launch_bounds__(512) void proj_gates_kernel(ProjGateArgs ga)
                                        (unsigned)f32_to_bf16(acc[0][mt][2] + b4[2]) | ((unsigned)f32_to_bf16(acc[0][mt][3] + b4[3]) << 16));
             if (row < (size_t)a.M) *reinterpret_cast<uint2*>(dst + row * wd + cbase) = o;
             if (ot < ntile_norm) {                                    // sums of squares of the values as stored (bf16)
-                const float v0 = __uint_as_float(o.x << 16), v1 = __uint_as_float(o.x & 0xffff0000u);
-                const float v2 = __uint_as_float(o.y << 16), v3 = __uint_as_float(o.y & 0xffff0000u);
+                const float v0 = bf16_lo(o.x), v1 = bf16_hi(o.x);
+                const float v2 = bf16_lo(o.y), v3 = bf16_hi(o.y);
                 float ss = v0 * v0 + v1 * v1 + v2 * v2 + v3 * v3;
                 ss += __shfl_xor(ss, 16);
                 ss += __shfl_xor(ss, 32);

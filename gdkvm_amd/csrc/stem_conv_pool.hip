@@ -14,7 +14,7 @@
 //     max) and writes bf16 into the LDS tile; after one barrier all 512 threads pool 3 x 3 windows out of LDS and store the
 //     pooled pixels -- 51 MB instead of 213 + 213 + 51.
 #include <atomic>
-#include "gdkvm_common.hpp"
+#include "gdkvm_device.hpp"
 
 namespace {
 
@@ -105,8 +105,7 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
             const int by = pix / SP_BC, bx = pix - by * SP_BC, yy = y0 + by, xx = x0 + bx;
             const bool ok = pix < SP_BR * SP_BC && yy >= 0 && yy < a.Hs && xx >= 0 && xx < a.Ws;
             const bf16_t* src = ok ? a.xs + ((((size_t)n * a.Hs + yy) * a.Ws + xx) * 16 + c * 8) : reinterpret_cast<const bf16_t*>(&g_stem_zero16);
-            __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(
-                reinterpret_cast<uintptr_t>(band2 + buf * SP_BAND_BYTES + 1024 * j)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src, lds_dma_dst(band2 + buf * SP_BAND_BYTES + 1024 * j), 16, 0, 0);
         }
     };
 
@@ -114,10 +113,9 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
     // The 16 loads of a tile are unconditional buffer loads through a descriptor over the tile's frame (all its channels).  What does not
     // depend on the tile is computed once, here, as per-lane 32-bit values: the slot's band position (by << 8 | bx, -1 = no such slot) and
     // its BYTE offset from the band's (0, 0) pixel inside a channel plane, and per load the plane / row-parity offset.  A tile adds a
-    // scalar (its band origin) and the row / column test; a slot outside the image gets SP_DEAD, which is out of the descriptor's range
+    // scalar (its band origin) and the row / column test; a slot outside the image gets RSRC_DEAD, which is out of the descriptor's range
     // with any plane offset added (the launcher keeps four planes below 2^31 bytes), and so do the planes of channels >= Cf: the range
     // check supplies the zeros, no load stands under a branch, and no address outside the frame is formed.
-    constexpr unsigned SP_DEAD = 0x80000000u;
     unsigned stage[PP][4];
     int s_byx[NCHW ? PP : 1];
     unsigned s_rel[NCHW ? PP : 1], s_ce[4];
@@ -137,14 +135,13 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
     auto fetch_nchw = [&](TilePos p, bool on) __attribute__((always_inline)) {          // !on: every slot dead (nothing is read)
         const int y0 = (POOL ? 2 * SP_TPY * p.ty - 1 : SP_CR * p.ty) - 2, x0 = (POOL ? 2 * SP_TPX * p.tx - 1 : (SP_CC - 7) * p.tx) - 2;
         const int H = 2 * a.Hs, W = 2 * a.Ws;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.xf + (long long)(on ? p.n : 0) * a.Cf * H * W), 0,
-                                                                              a.Cf * H * W * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(a.xf + (long long)(on ? p.n : 0) * a.Cf * H * W, a.Cf * H * W * 2);
         const unsigned ts = (unsigned)((2 * y0 * W + 2 * x0) * 2);
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
             const int yy = y0 + (s_byx[u] >> 8), xx = x0 + (s_byx[u] & 255);
             const bool ok = on & (s_byx[u] >= 0) & ((unsigned)yy < (unsigned)a.Hs) & ((unsigned)xx < (unsigned)a.Ws);      // (no short circuit: no branch)
-            const unsigned b = ok ? s_rel[u] + ts : SP_DEAD;
+            const unsigned b = ok ? s_rel[u] + ts : RSRC_DEAD;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 stage[u][e] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(b + s_ce[e]), 0, 0);
@@ -222,7 +219,7 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
                         unsigned ow[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
-                            ow[q] = (unsigned)f32_to_bf16(acc[r][q >> 1][2 * (q & 1)]) | ((unsigned)f32_to_bf16(acc[r][q >> 1][2 * (q & 1) + 1]) << 16);
+                            ow[q] = pack_bf16x2(acc[r][q >> 1][2 * (q & 1)], acc[r][q >> 1][2 * (q & 1) + 1]);
                         *reinterpret_cast<uint4*>(a.y + (((size_t)n * a.Hs + cy) * a.Ws + cx) * 64 + 32 * wn + 8 * g) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
                     }
                 }
@@ -233,14 +230,13 @@ __global__ __launch_bounds__(512, 1) void stem_conv_pool_kernel(StemArgs a)
             for (int r = 0; r < 3; ++r) {
                 const int cr = 3 * grp + r, cy = cy0 + cr;
                 const float keep = (col_ok && cy >= 0 && cy < a.Hs) ? 1.f : 0.f;        // (values are >= 0 after the ReLU: masking is a multiply)
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
                 unsigned ow[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {                                            // packed fp32 pairs: add, max, mul
                     const f32x2 t = {acc[r][q >> 1][2 * (q & 1)], acc[r][q >> 1][2 * (q & 1) + 1]};
                     const f32x2 bb = {bia[2 * q], bia[2 * q + 1]};
                     f32x2 v = __builtin_elementwise_max(t + bb, f32x2{0.f, 0.f}) * f32x2{keep, keep};
-                    ow[q] = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
+                    ow[q] = pack_bf16x2(v[0], v[1]);
                 }
                 *reinterpret_cast<uint4*>(ctile + (cr * SP_CC + 16 * wm + li) * SP_CPIX + (32 * wn + 8 * g) * 2) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
             }
@@ -355,7 +351,7 @@ __global__ __launch_bounds__(256, 3) void stem_wgrad_kernel(StemWgradArgs a)
             const int py = pix / SW_TW, px = pix - py * SW_TW, cy = cy0 + py, cx = cx0 + px;
             const bool ok = c < 8 && pix < SW_TH * SW_TW && cy < a.Hs && cx < a.Ws;
             const bf16_t* src = ok ? a.dy + ((((size_t)n * a.Hs + cy) * a.Ws + cx) * 64 + c * 8) : reinterpret_cast<const bf16_t*>(&g_stem_zero16);
-            __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(reinterpret_cast<uintptr_t>(s_y + 1024 * j)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src, lds_dma_dst(s_y + 1024 * j), 16, 0, 0);
         }
 #pragma unroll
         for (int u = 0; u < SW_BPT; ++u) {

@@ -1,7 +1,10 @@
 """CPU checks of round 6's host-side rules: pack / graph invalidation is per model and only on real changes, a convolution that leaves the
 hand-written path says so (and raises under GDKVM_STRICT=1), the launcher honours the reference guide's CUDA_VISIBLE_DEVICES, the
-flat-gradient exchange refuses a parameter without a gradient, stream groups of a captured segment must keep 16-byte output slabs."""
+flat-gradient exchange refuses a parameter without a gradient, stream groups of a captured segment must keep 16-byte output slabs.  And one rule of the kernel sources: the shared device idioms are
+written once, in csrc/gdkvm_device.hpp."""
+import glob
 import os
+import re
 import subprocess
 import types
 import warnings
@@ -166,3 +169,42 @@ def test_segment_stream_groups_need_aligned_output_slabs():
     tgt = object()
     with pytest.raises(ValueError, match="16-byte"):
         M.GraphedSegment(m, fake, tgt, streams=2)
+
+
+# The kernel sources that build.source_hash() pins (bench.py quotes the committed PMC summaries while they are unchanged) keep their own copies.
+_FROZEN = {"gdr_prep.hip", "gdr_scan.hip", "gdr_device.hpp", "gdr_ws.hpp", "gdkvm_common.hpp"}
+_RAW_IDIOMS = {
+    "bf16 pair pack": r"\(unsigned\)\s*f32_to_bf16\([^;]*\|\s*\(\s*\(unsigned\)\s*f32_to_bf16\([^;]*<<\s*16",
+    "bf16 pair unpack": r"__uint_as_float\([^;{}]*?(<<\s*16|&\s*0xffff0000u)\s*\)",
+    "LDS-DMA destination cast": r"address_space\(3\)",
+    "raw buffer descriptor": r"make_buffer_rsrc",
+}
+# Sites left as they were because the helper changed the file's gfx950 assembly (tools/isa_equal.py): (file, idiom) -> reason
+_RAW_IDIOM_ALLOWED = {
+    ("gdr_normalizer.hip", "bf16 pair pack"): "the packed values are quotients computed in the arguments: through pack_bf16x2 both divisions come "
+                                              "before both conversions and the schedule changes (76 assembly lines)",
+    ("gdr_step.hip", "bf16 pair pack"): "the packed values are products computed in the arguments: same reordering (6 assembly lines)",
+    ("kpff.hip", "bf16 pair pack"): "the two bias-add epilogues pack sums computed in the arguments: same reordering (152 assembly lines)",
+}
+
+
+def test_device_idioms_live_in_one_header():
+    csrc = os.path.join(ROOT, "gdkvm_amd", "csrc")
+    found, local_defs = set(), []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))):
+        name = os.path.basename(path)
+        with open(path) as f:
+            text = f.read()
+        if name != "gdkvm_device.hpp" and name not in _FROZEN:
+            found |= {(name, idiom) for idiom, rx in _RAW_IDIOMS.items() if re.search(rx, text)}
+        if name.endswith(".hip"):
+            # static_for_desc (gdr_scan_bwd.hip) counts DOWN: a different function, it stays
+            local_defs += [(name, d) for d in re.findall(r"\bvoid\s+(\w*static_for\w*)\s*\(", text) if d != "static_for_desc"]
+            local_defs += [(name, d) for d in re.findall(r"\b(\w+_div)\s*\(\s*int\s+n\s*,\s*float\s+inv\s*\)", text)]
+    assert not local_defs, f"compile-time loop / reciprocal division defined outside gdkvm_device.hpp: {local_defs}"
+    assert found == set(_RAW_IDIOM_ALLOWED), (f"raw idioms outside gdkvm_device.hpp that are not allowed: {sorted(found - set(_RAW_IDIOM_ALLOWED))}; "
+                                              f"allowed but gone: {sorted(set(_RAW_IDIOM_ALLOWED) - found)}")
+    with open(os.path.join(csrc, "gdkvm_device.hpp")) as f:
+        header = f.read()
+    assert all(re.search(rx, header) for rx in _RAW_IDIOMS.values())          # the patterns above do match the idioms they name
+    assert re.search(r"\bvoid\s+static_for\s*\(", header) and re.search(r"\bidx_div\s*\(\s*int\s+n\s*,\s*float\s+inv\s*\)", header)
