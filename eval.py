@@ -2,7 +2,10 @@
 """Evaluation entry point: per-class Dice / IoU of the argmax masks over a dataset split and, for class `data.lv_class`, the left-ventricular
 volumes and ejection fraction measured from the masks on the device (ops.lv_measure / lv_ef: pixel^3 of the network's input grid, isotropic
 pixels assumed; EF is a ratio); clips sharded over the GPUs of one node (no data-path collective; only the integer Dice counts and the eight
-EF sums are summed at the end).
+EF sums are summed at the end).  With `data.lv_keep_largest` = 4 or 8 the PREDICTED mask is measured after ops.largest_component kept the
+largest 4- / 8-connected component of that class (fill 0; the target is a tracing and is measured as it is): the `lv` block is then the
+post-processed one, a `largest_component` block reports what was removed and the class's Dice / IoU after it, and every other key is still
+computed from the unfiltered mask.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [key=value ...]"""
 from __future__ import annotations
@@ -55,6 +58,9 @@ def main(argv=None):
     counts = torch.zeros(cfg.data.num_classes, 3, dtype=torch.int64, device=dev)
     lv_cls = cfg.data.lv_class
     ef_sums = torch.zeros(8, dtype=torch.float64, device=dev)     # ops.ef_summary, accumulated on the device and read once at the end
+    keep = cfg.data.lv_keep_largest if lv_cls >= 0 else 0         # 0 = off: no new call below
+    # the filtered mask's counts [ncls, 3], then frames changed and pixels removed: accumulated on the device, read once at the end
+    lc_acc = torch.zeros(cfg.data.num_classes * 3 + 2, dtype=torch.int64, device=dev) if keep else None
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -67,32 +73,39 @@ def main(argv=None):
         """(mask, counts, target's LV measurement) per batch, one batch behind the submissions: the host queues batch i + 1 (copy, cast, replay)
         before it reads batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time).
         The TARGET is measured right behind the submission, on the stream where the prefetcher handed it out: its slot is recycled once the
-        consumer asks for the next batch, so nothing may read it later."""
+        consumer asks for the next batch, so nothing may read it later -- the largest-component filter of the prediction, one batch behind,
+        wants the target for its hit counts and gets a copy made here."""
         pending = None
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
             nxt = runner.submit(frames, target)
             if lv_cls >= 0:
                 t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
-                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous())
+                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), target.clone() if keep else None)
             else:
-                nxt = (nxt, None, None)
+                nxt = (nxt, None, None, None)
             if pending is not None:
                 yield pending[0].get() + pending[1:]
             pending = nxt
         if pending is not None:
             yield pending[0].get() + pending[1:]
 
-    for mask, c, t_vol, t_npix in batches():
-        if lv_cls >= 0:
-            # the prediction's volumes at the TARGET's end-diastolic / end-systolic frames (EchoNet-Dynamic: the two traced frames; unlabelled
-            # frames hold no pixel of the class and are no candidates); a clip counts when its target has two such frames and a volume
-            p_stats, _, p_geom = ops.lv_measure(mask, cls=lv_cls)
-            r_idx, r_val = ops.lv_ef(t_vol, t_npix)
-            _, p_val = ops.lv_ef(p_geom[..., 1], p_stats[..., 0], pick_vol=t_vol, pick_npix=t_npix)
-            ef_sums += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
+    for mask, c, t_vol, t_npix, t_copy in batches():
         # only frames that carry labels count (EchoNet-Dynamic: the two traced frames of a clip -- gdkvm_amd.data.IGNORE_LABEL everywhere
         # else, where a predicted pixel must not enter |A|): a labelled frame has a non-empty target in some class
         labelled = (c[..., 2].sum(-1, keepdim=True) > 0).unsqueeze(-1)
+        measured = mask
+        if keep:
+            measured, lc = ops.largest_component(mask, cls=lv_cls, connectivity=keep, fill=0, target=t_copy)
+            removed = (lc[..., 1] - lc[..., 2]).long()
+            lc_acc += torch.cat([(ops.counts_after_largest(c, lc, lv_cls, 0) * labelled).sum((0, 1)).long().reshape(-1),
+                                 torch.stack([(removed > 0).sum(), removed.sum()])])
+        if lv_cls >= 0:
+            # the prediction's volumes at the TARGET's end-diastolic / end-systolic frames (EchoNet-Dynamic: the two traced frames; unlabelled
+            # frames hold no pixel of the class and are no candidates); a clip counts when its target has two such frames and a volume
+            p_stats, _, p_geom = ops.lv_measure(measured, cls=lv_cls)
+            r_idx, r_val = ops.lv_ef(t_vol, t_npix)
+            _, p_val = ops.lv_ef(p_geom[..., 1], p_stats[..., 0], pick_vol=t_vol, pick_npix=t_npix)
+            ef_sums += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
         counts += (c * labelled).sum((0, 1)).long()
         if vis_left > 0:
             from PIL import Image
@@ -105,6 +118,8 @@ def main(argv=None):
         torch.distributed.all_reduce(counts)                      # the only exchanges: 3 integers per class ...
         if lv_cls >= 0:
             torch.distributed.all_reduce(ef_sums)                 # ... and the eight EF sums
+        if keep:
+            torch.distributed.all_reduce(lc_acc)                  # ... and the filtered mask's counts and removal totals
     if rank == 0:
         dice = ops.dice_from_counts(counts).tolist()
         iou = ops.iou_from_counts(counts).tolist()
@@ -115,6 +130,12 @@ def main(argv=None):
                "mean_foreground_iou": round(sum(iou[1:]) / max(len(iou) - 1, 1), 5)}
         if lv_cls >= 0:
             res["lv"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.ef_stats(ef_sums.cpu()).items()}
+        if keep:
+            acc = lc_acc.cpu()
+            lc_counts = acc[:-2].view(cfg.data.num_classes, 3)
+            res["largest_component"] = {"connectivity": keep, "frames_changed": int(acc[-2]), "pixels_removed": int(acc[-1]),
+                                        "dice_lv": round(float(ops.dice_from_counts(lc_counts)[lv_cls]), 5),
+                                        "iou_lv": round(float(ops.iou_from_counts(lc_counts)[lv_cls]), 5)}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -24,6 +24,8 @@ class DataCfg:
     size: int = 256
     num_classes: int = 4
     lv_class: int = 1                # eval.py: the class whose volumes and ejection fraction are measured (ops.lv_measure / lv_ef); -1 = off
+    lv_keep_largest: int = 0         # eval.py: keep the largest connected component of lv_class in the PREDICTED mask before it is measured
+                                     # (ops.largest_component, fill = 0); 0 = off, 4 or 8 = the connectivity
 
 
 @dataclass
@@ -100,4 +102,6 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
         node[parts[-1]] = yaml.safe_load(val)
     cfg = _build(RunConfig, raw)
     cfg.learning_rate = float(cfg.learning_rate)
+    if isinstance(cfg.data.lv_keep_largest, bool) or cfg.data.lv_keep_largest not in (0, 4, 8):
+        raise ValueError(f"data.lv_keep_largest = {cfg.data.lv_keep_largest!r}: 0 (off), 4 or 8 (the connectivity)")
     return cfg

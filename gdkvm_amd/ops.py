@@ -116,6 +116,8 @@ SIGNATURES = {
     "gdkvm_augment_clips": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
     "gdkvm_lv_measure": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
+    "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
+    "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
 }
 
 
@@ -2155,3 +2157,67 @@ def ef_stats(sums) -> dict:
     vp, vg, cov = n * spp - sp * sp, n * sgg - sg * sg, n * spg - sp * sg
     r = cov / (vp * vg) ** 0.5 if n >= 2 and vp > 0 and vg > 0 else 0.0
     return {"clips_with_ef": int(n), "ef_mae": sae / n, "ef_bias": se / n, "ef_pearson_r": r, "mean_ref_ef": sg / n, "mean_pred_ef": sp / n}
+
+
+def largest_component(mask: torch.Tensor, cls: int = 1, connectivity: int = 4, fill: int = 0, target: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None):
+    """gdkvm_largest_component: per frame of mask [..., H, W] uint8 keep the largest connected component of class `cls` (4- or 8-connected;
+    ties: the component with the smallest linear index) and write `fill` over the class's other pixels (definition: include/gdkvm.h; every
+    output is an exact integer).  Returns (out uint8 like mask, info int32 [..., 8] = components, n, n_kept, label_kept (-1: no pixel of the
+    class), removed_hit_cls, removed_hit_fill, 0, 0); the two hit counts say what the removed pixels were in `target` (same shape; 0 without
+    one), which is what counts_after_largest needs.  out=mask filters in place; mask, target and out may start at any byte address."""
+    lib = load()
+    if mask.dtype != torch.uint8 or mask.dim() < 2:
+        raise GdkvmError(f"largest_component: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
+    H, W = mask.shape[-2:]
+    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
+        raise GdkvmError(f"largest_component: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
+    if not 0 <= int(cls) <= 254:
+        raise GdkvmError(f"largest_component: cls = {cls} outside 0..254")
+    if int(connectivity) not in (4, 8):
+        raise GdkvmError(f"largest_component: connectivity = {connectivity} is neither 4 nor 8")
+    if not 0 <= int(fill) <= 255 or int(fill) == int(cls):
+        raise GdkvmError(f"largest_component: fill = {fill} must lie in 0..255 and differ from cls = {cls}")
+    for name, t in (("target", target), ("out", out)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != tuple(mask.shape)):
+            raise GdkvmError(f"largest_component: {name} must be uint8 {tuple(mask.shape)}, got {t.dtype} {tuple(t.shape)}")
+    dev = _dev(mask, target, out)
+    lead = tuple(mask.shape[:-2])
+    frames = 1
+    for s in lead:
+        frames *= s
+    if out is None:
+        out = torch.empty_like(mask)
+    info = torch.empty(lead + (8,), dtype=torch.int32, device=dev)
+    # (allocated per call like every workspace of this module: under graph capture it comes from the graph's own pool and is replayed with it)
+    need = int(lib.gdkvm_largest_component_workspace_bytes(frames, H, W))
+    ws = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.gdkvm_largest_component(_ptr(mask), _ptr(target), _ptr(out), _ptr(info), _ptr(ws), ws.numel(), frames, H, W, int(cls),
+                                         int(connectivity), int(fill), _stream(dev))
+    _check(rc, "gdkvm_largest_component")
+    return out, info
+
+
+def counts_after_largest(counts: torch.Tensor, info: torch.Tensor, cls: int, fill: int) -> torch.Tensor:
+    """The argmax_dice-style counts [..., ncls, 3] = |A n B|, |A|, |B| of the mask largest_component(mask, cls, fill=fill, target=target)
+    wrote, from the counts of the unfiltered mask and that call's info [..., 8]: the removed pixels leave class `cls` (|A| -= n - n_kept,
+    |A n B| -= removed_hit_cls) and join class `fill` when it is one of the counted classes (|A| += n - n_kept, |A n B| += removed_hit_fill);
+    every other entry is unchanged.  Pure torch on either device, integer-exact."""
+    if counts.dim() < 2 or counts.shape[-1] != 3 or info.shape[-1] != 8 or tuple(counts.shape[:-2]) != tuple(info.shape[:-1]):
+        raise GdkvmError(f"counts_after_largest: counts [..., ncls, 3] and info [..., 8] must share their leading dimensions, got "
+                         f"{tuple(counts.shape)} and {tuple(info.shape)}")
+    ncls = counts.shape[-2]
+    if not 0 <= int(cls) < ncls:
+        raise GdkvmError(f"counts_after_largest: cls = {cls} is none of the {ncls} counted classes")
+    if torch.is_floating_point(counts):
+        raise GdkvmError("counts_after_largest: counts must be integers")
+    inf = info.to(counts.dtype)
+    removed = inf[..., 1] - inf[..., 2]
+    res = counts.clone()
+    res[..., int(cls), 0] -= inf[..., 4]
+    res[..., int(cls), 1] -= removed
+    if 0 <= int(fill) < ncls:
+        res[..., int(fill), 0] += inf[..., 5]
+        res[..., int(fill), 1] += removed
+    return res

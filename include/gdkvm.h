@@ -620,6 +620,31 @@ int gdkvm_lv_measure(const uint8_t* mask, int64_t* stats, int64_t* disks, double
 int gdkvm_lv_ef(const double* vol, const int64_t* npix, const double* pick_vol, const int64_t* pick_npix,
                 int32_t* ed_es_nvalid, double* edv_esv_ef, int B, int T, int64_t min_pixels, void* stream);
 
+/* Keep the largest connected component of one class of label masks (the clean-up in front of gdkvm_lv_measure: an argmax mask is no tracing,
+ * and a false-positive island far from the ventricle enters tmin / tmax, the long axis and the disks; csrc/largest_component.hip).  Every
+ * output is an integer that depends on neither the algorithm nor the schedule.
+ * Per frame mask [H, W] uint8, class cls (0..254), connectivity 4 or 8, fill (0..255, != cls), H, W in 1..1024:
+ *   1. P = the pixels with mask[y][x] == cls; every other byte, 255 and every other class included, is "not cls".
+ *   2. Two pixels of P in the SAME frame are adjacent when |dx| + |dy| == 1 (connectivity 4) or max(|dx|, |dy|) == 1 (connectivity 8).
+ *      Adjacency is geometric, not by linear index: (W - 1, y) and (0, y + 1) are no neighbours, nor are the last pixel of frame f and the
+ *      first pixel of frame f + 1.
+ *   3. A component is an equivalence class of the transitive closure of adjacency; its LABEL is its smallest linear index y W + x.
+ *   4. The KEPT component is the one with the most pixels; on a tie the smallest label wins.
+ *   5. out[p] = mask[p] when mask[p] != cls or p lies in the kept component, otherwise out[p] = fill.
+ *   6. info [frames, 8] int32 = components (their number), n = |P|, n_kept, label_kept (-1 when P is empty),
+ *        removed_hit_cls = |{p removed : target[p] == cls}|, removed_hit_fill = |{p removed : target[p] == fill}| (both 0 when target == NULL),
+ *        0, 0.   P empty: out = mask and info = {0, 0, 0, -1, 0, 0, 0, 0}.
+ * mask, target (optional) and out are [frames, H, W] contiguous at ANY byte address (frames of H W bytes follow each other); out is either
+ * exactly mask (in place) or does not overlap it; info is 16-byte aligned.  The workspace (16-byte aligned, at least
+ * gdkvm_largest_component_workspace_bytes(frames, H, W) bytes: 0 while H W <= 15360, where the labels live in LDS, else 4 bytes per pixel with
+ * each frame's slice rounded up to 16 bytes) is scratch.  One workgroup per frame; neither entry allocates or synchronises; bit-reproducible.
+ * Every loop of the kernel is bounded by H W; should a frame ever reach that bound (the derivation in the source says it cannot), it reports
+ * components = -1, n_kept = n, label_kept = -1 and out = mask.  Bad arguments (shape, cls, connectivity, fill, null or misaligned pointers,
+ * a short workspace, a partial overlap) are GDKVM_ERR_SHAPE before any device call; frames == 0 is GDKVM_OK without a launch. */
+size_t gdkvm_largest_component_workspace_bytes(int frames, int H, int W);
+int gdkvm_largest_component(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, void* workspace, size_t workspace_bytes,
+                            int frames, int H, int W, int cls, int connectivity, int fill, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What the LV measurement costs (profiles/r10_a_lv_probe.txt).  python3 tools/lv_probe.py [--quick] [--no-eval]
+"""What the LV measurement and the largest-component filter in front of it cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt).
+python3 tools/lv_probe.py [--quick] [--no-eval]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -7,9 +8,11 @@
     empty queue would time the host's way to the launch, not a kernel of a few microseconds); time per launch = window / CALLS, the forms
     alternated window by window over four rotating inputs, median and minimum over the windows.  Masks: one rotated ellipse per frame covering
     about a tenth of it (a ventricle); every pixel of the class (the worst case for the per-pixel passes); no pixel of the class.  The floor is
-    the bytes read (and, for the mask kernel, written) once over the 6.3 TB/s achievable HBM rate.
-(b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1 and -1,
-    alternated, twice each."""
+    the bytes read (and, for the mask kernel, written) once over the 6.3 TB/s achievable HBM rate.  gdkvm_largest_component (class 1,
+    4-connected, fill 0, out of place, with a target) runs in the same windows on the same three fills, the ellipses with three islands each
+    (discs of radius 1 to 5 % of the side; the kernel removes them), and at 8-connectivity on the first.
+(b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
+    data.lv_keep_largest=4 on top of it, and with data.lv_class=-1, alternated, twice each."""
 import math
 import os
 import statistics
@@ -40,6 +43,19 @@ def ellipse_masks(F, S, seed):
     return out
 
 
+def add_islands(masks, seed):
+    """Three discs of class 1 per frame, away from the centre where the ellipse lies (they may touch it: then they are no islands)."""
+    rng = np.random.default_rng(seed)
+    F, S, _ = masks.shape
+    yy, xx = np.mgrid[0:S, 0:S]
+    out = masks.copy()
+    for f in range(F):
+        for _ in range(3):
+            cy, cx = (rng.uniform(0.04, 0.16) * S if rng.random() < 0.5 else rng.uniform(0.84, 0.96) * S for _ in range(2))
+            out[f][(yy - cy) ** 2 + (xx - cx) ** 2 <= (rng.uniform(0.01, 0.05) * S) ** 2] = 1
+    return out
+
+
 CALLS = 20            # launches per timed window
 
 
@@ -47,7 +63,12 @@ def part_a(dev, F, S, reps, n_in=4):
     lib = ops.load()
     st = torch.cuda.current_stream(dev).cuda_stream
     g = torch.Generator().manual_seed(S)
-    masks = [torch.from_numpy(ellipse_masks(F, S, s)).to(dev) for s in range(n_in)]
+    masks_np = [ellipse_masks(F, S, s) for s in range(n_in)]
+    masks = [torch.from_numpy(m).to(dev) for m in masks_np]
+    isl = [torch.from_numpy(add_islands(m, s)).to(dev) for s, m in enumerate(masks_np)]
+    cc_out = torch.empty((F, S, S), dtype=torch.uint8, device=dev)
+    cc_info = torch.empty((F, 8), dtype=torch.int32, device=dev)
+    cc_ws = torch.empty(max(16, int(lib.gdkvm_largest_component_workspace_bytes(F, S, S))), dtype=torch.uint8, device=dev)
     full = torch.ones((F, S, S), dtype=torch.uint8, device=dev)
     logits = [torch.randn((F, 2, S // 4, S // 4), generator=g).to(dev).bfloat16() for _ in range(n_in)]
     m_out = torch.empty((F, S, S), dtype=torch.uint8, device=dev)
@@ -58,6 +79,11 @@ def part_a(dev, F, S, reps, n_in=4):
 
     def lv(mask, cls):
         rc = lib.gdkvm_lv_measure(mask.data_ptr(), stats.data_ptr(), disks.data_ptr(), geom.data_ptr(), F, S, S, cls, 20, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def cc(mask, target, cls, conn=4):
+        rc = lib.gdkvm_largest_component(mask.data_ptr(), target.data_ptr(), cc_out.data_ptr(), cc_info.data_ptr(), cc_ws.data_ptr(), cc_ws.numel(),
+                                         F, S, S, cls, conn, 0, st)
         assert rc == 0, lib.gdkvm_last_error()
 
     def up(i):
@@ -71,7 +97,17 @@ def part_a(dev, F, S, reps, n_in=4):
         "lv_measure, every pixel of the class": (lambda i: lv(full, 1), F * S * S),
         "lv_measure, no pixel of the class": (lambda i: lv(full, 2), F * S * S),
         "upsample_argmax_dice (writes the mask)": (up, F * (2 * 2 * (S // 4) ** 2 + 2 * S * S)),
+        "largest_component, ellipse + 3 islands": (lambda i: cc(isl[i], masks[i], 1), 2 * F * S * S),
+        "largest_component, the same, 8-connected": (lambda i: cc(isl[i], masks[i], 1, 8), 2 * F * S * S),
+        "largest_component, ellipse alone (a copy)": (lambda i: cc(masks[i], masks[i], 1), 2 * F * S * S),
+        "largest_component, every pixel of the class": (lambda i: cc(full, masks[i], 1), 2 * F * S * S),
+        "largest_component, no pixel of the class": (lambda i: cc(full, masks[i], 2), 2 * F * S * S),
     }
+    cc(isl[0], masks[0], 1)
+    torch.cuda.synchronize()
+    removed = (cc_info[:, 1] - cc_info[:, 2]).float()
+    print(f"    (islands: {float(cc_info[:, 0].float().mean()):.2f} components per frame, {float(removed.mean()):.0f} of {float(cc_info[:, 1].float().mean()):.0f} "
+          f"pixels removed; label words in {'LDS' if cc_ws.numel() == 16 else 'the workspace, ' + str(cc_ws.numel() >> 20) + ' MiB'})")
     times = {name: [] for name in forms}
     for r in range(reps + 3):
         for name, (fn, _) in forms.items():
@@ -94,15 +130,14 @@ def part_a(dev, F, S, reps, n_in=4):
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
-        for lv in (1, -1):
+        for keys in (["data.lv_class=1", "data.lv_keep_largest=0"], ["data.lv_class=1", "data.lv_keep_largest=4"], ["data.lv_class=-1"]):
             t0 = time.perf_counter()
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "eval.py"), f"data.lv_class={lv}"] + overrides, capture_output=True, text=True,
-                                 timeout=600)
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "eval.py")] + keys + overrides, capture_output=True, text=True, timeout=600)
             dt = time.perf_counter() - t0
             if out.returncode != 0:
                 print(out.stderr[-2000:])
-                raise SystemExit(f"eval.py failed with data.lv_class={lv}")
-            print(f"  run {run + 1} data.lv_class={lv:2d}: {dt:6.2f} s   {out.stdout.strip().splitlines()[-1]}", flush=True)
+                raise SystemExit(f"eval.py failed with {' '.join(keys)}")
+            print(f"  run {run + 1} {' '.join(keys):44s}: {dt:6.2f} s   {out.stdout.strip().splitlines()[-1]}", flush=True)
 
 
 def main():
