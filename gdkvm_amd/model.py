@@ -688,8 +688,7 @@ class GDKVM(nn.Module):
         missed = []
 
         def pack_and_run():
-            ws = torch.empty(ops.load().gdkvm_kpff_workspace_bytes(local.shape[-1], glob.shape[-1], pixel.shape[-1], ops._io_dtype(local)),
-                             dtype=torch.uint8, device=local.device)
+            ws = ops.kpff_workspace(local, glob, pixel)
             missed.append(ops.kpff_fwd(local, glob, pixel, p.wa, p.ba, p.wl, p.wg, h, w, workspace=ws, packed=False))
             return ws
 

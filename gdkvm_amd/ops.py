@@ -3,9 +3,14 @@
 Every function checks shapes on the host, hands raw device pointers + the current HIP stream to
 libgdkvm_hip.so and returns torch tensors.  No fallback path exists: a missing library or a CPU tensor
 raises (the product must never silently run anything but the HIP kernels).
+
+The rule of this module: ONE helper launches (_call: device, symbol, C arguments, stream, error under the name of the entry that
+ran), ONE sizes workspaces (_bytes, with _workspace / _grown_workspace allocating from it); a wrapper checks shapes, allocates its
+outputs and names its entry point once.  Pointers are never taken by hand: tensors go to _call as they are, workspaces as _Ws(t).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional, Tuple
@@ -190,6 +195,113 @@ def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
+class _Ws:
+    """Marks a tensor as a workspace argument of _call: it becomes (pointer, size in BYTES); _Ws(None) is (NULL, 0)."""
+    __slots__ = ("t",)
+
+    def __init__(self, t: Optional[torch.Tensor]):
+        self.t = t
+
+
+def _c_args(args) -> list:
+    """The C values of a wrapper's arguments (pure: no device needed): a tensor is its pointer, None and an empty tensor are NULL (_ptr),
+    a _Ws is pointer and byte count, everything else (ints, floats, ctypes values) passes through.  Runs once per launch, for ~20
+    arguments: ints leave on the first test, and an empty tensor's data_ptr() is 0, which `or None` turns into what _ptr returns."""
+    out = []
+    add = out.append
+    for a in args:
+        if type(a) is int:
+            add(a)
+        elif isinstance(a, torch.Tensor):
+            add(a.data_ptr() or None)
+        elif type(a) is _Ws:
+            out += (None, 0) if a.t is None else (a.t.data_ptr() or None, a.t.nbytes)
+        else:
+            add(a)
+    return out
+
+
+_BOUND = {}
+
+
+def _call(name: str, dev, *args) -> None:
+    """THE launch: entry point `name` (looked up once) with `dev` current, on dev's current stream (appended as the last argument).  Raises
+    GdkvmError naming `name` with the library's own message."""
+    fn = _BOUND.get(name)
+    if fn is None:
+        fn = _BOUND[name] = getattr(load(), name)
+    with torch.cuda.device(dev):
+        rc = fn(*_c_args(args), _stream(dev))
+    if rc:
+        _check(rc, name)
+
+
+_SIZES = {}
+
+
+def _bytes(name: str, dev, *dims) -> int:
+    """Size query `name`(*dims), asked once per (entry, device, dims) with `dev` current (some sizes depend on the device's CU count; dev
+    None: whichever is current) and remembered: a size is a pure function of these."""
+    n = _SIZES.get((name, dev, dims))
+    if n is None:
+        with torch.cuda.device(dev) if dev is not None else contextlib.nullcontext():
+            n = _SIZES[(name, dev, dims)] = int(getattr(load(), name)(*dims))
+    return n
+
+
+def _workspace(name: str, dev, *dims, floor: int = 0) -> torch.Tensor:
+    """A fresh uint8 workspace of the size the `*_workspace_bytes` entry `name` asks for (at least `floor` bytes)."""
+    return torch.empty(max(floor, _bytes(name, dev, *dims)), dtype=torch.uint8, device=dev)
+
+
+_GROWN_WS = {}
+
+
+def _grown_workspace(name: str, dev, *dims) -> torch.Tensor:
+    """One workspace per (size entry, device, stream), grown to the largest request and never shrunk: calls on a stream are ordered,
+    so the next layer may overwrite it.  Different size entries never share a buffer."""
+    need = max(16, _bytes(name, dev, *dims))
+    key = (name, dev, _stream(dev))
+    ws = _GROWN_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _GROWN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _channels_last(what: str, *ts, dtype=None, shape: str = "[N,C,H,W]") -> None:
+    for t in ts:
+        if t.dim() != 4 or not t.is_cuda or (dtype is not None and t.dtype != dtype) or not t.is_contiguous(memory_format=torch.channels_last):
+            raise GdkvmError(f"{what} needs channels_last{'' if dtype is None else ' ' + str(dtype)[6:]} {shape} device tensors (no CPU path)")
+
+
+def _u8_target(target: Optional[torch.Tensor], BT: int, H: int, W: int) -> None:
+    if target is not None and (target.dtype != torch.uint8 or tuple(target.shape) != (BT, H, W)):
+        raise GdkvmError("target must be uint8 [BT,H,W]")
+
+
+def _f32_vectors(what: str, c: int, *ts) -> None:
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or t.numel() != c or not t.is_contiguous()):
+            raise GdkvmError(f"{what}: weight / bias / running statistics must be contiguous float32 [C]")
+
+
+def _scan_operands(q, k, v, alpha, beta, state):
+    """The shape / dtype contract every scan entry shares; returns (B, T, N, Hh, Dk, Dv)."""
+    if q.dim() != 5 or k.shape != q.shape or v.dim() != 5 or v.shape[:4] != q.shape[:4]:
+        raise GdkvmError(f"bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}")
+    B, T, N, Hh, Dk = q.shape
+    Dv = v.shape[-1]
+    if tuple(alpha.shape) != (B, T, Hh) or tuple(beta.shape) != (B, T, N, Hh):
+        raise GdkvmError(f"bad gate shapes alpha{tuple(alpha.shape)} beta{tuple(beta.shape)}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise GdkvmError("q, k, v must share one dtype")
+    if alpha.dtype != torch.float32 or beta.dtype != torch.float32:
+        raise GdkvmError("alpha / beta must be float32")
+    if state is not None and (tuple(state.shape) != (B, Hh, Dk, Dv) or state.dtype != torch.float32):
+        raise GdkvmError("state must be float32 [B,Hh,Dk,Dv]")
+    return B, T, N, Hh, Dk, Dv
+
+
 KERNEL_DK = 64                # per-head key dim the fast kernels are built for (include/gdkvm.h; narrower keys run on them through zero
                               # channels, wider ones -- up to 256 -- on the general kernel of csrc/gdr_general.hip, trained through gdr_general_bwd.hip)
 
@@ -204,7 +316,7 @@ def _pad_keys(q, k, state):
 
 
 def scan_workspace_bytes(B, T, Hh, N, Dk, Dv) -> int:
-    return int(load().gdkvm_scan_workspace_bytes(B, T, Hh, N, Dk, Dv))
+    return _bytes("gdkvm_scan_workspace_bytes", None, B, T, Hh, N, Dk, Dv)
 
 
 def scan_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor,
@@ -222,9 +334,7 @@ def scan_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, alpha: torch.Ten
     check=True: wait for the call and raise GdkvmError if the data left that range (gdkvm_scan_status; synchronises the stream).
     norms [B*T*N, Hh, 2] fp32 (ops.proj_gates): the inverse key / query norms came with the projections (gdkvm_scan_fwd_normed:
     the frame-parallel kernel neither reads q nor reduces anything in its first phase); needs FLAG_NORMALIZE_QK, Dk = 64."""
-    lib = load()
-    if q.dim() != 5 or k.shape != q.shape or v.dim() != 5 or v.shape[:4] != q.shape[:4]:
-        raise GdkvmError(f"bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}")
+    B, T, N, Hh, Dk, Dv = _scan_operands(q, k, v, alpha, beta, state)
     if q.shape[-1] < KERNEL_DK and state_hist is None and q.shape[-1] % 8:      # key widths that are no multiple of 8: padded here
         qp, kp, sp = _pad_keys(q, k, state)                # (multiples of 8 below 64: gdkvm_scan_fwd zero-extends them itself)
         r, s = scan_fwd(qp, kp, v, alpha, beta, sp, rule, flags, workspace, out, None, None, readout, None, check)
@@ -233,40 +343,20 @@ def scan_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, alpha: torch.Ten
             state_out.copy_(s)
             s = state_out
         return r, s
-    B, T, N, Hh, Dk = q.shape
-    Dv = v.shape[-1]
-    if tuple(alpha.shape) != (B, T, Hh) or tuple(beta.shape) != (B, T, N, Hh):
-        raise GdkvmError(f"bad gate shapes alpha{tuple(alpha.shape)} beta{tuple(beta.shape)}")
-    if k.dtype != q.dtype or v.dtype != q.dtype:
-        raise GdkvmError("q, k, v must share one dtype")
-    if alpha.dtype != torch.float32 or beta.dtype != torch.float32:
-        raise GdkvmError("alpha / beta must be float32")
-    if state is not None and (tuple(state.shape) != (B, Hh, Dk, Dv) or state.dtype != torch.float32):
-        raise GdkvmError("state must be float32 [B,Hh,Dk,Dv]")
     dev = _dev(q, k, v, alpha, beta, state, workspace, out, state_out, state_hist)
     io = _io_dtype(q)
-    need = scan_workspace_bytes(B, T, Hh, N, Dk, Dv)
     if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        workspace = _workspace("gdkvm_scan_workspace_bytes", dev, B, T, Hh, N, Dk, Dv)
     r = None if not readout else (out if out is not None else torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev))
     s = state_out if state_out is not None else torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
     if norms is not None:
         if state_hist is not None or norms.dtype != torch.float32 or norms.numel() != B * T * N * Hh * 2 or not norms.is_contiguous() \
                 or norms.device != dev:
             raise GdkvmError("scan_fwd: norms must be contiguous float32 [B*T*N, Hh, 2] on the inputs' device (inference: no state_hist)")
-        with torch.cuda.device(dev):
-            rc = lib.gdkvm_scan_fwd_normed(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), norms.data_ptr(), _ptr(state), _ptr(r), _ptr(s),
-                                           workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                           B, T, Hh, N, Dk, Dv, io, rule, flags, _stream(dev))
-        _check(rc, "gdkvm_scan_fwd_normed")
-        if check:
-            scan_status(workspace, B, T, Hh, N, Dk, Dv, flags | (FLAG_WIDE_RANGE if rule == RULE_DELTA_PARALLEL else 0))
-        return r, s
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_scan_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(state), _ptr(r), _ptr(s),
-                                _ptr(state_hist), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                B, T, Hh, N, Dk, Dv, io, rule, flags, _stream(dev))
-    _check(rc, "gdkvm_scan_fwd")
+        name, extra = "gdkvm_scan_fwd_normed", (norms, state, r, s)      # (norms where the history's pointer is not: no state_hist here)
+    else:
+        name, extra = "gdkvm_scan_fwd", (state, r, s, state_hist)
+    _call(name, dev, q, k, v, alpha, beta, *extra, _Ws(workspace), B, T, Hh, N, Dk, Dv, io, rule, flags)
     if check:
         scan_status(workspace, B, T, Hh, N, Dk, Dv, flags | (FLAG_WIDE_RANGE if rule == RULE_DELTA_PARALLEL else 0))
     return r, s
@@ -277,36 +367,22 @@ def scan_fwd_normalizer(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, alpha
                         flags: int = 0, eps: float = 1e-6):
     """gdkvm_scan_fwd_normalizer (SURVEY.md A.1's `normalizer` flag): the scan with z [B,Hh,Dk] carried beside S and the read-out divided
     by |q . z| + eps.  Returns (R [B,T,N,Hh,Dv], S_T [B,Hh,Dk,Dv] fp32, z_T [B,Hh,Dk] fp32).  Inference only; Dk = 64."""
-    lib = load()
-    if q.dim() != 5 or k.shape != q.shape or v.dim() != 5 or v.shape[:4] != q.shape[:4]:
-        raise GdkvmError(f"bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}")
-    B, T, N, Hh, Dk = q.shape
-    Dv = v.shape[-1]
-    if tuple(alpha.shape) != (B, T, Hh) or tuple(beta.shape) != (B, T, N, Hh) or alpha.dtype != torch.float32 or beta.dtype != torch.float32:
-        raise GdkvmError(f"bad gates alpha{tuple(alpha.shape)} beta{tuple(beta.shape)} (float32)")
-    if k.dtype != q.dtype or v.dtype != q.dtype:
-        raise GdkvmError("q, k, v must share one dtype")
-    if state is not None and (tuple(state.shape) != (B, Hh, Dk, Dv) or state.dtype != torch.float32):
-        raise GdkvmError("state must be float32 [B,Hh,Dk,Dv]")
+    B, T, N, Hh, Dk, Dv = _scan_operands(q, k, v, alpha, beta, state)
     if z is not None and (tuple(z.shape) != (B, Hh, Dk) or z.dtype != torch.float32):
         raise GdkvmError("z must be float32 [B,Hh,Dk]")
     dev = _dev(q, k, v, alpha, beta, state, z)
     io = _io_dtype(q)
-    ws = torch.empty(int(lib.gdkvm_scan_normalizer_workspace_bytes(B, T, Hh, N, Dk, Dv, io)), dtype=torch.uint8, device=dev)
+    ws = _workspace("gdkvm_scan_normalizer_workspace_bytes", dev, B, T, Hh, N, Dk, Dv, io)
     r = torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev)
     s = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
     zo = torch.empty((B, Hh, Dk), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_scan_fwd_normalizer(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(state), _ptr(z), _ptr(r), _ptr(s), _ptr(zo),
-                                           ws.data_ptr(), ws.numel(), B, T, Hh, N, Dk, Dv, io, rule, flags, float(eps), _stream(dev))
-    _check(rc, "gdkvm_scan_fwd_normalizer")
+    _call("gdkvm_scan_fwd_normalizer", dev, q, k, v, alpha, beta, state, z, r, s, zo, _Ws(ws), B, T, Hh, N, Dk, Dv, io, rule, flags, float(eps))
     return r, s, zo
 
 
 def lkva_read(q: torch.Tensor, state: torch.Tensor, flags: int = 0, norms: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """gdkvm_lkva_read: R [B,N,Hh,Dv] = Qn S for ONE frame per clip (the read half of a per-frame step).  q [B,N,Hh,Dk] f32|bf16,
     state [B,Hh,Dk,Dv] fp32, norms [B*N,Hh,2] fp32 from ops.proj_gates or None."""
-    lib = load()
     if q.dim() != 4 or state.dim() != 4 or state.shape[0] != q.shape[0] or state.shape[1] != q.shape[2] or state.shape[2] != q.shape[3]:
         raise GdkvmError(f"lkva_read: bad shapes q{tuple(q.shape)} state{tuple(state.shape)}")
     if state.dtype != torch.float32:
@@ -317,25 +393,19 @@ def lkva_read(q: torch.Tensor, state: torch.Tensor, flags: int = 0, norms: Optio
     if norms is not None and (norms.dtype != torch.float32 or norms.numel() != B * N * Hh * 2):
         raise GdkvmError("lkva_read: norms must be float32 [B*N, Hh, 2]")
     r = _out_like(out, (B, N, Hh, Dv), q.dtype, dev, "lkva_read") if out is not None else torch.empty((B, N, Hh, Dv), dtype=q.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_lkva_read(_ptr(q), _ptr(norms), _ptr(state), _ptr(r), B, N, Hh, Dk, Dv, _io_dtype(q), flags, _stream(dev))
-    _check(rc, "gdkvm_lkva_read")
+    _call("gdkvm_lkva_read", dev, q, norms, state, r, B, N, Hh, Dk, Dv, _io_dtype(q), flags)
     return r
 
 
 def mask_embed_add_(v: torch.Tensor, mask: torch.Tensor, w_embed: torch.Tensor, h: int, w: int) -> torch.Tensor:
     """gdkvm_mask_embed_add, in place: v [BT, h*w, C] += w_embed[c] * adaptive_avg_pool(mask != 0) per token.  mask uint8 [BT,H,W],
     w_embed fp32 [C]."""
-    lib = load()
     if v.dim() != 3 or mask.dim() != 3 or mask.dtype != torch.uint8 or mask.shape[0] != v.shape[0] or v.shape[1] != h * w:
         raise GdkvmError(f"mask_embed_add_: bad shapes v{tuple(v.shape)} mask{tuple(mask.shape)} {mask.dtype} tokens {h}x{w}")
     if w_embed.dtype != torch.float32 or w_embed.numel() != v.shape[2]:
         raise GdkvmError("mask_embed_add_: w_embed must be float32 [C]")
     dev = _dev(v, mask, w_embed)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_mask_embed_add(_ptr(mask), _ptr(w_embed), _ptr(v), v.shape[0], mask.shape[1], mask.shape[2], h, w, v.shape[2],
-                                      _io_dtype(v), _stream(dev))
-    _check(rc, "gdkvm_mask_embed_add")
+    _call("gdkvm_mask_embed_add", dev, mask, w_embed, v, v.shape[0], mask.shape[1], mask.shape[2], h, w, v.shape[2], _io_dtype(v))
     return v
 
 
@@ -343,18 +413,14 @@ def mask_embed_wgrad(mask: torch.Tensor, d_v: torch.Tensor, h: int, w: int, work
     """gdkvm_mask_embed_wgrad: d_w fp32 [C] = sum over the token rows of adaptive_avg_pool(mask != 0) * d_v -- the weight gradient of
     mask_embed_add_.  mask uint8 [F,H,W], d_v [F, h*w, C] f32|bf16; workspace: uint8 of at least
     gdkvm_mask_embed_wgrad_workspace_bytes(F, h, w, C) bytes (allocated here when None)."""
-    lib = load()
     if d_v.dim() != 3 or mask.dim() != 3 or mask.dtype != torch.uint8 or mask.shape[0] != d_v.shape[0] or d_v.shape[1] != h * w:
         raise GdkvmError(f"mask_embed_wgrad: bad shapes d_v{tuple(d_v.shape)} mask{tuple(mask.shape)} {mask.dtype} tokens {h}x{w}")
     F_, C = d_v.shape[0], d_v.shape[2]
     dev = _dev(d_v, mask, workspace)
     if workspace is None:
-        workspace = torch.empty(max(16, int(lib.gdkvm_mask_embed_wgrad_workspace_bytes(F_, h, w, C))), dtype=torch.uint8, device=dev)
+        workspace = _workspace("gdkvm_mask_embed_wgrad_workspace_bytes", dev, F_, h, w, C, floor=16)
     dw = torch.empty(C, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_mask_embed_wgrad(_ptr(mask), _ptr(d_v), _ptr(dw), _ptr(workspace), workspace.numel() * workspace.element_size(),
-                                        F_, mask.shape[1], mask.shape[2], h, w, C, _io_dtype(d_v), _stream(dev))
-    _check(rc, "gdkvm_mask_embed_wgrad")
+    _call("gdkvm_mask_embed_wgrad", dev, mask, d_v, dw, _Ws(workspace), F_, mask.shape[1], mask.shape[2], h, w, C, _io_dtype(d_v))
     return dw
 
 
@@ -388,17 +454,13 @@ def mask_embed(v: torch.Tensor, mask: torch.Tensor, weight: torch.Tensor, h: int
 def scan_status(workspace: torch.Tensor, B: int, T: int, Hh: int, N: int, Dk: int, Dv: int, flags: int = 0) -> None:
     """Raises GdkvmError (GDKVM_ERR_RANGE) if the last scan_fwd / scan_apply on ``workspace`` left the range of its fp16-pair operands
     (its results are NaNs then); returns None otherwise.  Waits for the current stream (gdkvm_scan_status)."""
-    dev = _dev(workspace)
-    with torch.cuda.device(dev):
-        rc = load().gdkvm_scan_status(workspace.data_ptr(), workspace.numel() * workspace.element_size(), B, T, Hh, N, Dk, Dv, flags, _stream(dev))
-    _check(rc, "gdkvm_scan_status")
+    _call("gdkvm_scan_status", _dev(workspace), _Ws(workspace), B, T, Hh, N, Dk, Dv, flags)
 
 
 def scan_bwd(q, k, v, alpha, beta, state_hist, workspace, d_r, d_state_out=None, rule=RULE_DELTA_SEQUENTIAL, flags=0,
              need_d_state_in=True):
     """Backward of scan_fwd (gdkvm_scan_bwd).  ``state_hist`` and ``workspace`` are the ones the forward call filled.
     Returns (d_q, d_k, d_v, d_alpha, d_beta, d_state_in | None)."""
-    lib = load()
     B, T, N, Hh, Dk = q.shape
     Dv = v.shape[-1]
     dev = _dev(q, k, v, alpha, beta, state_hist, workspace, d_r, d_state_out)
@@ -408,13 +470,9 @@ def scan_bwd(q, k, v, alpha, beta, state_hist, workspace, d_r, d_state_out=None,
     da = torch.empty((B, T, Hh), dtype=torch.float32, device=dev)
     db = torch.empty((B, T, N, Hh), dtype=torch.float32, device=dev)
     ds = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev) if need_d_state_in else None
-    bws = torch.empty(int(lib.gdkvm_scan_bwd_workspace_bytes(B, T, Hh, N, Dk, Dv)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_scan_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(state_hist), workspace.data_ptr(),
-                                workspace.numel(), _ptr(d_r), _ptr(d_state_out), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(da),
-                                _ptr(db), _ptr(ds), bws.data_ptr(), bws.numel(), B, T, Hh, N, Dk, Dv, _io_dtype(q), rule,
-                                flags, _stream(dev))
-    _check(rc, "gdkvm_scan_bwd")
+    bws = _workspace("gdkvm_scan_bwd_workspace_bytes", dev, B, T, Hh, N, Dk, Dv)
+    _call("gdkvm_scan_bwd", dev, q, k, v, alpha, beta, state_hist, _Ws(workspace), d_r, d_state_out, dq, dk, dv, da, db, ds, _Ws(bws),
+          B, T, Hh, N, Dk, Dv, _io_dtype(q), rule, flags)
     return dq, dk, dv, da, db, ds
 
 
@@ -425,7 +483,7 @@ class _ScanFunction(torch.autograd.Function):
     def forward(ctx, q, k, v, alpha, beta, state, rule, flags):
         B, T, N, Hh, Dk = q.shape
         Dv = v.shape[-1]
-        ws = torch.empty(scan_workspace_bytes(B, T, Hh, N, Dk, Dv), dtype=torch.uint8, device=q.device)
+        ws = new_workspace(B, T, Hh, N, Dk, Dv, q.device)
         hist = torch.empty((B, T, Hh, Dk, Dv), dtype=torch.float32, device=q.device)
         r, s = scan_fwd(q, k, v, alpha, beta, state, rule=rule, flags=flags, workspace=ws, state_hist=hist)
         ctx.save_for_backward(q, k, v, alpha, beta, hist, ws)
@@ -446,7 +504,6 @@ def scan_state_bwd(k, v, alpha, beta, state_hist, workspace, d_hist=None, d_stat
                    need_d_state_in=True):
     """Backward of the state recurrence alone (gdkvm_scan_state_bwd): ``d_hist`` [B,T,Hh,Dk,Dv] is the gradient with respect to
     the state before every frame.  Returns (d_k, d_v, d_alpha, d_beta, d_state_in | None)."""
-    lib = load()
     B, T, N, Hh, Dk = k.shape
     Dv = v.shape[-1]
     dev = _dev(k, v, alpha, beta, state_hist, workspace, d_hist, d_state_out)
@@ -454,13 +511,9 @@ def scan_state_bwd(k, v, alpha, beta, state_hist, workspace, d_hist=None, d_stat
     da = torch.empty((B, T, Hh), dtype=torch.float32, device=dev)
     db = torch.empty((B, T, N, Hh), dtype=torch.float32, device=dev)
     ds = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev) if need_d_state_in else None
-    bws = torch.empty(int(lib.gdkvm_scan_bwd_workspace_bytes(B, T, Hh, N, Dk, Dv)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_scan_state_bwd(_ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(state_hist), workspace.data_ptr(),
-                                      workspace.numel(), _ptr(d_hist), _ptr(d_state_out), _ptr(dk), _ptr(dv), _ptr(da), _ptr(db),
-                                      _ptr(ds), bws.data_ptr(), bws.numel(), B, T, Hh, N, Dk, Dv, _io_dtype(k), rule, flags,
-                                      _stream(dev))
-    _check(rc, "gdkvm_scan_state_bwd")
+    bws = _workspace("gdkvm_scan_bwd_workspace_bytes", dev, B, T, Hh, N, Dk, Dv)
+    _call("gdkvm_scan_state_bwd", dev, k, v, alpha, beta, state_hist, _Ws(workspace), d_hist, d_state_out, dk, dv, da, db, ds, _Ws(bws),
+          B, T, Hh, N, Dk, Dv, _io_dtype(k), rule, flags)
     return dk, dv, da, db, ds
 
 
@@ -478,9 +531,7 @@ class _ReadoutFunction(torch.autograd.Function):
         if hist.dtype != torch.float32 or tuple(hist.shape) != (B, T * chunks, Hh, Dk, Dv):
             raise GdkvmError(f"state history must be float32 [B, T*chunks, Hh, Dk, Dv], got {tuple(hist.shape)}")
         r = torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev)
-        with torch.cuda.device(dev):
-            rc = load().gdkvm_readout_fwd(_ptr(q), _ptr(hist), _ptr(r), B, T, Hh, N, Dk, Dv, chunks, _io_dtype(q), flags, _stream(dev))
-        _check(rc, "gdkvm_readout_fwd")
+        _call("gdkvm_readout_fwd", dev, q, hist, r, B, T, Hh, N, Dk, Dv, chunks, _io_dtype(q), flags)
         ctx.save_for_backward(q, hist)
         ctx.chunks, ctx.flags = chunks, flags
         return r
@@ -495,10 +546,7 @@ class _ReadoutFunction(torch.autograd.Function):
             d_r = d_r.to(q.dtype)
         dq = torch.empty_like(q)
         d_hist = torch.zeros_like(hist)                     # only the states before the frames receive a gradient here
-        with torch.cuda.device(q.device):
-            rc = load().gdkvm_readout_bwd(_ptr(q), _ptr(hist), _ptr(d_r), _ptr(dq), _ptr(d_hist), B, T, Hh, N, Dk, Dv, ctx.chunks,
-                                          _io_dtype(q), ctx.flags, _stream(q.device))
-        _check(rc, "gdkvm_readout_bwd")
+        _call("gdkvm_readout_bwd", q.device, q, hist, d_r, dq, d_hist, B, T, Hh, N, Dk, Dv, ctx.chunks, _io_dtype(q), ctx.flags)
         return dq, d_hist, None, None
 
 
@@ -509,26 +557,21 @@ class _ScanTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, alpha, beta, state, rule, flags):
-        lib = load()
         B, T, N, Hh, Dk = q.shape
         Dv = v.shape[-1]
         q, k, v, alpha, beta = (t.contiguous() for t in (q, k, v, alpha, beta))
         dev = _dev(q, k, v, alpha, beta, state)
         io = _io_dtype(q)
-        ws = torch.empty(int(lib.gdkvm_scan_train_workspace_bytes(B, T, Hh, N, Dk, Dv, io)), dtype=torch.uint8, device=dev)
+        ws = _workspace("gdkvm_scan_train_workspace_bytes", dev, B, T, Hh, N, Dk, Dv, io)
         r = torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev)
         s = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gdkvm_scan_train_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(state), _ptr(r), _ptr(s),
-                                          ws.data_ptr(), ws.numel(), B, T, Hh, N, Dk, Dv, io, rule, flags, _stream(dev))
-        _check(rc, "gdkvm_scan_train_fwd")
+        _call("gdkvm_scan_train_fwd", dev, q, k, v, alpha, beta, state, r, s, _Ws(ws), B, T, Hh, N, Dk, Dv, io, rule, flags)
         ctx.save_for_backward(q, k, v, alpha, beta, ws)
         ctx.rule, ctx.flags, ctx.has_state = rule, flags, state is not None
         return r, s
 
     @staticmethod
     def backward(ctx, d_r, d_s):
-        lib = load()
         q, k, v, alpha, beta, ws = ctx.saved_tensors
         B, T, N, Hh, Dk = q.shape
         Dv = v.shape[-1]
@@ -541,11 +584,8 @@ class _ScanTrainFunction(torch.autograd.Function):
         da = torch.empty((B, T, Hh), dtype=torch.float32, device=dev)
         db = torch.empty((B, T, N, Hh), dtype=torch.float32, device=dev)
         ds = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev) if ctx.has_state else None
-        with torch.cuda.device(dev):
-            rc = lib.gdkvm_scan_train_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(d_r), _ptr(d_s), _ptr(dq), _ptr(dk),
-                                          _ptr(dv), _ptr(da), _ptr(db), _ptr(ds), ws.data_ptr(), ws.numel(), B, T, Hh, N, Dk, Dv,
-                                          _io_dtype(q), ctx.rule, ctx.flags, _stream(dev))
-        _check(rc, "gdkvm_scan_train_bwd")
+        _call("gdkvm_scan_train_bwd", dev, q, k, v, alpha, beta, d_r, d_s, dq, dk, dv, da, db, ds, _Ws(ws), B, T, Hh, N, Dk, Dv,
+              _io_dtype(q), ctx.rule, ctx.flags)
         return dq, dk, dv, da, db, ds, None, None
 
 
@@ -566,14 +606,11 @@ def scan_prep(q, k, v, beta, workspace, rule=RULE_DELTA_SEQUENTIAL, flags=0):
     B, T, N, Hh, Dk = k.shape
     Dv = v.shape[-1]
     dev = _dev(q, k, v, beta, workspace)
-    with torch.cuda.device(dev):
-        rc = load().gdkvm_scan_prep(_ptr(q), _ptr(k), _ptr(v), _ptr(beta), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                    B, T, Hh, N, Dk, Dv, _io_dtype(k), rule, flags, _stream(dev))
-    _check(rc, "gdkvm_scan_prep")
+    _call("gdkvm_scan_prep", dev, q, k, v, beta, _Ws(workspace), B, T, Hh, N, Dk, Dv, _io_dtype(k), rule, flags)
 
 
 def new_workspace(B, T, Hh, N, Dk, Dv, device) -> torch.Tensor:
-    return torch.empty(scan_workspace_bytes(B, T, Hh, N, Dk, Dv), dtype=torch.uint8, device=device)
+    return _workspace("gdkvm_scan_workspace_bytes", device, B, T, Hh, N, Dk, Dv)
 
 
 def scan_transition(q, alpha, workspace, Dv, flags=0):
@@ -582,10 +619,7 @@ def scan_transition(q, alpha, workspace, Dv, flags=0):
     B, T, N, Hh, Dk = q.shape
     dev = _dev(q, alpha, workspace)
     phi = torch.empty((B, Hh, Dk, Dk), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = load().gdkvm_scan_transition(_ptr(q), _ptr(alpha), _ptr(phi), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                          B, T, Hh, N, Dk, Dv, _io_dtype(q), flags, _stream(dev))
-    _check(rc, "gdkvm_scan_transition")
+    _call("gdkvm_scan_transition", dev, q, alpha, phi, _Ws(workspace), B, T, Hh, N, Dk, Dv, _io_dtype(q), flags)
     return phi
 
 
@@ -599,9 +633,7 @@ def scan_stitch(phi: torch.Tensor, s_loc: torch.Tensor, state: Optional[torch.Te
     phi, s_loc = phi.contiguous(), s_loc.contiguous()
     starts = torch.empty_like(s_loc)
     end = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = load().gdkvm_scan_stitch(phi.data_ptr(), s_loc.data_ptr(), _ptr(state), starts.data_ptr(), end.data_ptr(), B, S, Hh, Dk, Dv, _stream(dev))
-    _check(rc, "gdkvm_scan_stitch")
+    _call("gdkvm_scan_stitch", dev, phi, s_loc, state, starts, end, B, S, Hh, Dk, Dv)
     return starts, end
 
 
@@ -612,28 +644,17 @@ def scan_fwd_segmented(q, k, v, alpha, beta, state=None, segments: int = 0, rule
     stitch S_start_{c+1} = Phi_c S_start_c + S_loc_c, then every segment is scanned from its true start state.  2.25x the
     recurrence work on `segments`x the workgroups.  ``segments`` = 0: chosen by shape (gdkvm_scan_segments; 1 = the serial scan).
     Equal to scan_fwd up to fp32 re-association (not bit-identical)."""
-    lib = load()
-    B, T, N, Hh, Dk = q.shape
-    Dv = v.shape[-1]
+    B, T, N, Hh, Dk, Dv = _scan_operands(q, k, v, alpha, beta, state)
     if segments < 0 or (segments and T % segments):
         raise GdkvmError(f"segments={segments} must divide T={T}")
-    if k.shape != q.shape or tuple(v.shape[:4]) != (B, T, N, Hh) or tuple(alpha.shape) != (B, T, Hh) or tuple(beta.shape) != (B, T, N, Hh):
-        raise GdkvmError("bad scan shapes")
-    if k.dtype != q.dtype or v.dtype != q.dtype or alpha.dtype != torch.float32 or beta.dtype != torch.float32:
-        raise GdkvmError("q, k, v share one dtype; alpha / beta are float32")
-    if state is not None and (tuple(state.shape) != (B, Hh, Dk, Dv) or state.dtype != torch.float32):
-        raise GdkvmError("state must be float32 [B,Hh,Dk,Dv]")
     dev = _dev(q, k, v, alpha, beta, state, workspace)
     q, k, v, alpha, beta = (t.contiguous() for t in (q, k, v, alpha, beta))
-    with torch.cuda.device(dev):                           # (the choice by shape asks the current device for its CU count)
-        if workspace is None:
-            workspace = torch.empty(int(lib.gdkvm_scan_segmented_workspace_bytes(B, T, Hh, N, Dk, Dv, segments)), dtype=torch.uint8, device=dev)
-        r = torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev)
-        s = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
-        rc = lib.gdkvm_scan_fwd_segmented(_ptr(q), _ptr(k), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(state), _ptr(r), _ptr(s),
-                                          workspace.data_ptr(), workspace.numel(), B, T, Hh, N, Dk, Dv, segments, _io_dtype(q), rule,
-                                          flags, _stream(dev))
-    _check(rc, "gdkvm_scan_fwd_segmented")
+    if workspace is None:                                  # (the choice by shape asks the current device for its CU count: _bytes)
+        workspace = _workspace("gdkvm_scan_segmented_workspace_bytes", dev, B, T, Hh, N, Dk, Dv, segments)
+    r = torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev)
+    s = torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
+    _call("gdkvm_scan_fwd_segmented", dev, q, k, v, alpha, beta, state, r, s, _Ws(workspace), B, T, Hh, N, Dk, Dv, segments, _io_dtype(q),
+          rule, flags)
     return r, s
 
 
@@ -641,22 +662,16 @@ def scan_apply(q, alpha, workspace, Dv, state=None, flags=0, out=None, state_out
     """Stage 2 of scan_fwd alone (gdkvm_scan_apply): the serial read/write recurrence over a prepared workspace."""
     B, T, N, Hh, Dk = q.shape
     dev = _dev(q, alpha, workspace, state, out, state_out)
-    if not want_readout:
-        s = state_out if state_out is not None else torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = load().gdkvm_scan_apply(_ptr(q), _ptr(alpha), _ptr(state), None, _ptr(s), None, workspace.data_ptr(),
-                                         workspace.numel() * workspace.element_size(), B, T, Hh, N, Dk, Dv, _io_dtype(q), flags,
-                                         _stream(dev))
-        _check(rc, "gdkvm_scan_apply")
-        return None, s
-    r = out if out is not None else torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev)
+    r = None if not want_readout else (out if out is not None else torch.empty((B, T, N, Hh, Dv), dtype=q.dtype, device=dev))
     s = state_out if state_out is not None else torch.empty((B, Hh, Dk, Dv), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = load().gdkvm_scan_apply(_ptr(q), _ptr(alpha), _ptr(state), _ptr(r), _ptr(s), None, workspace.data_ptr(),
-                                     workspace.numel() * workspace.element_size(), B, T, Hh, N, Dk, Dv, _io_dtype(q), flags,
-                                     _stream(dev))
-    _check(rc, "gdkvm_scan_apply")
+    _call("gdkvm_scan_apply", dev, q, alpha, state, r, s, None, _Ws(workspace), B, T, Hh, N, Dk, Dv, _io_dtype(q), flags)
     return r, s
+
+
+def kpff_workspace(local: torch.Tensor, glob: torch.Tensor, pixel: torch.Tensor) -> torch.Tensor:
+    """A fresh workspace for kpff_fwd on these features (gdkvm_kpff_workspace_bytes): it holds the bf16 weight pack, so a caller may keep
+    it and pass it back with packed=True while the weights are unchanged."""
+    return _workspace("gdkvm_kpff_workspace_bytes", local.device, local.shape[-1], glob.shape[-1], pixel.shape[-1], _io_dtype(local))
 
 
 def kpff_fwd(local: torch.Tensor, glob: torch.Tensor, pixel: torch.Tensor, wa: torch.Tensor, ba: torch.Tensor,
@@ -666,7 +681,6 @@ def kpff_fwd(local: torch.Tensor, glob: torch.Tensor, pixel: torch.Tensor, wa: t
     wa [2Cp,Cp+Ck+Cv] ba [2Cp] wl [Cp,Ck] wg [Cp,Cv] float32.  Returns F [BT,N,Cp] in the io dtype.
     exact (float32 features only): no workspace is handed over, which selects the exact fp32-MFMA arm instead of the arm on
     bf16 splits (include/gdkvm.h)."""
-    lib = load()
     BT, N, Ck = local.shape
     Cv, Cp = glob.shape[-1], pixel.shape[-1]
     if N != h * w or glob.shape[:2] != (BT, N) or pixel.shape[:2] != (BT, N):
@@ -686,13 +700,9 @@ def kpff_fwd(local: torch.Tensor, glob: torch.Tensor, pixel: torch.Tensor, wa: t
         if local.dtype != torch.float32 or workspace is not None or packed:
             raise GdkvmError("kpff_fwd(exact=True) is the float32 arm without a workspace")
     elif workspace is None:
-        workspace = torch.empty(int(lib.gdkvm_kpff_workspace_bytes(Ck, Cv, Cp, io)), dtype=torch.uint8, device=dev)
-    fn = lib.gdkvm_kpff_fwd_packed if packed else lib.gdkvm_kpff_fwd     # packed: `workspace` already holds these weights
-    with torch.cuda.device(dev):
-        rc = fn(_ptr(local), _ptr(glob), _ptr(pixel), _ptr(wa), _ptr(ba), _ptr(wl), _ptr(wg), _ptr(f),
-                workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0,
-                BT, Ck, Cv, Cp, h, w, io, _stream(dev))
-    _check(rc, "gdkvm_kpff_fwd")
+        workspace = kpff_workspace(local, glob, pixel)
+    _call("gdkvm_kpff_fwd_packed" if packed else "gdkvm_kpff_fwd", dev,     # packed: `workspace` already holds these weights
+          local, glob, pixel, wa, ba, wl, wg, f, _Ws(workspace), BT, Ck, Cv, Cp, h, w, io)
     return f
 
 
@@ -702,7 +712,6 @@ class _KpffFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, local, glob, pixel, wa, ba, wl, wg, h, w):
-        lib = load()
         BT, N, Ck = local.shape
         Cv, Cp = glob.shape[-1], pixel.shape[-1]
         dev = _dev(local, glob, pixel, wa, ba, wl, wg)
@@ -711,19 +720,14 @@ class _KpffFunction(torch.autograd.Function):
         gates = torch.empty((BT * N, 2 * Cp), dtype=local.dtype, device=dev)
         lp, gp = (torch.empty((BT * N, Cp), dtype=local.dtype, device=dev) for _ in range(2))
         gms = torch.empty((BT * N, Cv), dtype=local.dtype, device=dev)
-        ws = torch.empty(int(lib.gdkvm_kpff_workspace_bytes(Ck, Cv, Cp, io)), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gdkvm_kpff_fwd_train(_ptr(local), _ptr(glob), _ptr(pixel), _ptr(wa), _ptr(ba), _ptr(wl), _ptr(wg), _ptr(f),
-                                          _ptr(gates), _ptr(lp), _ptr(gp), _ptr(gms), ws.data_ptr(), ws.numel(),
-                                          BT, Ck, Cv, Cp, h, w, io, _stream(dev))
-        _check(rc, "gdkvm_kpff_fwd_train")
+        ws = kpff_workspace(local, glob, pixel)
+        _call("gdkvm_kpff_fwd_train", dev, local, glob, pixel, wa, ba, wl, wg, f, gates, lp, gp, gms, _Ws(ws), BT, Ck, Cv, Cp, h, w, io)
         ctx.save_for_backward(local, pixel, wa, wl, wg, gates, lp, gp, gms)
         ctx.hw = (h, w)
         return f
 
     @staticmethod
     def backward(ctx, d_f):
-        lib = load()
         local, pixel, wa, wl, wg, gates, lp, gp, gms = ctx.saved_tensors
         h, w = ctx.hw
         BT, N, Ck = local.shape
@@ -733,9 +737,7 @@ class _KpffFunction(torch.autograd.Function):
         d_f = d_f.contiguous()
         dz = torch.empty((M, 2 * Cp), dtype=dt, device=dev)
         dlp, dgp = (torch.empty((M, Cp), dtype=dt, device=dev) for _ in range(2))
-        with torch.cuda.device(dev):
-            _check(lib.gdkvm_kpff_bwd_pre(_ptr(d_f), _ptr(gates), _ptr(lp), _ptr(gp), _ptr(dz), _ptr(dlp), _ptr(dgp),
-                                          BT, N, Cp, io, _stream(dev)), "gdkvm_kpff_bwd_pre")
+        _call("gdkvm_kpff_bwd_pre", dev, d_f, gates, lp, gp, dz, dlp, dgp, BT, N, Cp, io)
         L2, P2 = local.reshape(M, Ck), pixel.reshape(M, Cp)
         # the six products of the backward on the hand-written kernels (csrc/gemm.hip): dX-type ones as gdkvm_gemm_nt against
         # the weight with its input index leading (a one-off transpose of a small matrix), dW-type ones as gdkvm_gemm_tn
@@ -750,9 +752,7 @@ class _KpffFunction(torch.autograd.Function):
         d_wl = wgrad(dlp, L2)
         d_wg = wgrad(dgp, gms)
         d_p, d_l, d_g = torch.empty_like(pixel), torch.empty_like(local), torch.empty((BT, N, Cv), dtype=dt, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib.gdkvm_kpff_bwd_post(_ptr(d_f), _ptr(dx), _ptr(dl_add), _ptr(dg_add), _ptr(d_p), _ptr(d_l), _ptr(d_g),
-                                           BT, Ck, Cv, Cp, h, w, io, _stream(dev)), "gdkvm_kpff_bwd_post")
+        _call("gdkvm_kpff_bwd_post", dev, d_f, dx, dl_add, dg_add, d_p, d_l, d_g, BT, Ck, Cv, Cp, h, w, io)
         return d_l, d_g, d_p, d_wa, d_ba, d_wl, d_wg, None, None
 
 
@@ -764,17 +764,12 @@ def kpff(local, glob, pixel, wa, ba, wl, wg, h: int, w: int):
 def argmax_dice(logits: torch.Tensor, target: Optional[torch.Tensor] = None):
     """mask = argmax over classes (ties -> lowest index) and, with a target, integer Dice counts
     (gdkvm_argmax_dice).  logits [BT,ncls,H,W]; target [BT,H,W] uint8.  Returns (mask u8, counts i32|None)."""
-    lib = load()
     BT, ncls, H, W = logits.shape
     dev = _dev(logits, target)
-    if target is not None and (target.dtype != torch.uint8 or tuple(target.shape) != (BT, H, W)):
-        raise GdkvmError("target must be uint8 [BT,H,W]")
+    _u8_target(target, BT, H, W)
     mask = torch.empty((BT, H, W), dtype=torch.uint8, device=dev)
     counts = torch.empty((BT, ncls, 3), dtype=torch.int32, device=dev) if target is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_argmax_dice(_ptr(logits), _ptr(target), _ptr(mask), _ptr(counts), BT, ncls, H, W,
-                                   _io_dtype(logits), _stream(dev))
-    _check(rc, "gdkvm_argmax_dice")
+    _call("gdkvm_argmax_dice", dev, logits, target, mask, counts, BT, ncls, H, W, _io_dtype(logits))
     return mask, counts
 
 
@@ -782,17 +777,12 @@ def upsample_argmax_dice(logits: torch.Tensor, H: int, W: int, target: Optional[
                          mask_out: Optional[torch.Tensor] = None, counts_out: Optional[torch.Tensor] = None):
     """Fused bilinear upsample (align_corners=False) + argmax + Dice counts (gdkvm_upsample_argmax_dice).
     logits [BT,ncls,hl,wl] low-resolution; returns (mask u8 [BT,H,W], counts i32 [BT,ncls,3] | None); mask_out / counts_out: write there."""
-    lib = load()
     BT, ncls, hl, wl = logits.shape
     dev = _dev(logits, target)
-    if target is not None and (target.dtype != torch.uint8 or tuple(target.shape) != (BT, H, W)):
-        raise GdkvmError("target must be uint8 [BT,H,W]")
+    _u8_target(target, BT, H, W)
     mask = _out_like(mask_out, (BT, H, W), torch.uint8, dev, "mask_out")
     counts = _out_like(counts_out, (BT, ncls, 3), torch.int32, dev, "counts_out") if target is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_upsample_argmax_dice(_ptr(logits), _ptr(target), _ptr(mask), _ptr(counts), BT, ncls, hl, wl, H, W,
-                                            _io_dtype(logits), _stream(dev))
-    _check(rc, "gdkvm_upsample_argmax_dice")
+    _call("gdkvm_upsample_argmax_dice", dev, logits, target, mask, counts, BT, ncls, hl, wl, H, W, _io_dtype(logits))
     return mask, counts
 
 
@@ -812,9 +802,7 @@ def head_upsample_argmax_dice(x: torch.Tensor, weight: torch.Tensor, bias: torch
     """The decoder's 1x1 head + bilinear upsample + argmax + Dice counts in one kernel (gdkvm_head_upsample_argmax_dice): x is the
     channels_last stride-4 feature [BT,C,hl,wl], weight fp32 [classes, C], bias fp32 [classes]; the class planes never reach memory.
     Bit-identical to head_logits followed by upsample_argmax_dice.  Returns (mask u8 [BT,H,W], counts i32 [BT,classes,3] | None)."""
-    lib = load()
-    if x.dim() != 4 or not x.is_cuda or not x.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("head_upsample_argmax_dice needs a channels_last [BT,C,hl,wl] device tensor (no CPU path)")
+    _channels_last("head_upsample_argmax_dice", x, shape="[BT,C,hl,wl]")
     BT, C, hl, wl = x.shape
     ncls = weight.shape[0]
     if weight.dtype != torch.float32 or bias.dtype != torch.float32 or tuple(weight.shape) != (ncls, C) or bias.numel() != ncls \
@@ -823,14 +811,10 @@ def head_upsample_argmax_dice(x: torch.Tensor, weight: torch.Tensor, bias: torch
     dev = _dev(weight, bias, target)                       # (x is channels_last: checked above)
     if dev != x.device:
         raise GdkvmError("all tensors must live on one device")
-    if target is not None and (target.dtype != torch.uint8 or tuple(target.shape) != (BT, H, W)):
-        raise GdkvmError("target must be uint8 [BT,H,W]")
+    _u8_target(target, BT, H, W)
     mask = _out_like(mask_out, (BT, H, W), torch.uint8, dev, "mask_out")
     counts = _out_like(counts_out, (BT, ncls, 3), torch.int32, dev, "counts_out") if target is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_head_upsample_argmax_dice(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(target), _ptr(mask), _ptr(counts),
-                                                 BT, C, ncls, hl, wl, H, W, _io_dtype(x), _stream(dev))
-    _check(rc, "gdkvm_head_upsample_argmax_dice")
+    _call("gdkvm_head_upsample_argmax_dice", dev, x, weight, bias, target, mask, counts, BT, C, ncls, hl, wl, H, W, _io_dtype(x))
     return mask, counts
 
 
@@ -841,7 +825,6 @@ def augment_clips(frames: torch.Tensor, target: Optional[torch.Tensor], params: 
     int64 [B,T,H,W] or None, params fp32 [B,12] on the device (data.ClipAugment.params: m00 m01 m02 m10 m11 m12 gain bias gamma 0 0 0, the
     matrix mapping destination to source pixel indices), frames_dtype float32 | bfloat16.  Returns (frames_out, target_out | None); with
     the identity row the frames are torch.mul(frames, 1/255) bit for bit."""
-    lib = load()
     if frames.dtype != torch.uint8 or frames.dim() != 5:
         raise GdkvmError(f"augment_clips: frames must be uint8 [B,T,C,H,W], got {frames.dtype} {tuple(frames.shape)} (float frames are not augmented)")
     B, T, C, H, W = frames.shape
@@ -860,16 +843,13 @@ def augment_clips(frames: torch.Tensor, target: Optional[torch.Tensor], params: 
     t_out = None if target is None else _out_like(target_out, target.shape, target.dtype, dev, "augment_clips: target_out")
     if B * T > 0 and (f_out.data_ptr() == frames.data_ptr() or (target is not None and t_out.data_ptr() == target.data_ptr())):
         raise GdkvmError("augment_clips: the outputs must not alias the inputs (a gather)")
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_augment_clips(_ptr(frames), _ptr(target), _ptr(params), _ptr(f_out), _ptr(t_out), B, T, C, H, W, _io_dtype(f_out),
-                                     1 if target is None else target.element_size(), int(fill_label), _stream(dev))
-    _check(rc, "gdkvm_augment_clips")
+    _call("gdkvm_augment_clips", dev, frames, target, params, f_out, t_out, B, T, C, H, W, _io_dtype(f_out),
+          1 if target is None else target.element_size(), int(fill_label))
     return f_out, t_out
 
 
 def bias_act_(x: torch.Tensor, bias: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = True) -> torch.Tensor:
     """In-place fused epilogue on an NHWC (channels_last) conv output: x <- act(x + bias[c] (+ residual))  (gdkvm_bias_act)."""
-    lib = load()
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
         raise GdkvmError("bias_act_ needs a channels_last [N,C,H,W] tensor")
     if residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype or
@@ -880,29 +860,21 @@ def bias_act_(x: torch.Tensor, bias: torch.Tensor, residual: Optional[torch.Tens
     if not x.is_cuda:
         raise GdkvmError("GDKVM ops need device tensors (no CPU path)")
     n, c, hh, ww = x.shape
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_bias_act(x.data_ptr(), bias.data_ptr(), None if residual is None else residual.data_ptr(), x.data_ptr(),
-                                n * hh * ww, c, int(relu), _io_dtype(x), _stream(x.device))
-    _check(rc, "gdkvm_bias_act")
+    _call("gdkvm_bias_act", x.device, x, bias, residual, x, n * hh * ww, c, int(relu), _io_dtype(x))
     return x
 
 
 def head_logits(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """1x1 convolution + bias of a channels_last feature [N,C,H,W] to contiguous NCHW class planes [N,classes,H,W] in x's dtype
     (gdkvm_head_logits); weight fp32 [classes, C], bias fp32 [classes]."""
-    lib = load()
-    if x.dim() != 4 or not x.is_cuda or not x.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("head_logits needs a channels_last [N,C,H,W] device tensor (no CPU path)")
+    _channels_last("head_logits", x)
     n, c, hh, ww = x.shape
     ncls = weight.shape[0]
     if weight.dtype != torch.float32 or bias.dtype != torch.float32 or tuple(weight.shape) != (ncls, c) or bias.numel() != ncls \
             or not weight.is_contiguous():
         raise GdkvmError("head_logits: weight fp32 [classes, C] (contiguous), bias fp32 [classes]")
     out = torch.empty((n, ncls, hh, ww), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_head_logits(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), n, hh, ww, c, ncls,
-                                   _io_dtype(x), _stream(x.device))
-    _check(rc, "gdkvm_head_logits")
+    _call("gdkvm_head_logits", x.device, x, weight, bias, out, n, hh, ww, c, ncls, _io_dtype(x))
     return out
 
 
@@ -922,7 +894,6 @@ class _HeadFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz):
-        lib = load()
         xc, w2 = ctx.saved_tensors
         n, c, hh, ww = xc.shape
         ncls = w2.shape[0]
@@ -930,12 +901,8 @@ class _HeadFunction(torch.autograd.Function):
         dx = torch.empty_like(xc)
         dw = torch.empty((ncls, c), dtype=torch.float32, device=xc.device)
         db = torch.empty(ncls, dtype=torch.float32, device=xc.device)
-        need = int(lib.gdkvm_head_bwd_workspace_bytes(c, ncls))
-        ws = torch.empty(need, dtype=torch.uint8, device=xc.device)
-        with torch.cuda.device(xc.device):
-            rc = lib.gdkvm_head_bwd(xc.data_ptr(), dz.data_ptr(), w2.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), need,
-                                    n, hh, ww, c, ncls, _io_dtype(xc), _stream(xc.device))
-        _check(rc, "gdkvm_head_bwd")
+        ws = _workspace("gdkvm_head_bwd_workspace_bytes", xc.device, c, ncls)
+        _call("gdkvm_head_bwd", xc.device, xc, dz, w2, dx, dw, db, _Ws(ws), n, hh, ww, c, ncls, _io_dtype(xc))
         wdt, wshape, bdt = ctx.meta
         return dx, dw.reshape(wshape).to(wdt), db.to(bdt)
 
@@ -966,7 +933,6 @@ def pack_rows_weight(weight: torch.Tensor) -> torch.Tensor:
 def proj_rows(x2d: torch.Tensor, wpack: torch.Tensor, bias: torch.Tensor, widths) -> Tuple[torch.Tensor, ...]:
     """The key / query / value projections of token rows x2d [rows, K] (bf16) in one pass (gdkvm_proj_rows): returns one
     contiguous [rows, w] tensor per entry of `widths` (up to three)."""
-    lib = load()
     if x2d.dim() != 2 or not x2d.is_cuda or x2d.dtype != torch.bfloat16 or not x2d.is_contiguous():
         raise GdkvmError("proj_rows needs a contiguous bf16 [rows, K] device tensor (no CPU path)")
     rows, k = x2d.shape
@@ -975,17 +941,13 @@ def proj_rows(x2d: torch.Tensor, wpack: torch.Tensor, bias: torch.Tensor, widths
             or wpack.numel() != sum(widths) * k:
         raise GdkvmError("proj_rows: up to three widths, fp32 bias [sum(widths)], packed bf16 weight [sum(widths) * K]")
     outs = [torch.empty((rows, w), dtype=x2d.dtype, device=x2d.device) if w else None for w in widths]
-    with torch.cuda.device(x2d.device):
-        rc = lib.gdkvm_proj_rows(x2d.data_ptr(), wpack.data_ptr(), bias.data_ptr(), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                                 rows, k, widths[0], widths[1], widths[2], BF16, _stream(x2d.device))
-    _check(rc, "gdkvm_proj_rows")
+    _call("gdkvm_proj_rows", x2d.device, x2d, wpack, bias, *outs, rows, k, *widths, BF16)
     return tuple(o for o in outs if o is not None)
 
 
 def gate_logits(p_tok: torch.Tensor, w_gate: torch.Tensor, b_gate: torch.Tensor, w_decay: torch.Tensor, b_decay: torch.Tensor):
     """(beta_logit [F,N,Hh], alpha_logit [F,Hh]) in fp32 from the pixel feature p_tok [F,N,Cp] in one pass (gdkvm_gate_logits):
     the gate projection per token and the decay projection of the token mean."""
-    lib = load()
     if p_tok.dim() != 3 or not p_tok.is_cuda or not p_tok.is_contiguous():
         raise GdkvmError("gate_logits needs a contiguous [frames, N, Cp] device tensor (no CPU path)")
     fr, n, cp = p_tok.shape
@@ -995,10 +957,7 @@ def gate_logits(p_tok: torch.Tensor, w_gate: torch.Tensor, b_gate: torch.Tensor,
         raise GdkvmError("gate_logits: weights must be [Hh, Cp], biases [Hh]")
     beta = torch.empty((fr, n, hh), dtype=torch.float32, device=p_tok.device)
     alpha = torch.empty((fr, hh), dtype=torch.float32, device=p_tok.device)
-    with torch.cuda.device(p_tok.device):
-        rc = lib.gdkvm_gate_logits(p_tok.data_ptr(), ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), ws[3].data_ptr(),
-                                   beta.data_ptr(), alpha.data_ptr(), fr, n, cp, hh, _io_dtype(p_tok), _stream(p_tok.device))
-    _check(rc, "gdkvm_gate_logits")
+    _call("gdkvm_gate_logits", p_tok.device, p_tok, *ws, beta, alpha, fr, n, cp, hh, _io_dtype(p_tok))
     return beta, alpha
 
 
@@ -1009,7 +968,6 @@ def proj_gates(p_tok: torch.Tensor, wpack: torch.Tensor, bias: torch.Tensor, w_g
     alpha_logit [frames, Hh]) in fp32, and norms [rows, Hh, 2] fp32 -- the inverse L2 norms of the stored key / query rows, which
     scan_fwd(..., norms=norms) takes instead of computing them.  wpack / bias: pack_rows_weight of the stacked key, query, value
     weights and their fp32 biases; gate weights fp32 [Hh, Cp]."""
-    lib = load()
     if p_tok.dim() != 3 or not p_tok.is_cuda or p_tok.dtype != torch.bfloat16 or not p_tok.is_contiguous():
         raise GdkvmError("proj_gates needs a contiguous bf16 [frames, N, Cp] device tensor (no CPU path)")
     fr, n, cp = p_tok.shape
@@ -1025,11 +983,7 @@ def proj_gates(p_tok: torch.Tensor, wpack: torch.Tensor, bias: torch.Tensor, w_g
     beta = torch.empty((fr, n, heads), dtype=torch.float32, device=dev)
     alpha = torch.empty((fr, heads), dtype=torch.float32, device=dev)
     norms = torch.empty((rows, heads, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_proj_gates(p_tok.data_ptr(), wpack.data_ptr(), bias.data_ptr(), k.data_ptr(), q.data_ptr(), v.data_ptr(),
-                                  gw[0].data_ptr(), gw[1].data_ptr(), gw[2].data_ptr(), gw[3].data_ptr(), beta.data_ptr(), alpha.data_ptr(),
-                                  norms.data_ptr(), fr, n, cp, heads, key_dim, value_dim, BF16, _stream(dev))
-    _check(rc, "gdkvm_proj_gates")
+    _call("gdkvm_proj_gates", dev, p_tok, wpack, bias, k, q, v, *gw, beta, alpha, norms, fr, n, cp, heads, key_dim, value_dim, BF16)
     return (k, q, v), (beta, alpha), norms
 
 
@@ -1039,15 +993,12 @@ CONV_PACKED_WEIGHTS = 32
 def conv3x3_pack_weights(weight: torch.Tensor) -> torch.Tensor:
     """The fragment-ordered copy of channels_last bf16 [K,C,3,3] weights that conv_bias_act(..., packed=...) reads
     (gdkvm_conv3x3_pack_weights): K a multiple of 16, C of 64.  Same bytes, another order; keep it next to the weights."""
-    lib = load()
     if weight.dim() != 4 or weight.dtype != torch.bfloat16 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_cuda or \
             not weight.is_contiguous(memory_format=torch.channels_last):
         raise GdkvmError("conv3x3_pack_weights: weight must be a channels_last bf16 [K,C,3,3] device tensor")
     k, c = weight.shape[:2]
     packed = torch.empty(k * 9 * c, dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.gdkvm_conv3x3_pack_weights(weight.data_ptr(), packed.data_ptr(), k, c, BF16, _stream(weight.device))
-    _check(rc, "gdkvm_conv3x3_pack_weights")
+    _call("gdkvm_conv3x3_pack_weights", weight.device, weight, packed, k, c, BF16)
     return packed
 
 
@@ -1057,14 +1008,10 @@ CONV_KERNEL_IGEMM = 9         # gdkvm_conv_bias_act's general implicit-GEMM kern
 def conv_igemm_pack_weights(weight: torch.Tensor) -> torch.Tensor:
     """The fragment-ordered copy of channels_last bf16 [K,C,R,S] weights that conv_bias_act(..., tile=CONV_KERNEL_IGEMM, packed=...)
     reads (gdkvm_conv_igemm_pack_weights): K a multiple of 16 (128 for the kernel), C of 32."""
-    lib = load()
-    if weight.dim() != 4 or weight.dtype != torch.bfloat16 or not weight.is_cuda or not weight.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("conv_igemm_pack_weights: weight must be a channels_last bf16 [K,C,R,S] device tensor")
+    _channels_last("conv_igemm_pack_weights: the weight", weight, dtype=torch.bfloat16, shape="[K,C,R,S]")
     k, c, r, s = weight.shape
     packed = torch.empty(weight.numel(), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.gdkvm_conv_igemm_pack_weights(weight.data_ptr(), packed.data_ptr(), k, c, r, s, BF16, _stream(weight.device))
-    _check(rc, "gdkvm_conv_igemm_pack_weights")
+    _call("gdkvm_conv_igemm_pack_weights", weight.device, weight, packed, k, c, r, s, BF16)
     return packed
 
 
@@ -1073,9 +1020,7 @@ def conv_down_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor
     """A residual block's first convolution and its 1x1 downsample branch in one launch (gdkvm_conv_down_bias_act):
     (act(conv(x, weight, stride, pad = R // 2) + bias), conv(x, down_weight, stride) (+ down_bias)); channels_last bf16, the packs as
     conv_igemm_pack_weights made them."""
-    lib = load()
-    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("conv_down_bias_act needs a channels_last bf16 [N,C,H,W] device tensor (no CPU path)")
+    _channels_last("conv_down_bias_act", x, dtype=torch.bfloat16)
     n, c, hh, ww = x.shape
     k, _, r, s = weight.shape
     if tuple(down_weight.shape) != (k, c, 1, 1) or weight.shape[1] != c or packed.numel() != weight.numel() or down_packed.numel() != k * c \
@@ -1087,10 +1032,7 @@ def conv_down_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor
     ho, wo = (hh + 2 * pad - r) // stride + 1, (ww + 2 * pad - s) // stride + 1
     y = torch.empty((n, k, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     yd = torch.empty_like(y)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_conv_down_bias_act(x.data_ptr(), packed.data_ptr(), bias.data_ptr(), y.data_ptr(), int(relu), down_packed.data_ptr(),
-                                          _ptr(down_bias), yd.data_ptr(), n, c, hh, ww, k, r, s, stride, pad, BF16, _stream(x.device))
-    _check(rc, "gdkvm_conv_down_bias_act")
+    _call("gdkvm_conv_down_bias_act", x.device, x, packed, bias, y, int(relu), down_packed, down_bias, yd, n, c, hh, ww, k, r, s, stride, pad, BF16)
     return y, yd
 
 
@@ -1099,10 +1041,7 @@ def _conv3x3_packed(x: torch.Tensor, packed: torch.Tensor, k_out: int, bias: tor
     residual [N, k_out, H, W] of x's type added in the kernel's epilogue)."""
     n, c, hh, ww = x.shape
     y = torch.empty((n, k_out, hh, ww), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        rc = load().gdkvm_conv_bias_act(x.data_ptr(), packed.data_ptr(), bias.data_ptr(), _ptr(residual), y.data_ptr(), n, c, hh, ww, k_out, 3, 3, 1, 1,
-                                        0, CONV_PACKED_WEIGHTS, BF16, _stream(x.device))
-    _check(rc, "gdkvm_conv_bias_act")
+    _call("gdkvm_conv_bias_act", x.device, x, packed, bias, residual, y, n, c, hh, ww, k_out, 3, 3, 1, 1, 0, CONV_PACKED_WEIGHTS, BF16)
     return y
 
 
@@ -1130,7 +1069,6 @@ def conv3x3_train_packs(weights) -> int:
     buffers kept on the parameter; EVERY call re-packs every weight (a fused optimiser step leaves no trace a cache could key on) and opens a
     new pack scope: ops.conv3x3 uses a weight's packs only while the scope of the call that made them is open (``end_train_packs`` closes it;
     ``train_packs`` is the context-manager form).  Returns the number of layers packed."""
-    lib = load()
     todo = []
     _PACK_TOKENS[0] += 1
     token = _PACK_TOKENS[0]
@@ -1153,12 +1091,7 @@ def conv3x3_train_packs(weights) -> int:
         ks = (ctypes.c_int * n)(*[w.shape[0] for w in part])
         cs = (ctypes.c_int * n)(*[w.shape[1] for w in part])
         st = (ctypes.c_longlong * (4 * n))(*[x for w in part for x in w.stride()])
-        dev = part[0].device
-        with torch.cuda.device(dev):
-            rc = lib.gdkvm_conv3x3_pack_weights_train(n, ctypes.cast(wp, ctypes.c_void_p), ctypes.cast(fp, ctypes.c_void_p), ctypes.cast(dp, ctypes.c_void_p),
-                                                      ctypes.cast(ks, ctypes.c_void_p), ctypes.cast(cs, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p),
-                                                      _stream(dev))
-        _check(rc, "gdkvm_conv3x3_pack_weights_train")
+        _call("gdkvm_conv3x3_pack_weights_train", part[0].device, n, *(ctypes.cast(a, ctypes.c_void_p) for a in (wp, fp, dp, ks, cs, st)))
     _PACK_SCOPE[0] = token
     return len(todo)
 
@@ -1202,19 +1135,18 @@ class _Conv3x3Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, fork=False):
-        lib = load()
         xb = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         k, c = weight.shape[:2]
         ctx.fork = bool(fork)
         if fork:
             # conv3x3_fork: a second output that IS the input (for the residual branch of the block).  Its gradient then arrives HERE, together
             # with the convolution's, and is added in the data-gradient kernel's epilogue instead of by a separate pass over both tensors
-            y, dummy = _Conv3x3Function._fwd(ctx, lib, x, xb, weight, k, c)
+            y, dummy = _Conv3x3Function._fwd(ctx, x, xb, weight, k, c)
             return y, xb.view(xb.shape)
-        return _Conv3x3Function._fwd(ctx, lib, x, xb, weight, k, c)[0]
+        return _Conv3x3Function._fwd(ctx, x, xb, weight, k, c)[0]
 
     @staticmethod
-    def _fwd(ctx, lib, x, xb, weight, k, c):
+    def _fwd(ctx, x, xb, weight, k, c):
         packs = _train_packs_of(weight)                    # (conv3x3_train_packs ran for this version of the weight: nothing to cast or pack here)
         ctx.kc, ctx.wdtype, ctx.xdtype = (k, c), weight.dtype, x.dtype
         ctx.w_cl = weight.is_contiguous(memory_format=torch.channels_last) and not weight.is_contiguous()
@@ -1226,8 +1158,7 @@ class _Conv3x3Function(torch.autograd.Function):
             return _conv3x3_packed(xb, packs[0], k, _zero_bias(k, xb.device)), None
         wb = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         packed = torch.empty(k * 9 * c, dtype=torch.bfloat16, device=xb.device)
-        with torch.cuda.device(xb.device):
-            _check(lib.gdkvm_conv3x3_pack_weights(wb.data_ptr(), packed.data_ptr(), k, c, BF16, _stream(xb.device)), "gdkvm_conv3x3_pack_weights")
+        _call("gdkvm_conv3x3_pack_weights", xb.device, wb, packed, k, c, BF16)
         ctx.dgrad_pack = None
         ctx.save_for_backward(xb, wb)
         return _conv3x3_packed(xb, packed, k, _zero_bias(k, xb.device)), None
@@ -1248,9 +1179,7 @@ class _Conv3x3Function(torch.autograd.Function):
             packed = ctx.dgrad_pack
             if packed is None:
                 packed = torch.empty(k * 9 * c, dtype=torch.bfloat16, device=dyb.device)
-                with torch.cuda.device(dyb.device):
-                    _check(load().gdkvm_conv3x3_pack_weights_dgrad(wb.data_ptr(), packed.data_ptr(), k, c, BF16, _stream(dyb.device)),
-                           "gdkvm_conv3x3_pack_weights_dgrad")
+                _call("gdkvm_conv3x3_pack_weights_dgrad", dyb.device, wb, packed, k, c, BF16)
             dx = _conv3x3_packed(dyb, packed, c, _zero_bias(c, dyb.device), res).to(ctx.xdtype)
         elif res is not None:
             dx = res.to(ctx.xdtype)
@@ -1259,34 +1188,19 @@ class _Conv3x3Function(torch.autograd.Function):
         return dx, dw, None
 
 
-_WGRAD_WS = {}
-
-
 def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
     """dW [K,C,3,3] fp32 of a 3x3 / stride 1 / pad 1 convolution from channels_last bf16 x [N,C,H,W] and dy [N,K,H,W]
     (gdkvm_conv3x3_wgrad): C, K multiples of 64, rows of at most 64 pixels; deterministic.  channels_last: the result in the memory
     order of a channels_last parameter (gdkvm_conv3x3_wgrad_krsc) -- the same numbers, no re-layout copy when it becomes that
     parameter's .grad."""
-    lib = load()
-    for t in (x, dy):
-        if t.dim() != 4 or not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous(memory_format=torch.channels_last):
-            raise GdkvmError("conv3x3_wgrad needs channels_last bf16 [N,C,H,W] device tensors (no CPU path)")
+    _channels_last("conv3x3_wgrad", x, dy, dtype=torch.bfloat16)
     n, c, hh, ww = x.shape
     k = dy.shape[1]
     if tuple(dy.shape) != (n, k, hh, ww):
         raise GdkvmError("conv3x3_wgrad: x and dy must agree in batch and size")
     dw = torch.empty((k, c, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    # one workspace per device and stream, grown to the largest layer (up to 75 MB of partial blocks): calls on a stream are
-    # ordered, so the next layer's gradient may overwrite it
-    need = max(16, int(lib.gdkvm_conv3x3_wgrad_workspace_bytes(n, c, hh, ww, k)))
-    key = (x.device, _stream(x.device))
-    ws = _WGRAD_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WGRAD_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        fn = lib.gdkvm_conv3x3_wgrad_krsc if channels_last else lib.gdkvm_conv3x3_wgrad
-        rc = fn(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), n, c, hh, ww, k, BF16, _stream(x.device))
-    _check(rc, "gdkvm_conv3x3_wgrad")
+    ws = _grown_workspace("gdkvm_conv3x3_wgrad_workspace_bytes", x.device, n, c, hh, ww, k)      # (grown to the largest layer: up to 75 MB of partial blocks)
+    _call("gdkvm_conv3x3_wgrad_krsc" if channels_last else "gdkvm_conv3x3_wgrad", x.device, x, dy, dw, _Ws(ws), n, c, hh, ww, k, BF16)
     return dw
 
 
@@ -1310,40 +1224,25 @@ def conv3x3_fork(x: torch.Tensor, weight: torch.Tensor) -> Tuple[torch.Tensor, t
     return _Conv3x3Function.apply(x, weight, True)
 
 
-_S2_WS = {}
-
-
 def conv_wgrad_strided(x: torch.Tensor, dy: torch.Tensor, weight_like: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
     """dW (fp32, in `weight_like`'s shape [K,C,R,S] AND memory format) of conv2d(x, w, stride, pad) from channels_last bf16 x [N,C,H,W] and
     dy [N,K,Ho,Wo] (gdkvm_conv_wgrad_strided): any window / stride / pad, C a multiple of 64, K of 8; fixed-order sums -- the same bits on
     every run."""
-    lib = load()
-    for t in (x, dy):
-        if t.dim() != 4 or not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous(memory_format=torch.channels_last):
-            raise GdkvmError("conv_wgrad_strided needs channels_last bf16 [N,C,H,W] device tensors (no CPU path)")
+    _channels_last("conv_wgrad_strided", x, dy, dtype=torch.bfloat16)
     n, c, hh, ww = x.shape
     k, c2, r, s_ = weight_like.shape
     ho, wo = (hh + 2 * pad - r) // stride + 1, (ww + 2 * pad - s_) // stride + 1
     if c2 != c or tuple(dy.shape) != (n, k, ho, wo):
         raise GdkvmError(f"conv_wgrad_strided: x {tuple(x.shape)}, dy {tuple(dy.shape)} and weight {tuple(weight_like.shape)} do not fit stride {stride} pad {pad}")
     dw = torch.empty_strided(tuple(weight_like.shape), tuple(weight_like.stride()), dtype=torch.float32, device=x.device)
-    need = max(16, int(lib.gdkvm_conv_wgrad_strided_workspace_bytes(n, c, hh, ww, k, r, s_, stride, pad)))
-    key = (x.device, _stream(x.device))
-    ws = _S2_WS.get(key)
-    if ws is None or ws.numel() < need:                     # one workspace per device and stream, grown to the largest layer (~30 MB)
-        ws = _S2_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-    sk, sc, sr, ss = dw.stride()
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_conv_wgrad_strided(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), sk, sc, sr, ss, ws.data_ptr(), ws.numel(),
-                                          n, c, hh, ww, k, r, s_, stride, pad, BF16, _stream(x.device))
-    _check(rc, "gdkvm_conv_wgrad_strided")
+    ws = _grown_workspace("gdkvm_conv_wgrad_strided_workspace_bytes", x.device, n, c, hh, ww, k, r, s_, stride, pad)     # (the largest layer: ~30 MB)
+    _call("gdkvm_conv_wgrad_strided", x.device, x, dy, dw, *dw.stride(), _Ws(ws), n, c, hh, ww, k, r, s_, stride, pad, BF16)
     return dw
 
 
 def conv_s2_packs(weight: torch.Tensor, down_weight: Optional[torch.Tensor]):
     """(forward pack, forward pack of the 1x1 branch | None, data-gradient pack) of a [K,C,3,3] fp32 weight and its block's [K,C,1,1] branch,
     ONE launch from the master weights in whatever memory format they have (gdkvm_conv_s2_pack_train)."""
-    lib = load()
     k, c = weight.shape[:2]
     if weight.dtype != torch.float32 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_cuda:
         raise GdkvmError("conv_s2_packs: fp32 [K,C,3,3] device weight")
@@ -1352,14 +1251,11 @@ def conv_s2_packs(weight: torch.Tensor, down_weight: Optional[torch.Tensor]):
     dev = weight.device
     fwd = torch.empty(k * 9 * c, dtype=torch.bfloat16, device=dev)
     fwd_d = None if down_weight is None else torch.empty(k * c, dtype=torch.bfloat16, device=dev)
-    dg = torch.empty(int(lib.gdkvm_conv_s2_dgrad_pack_bytes(c, k, int(down_weight is not None))) // 2, dtype=torch.bfloat16, device=dev)
+    dg = torch.empty(_bytes("gdkvm_conv_s2_dgrad_pack_bytes", dev, c, k, int(down_weight is not None)) // 2, dtype=torch.bfloat16, device=dev)
     st = (ctypes.c_longlong * 4)(*weight.stride())
     sd = None if down_weight is None else (ctypes.c_longlong * 2)(*down_weight.stride()[:2])
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_conv_s2_pack_train(weight.data_ptr(), ctypes.cast(st, ctypes.c_void_p), _ptr(down_weight),
-                                          None if sd is None else ctypes.cast(sd, ctypes.c_void_p), fwd.data_ptr(), _ptr(fwd_d), dg.data_ptr(),
-                                          k, c, _stream(dev))
-    _check(rc, "gdkvm_conv_s2_pack_train")
+    _call("gdkvm_conv_s2_pack_train", dev, weight, ctypes.cast(st, ctypes.c_void_p), down_weight,
+          None if sd is None else ctypes.cast(sd, ctypes.c_void_p), fwd, fwd_d, dg, k, c)
     return fwd, fwd_d, dg
 
 
@@ -1370,7 +1266,6 @@ class _ConvS2BlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, down_weight):
-        lib = load()
         xb = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         n, c, hh, ww = xb.shape
         k = weight.shape[0]
@@ -1378,17 +1273,13 @@ class _ConvS2BlockFunction(torch.autograd.Function):
         ho, wo = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
         y = torch.empty((n, k, ho, wo), dtype=torch.bfloat16, device=xb.device, memory_format=torch.channels_last)
         yd = torch.empty_like(y)
-        with torch.cuda.device(xb.device):
-            rc = lib.gdkvm_conv_down_bias_act(xb.data_ptr(), fwd.data_ptr(), _zero_bias(k, xb.device).data_ptr(), y.data_ptr(), 0, fwd_d.data_ptr(),
-                                              None, yd.data_ptr(), n, c, hh, ww, k, 3, 3, 2, 1, BF16, _stream(xb.device))
-        _check(rc, "gdkvm_conv_down_bias_act")
+        _call("gdkvm_conv_down_bias_act", xb.device, xb, fwd, _zero_bias(k, xb.device), y, 0, fwd_d, None, yd, n, c, hh, ww, k, 3, 3, 2, 1, BF16)
         ctx.save_for_backward(xb, dg, weight, down_weight)
         ctx.xdtype = x.dtype
         return y, yd
 
     @staticmethod
     def backward(ctx, dy, dyd):
-        lib = load()
         xb, dg, weight, down_weight = ctx.saved_tensors
         n, c, hh, ww = xb.shape
         k = weight.shape[0]
@@ -1398,9 +1289,7 @@ class _ConvS2BlockFunction(torch.autograd.Function):
         dx = dw = dwd = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(xb)
-            with torch.cuda.device(xb.device):
-                rc = lib.gdkvm_conv_s2_dgrad(dyb.data_ptr(), dydb.data_ptr(), dg.data_ptr(), dx.data_ptr(), n, c, hh, ww, k, 1, BF16, _stream(xb.device))
-            _check(rc, "gdkvm_conv_s2_dgrad")
+            _call("gdkvm_conv_s2_dgrad", xb.device, dyb, dydb, dg, dx, n, c, hh, ww, k, 1, BF16)
             dx = dx.to(ctx.xdtype)
         if ctx.needs_input_grad[1]:
             dw = conv_wgrad_strided(xb, dyb, weight, 2, 1).to(weight.dtype)
@@ -1432,9 +1321,7 @@ def conv_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, res
     """act(conv2d(x, weight) + bias[k] (+ residual)) as ONE kernel on channels_last bf16 tensors (gdkvm_conv_bias_act): the
     epilogue runs on the fp32 accumulator inside the implicit-GEMM kernel, no second pass over the output.  packed: the
     conv3x3_pack_weights copy of `weight` (kernel 5 reads it instead: faster, same result)."""
-    lib = load()
-    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("conv_bias_act needs a channels_last bf16 [N,C,H,W] device tensor (no CPU path)")
+    _channels_last("conv_bias_act", x, dtype=torch.bfloat16)
     if weight.dim() != 4 or weight.dtype != torch.bfloat16 or weight.shape[1] != x.shape[1] or \
             not weight.is_contiguous(memory_format=torch.channels_last):
         raise GdkvmError("conv_bias_act: weight must be channels_last bf16 [K,C,R,S]")
@@ -1447,21 +1334,18 @@ def conv_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, res
     if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or
                                  not residual.is_contiguous(memory_format=torch.channels_last)):
         raise GdkvmError("residual must match the output (shape, dtype, channels_last)")
-    with torch.cuda.device(x.device):
-        if packed is not None:
-            if packed.dtype != torch.bfloat16 or packed.numel() != weight.numel() or packed.device != x.device:
-                raise GdkvmError("conv_bias_act: packed must be conv3x3_pack_weights(weight)")
-            tile |= CONV_PACKED_WEIGHTS
-        rc = lib.gdkvm_conv_bias_act(x.data_ptr(), (packed if packed is not None else weight).data_ptr(), bias.data_ptr(), _ptr(residual),
-                                     y.data_ptr(), n, c, hh, ww, k, r, s, stride, padding, int(relu), tile, BF16, _stream(x.device))
-    _check(rc, "gdkvm_conv_bias_act")
+    if packed is not None:
+        if packed.dtype != torch.bfloat16 or packed.numel() != weight.numel() or packed.device != x.device:
+            raise GdkvmError("conv_bias_act: packed must be conv3x3_pack_weights(weight)")
+        tile |= CONV_PACKED_WEIGHTS
+    _call("gdkvm_conv_bias_act", x.device, x, packed if packed is not None else weight, bias, residual, y,
+          n, c, hh, ww, k, r, s, stride, padding, int(relu), tile, BF16)
     return y
 
 
 def bias_relu_maxpool(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """relu(max_pool2d(x, 3, 2, 1) + bias[c]) on a channels_last conv output in one pass (gdkvm_bias_relu_maxpool);
     equals max_pool2d(relu(x + bias), 3, 2, 1).  x may be a top-left spatial crop (a view) of a larger channels_last tensor."""
-    lib = load()
     if x.dim() != 4 or not x.is_cuda:
         raise GdkvmError("bias_relu_maxpool needs a channels_last [N,C,H,W] device tensor (or a spatial crop of one)")
     n, c, hh, ww = x.shape
@@ -1477,39 +1361,29 @@ def bias_relu_maxpool(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
         raise GdkvmError("bias must be float32 [C]")
     out = torch.empty((n, c, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1), device=x.device, dtype=x.dtype,
                       memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_bias_relu_maxpool(x.data_ptr(), bias.data_ptr(), out.data_ptr(), n, hh, ww, c, x_rows, x_cols,
-                                         _io_dtype(x), _stream(x.device))
-    _check(rc, "gdkvm_bias_relu_maxpool")
+    _call("gdkvm_bias_relu_maxpool", x.device, x, bias, out, n, hh, ww, c, x_rows, x_cols, _io_dtype(x))
     return out
 
 
 def stem_s2d(x: torch.Tensor, cpad: int) -> torch.Tensor:
     """Space-to-depth of NCHW frames for the stem: [N,C,H,W] contiguous -> channels_last [N,cpad,H/2,W/2] with channel
     (c*2+p)*2+q = x[c, 2i+p, 2j+q] and zeros above 4C (gdkvm_stem_s2d)."""
-    lib = load()
     if x.dim() != 4 or not x.is_cuda or not x.is_contiguous():
         raise GdkvmError("stem_s2d needs a contiguous NCHW device tensor")
     n, c, hh, ww = x.shape
     out = torch.empty((n, cpad, hh // 2, ww // 2), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_stem_s2d(x.data_ptr(), out.data_ptr(), n, c, hh, ww, cpad, _io_dtype(x), _stream(x.device))
-    _check(rc, "gdkvm_stem_s2d")
+    _call("gdkvm_stem_s2d", x.device, x, out, n, c, hh, ww, cpad, _io_dtype(x))
     return out
 
 
 def upsample_bilinear(lo: torch.Tensor, size) -> torch.Tensor:
     """F.interpolate(lo, size, mode="bilinear", align_corners=False) on a channels_last bf16 [N,C,h,w] device tensor
     (gdkvm_upsample_cat without a skip tensor): what conv_cat_bias_act reads next to the skip feature."""
-    lib = load()
-    if lo.dim() != 4 or not lo.is_cuda or lo.dtype != torch.bfloat16 or not lo.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("upsample_bilinear needs a channels_last bf16 [N,C,h,w] device tensor (no CPU path)")
+    _channels_last("upsample_bilinear", lo, dtype=torch.bfloat16, shape="[N,C,h,w]")
     n, c1, hl, wl = lo.shape
     H, W = int(size[0]), int(size[1])
     out = torch.empty((n, c1, H, W), dtype=lo.dtype, device=lo.device, memory_format=torch.channels_last)
-    with torch.cuda.device(lo.device):
-        rc = lib.gdkvm_upsample_cat(lo.data_ptr(), None, out.data_ptr(), n, hl, wl, H, W, c1, 0, BF16, _stream(lo.device))
-    _check(rc, "gdkvm_upsample_cat")
+    _call("gdkvm_upsample_cat", lo.device, lo, None, out, n, hl, wl, H, W, c1, 0, BF16)
     return out
 
 
@@ -1518,10 +1392,7 @@ def conv_cat_bias_act(x1: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, 
                       packed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv_bias_act(torch.cat([x1, x2], 1), weight, ...) for a 3x3 / stride 1 / pad 1 layer WITHOUT the concatenated tensor
     (gdkvm_conv_cat_bias_act): channel counts in multiples of 64, same result bit for bit."""
-    lib = load()
-    for t in (x1, x2):
-        if t.dim() != 4 or not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous(memory_format=torch.channels_last):
-            raise GdkvmError("conv_cat_bias_act needs channels_last bf16 [N,C,H,W] device tensors (no CPU path)")
+    _channels_last("conv_cat_bias_act", x1, x2, dtype=torch.bfloat16)
     n, c1, hh, ww = x1.shape
     c2 = x2.shape[1]
     if tuple(x2.shape) != (n, c2, hh, ww):
@@ -1540,33 +1411,25 @@ def conv_cat_bias_act(x1: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, 
         if packed.dtype != torch.bfloat16 or packed.numel() != weight.numel() or packed.device != x1.device:
             raise GdkvmError("conv_cat_bias_act: packed must be conv3x3_pack_weights(weight)")
         tile |= CONV_PACKED_WEIGHTS
-    with torch.cuda.device(x1.device):
-        rc = lib.gdkvm_conv_cat_bias_act(x1.data_ptr(), x2.data_ptr(), (packed if packed is not None else weight).data_ptr(), bias.data_ptr(),
-                                         _ptr(residual), y.data_ptr(), n, c1, c2, hh, ww, k, int(relu), tile, BF16, _stream(x1.device))
-    _check(rc, "gdkvm_conv_cat_bias_act")
+    _call("gdkvm_conv_cat_bias_act", x1.device, x1, x2, packed if packed is not None else weight, bias, residual, y,
+          n, c1, c2, hh, ww, k, int(relu), tile, BF16)
     return y
 
 
 def _upsample_cat_fwd(lo: torch.Tensor, skip: torch.Tensor) -> torch.Tensor:
-    lib = load()
-    for t in (lo, skip):
-        if t.dim() != 4 or not t.is_cuda or not t.is_contiguous(memory_format=torch.channels_last):
-            raise GdkvmError("upsample_cat needs channels_last device tensors")
+    _channels_last("upsample_cat", lo, skip)
     if lo.dtype != torch.bfloat16 or skip.dtype != torch.bfloat16 or lo.shape[0] != skip.shape[0]:
         raise GdkvmError("upsample_cat: bf16 tensors with equal batch")
     n, c1, hl, wl = lo.shape
     _, c2, H, W = skip.shape
     out = torch.empty((n, c1 + c2, H, W), dtype=lo.dtype, device=lo.device, memory_format=torch.channels_last)
-    with torch.cuda.device(lo.device):
-        rc = lib.gdkvm_upsample_cat(lo.data_ptr(), skip.data_ptr(), out.data_ptr(), n, hl, wl, H, W, c1, c2, BF16, _stream(lo.device))
-    _check(rc, "gdkvm_upsample_cat")
+    _call("gdkvm_upsample_cat", lo.device, lo, skip, out, n, hl, wl, H, W, c1, c2, BF16)
     return out
 
 
 def stem_conv_pool(xs: torch.Tensor, w_s2d: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """max_pool2d(relu(conv2d(xs, w_s2d, padding=2)[..., :Hs, :Ws] + bias), 3, 2, 1) in one kernel (gdkvm_stem_conv_pool):
     xs channels_last bf16 [N,16,Hs,Ws] (ops.stem_s2d), w_s2d channels_last bf16 [64,16,4,4], bias fp32 [64]."""
-    lib = load()
     if xs.dim() != 4 or not xs.is_cuda or xs.dtype != torch.bfloat16 or xs.shape[1] != 16 or \
             not xs.is_contiguous(memory_format=torch.channels_last):
         raise GdkvmError("stem_conv_pool needs a channels_last bf16 [N,16,Hs,Ws] device tensor (no CPU path)")
@@ -1576,16 +1439,13 @@ def stem_conv_pool(xs: torch.Tensor, w_s2d: torch.Tensor, bias: torch.Tensor) ->
         raise GdkvmError("bias must be float32 [64]")
     n, _, hs, ws = xs.shape
     y = torch.empty((n, 64, (hs - 1) // 2 + 1, (ws - 1) // 2 + 1), dtype=xs.dtype, device=xs.device, memory_format=torch.channels_last)
-    with torch.cuda.device(xs.device):
-        rc = lib.gdkvm_stem_conv_pool(xs.data_ptr(), w_s2d.data_ptr(), bias.data_ptr(), y.data_ptr(), n, hs, ws, BF16, _stream(xs.device))
-    _check(rc, "gdkvm_stem_conv_pool")
+    _call("gdkvm_stem_conv_pool", xs.device, xs, w_s2d, bias, y, n, hs, ws, BF16)
     return y
 
 
 def stem_conv_pool_nchw(x: torch.Tensor, w_s2d: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """stem_conv_pool(stem_s2d(x, 16), w_s2d, bias) without the space-to-depth copy (gdkvm_stem_conv_pool_nchw): x contiguous NCHW bf16
     [N, C <= 4, H, W] with H, W even; bit-identical to the two-kernel form."""
-    lib = load()
     if x.dim() != 4 or not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.shape[1] > 4 or x.shape[2] % 2 or x.shape[3] % 2:
         raise GdkvmError("stem_conv_pool_nchw needs a contiguous NCHW bf16 [N, C <= 4, H, W] device tensor with even H, W (no CPU path)")
     if tuple(w_s2d.shape) != (64, 16, 4, 4) or w_s2d.dtype != torch.bfloat16 or not w_s2d.is_contiguous(memory_format=torch.channels_last):
@@ -1595,9 +1455,7 @@ def stem_conv_pool_nchw(x: torch.Tensor, w_s2d: torch.Tensor, bias: torch.Tensor
     n, c, hh, ww = x.shape
     hs, ws = hh // 2, ww // 2
     y = torch.empty((n, 64, (hs - 1) // 2 + 1, (ws - 1) // 2 + 1), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_stem_conv_pool_nchw(x.data_ptr(), w_s2d.data_ptr(), bias.data_ptr(), y.data_ptr(), n, c, hh, ww, BF16, _stream(x.device))
-    _check(rc, "gdkvm_stem_conv_pool_nchw")
+    _call("gdkvm_stem_conv_pool_nchw", x.device, x, w_s2d, bias, y, n, c, hh, ww, BF16)
     return y
 
 
@@ -1608,15 +1466,13 @@ class _StemConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight):
-        lib = load()
         xb = x.detach().to(torch.bfloat16).contiguous()
         n, c, hh, ww = xb.shape
         w4 = torch.empty(64 * 256, dtype=torch.bfloat16, device=xb.device)
         y = torch.empty((n, 64, hh // 2, ww // 2), dtype=torch.bfloat16, device=xb.device, memory_format=torch.channels_last)
         wd = weight.detach()
-        with torch.cuda.device(xb.device):
-            _check(lib.gdkvm_stem_pack_s2d(wd.data_ptr(), w4.data_ptr(), c, *wd.stride(), _stream(xb.device)), "gdkvm_stem_pack_s2d")
-            _check(lib.gdkvm_stem_conv_nchw(xb.data_ptr(), w4.data_ptr(), y.data_ptr(), n, c, hh, ww, BF16, _stream(xb.device)), "gdkvm_stem_conv_nchw")
+        _call("gdkvm_stem_pack_s2d", xb.device, wd, w4, c, *wd.stride())
+        _call("gdkvm_stem_conv_nchw", xb.device, xb, w4, y, n, c, hh, ww, BF16)
         ctx.save_for_backward(xb, weight)
         return y
 
@@ -1632,7 +1488,6 @@ class _StemConvFunction(torch.autograd.Function):
 def stem_wgrad(x: torch.Tensor, dy: torch.Tensor, like: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Weight gradient [64, C, 7, 7] fp32 of the stem convolution (7x7 / stride 2 / pad 3) for NCHW bf16 frames x [N, C <= 4, H, W] and
     dy [N, 64, H/2, W/2] (channels_last bf16), on gdkvm_stem_wgrad_nchw: fixed summation order, in the memory format of `like`."""
-    lib = load()
     xb = x.detach().to(torch.bfloat16).contiguous()
     dyb = _nhwc(dy.detach(), "stem_wgrad")
     if dyb.dtype != torch.bfloat16:
@@ -1641,11 +1496,8 @@ def stem_wgrad(x: torch.Tensor, dy: torch.Tensor, like: Optional[torch.Tensor] =
     if tuple(dyb.shape) != (n, 64, hh // 2, ww // 2):
         raise GdkvmError(f"stem_wgrad: dy {tuple(dyb.shape)} does not match x {tuple(xb.shape)}")
     dw = torch.empty_like(like, dtype=torch.float32) if like is not None else torch.empty((64, c, 7, 7), dtype=torch.float32, device=xb.device)
-    need = lib.gdkvm_stem_wgrad_workspace_bytes(n, hh, ww)
-    ws = torch.empty(need, dtype=torch.uint8, device=xb.device)
-    with torch.cuda.device(xb.device):
-        _check(lib.gdkvm_stem_wgrad_nchw(xb.data_ptr(), dyb.data_ptr(), dw.data_ptr(), *dw.stride(), ws.data_ptr(), need, n, c, hh, ww, BF16,
-                                         _stream(xb.device)), "gdkvm_stem_wgrad_nchw")
+    ws = _workspace("gdkvm_stem_wgrad_workspace_bytes", xb.device, n, hh, ww)
+    _call("gdkvm_stem_wgrad_nchw", xb.device, xb, dyb, dw, *dw.stride(), _Ws(ws), n, c, hh, ww, BF16)
     return dw
 
 
@@ -1664,7 +1516,6 @@ def stem_conv(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 def upsample_cat_bwd(dout: torch.Tensor, lo_shape, skip_shape) -> Tuple[torch.Tensor, torch.Tensor]:
     """(d_lo, d_skip) of upsample_cat for d_out [N,C1+C2,H,W] channels_last bf16 (gdkvm_upsample_cat_bwd)."""
-    lib = load()
     dout = _nhwc(dout, "upsample_cat_bwd")
     if dout.dtype != torch.bfloat16:
         dout = dout.to(torch.bfloat16)
@@ -1674,10 +1525,7 @@ def upsample_cat_bwd(dout: torch.Tensor, lo_shape, skip_shape) -> Tuple[torch.Te
         raise GdkvmError(f"upsample_cat_bwd: d_out {tuple(dout.shape)} does not match {lo_shape} + {skip_shape}")
     dlo = torch.empty((n, c1, hl, wl), dtype=dout.dtype, device=dout.device, memory_format=torch.channels_last)
     dskip = torch.empty((n, c2, H, W), dtype=dout.dtype, device=dout.device, memory_format=torch.channels_last)
-    with torch.cuda.device(dout.device):
-        rc = lib.gdkvm_upsample_cat_bwd(dout.data_ptr(), dlo.data_ptr(), dskip.data_ptr(), n, hl, wl, H, W, c1, c2, BF16,
-                                        _stream(dout.device))
-    _check(rc, "gdkvm_upsample_cat_bwd")
+    _call("gdkvm_upsample_cat_bwd", dout.device, dout, dlo, dskip, n, hl, wl, H, W, c1, c2, BF16)
     return dlo, dskip
 
 
@@ -1712,31 +1560,24 @@ def bn_act_fwd(x, weight, bias, running_mean=None, running_var=None, residual=No
     """Batch-statistics BatchNorm + optional residual add + optional ReLU on a channels_last tensor in three streaming
     passes (gdkvm_bn_fwd_train).  Updates running_mean / running_var in place.  Returns (y, stats) with stats fp32 [4, C] =
     (mean, 1/sqrt(var + eps), scale, shift)."""
-    lib = load()
     x = _nhwc(x, "bn_act_fwd")
     n, c, hh, ww = x.shape
     if residual is not None:
         residual = _nhwc(residual, "bn_act_fwd")
         if residual.shape != x.shape or residual.dtype != x.dtype:
             raise GdkvmError("bn_act_fwd: residual must match x (shape, dtype)")
-    for t in (weight, bias, running_mean, running_var):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != c or not t.is_contiguous()):
-            raise GdkvmError("bn_act_fwd: weight / bias / running statistics must be contiguous float32 [C]")
+    _f32_vectors("bn_act_fwd", c, weight, bias, running_mean, running_var)
     y = torch.empty_like(x)
     stats = torch.empty((4, c), dtype=torch.float32, device=x.device)
-    ws = torch.empty(int(lib.gdkvm_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_bn_fwd_train(x.data_ptr(), _ptr(residual), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean),
-                                    _ptr(running_var), y.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    n * hh * ww, c, float(eps), float(momentum), int(relu), _io_dtype(x), _stream(x.device))
-    _check(rc, "gdkvm_bn_fwd_train")
+    ws = _workspace("gdkvm_bn_workspace_bytes", x.device, c)
+    _call("gdkvm_bn_fwd_train", x.device, x, residual, weight, bias, running_mean, running_var, y, stats, _Ws(ws),
+          n * hh * ww, c, float(eps), float(momentum), int(relu), _io_dtype(x))
     return y, stats
 
 
 def bn_act_bwd(x, y, dy, weight, stats, relu: bool = True, want_dres: bool = False):
     """Backward of bn_act_fwd (gdkvm_bn_bwd): returns (dx, dres | None, dweight, dbias).  y = None with relu: the forward had
     no residual and the ReLU mask is recomputed from x (one tensor less to read)."""
-    lib = load()
     x, dy = _nhwc(x, "bn_act_bwd"), _nhwc(dy, "bn_act_bwd")
     if dy.dtype != x.dtype:
         dy = dy.to(x.dtype)
@@ -1748,12 +1589,9 @@ def bn_act_bwd(x, y, dy, weight, stats, relu: bool = True, want_dres: bool = Fal
     dres = torch.empty_like(x) if (want_dres and relu) else None
     dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
-    ws = torch.empty(int(lib.gdkvm_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.gdkvm_bn_bwd(x.data_ptr(), _ptr(y) if mode == 1 else None, dy.data_ptr(), weight.data_ptr(), stats.data_ptr(),
-                              dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
-                              ws.numel(), n * hh * ww, c, mode, _io_dtype(x), _stream(x.device))
-    _check(rc, "gdkvm_bn_bwd")
+    ws = _workspace("gdkvm_bn_workspace_bytes", x.device, c)
+    _call("gdkvm_bn_bwd", x.device, x, y if mode == 1 else None, dy, weight, stats, dx, dres, dgamma, dbeta, _Ws(ws),
+          n * hh * ww, c, mode, _io_dtype(x))
     if want_dres and not relu:
         dres = dy                                           # no mask: the residual branch receives dy itself
     return dx, dres, dgamma, dbeta
@@ -1789,28 +1627,21 @@ class _BNReluPoolFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps):
-        lib = load()
         x = _nhwc(x, "bn_relu_pool")
         n, c, hh, ww = x.shape
         ho, wo = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
-        for t in (weight, bias, running_mean, running_var):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != c or not t.is_contiguous()):
-                raise GdkvmError("bn_relu_pool: weight / bias / running statistics must be contiguous float32 [C]")
+        _f32_vectors("bn_relu_pool", c, weight, bias, running_mean, running_var)
         y = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device)
         stats = torch.empty((4, c), dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(lib.gdkvm_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.gdkvm_bn_pool_fwd_train(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean), _ptr(running_var),
-                                             y.data_ptr(), idx.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), n, hh, ww, c,
-                                             float(eps), float(momentum), _io_dtype(x), _stream(x.device))
-        _check(rc, "gdkvm_bn_pool_fwd_train")
+        ws = _workspace("gdkvm_bn_workspace_bytes", x.device, c)
+        _call("gdkvm_bn_pool_fwd_train", x.device, x, weight, bias, running_mean, running_var, y, idx, stats, _Ws(ws), n, hh, ww, c,
+              float(eps), float(momentum), _io_dtype(x))
         ctx.save_for_backward(x, idx, weight, stats)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load()
         x, idx, weight, stats = ctx.saved_tensors
         n, c, hh, ww = x.shape
         dy = _nhwc(dy, "bn_relu_pool backward")
@@ -1819,11 +1650,8 @@ class _BNReluPoolFunction(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
         dbeta = torch.empty_like(dgamma)
-        ws = torch.empty(int(lib.gdkvm_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.gdkvm_bn_pool_bwd(x.data_ptr(), dy.data_ptr(), idx.data_ptr(), weight.data_ptr(), stats.data_ptr(), dx.data_ptr(),
-                                       dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), n, hh, ww, c, _io_dtype(x), _stream(x.device))
-        _check(rc, "gdkvm_bn_pool_bwd")
+        ws = _workspace("gdkvm_bn_workspace_bytes", x.device, c)
+        _call("gdkvm_bn_pool_bwd", x.device, x, dy, idx, weight, stats, dx, dgamma, dbeta, _Ws(ws), n, hh, ww, c, _io_dtype(x))
         return dx, dgamma, dbeta, None, None, None, None
 
 
@@ -1840,29 +1668,23 @@ def bn_relu_pool(x, weight, bias, running_mean=None, running_var=None, momentum:
 class _MaxPoolFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        lib = load()
         x = _nhwc(x, "maxpool3x3s2")
         n, c, hh, ww = x.shape
         ho, wo = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
         y = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.gdkvm_maxpool_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), n, hh, ww, c, _io_dtype(x), _stream(x.device))
-        _check(rc, "gdkvm_maxpool_fwd")
+        _call("gdkvm_maxpool_fwd", x.device, x, y, idx, n, hh, ww, c, _io_dtype(x))
         ctx.save_for_backward(idx)
         ctx.in_shape = (n, c, hh, ww)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load()
         (idx,) = ctx.saved_tensors
         n, c, hh, ww = ctx.in_shape
         dy = _nhwc(dy, "maxpool3x3s2 backward")
         dx = torch.empty((n, c, hh, ww), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
-        with torch.cuda.device(dy.device):
-            rc = lib.gdkvm_maxpool_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), n, hh, ww, c, _io_dtype(dy), _stream(dy.device))
-        _check(rc, "gdkvm_maxpool_bwd")
+        _call("gdkvm_maxpool_bwd", dy.device, dy, idx, dx, n, hh, ww, c, _io_dtype(dy))
         return dx
 
 
@@ -1875,7 +1697,6 @@ def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
 def gemm_nt(a: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C [M,N] = a [M,K] @ bt [N,K]^T (+ bias [N], fp32) on the hand-written MFMA kernel (gdkvm_gemm_nt); a, bt share one dtype
     (bf16 or fp32), C comes back in it, accumulation is fp32."""
-    lib = load()
     if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1] or a.dtype != bt.dtype:
         raise GdkvmError(f"gemm_nt: a [M,K] and bt [N,K] of one dtype, got {tuple(a.shape)} {a.dtype} / {tuple(bt.shape)} {bt.dtype}")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != bt.shape[0]):
@@ -1888,9 +1709,7 @@ def gemm_nt(a: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = No
     M, K = a.shape
     N = bt.shape[0]
     c = torch.empty((M, N), dtype=a.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_gemm_nt(_ptr(a), _ptr(bt), _ptr(bias), _ptr(c), M, N, K, _io_dtype(a), _stream(dev))
-    _check(rc, "gdkvm_gemm_nt")
+    _call("gdkvm_gemm_nt", dev, a, bt, bias, c, M, N, K, _io_dtype(a))
     return c
 
 
@@ -1899,7 +1718,6 @@ def wgrad(dy2d: torch.Tensor, x2d: torch.Tensor, colsum: bool = False):
     reduction over the tokens is split over workgroups into fp32 partial tiles and summed in a fixed order (gdkvm_gemm_tn);
     the sum never passes through bf16.  colsum=True: (dW, db) with db [M] (fp32) = the column sums of dy -- the bias gradient --
     from the same launch (gdkvm_gemm_tn_colsum)."""
-    lib = load()
     if dy2d.dim() != 2 or x2d.dim() != 2 or dy2d.shape[0] != x2d.shape[0]:
         raise GdkvmError("wgrad: dy [K,M] and x [K,N] with equal K")
     if dy2d.dtype != x2d.dtype:
@@ -1909,18 +1727,11 @@ def wgrad(dy2d: torch.Tensor, x2d: torch.Tensor, colsum: bool = False):
     K, M = dy2d.shape
     N = x2d.shape[1]
     c = torch.empty((M, N), dtype=torch.float32, device=dev)
-    if colsum:
-        db = torch.empty(M, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(lib.gdkvm_gemm_tn_colsum_workspace_bytes(K, M, N)), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gdkvm_gemm_tn_colsum(_ptr(dy2d), _ptr(x2d), _ptr(c), _ptr(db), ws.data_ptr(), ws.numel(), K, M, N, _io_dtype(dy2d), _stream(dev))
-        _check(rc, "gdkvm_gemm_tn_colsum")
-        return c, db
-    ws = torch.empty(int(lib.gdkvm_gemm_tn_workspace_bytes(K, M, N)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_gemm_tn(_ptr(dy2d), _ptr(x2d), _ptr(c), ws.data_ptr(), ws.numel(), K, M, N, _io_dtype(dy2d), _stream(dev))
-    _check(rc, "gdkvm_gemm_tn")
-    return c
+    name = "gdkvm_gemm_tn_colsum" if colsum else "gdkvm_gemm_tn"
+    outs = (c, torch.empty(M, dtype=torch.float32, device=dev)) if colsum else (c,)
+    ws = _workspace(name + "_workspace_bytes", dev, K, M, N)
+    _call(name, dev, dy2d, x2d, *outs, _Ws(ws), K, M, N, _io_dtype(dy2d))
+    return outs if colsum else c
 
 
 class _TokenLinear(torch.autograd.Function):
@@ -2030,7 +1841,6 @@ def token_projections(x2d: torch.Tensor, layers) -> Tuple[torch.Tensor, ...]:
 class _SegLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, target, H, W, dice_weight, eps):
-        lib = load()
         if z.dim() != 4 or not z.is_cuda or target.dim() != 3 or target.shape[0] != z.shape[0]:
             raise GdkvmError("seg_loss: logits [images,C,h,w] and labels [images,H,W] on the device (no CPU path)")
         if target.dtype not in (torch.int64, torch.uint8) or tuple(target.shape[1:]) != (H, W):
@@ -2038,27 +1848,20 @@ class _SegLossFunction(torch.autograd.Function):
         z, target = z.contiguous(), target.contiguous()
         ni, c, h, w = z.shape
         out = torch.empty(3, dtype=torch.float32, device=z.device)
-        ws = torch.empty(int(lib.gdkvm_seg_loss_workspace_bytes(c)), dtype=torch.uint8, device=z.device)
+        ws = _workspace("gdkvm_seg_loss_workspace_bytes", z.device, c)
         tb = 8 if target.dtype == torch.int64 else 1
-        with torch.cuda.device(z.device):
-            rc = lib.gdkvm_seg_loss_fwd(z.data_ptr(), target.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), ni, c, h, w, H, W,
-                                        float(dice_weight), float(eps), _io_dtype(z), tb, _stream(z.device))
-        _check(rc, "gdkvm_seg_loss_fwd")
+        _call("gdkvm_seg_loss_fwd", z.device, z, target, out, _Ws(ws), ni, c, h, w, H, W, float(dice_weight), float(eps), _io_dtype(z), tb)
         ctx.save_for_backward(z, target, ws)
         ctx.dims = (ni, c, h, w, H, W, tb)
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        lib = load()
         z, target, ws = ctx.saved_tensors
         ni, c, h, w, H, W, tb = ctx.dims
         g = g.to(torch.float32).reshape(1).contiguous()
         dz = torch.empty_like(z)
-        with torch.cuda.device(z.device):
-            rc = lib.gdkvm_seg_loss_bwd(z.data_ptr(), target.data_ptr(), ws.data_ptr(), ws.numel(), g.data_ptr(), dz.data_ptr(),
-                                        ni, c, h, w, H, W, _io_dtype(z), tb, _stream(z.device))
-        _check(rc, "gdkvm_seg_loss_bwd")
+        _call("gdkvm_seg_loss_bwd", z.device, z, target, _Ws(ws), g, dz, ni, c, h, w, H, W, _io_dtype(z), tb)
         return dz, None, None, None, None, None
 
 
@@ -2088,7 +1891,6 @@ def lv_measure(mask: torch.Tensor, cls: int = 1, disks: int = 20):
     `disks` disks along it and the single-plane method-of-disks volume (definition: include/gdkvm.h; integer-exact up to the disk areas).
     Returns (stats int64 [..., 12] = n sx sy sxx sxy syy Ux Uy tmin tmax Lt 0, disks int64 [..., D], geom float64 [..., 4] = L V cx cy);
     lengths in pixels of the mask's grid, V in pixel^3.  The mask may start at any byte address."""
-    lib = load()
     if mask.dtype != torch.uint8 or mask.dim() < 2:
         raise GdkvmError(f"lv_measure: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
     H, W = mask.shape[-2:]
@@ -2106,9 +1908,7 @@ def lv_measure(mask: torch.Tensor, cls: int = 1, disks: int = 20):
     stats = torch.empty(lead + (12,), dtype=torch.int64, device=dev)
     dk = torch.empty(lead + (int(disks),), dtype=torch.int64, device=dev)
     geom = torch.empty(lead + (4,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_lv_measure(_ptr(mask), _ptr(stats), _ptr(dk), _ptr(geom), frames, H, W, int(cls), int(disks), _stream(dev))
-    _check(rc, "gdkvm_lv_measure")
+    _call("gdkvm_lv_measure", dev, mask, stats, dk, geom, frames, H, W, int(cls), int(disks))
     return stats, dk, geom
 
 
@@ -2118,7 +1918,6 @@ def lv_ef(vol: torch.Tensor, npix: torch.Tensor, pick_vol: Optional[torch.Tensor
     (lv_measure's geom[..., 1] and stats[..., 0]; non-contiguous views are copied).  Frames with fewer than `min_pixels` pixels are not
     candidates; with pick_vol / pick_npix (both or neither, same shapes) ED / ES are chosen on THOSE -- the prediction's volumes at the
     target's frames.  Returns (ed_es_nvalid int32 [B, 3], edv_esv_ef float64 [B, 3]); fewer than two valid frames: ed = es = -1, EF = 0."""
-    lib = load()
     if (pick_vol is None) != (pick_npix is None):
         raise GdkvmError("lv_ef: pick_vol and pick_npix go together")
     if vol.dim() != 2 or vol.shape[1] < 1:
@@ -2132,9 +1931,7 @@ def lv_ef(vol: torch.Tensor, npix: torch.Tensor, pick_vol: Optional[torch.Tensor
     B, T = vol.shape
     idx = torch.empty((B, 3), dtype=torch.int32, device=dev)
     val = torch.empty((B, 3), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_lv_ef(_ptr(vol), _ptr(npix), _ptr(pick_vol), _ptr(pick_npix), _ptr(idx), _ptr(val), B, T, int(min_pixels), _stream(dev))
-    _check(rc, "gdkvm_lv_ef")
+    _call("gdkvm_lv_ef", dev, vol, npix, pick_vol, pick_npix, idx, val, B, T, int(min_pixels))
     return idx, val
 
 
@@ -2166,7 +1963,6 @@ def largest_component(mask: torch.Tensor, cls: int = 1, connectivity: int = 4, f
     output is an exact integer).  Returns (out uint8 like mask, info int32 [..., 8] = components, n, n_kept, label_kept (-1: no pixel of the
     class), removed_hit_cls, removed_hit_fill, 0, 0); the two hit counts say what the removed pixels were in `target` (same shape; 0 without
     one), which is what counts_after_largest needs.  out=mask filters in place; mask, target and out may start at any byte address."""
-    lib = load()
     if mask.dtype != torch.uint8 or mask.dim() < 2:
         raise GdkvmError(f"largest_component: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
     H, W = mask.shape[-2:]
@@ -2190,12 +1986,8 @@ def largest_component(mask: torch.Tensor, cls: int = 1, connectivity: int = 4, f
         out = torch.empty_like(mask)
     info = torch.empty(lead + (8,), dtype=torch.int32, device=dev)
     # (allocated per call like every workspace of this module: under graph capture it comes from the graph's own pool and is replayed with it)
-    need = int(lib.gdkvm_largest_component_workspace_bytes(frames, H, W))
-    ws = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gdkvm_largest_component(_ptr(mask), _ptr(target), _ptr(out), _ptr(info), _ptr(ws), ws.numel(), frames, H, W, int(cls),
-                                         int(connectivity), int(fill), _stream(dev))
-    _check(rc, "gdkvm_largest_component")
+    ws = _workspace("gdkvm_largest_component_workspace_bytes", dev, frames, H, W, floor=16)
+    _call("gdkvm_largest_component", dev, mask, target, out, info, _Ws(ws), frames, H, W, int(cls), int(connectivity), int(fill))
     return out, info
 
 

@@ -60,3 +60,46 @@ def test_host_side_of_the_library_is_clean_under_sanitizers():
     out = subprocess.run([os.path.join(here, "_build", "host_san")], capture_output=True, text=True, timeout=120,
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1"))
     assert out.returncode == 0 and "host_san: ok" in out.stdout, out.stdout + out.stderr
+
+
+_HELPERS = ("load", "_check", "_call", "_bytes")        # the only functions of ops.py that touch the library or the current device
+# entry points that launch but have no torch wrapper (reached from C, or from callers of the C ABI only), with the reason
+_C_ONLY = {"gdkvm_scan_prep_normed": "stage 1 of gdkvm_scan_fwd_normed; the split prep / apply pipeline of ops.py does not take norms"}
+
+
+def test_one_call_path_for_every_entry_point():
+    """ops.py reaches the library through ONE launch helper and ONE size-query helper: the marshalling of their arguments (pure, checked here on
+    CPU tensors), the names the wrappers pass (each a bound symbol; every launching symbol passed somewhere) and the absence of hand-written
+    launches outside the helpers."""
+    import ast
+    import ctypes
+    from gdkvm_amd import ops
+    t, w32, w8 = torch.zeros(5), torch.zeros(3, dtype=torch.float32), torch.zeros(7, dtype=torch.uint8)
+    assert ops._c_args((t, None, torch.empty(0), 3, 2.5)) == [t.data_ptr(), None, None, 3, 2.5]
+    assert ops._c_args((ops._Ws(w32), ops._Ws(w8), ops._Ws(None))) == [w32.data_ptr(), 12, w8.data_ptr(), 7, None, 0]
+    passed = ops._c_args((7, 0.5))
+    assert type(passed[0]) is int and type(passed[1]) is float
+
+    path = os.path.join(ROOT, "gdkvm_amd", "ops.py")
+    src = open(path).read()
+    tree = ast.parse(src)
+    skip = set()                                            # string nodes that are not names handed to a helper: SIGNATURES' keys and docstrings
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Assign) and any(isinstance(x, ast.Name) and x.id == "SIGNATURES" for x in node.targets):
+            skip.update(id(k) for k in node.value.keys)
+        if isinstance(node, (ast.Module, ast.FunctionDef, ast.ClassDef)) and ast.get_docstring(node, clean=False) is not None:
+            skip.add(id(node.body[0].value))
+    literals = {n.value for n in ast.walk(tree) if isinstance(n, ast.Constant) and isinstance(n.value, str) and id(n) not in skip
+                and re.fullmatch(r"gdkvm_[a-z_0-9]+", n.value)}
+    assert literals, "no entry-point names found in ops.py"
+    for name in sorted(literals):
+        assert name in ops.SIGNATURES, f"ops.py passes {name!r}, which has no signature"
+    launching = {n for n, (res, args) in ops.SIGNATURES.items() if res is ctypes.c_int and args and args[-1] is ctypes.c_void_p}
+    assert launching - literals == set(_C_ONLY), sorted((launching - literals) ^ set(_C_ONLY))
+
+    outside = src
+    for node in tree.body:                                  # blank the helpers out, then look at everything else
+        if isinstance(node, ast.FunctionDef) and node.name in _HELPERS:
+            outside = outside.replace(ast.get_source_segment(src, node), "")
+    assert not re.search(r"\.gdkvm_[a-z_0-9]+\s*\(", outside), "a hand-written library call outside the helpers"
+    assert "torch.cuda.device(" not in outside, "a hand-made device context outside the helpers"

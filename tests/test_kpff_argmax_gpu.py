@@ -517,3 +517,21 @@ def test_head_logits_planes(hip, dtype, case):
     assert got.shape == want.shape and got.is_contiguous() and got.dtype == dtype
     tol = 2.0 ** -7 if dtype == torch.bfloat16 else 1e-5
     assert (got.double() - want).abs().max() <= tol * max(1.0, want.abs().max().item())
+
+
+def test_failures_name_the_entry_that_ran(hip):
+    """An argument refusal (returned by the library before any launch) is reported under the name of the entry point that was called, also
+    where one wrapper chooses between two: kpff_fwd(packed=True) with a workspace too short for the packs runs gdkvm_kpff_fwd_packed, and
+    conv3x3_wgrad(channels_last=True) on rows wider than 64 pixels runs gdkvm_conv3x3_wgrad_krsc."""
+    BT, h, w, Ck, Cv, Cp = 5, 1, 1, 32, 32, 32
+    t = [_dev(x) for x in make_kpff_inputs(BT, h, w, Ck, Cv, Cp, seed=3)]
+    with pytest.raises(hip.GdkvmError, match=r"gdkvm_kpff_fwd_packed failed.*workspace"):
+        hip.kpff_fwd(*t, h, w, workspace=torch.empty(16, dtype=torch.uint8, device="cuda"), packed=True)
+    with pytest.raises(hip.GdkvmError, match=r"gdkvm_kpff_fwd failed.*workspace"):
+        hip.kpff_fwd(*t, h, w, workspace=torch.empty(16, dtype=torch.uint8, device="cuda"))
+    cl = dict(memory_format=torch.channels_last)
+    x, dy = (torch.zeros(1, 64, 8, 65, device="cuda", dtype=torch.bfloat16).contiguous(**cl) for _ in range(2))
+    with pytest.raises(hip.GdkvmError, match="gdkvm_conv3x3_wgrad_krsc failed"):
+        hip.conv3x3_wgrad(x, dy, channels_last=True)
+    with pytest.raises(hip.GdkvmError, match=r"gdkvm_conv3x3_wgrad failed"):
+        hip.conv3x3_wgrad(x, dy)
