@@ -5,7 +5,9 @@ pixels assumed; EF is a ratio); clips sharded over the GPUs of one node (no data
 EF sums are summed at the end).  With `data.lv_keep_largest` = 4 or 8 the PREDICTED mask is measured after ops.largest_component kept the
 largest 4- / 8-connected component of that class (fill 0; the target is a tracing and is measured as it is): the `lv` block is then the
 post-processed one, a `largest_component` block reports what was removed and the class's Dice / IoU after it, and every other key is still
-computed from the unfiltered mask.
+computed from the unfiltered mask.  With `data.surface_class` >= 0 a `surface` block reports the class's mean Hausdorff distance, HD95 and
+ASSD between predicted mask and target (ops.surface_distance / surface_metrics: pixels of the input grid, over the labelled frames where both
+have a surface).  The surface distances are those of the unfiltered mask, whatever `data.lv_keep_largest` says.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [key=value ...]"""
 from __future__ import annotations
@@ -61,6 +63,8 @@ def main(argv=None):
     keep = cfg.data.lv_keep_largest if lv_cls >= 0 else 0         # 0 = off: no new call below
     # the filtered mask's counts [ncls, 3], then frames changed and pixels removed: accumulated on the device, read once at the end
     lc_acc = torch.zeros(cfg.data.num_classes * 3 + 2, dtype=torch.int64, device=dev) if keep else None
+    s_cls = cfg.data.surface_class                                # -1 = off: no new call below
+    sd_sums = torch.zeros(5, dtype=torch.float64, device=dev) if s_cls >= 0 else None    # ops.surface_summary, accumulated on the device
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -73,16 +77,17 @@ def main(argv=None):
         """(mask, counts, target's LV measurement) per batch, one batch behind the submissions: the host queues batch i + 1 (copy, cast, replay)
         before it reads batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time).
         The TARGET is measured right behind the submission, on the stream where the prefetcher handed it out: its slot is recycled once the
-        consumer asks for the next batch, so nothing may read it later -- the largest-component filter of the prediction, one batch behind,
-        wants the target for its hit counts and gets a copy made here."""
+        consumer asks for the next batch, so nothing may read it later -- the largest-component filter of the prediction and its surface
+        distances, one batch behind, want the target and get a copy made here."""
         pending = None
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
             nxt = runner.submit(frames, target)
+            t_copy = target.clone() if keep or s_cls >= 0 else None
             if lv_cls >= 0:
                 t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
-                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), target.clone() if keep else None)
+                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy)
             else:
-                nxt = (nxt, None, None, None)
+                nxt = (nxt, None, None, t_copy)
             if pending is not None:
                 yield pending[0].get() + pending[1:]
             pending = nxt
@@ -106,6 +111,9 @@ def main(argv=None):
             r_idx, r_val = ops.lv_ef(t_vol, t_npix)
             _, p_val = ops.lv_ef(p_geom[..., 1], p_stats[..., 0], pick_vol=t_vol, pick_npix=t_npix)
             ef_sums += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
+        if s_cls >= 0:
+            surf = ops.surface_distance(mask, t_copy, cls=s_cls)
+            sd_sums += ops.surface_summary(*ops.surface_metrics(surf), surf, labelled[..., 0, 0])
         counts += (c * labelled).sum((0, 1)).long()
         if vis_left > 0:
             from PIL import Image
@@ -120,6 +128,8 @@ def main(argv=None):
             torch.distributed.all_reduce(ef_sums)                 # ... and the eight EF sums
         if keep:
             torch.distributed.all_reduce(lc_acc)                  # ... and the filtered mask's counts and removal totals
+        if s_cls >= 0:
+            torch.distributed.all_reduce(sd_sums)                 # ... and the five surface-distance sums
     if rank == 0:
         dice = ops.dice_from_counts(counts).tolist()
         iou = ops.iou_from_counts(counts).tolist()
@@ -136,6 +146,8 @@ def main(argv=None):
             res["largest_component"] = {"connectivity": keep, "frames_changed": int(acc[-2]), "pixels_removed": int(acc[-1]),
                                         "dice_lv": round(float(ops.dice_from_counts(lc_counts)[lv_cls]), 5),
                                         "iou_lv": round(float(ops.iou_from_counts(lc_counts)[lv_cls]), 5)}
+        if s_cls >= 0:
+            res["surface"] = {"class": s_cls, **{k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.surface_stats(sd_sums.cpu()).items()}}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -123,6 +123,8 @@ SIGNATURES = {
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
     "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
+    "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
+    "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
 }
 
 
@@ -2013,3 +2015,68 @@ def counts_after_largest(counts: torch.Tensor, info: torch.Tensor, cls: int, fil
         res[..., int(fill), 0] += inf[..., 5]
         res[..., int(fill), 1] += removed
     return res
+
+
+def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:
+    """gdkvm_surface_distance: per frame of mask and target [..., H, W] uint8 the surfaces of class `cls` (its pixels with a 4-neighbour
+    outside the class or the frame) and the exact squared Euclidean distances from each surface to the other (definition: include/gdkvm.h;
+    every output is an exact integer).  Returns surf int64 [..., 8] = nA, nB, hAB, hBA, sAB, sBA, q_lo, q_hi: the surface sizes of mask and
+    target, the largest squared distance per direction, the per-direction sums of the distances in units of 2^-16 pixel (each rounded down)
+    and the two squared distances that enclose the pooled 95th percentile; an empty surface leaves the six other fields 0.  surface_metrics
+    turns it into HD, HD95 and ASSD.  mask and target may start at any byte address."""
+    if mask.dtype != torch.uint8 or mask.dim() < 2:
+        raise GdkvmError(f"surface_distance: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
+    if target.dtype != torch.uint8 or tuple(target.shape) != tuple(mask.shape):
+        raise GdkvmError(f"surface_distance: target must be uint8 {tuple(mask.shape)}, got {target.dtype} {tuple(target.shape)}")
+    H, W = mask.shape[-2:]
+    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
+        raise GdkvmError(f"surface_distance: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
+    if not 0 <= int(cls) <= 254:
+        raise GdkvmError(f"surface_distance: cls = {cls} outside 0..254")
+    dev = _dev(mask, target)
+    lead = tuple(mask.shape[:-2])
+    frames = 1
+    for s in lead:
+        frames *= s
+    surf = torch.empty(lead + (8,), dtype=torch.int64, device=dev)
+    ws = _workspace("gdkvm_surface_distance_workspace_bytes", dev, frames, H, W, floor=16)
+    _call("gdkvm_surface_distance", dev, mask, target, surf, _Ws(ws), frames, H, W, int(cls))
+    return surf
+
+
+def surface_metrics(surf: torch.Tensor):
+    """(metrics float64 [..., 3] = HD, HD95, ASSD in pixels, valid bool [...]) from surface_distance's surf [..., 8]; valid = both surfaces
+    have pixels, and the metrics of an invalid frame are 0.  HD = sqrt(max(hAB, hBA)); HD95 = a + (b - a) (95 (n - 1) mod 100) / 100 with
+    a = sqrt(q_lo), b = sqrt(q_hi), n = nA + nB -- the linearly interpolated 95th percentile of the pooled distances (sorting d^2 sorts d);
+    ASSD = (sAB / nA + sBA / nB) / 2 / 65536 (at most 2^-16 pixel below the mean of the unrounded distances).  Pure torch on either device."""
+    if surf.shape[-1] != 8 or torch.is_floating_point(surf):
+        raise GdkvmError(f"surface_metrics: surf must be integers [..., 8], got {surf.dtype} {tuple(surf.shape)}")
+    s = surf.to(torch.int64)
+    nA, nB = s[..., 0], s[..., 1]
+    valid = (nA > 0) & (nB > 0)
+    d = s.to(torch.float64)
+    hd = torch.maximum(d[..., 2], d[..., 3]).sqrt()
+    a, b = d[..., 6].sqrt(), d[..., 7].sqrt()
+    frac = ((95 * (nA + nB - 1).clamp(min=0)) % 100).to(torch.float64) / 100.0
+    hd95 = a + (b - a) * frac
+    assd = (d[..., 4] / d[..., 0].clamp(min=1.0) + d[..., 5] / d[..., 1].clamp(min=1.0)) / 2.0 / 65536.0
+    metrics = torch.stack([hd, hd95, assd], -1) * valid.unsqueeze(-1).to(torch.float64)
+    return metrics, valid
+
+
+def surface_summary(metrics: torch.Tensor, valid: torch.Tensor, surf: torch.Tensor, labelled: torch.Tensor) -> torch.Tensor:
+    """The five running sums of a surface-distance evaluation over the frames where `labelled` (bool, the shape of `valid`): frames counted
+    (labelled and valid), frames where exactly one of the two surfaces is empty (no distance exists; they are reported, not averaged),
+    sum HD, sum HD95, sum ASSD (float64 [5], on the inputs' device).  Sums of batches and of ranks add; surface_stats makes the means."""
+    lab = labelled.to(torch.bool).expand(valid.shape)
+    k = (valid & lab).to(torch.float64)
+    one = (((surf[..., 0] > 0) != (surf[..., 1] > 0)) & lab).to(torch.float64)
+    m = metrics.to(torch.float64) * k.unsqueeze(-1)
+    return torch.stack([k.sum(), one.sum(), m[..., 0].sum(), m[..., 1].sum(), m[..., 2].sum()])
+
+
+def surface_stats(sums) -> dict:
+    """{frames, frames_one_empty, hd_mean, hd95_mean, assd_mean} from surface_summary's sums (host numbers, pixels; 0 when no frame counts)."""
+    n, one, hd, hd95, assd = (float(v) for v in sums)
+    d = n if n >= 1 else 1.0
+    return {"frames": int(n), "frames_one_empty": int(one), "hd_mean": hd / d, "hd95_mean": hd95 / d, "assd_mean": assd / d}

@@ -645,6 +645,32 @@ size_t gdkvm_largest_component_workspace_bytes(int frames, int H, int W);
 int gdkvm_largest_component(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, void* workspace, size_t workspace_bytes,
                             int frames, int H, int W, int cls, int connectivity, int fill, void* stream);
 
+/* Surface distances between one class of a predicted mask and of its target (what HD, HD95 and ASSD are made of; csrc/surface_distance.hip).
+ * Every output is an integer that depends on neither the algorithm nor the schedule; the three floating-point metrics are a few lines on top
+ * (gdkvm_amd.ops.surface_metrics) and not part of this ABI.  Distances are in pixels of the masks' grid (isotropic pixels assumed).
+ * Per frame mask [H, W], target [H, W] uint8, class cls (0..254), H, W in 1..1024:
+ *   1. A = the pixels with mask[y][x] == cls, B = those with target[y][x] == cls; every other byte, 255 and every other class included, is
+ *      "not cls".
+ *   2. The SURFACE S(X) of a set X is its pixels with at least one of the four neighbours (x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1)
+ *      outside X.  A neighbour outside the frame is outside X.  Adjacency is geometric, as for gdkvm_largest_component: (W - 1, y) and
+ *      (0, y + 1) are no neighbours, nor are pixels of two frames.  (X minus its erosion by the 4-neighbour cross with a zero border.)
+ *   3. Directed squared distances, integers below 2^21:  for p in S(A)  d2_AB(p) = min over q in S(B) of (px - qx)^2 + (py - qy)^2;
+ *      for q in S(B)  d2_BA(q) likewise against S(A).
+ *   4. surf [frames, 8] int64 = nA = |S(A)|, nB = |S(B)|, hAB = max d2_AB, hBA = max d2_BA, sAB = sum over S(A) of isqrt(d2_AB(p) 2^32),
+ *      sBA likewise, q_lo, q_hi.  isqrt(n) = floor(sqrt(n)): every term is a distance in units of 2^-16 pixel, rounded down.
+ *   5. With n = nA + nB, lo = floor(95 (n - 1) / 100) and hi = min(lo + 1, n - 1):  q_lo and q_hi are the values at the 0-based ranks lo and hi
+ *      of the ascending pooled multiset of all d2_AB and d2_BA (the two neighbours of the pooled 95th percentile with linear interpolation).
+ *   6. nA == 0 or nB == 0: the six other fields are 0 -- the frame has no surface distance.
+ * mask and target are [frames, H, W] contiguous at ANY byte address (frames of H W bytes follow each other); surf is 16-byte aligned.  The
+ * workspace (16-byte aligned, at least gdkvm_surface_distance_workspace_bytes(frames, H, W) bytes) is scratch: 0 while H W <= 14336 -- a
+ * frame's 4.5 bytes per pixel (one 32-bit word per pixel and four bitmaps) then live in 63 KiB of LDS, which covers the 112 x 112 mask of
+ * cfg2 -- else those 4.5 bytes per pixel with each frame's slice rounded up to 128 bytes.  One workgroup per frame; neither entry allocates
+ * or synchronises; bit-reproducible; every loop of the kernel is bounded by H, W, H W or a constant.  Bad arguments (shape, cls, null or
+ * misaligned pointers, a short workspace) are GDKVM_ERR_SHAPE before any device call; frames == 0 is GDKVM_OK without a launch. */
+size_t gdkvm_surface_distance_workspace_bytes(int frames, int H, int W);
+int gdkvm_surface_distance(const uint8_t* mask, const uint8_t* target, int64_t* surf, void* workspace, size_t workspace_bytes,
+                           int frames, int H, int W, int cls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What the LV measurement and the largest-component filter in front of it cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt).
+"""What the LV measurement, the largest-component filter in front of it and the surface distances cost (profiles/r10_a_lv_probe.txt,
+profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt).
 python3 tools/lv_probe.py [--quick] [--no-eval]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
@@ -10,9 +11,12 @@ python3 tools/lv_probe.py [--quick] [--no-eval]
     about a tenth of it (a ventricle); every pixel of the class (the worst case for the per-pixel passes); no pixel of the class.  The floor is
     the bytes read (and, for the mask kernel, written) once over the 6.3 TB/s achievable HBM rate.  gdkvm_largest_component (class 1,
     4-connected, fill 0, out of place, with a target) runs in the same windows on the same three fills, the ellipses with three islands each
-    (discs of radius 1 to 5 % of the side; the kernel removes them), and at 8-connectivity on the first.
+    (discs of radius 1 to 5 % of the side; the kernel removes them), and at 8-connectivity on the first.  gdkvm_surface_distance (class 1)
+    runs in the same windows: ellipse against the next input's ellipse (a prediction close to its target), the ellipse with islands against
+    it, a checkerboard against a one-pixel-shifted checkerboard (every pixel of the class is surface) and against the ellipse (every row
+    walk of the ellipse's surface ends at once, every walk of the checkerboard's is as long as the ellipse is far), and an empty class.
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
-    data.lv_keep_largest=4 on top of it, and with data.lv_class=-1, alternated, twice each."""
+    data.lv_keep_largest=4 on top of it, with data.surface_class=1 instead, and with data.lv_class=-1, alternated, twice each."""
 import math
 import os
 import statistics
@@ -70,6 +74,10 @@ def part_a(dev, F, S, reps, n_in=4):
     cc_info = torch.empty((F, 8), dtype=torch.int32, device=dev)
     cc_ws = torch.empty(max(16, int(lib.gdkvm_largest_component_workspace_bytes(F, S, S))), dtype=torch.uint8, device=dev)
     full = torch.ones((F, S, S), dtype=torch.uint8, device=dev)
+    board = ((torch.arange(S, device=dev)[:, None] + torch.arange(S, device=dev)[None, :]) % 2 == 0).to(torch.uint8).expand(F, S, S).contiguous()
+    board_shifted = (1 - board).contiguous()
+    sd_out = torch.empty((F, 8), dtype=torch.int64, device=dev)
+    sd_ws = torch.empty(max(16, int(lib.gdkvm_surface_distance_workspace_bytes(F, S, S))), dtype=torch.uint8, device=dev)
     logits = [torch.randn((F, 2, S // 4, S // 4), generator=g).to(dev).bfloat16() for _ in range(n_in)]
     m_out = torch.empty((F, S, S), dtype=torch.uint8, device=dev)
     c_out = torch.empty((F, 2, 3), dtype=torch.int32, device=dev)
@@ -84,6 +92,10 @@ def part_a(dev, F, S, reps, n_in=4):
     def cc(mask, target, cls, conn=4):
         rc = lib.gdkvm_largest_component(mask.data_ptr(), target.data_ptr(), cc_out.data_ptr(), cc_info.data_ptr(), cc_ws.data_ptr(), cc_ws.numel(),
                                          F, S, S, cls, conn, 0, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def sd(mask, target, cls):
+        rc = lib.gdkvm_surface_distance(mask.data_ptr(), target.data_ptr(), sd_out.data_ptr(), sd_ws.data_ptr(), sd_ws.numel(), F, S, S, cls, st)
         assert rc == 0, lib.gdkvm_last_error()
 
     def up(i):
@@ -102,12 +114,23 @@ def part_a(dev, F, S, reps, n_in=4):
         "largest_component, ellipse alone (a copy)": (lambda i: cc(masks[i], masks[i], 1), 2 * F * S * S),
         "largest_component, every pixel of the class": (lambda i: cc(full, masks[i], 1), 2 * F * S * S),
         "largest_component, no pixel of the class": (lambda i: cc(full, masks[i], 2), 2 * F * S * S),
+        "surface_distance, ellipse against ellipse": (lambda i: sd(masks[i], masks[(i + 1) % n_in], 1), 2 * F * S * S),
+        "surface_distance, ellipse + 3 islands against it": (lambda i: sd(isl[i], masks[i], 1), 2 * F * S * S),
+        "surface_distance, checkerboard against shifted": (lambda i: sd(board, board_shifted, 1), 2 * F * S * S),
+        "surface_distance, checkerboard against ellipse": (lambda i: sd(board, masks[i], 1), 2 * F * S * S),
+        "surface_distance, no pixel of the class": (lambda i: sd(full, masks[i], 2), 2 * F * S * S),
     }
     cc(isl[0], masks[0], 1)
     torch.cuda.synchronize()
     removed = (cc_info[:, 1] - cc_info[:, 2]).float()
     print(f"    (islands: {float(cc_info[:, 0].float().mean()):.2f} components per frame, {float(removed.mean()):.0f} of {float(cc_info[:, 1].float().mean()):.0f} "
           f"pixels removed; label words in {'LDS' if cc_ws.numel() == 16 else 'the workspace, ' + str(cc_ws.numel() >> 20) + ' MiB'})")
+    sd(masks[0], masks[1], 1)
+    torch.cuda.synchronize()
+    met, ok = ops.surface_metrics(sd_out)
+    print(f"    (ellipse against ellipse: {float(sd_out[:, :2].float().mean()):.0f} surface pixels per set, mean HD {float(met[:, 0].mean()):.2f}, HD95 "
+          f"{float(met[:, 1].mean()):.2f}, ASSD {float(met[:, 2].mean()):.2f} pixels over {int(ok.sum())} frames; the frame's words in "
+          f"{'LDS' if sd_ws.numel() == 16 else 'the workspace, ' + str(sd_ws.numel() >> 20) + ' MiB'})")
     times = {name: [] for name in forms}
     for r in range(reps + 3):
         for name, (fn, _) in forms.items():
@@ -130,14 +153,15 @@ def part_a(dev, F, S, reps, n_in=4):
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
-        for keys in (["data.lv_class=1", "data.lv_keep_largest=0"], ["data.lv_class=1", "data.lv_keep_largest=4"], ["data.lv_class=-1"]):
+        for keys in (["data.lv_class=1", "data.lv_keep_largest=0"], ["data.lv_class=1", "data.lv_keep_largest=4"],
+                     ["data.lv_class=1", "data.lv_keep_largest=0", "data.surface_class=1"], ["data.lv_class=-1"]):
             t0 = time.perf_counter()
             out = subprocess.run([sys.executable, os.path.join(ROOT, "eval.py")] + keys + overrides, capture_output=True, text=True, timeout=600)
             dt = time.perf_counter() - t0
             if out.returncode != 0:
                 print(out.stderr[-2000:])
                 raise SystemExit(f"eval.py failed with {' '.join(keys)}")
-            print(f"  run {run + 1} {' '.join(keys):44s}: {dt:6.2f} s   {out.stdout.strip().splitlines()[-1]}", flush=True)
+            print(f"  run {run + 1} {' '.join(keys):66s}: {dt:6.2f} s   {out.stdout.strip().splitlines()[-1]}", flush=True)
 
 
 def main():
