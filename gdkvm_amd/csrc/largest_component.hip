@@ -18,7 +18,7 @@
 // link succeeded), so it ends within H*W retries.  Both loops count to H*W and, should that ever be reached, raise the frame's failure flag:
 // components = -1 and out = mask, rather than spinning.
 
-#include "gdkvm_device.hpp"
+#include "mask_frame.hpp"
 
 namespace {
 
@@ -33,15 +33,10 @@ struct CcArgs {
     int HW, W, stride, cls, fill, conn;
 };
 
-// The label words.  LDS: workgroup-scope relaxed atomics are plain ds instructions; workspace: agent scope, so loads and stores go to L2.
+// The label words, and what passes 3 and 5 make of one
 template <bool LDS>
-struct Labels {
-    unsigned* w;
-    static constexpr int SCOPE = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
-    __device__ __forceinline__ unsigned ld(unsigned i) const { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, SCOPE); }
-    __device__ __forceinline__ void st(unsigned i, unsigned v) const { __hip_atomic_store(w + i, v, __ATOMIC_RELAXED, SCOPE); }
-    __device__ __forceinline__ unsigned amin(unsigned i, unsigned v) const { return __hip_atomic_fetch_min(w + i, v, __ATOMIC_RELAXED, SCOPE); }
-    __device__ __forceinline__ void aadd(unsigned i, unsigned v) const { __hip_atomic_fetch_add(w + i, v, __ATOMIC_RELAXED, SCOPE); }
+struct Labels : FrameWords<LDS, unsigned> {
+    using FrameWords<LDS, unsigned>::ld;
     __device__ __forceinline__ bool in(unsigned i) const { return ld(i) != CC_NONE; }
     // the label of pixel p of the class, from pass 5 on
     __device__ __forceinline__ unsigned root(unsigned p) const { const unsigned v = ld(p); return (v & CC_ROOT) ? p : v; }
@@ -74,75 +69,6 @@ __device__ __forceinline__ void cc_unite(const Labels<LDS>& L, unsigned a, unsig
     fail = true;
 }
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// bit e = byte e of the vector equals cls
-__device__ __forceinline__ unsigned match16(const uint4& v, unsigned cls)
-{
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    unsigned m = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m |= (((w[q] >> (8 * e)) & 0xffu) == cls ? 1u : 0u) << (4 * q + e);
-    return m;
-}
-
-// f(p, x, y) for every set bit of m in ascending order; bit e is pixel p0 + e of the frame (row-major, rows of W)
-template <class F>
-__device__ __forceinline__ void visit_xy(unsigned m, int p0, int W, F&& f)
-{
-    if (!m) return;
-    int y = p0 / W, x = p0 - y * W, prev = 0;
-    while (m) {
-        const int e = __builtin_ctz(m);
-        m &= m - 1;
-        x += e - prev;
-        prev = e;
-        while (x >= W) { x -= W; ++y; }
-        f(p0 + e, x, y);
-    }
-}
-template <class F>
-__device__ __forceinline__ void visit_p(unsigned m, int p0, F&& f)
-{
-    while (m) {
-        const int e = __builtin_ctz(m);
-        m &= m - 1;
-        f(p0 + e);
-    }
-}
-
-// A frame at any byte address: up to 15 head bytes (lane t owns byte t), 16-byte vectors (lane t of NT owns vectors t, t + NT, ...), up to
-// 15 tail bytes.  A lane meets its pixels in ascending order.
-template <int NT>
-struct Frame {
-    const uint8_t* base; const uint4* body;
-    int head, nvec, tail, W;
-    unsigned cls;
-    template <class F>
-    __device__ __forceinline__ void sweep_xy(F&& f) const
-    {
-        const int tid = threadIdx.x;
-        if (tid < head && base[tid] == cls) visit_xy(1u, tid, W, f);
-        for (int v = tid; v < nvec; v += NT) visit_xy(match16(body[v], cls), head + 16 * v, W, f);
-        if (tid < tail && base[head + 16 * nvec + tid] == cls) visit_xy(1u, head + 16 * nvec + tid, W, f);
-    }
-    template <class F>
-    __device__ __forceinline__ void sweep_p(F&& f) const
-    {
-        const int tid = threadIdx.x;
-        if (tid < head && base[tid] == cls) f(tid);
-        for (int v = tid; v < nvec; v += NT) visit_p(match16(body[v], cls), head + 16 * v, f);
-        if (tid < tail && base[head + 16 * nvec + tid] == cls) f(head + 16 * nvec + tid);
-    }
-};
-
 template <bool LDS, int NT>
 __global__ __launch_bounds__(NT) void largest_component_kernel(CcArgs a)
 {
@@ -157,26 +83,26 @@ __global__ __launch_bounds__(NT) void largest_component_kernel(CcArgs a)
     const uint8_t* tgt = a.target ? a.target + f * (size_t)HW : nullptr;
     uint8_t* outb = a.out + f * (size_t)HW;
     int32_t* info = a.info + f * 8;
-    Frame<NT> fr;
+    // (MaskFrame's constructor written out: the constructor's tail, (HW - head) & 15, is other code than this kernel was measured with)
+    MaskFrame<NT> fr;
     fr.base = base; fr.W = W; fr.cls = cls;
     fr.head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u);
     if (fr.head > HW) fr.head = HW;
     fr.nvec = (HW - fr.head) >> 4;
+    fr.nbody = 16 * fr.nvec;
     fr.tail = HW - fr.head - 16 * fr.nvec;
     fr.body = reinterpret_cast<const uint4*>(base + fr.head);
     uint4* lab4;
     if constexpr (LDS) lab4 = s_lab;
     else lab4 = reinterpret_cast<uint4*>(a.ws + f * (size_t)a.stride);
-    const Labels<LDS> L{reinterpret_cast<unsigned*>(lab4)};
+    const Labels<LDS> L{{reinterpret_cast<unsigned*>(lab4)}};
     if (tid == 0) s_fail = 0;
 
     // pass 1: n
     int n;
     {
         int c = 0;
-        if (tid < fr.head && base[tid] == cls) ++c;
-        for (int v = tid; v < fr.nvec; v += NT) c += __builtin_popcount(match16(fr.body[v], cls));
-        if (tid < fr.tail && base[fr.head + 16 * fr.nvec + tid] == cls) ++c;
+        fr.sweep_bits([&](unsigned m, int) { c += __builtin_popcount(m); });
         c = wave_sum(c);
         if (lane == 0) s_n[wv] = c;
         __syncthreads();
@@ -282,7 +208,7 @@ __global__ __launch_bounds__(NT) void largest_component_kernel(CcArgs a)
             });
             c = wave_sum(c);
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
+            for (int o = 32; o > 0; o >>= 1) {             // (not wave_max: through the helper this pass schedules differently)
                 const u64 w = (u64)__shfl_xor((long long)best, o);
                 best = w > best ? w : best;
             }
@@ -338,7 +264,7 @@ __global__ __launch_bounds__(NT) void largest_component_kernel(CcArgs a)
                 }
                 obody[v] = make_uint4(w[0], w[1], w[2], w[3]);
             }
-            if (tid < fr.tail) byte_at(fr.head + 16 * fr.nvec + tid);
+            if (tid < fr.tail) byte_at(fr.head + fr.nbody + tid);
         } else {
             for (int p = tid; p < HW; p += NT) {
                 unsigned b = base[p];
@@ -365,35 +291,31 @@ __global__ __launch_bounds__(NT) void largest_component_kernel(CcArgs a)
 
 // label words per frame in the workspace: H*W rounded up to whole 16-byte vectors
 inline size_t cc_stride(int H, int W) { return ((size_t)H * (size_t)W + 3) & ~(size_t)3; }
-inline bool cc_shape_ok(int frames, int H, int W) { return frames >= 0 && H >= 1 && H <= 1024 && W >= 1 && W <= 1024; }
 
 }  // namespace
 
 extern "C" size_t gdkvm_largest_component_workspace_bytes(int frames, int H, int W)
 {
-    if (!cc_shape_ok(frames, H, W) || H * W <= CC_LDS_PIX) return 0;
+    if (!mask_shape_ok(frames, H, W) || H * W <= CC_LDS_PIX) return 0;
     return (size_t)frames * cc_stride(H, W) * sizeof(unsigned);
 }
 
 extern "C" int gdkvm_largest_component(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, void* workspace,
                                        size_t workspace_bytes, int frames, int H, int W, int cls, int connectivity, int fill, void* stream)
 {
-    if (!cc_shape_ok(frames, H, W))
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: bad shape frames=%d H=%d W=%d (H, W in 1..1024)", frames, H, W);
-    if (cls < 0 || cls > 254) return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: cls=%d outside 0..254", cls);
+    if (int rc = mask_check_shape("largest_component", frames, H, W)) return rc;
+    if (int rc = mask_check_cls("largest_component", GDKVM_ERR_SHAPE, cls)) return rc;
     if (connectivity != 4 && connectivity != 8) return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: connectivity=%d is neither 4 nor 8", connectivity);
     if (fill < 0 || fill > 255 || fill == cls)
         return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: fill=%d must lie in 0..255 and differ from cls=%d", fill, cls);
     if (frames == 0) return GDKVM_OK;
     if (!mask || !out || !info) return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: null pointer (mask, out and info are required)");
-    if (!gdkvm_aligned16(info)) return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: info must be 16-byte aligned");
+    if (int rc = mask_check_aligned16("largest_component", GDKVM_ERR_SHAPE, "info", {info})) return rc;
     const size_t total = (size_t)frames * (size_t)H * (size_t)W;
     if (out != mask && out < mask + total && mask < out + total)
         return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: out must be mask itself (in place) or not overlap it");
     const size_t need = gdkvm_largest_component_workspace_bytes(frames, H, W);
-    if (need && (!workspace || workspace_bytes < need || !gdkvm_aligned16(workspace)))
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "largest_component: frames of %d x %d need a 16-byte aligned workspace of %zu bytes, got %zu", H, W, need,
-                          workspace ? workspace_bytes : (size_t)0);
+    if (int rc = mask_check_workspace("largest_component", H, W, need, workspace, workspace_bytes)) return rc;
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     CcArgs a{mask, target, out, info, static_cast<unsigned*>(workspace), H * W, W, (int)cc_stride(H, W), cls, fill, connectivity};

@@ -6,7 +6,7 @@
 // in front of integers (the axis, fp64) is evaluated by every lane from the same totals with explicitly un-fused multiplies and adds.
 // ONE 256-lane workgroup per frame: no cross-workgroup reduction, no global atomics, no fences.
 
-#include "gdkvm_common.hpp"
+#include "mask_frame.hpp"
 
 // No fused multiply-add in this file's own arithmetic: the fp64 steps are the definition's operations, one rounding each.  The pragma is what
 // does it -- HIP's own _rn intrinsics are inline functions compiled with contraction allowed, and a product from one still fuses into a sum
@@ -31,67 +31,21 @@ struct LvArgs {
     int HW, W, cls, D;
 };
 
-__device__ __forceinline__ i64 wave_sum(i64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ i64 wave_min(i64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const i64 w = __shfl_xor(v, o); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ i64 wave_max(i64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const i64 w = __shfl_xor(v, o); v = w > v ? w : v; }
-    return v;
-}
-
-// bit e = byte e of the vector equals cls
-__device__ __forceinline__ unsigned match16(const uint4& v, unsigned cls)
-{
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    unsigned m = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m |= (((w[q] >> (8 * e)) & 0xffu) == cls ? 1u : 0u) << (4 * q + e);
-    return m;
-}
-
-// f(x, y) for every set bit of m; bit e is pixel p + e of the frame (row-major, rows of W)
-template <class F>
-__device__ __forceinline__ void visit(unsigned m, int p, int W, F&& f)
-{
-    if (!m) return;
-    int y = p / W, x = p - y * W, prev = 0;
-    while (m) {
-        const int e = __builtin_ctz(m);
-        m &= m - 1;
-        x += e - prev;
-        prev = e;
-        while (x >= W) { x -= W; ++y; }
-        f(x, y);
-    }
-}
-
 // One pass over the frame's pixels of the class.  RES: the match bits of the lane's vectors are in registers (mk, filled by the first pass);
 // otherwise the vectors are read again (the frame is L2-hot).  edge: bit 0 = the lane's head byte matches, bit 1 = its tail byte.
+// f(p, x, y) per pixel; the callbacks of this file use the coordinates only.
 template <bool RES, class F>
-__device__ __forceinline__ void sweep(const unsigned (&mk)[LV_RES], const uint4* body, int nvec, int head, int W, unsigned cls, unsigned edge, F&& f)
+__device__ __forceinline__ void sweep(const unsigned (&mk)[LV_RES], const MaskFrame<256>& fr, unsigned edge, F&& f)
 {
-    const int tid = threadIdx.x;
-    if (edge & 1u) visit(1u, tid, W, f);
+    const int tid = threadIdx.x, head = fr.head, W = fr.W;
+    if (edge & 1u) visit_xy(1u, tid, W, f);
     if constexpr (RES) {
 #pragma unroll
-        for (int k = 0; k < LV_RES; ++k) visit(mk[k], head + 16 * (tid + 256 * k), W, f);
+        for (int k = 0; k < LV_RES; ++k) visit_xy(mk[k], head + 16 * (tid + 256 * k), W, f);
     } else {
-        for (int v = tid; v < nvec; v += 256) visit(match16(body[v], cls), head + 16 * v, W, f);
+        for (int v = tid; v < fr.nvec; v += 256) visit_xy(match16(fr.body[v], fr.cls), head + 16 * v, W, f);
     }
-    if (edge & 2u) visit(1u, head + 16 * nvec + tid, W, f);
+    if (edge & 2u) visit_xy(1u, head + fr.nbody + tid, W, f);
 }
 
 template <bool RES>
@@ -104,23 +58,19 @@ __global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
     const size_t f = blockIdx.x;
     const unsigned cls = (unsigned)a.cls;
     const uint8_t* base = a.mask + f * (size_t)HW;
-    // a frame's base address is arbitrary (H*W need not be a multiple of 16): up to 15 head bytes, 16-byte vectors, up to 15 tail bytes
-    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u);
-    if (head > HW) head = HW;
-    const int nvec = (HW - head) >> 4, tail = HW - head - 16 * nvec;
-    const uint4* body = reinterpret_cast<const uint4*>(base + head);
+    const MaskFrame<256> fr(base, HW, W, cls);
     if (tid < LV_MAX_D) s_w[tid] = 0;
 
     unsigned edge = 0;
-    if (tid < head && base[tid] == cls) edge |= 1u;
-    if (tid < tail && base[head + 16 * nvec + tid] == cls) edge |= 2u;
+    if (tid < fr.head && base[tid] == cls) edge |= 1u;
+    if (tid < fr.tail && base[fr.head + fr.nbody + tid] == cls) edge |= 2u;
     unsigned mk[LV_RES];
     if constexpr (RES) {
         uint4 r[LV_RES];
 #pragma unroll
         for (int k = 0; k < LV_RES; ++k) {
             const int v = tid + 256 * k;
-            r[k] = v < nvec ? body[v] : make_uint4(~0u, ~0u, ~0u, ~0u);      // 255 is no class (cls <= 254)
+            r[k] = v < fr.nvec ? fr.body[v] : make_uint4(~0u, ~0u, ~0u, ~0u);      // 255 is no class (cls <= 254)
         }
 #pragma unroll
         for (int k = 0; k < LV_RES; ++k) mk[k] = match16(r[k], cls);
@@ -129,7 +79,7 @@ __global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
     // pass 1: moments.  A lane sees at most 4096 + 2 pixels of coordinates below 1024: n, sx, sy fit 32 bits, the second moments need 64
     unsigned n32 = 0, sx32 = 0, sy32 = 0;
     u64 sxx = 0, sxy = 0, syy = 0;
-    sweep<RES>(mk, body, nvec, head, W, cls, edge, [&](int x, int y) {
+    sweep<RES>(mk, fr, edge, [&](int, int x, int y) {
         ++n32; sx32 += (unsigned)x; sy32 += (unsigned)y;
         sxx += (unsigned)(x * x); sxy += (unsigned)(x * y); syy += (unsigned)(y * y);
     });
@@ -144,7 +94,7 @@ __global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
     __syncthreads();
     i64 tot[6];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) tot[i] = s_red[0][i] + s_red[1][i] + s_red[2][i] + s_red[3][i];
+    for (int i = 0; i < 6; ++i) tot[i] = wg_sum(s_red, i);
     const i64 n = tot[0], sx = tot[1], sy = tot[2];
     i64* st = a.stats + f * 12;
     i64* dk = a.disks + f * (size_t)D;
@@ -173,7 +123,7 @@ __global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
     const int n_i = (int)n, sx_i = (int)sx, sy_i = (int)sy;
     auto proj = [&](int x, int y) -> i64 { return (i64)(n_i * x - sx_i) * Ux + (i64)(n_i * y - sy_i) * Uy; };
     i64 tmin = 0x7fffffffffffffffLL, tmax = -0x7fffffffffffffffLL - 1;
-    sweep<RES>(mk, body, nvec, head, W, cls, edge, [&](int x, int y) {
+    sweep<RES>(mk, fr, edge, [&](int, int x, int y) {
         const i64 t = proj(x, y);
         tmin = t < tmin ? t : tmin;
         tmax = t > tmax ? t : tmax;
@@ -191,7 +141,7 @@ __global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
     // pass 4: pixel p covers [D (t_p - tmin), + D P1), disk j covers [j Lt, (j + 1) Lt): W_j = sum of the overlaps
     const i64 P1 = n * LV_Q, Lt = tmax - tmin + P1, DP1 = (i64)D * P1;
     const double inv_lt = 1.0 / (double)Lt;
-    sweep<RES>(mk, body, nvec, head, W, cls, edge, [&](int x, int y) {
+    sweep<RES>(mk, fr, edge, [&](int, int x, int y) {
         const i64 lo = (i64)D * (proj(x, y) - tmin), hi = lo + DP1;
         int j = (int)((double)lo * inv_lt);                // floor(lo / Lt) up to rounding, made exact below
         j = j < 0 ? 0 : (j > D - 1 ? D - 1 : j);
@@ -274,14 +224,12 @@ __global__ __launch_bounds__(64) void lv_ef_kernel(EfArgs a)
 extern "C" int gdkvm_lv_measure(const uint8_t* mask, int64_t* stats, int64_t* disks, double* geom,
                                 int frames, int H, int W, int cls, int D, void* stream)
 {
-    if (frames < 0 || H < 1 || H > 1024 || W < 1 || W > 1024)
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "lv_measure: bad shape frames=%d H=%d W=%d (H, W in 1..1024)", frames, H, W);
+    if (int rc = mask_check_shape("lv_measure", frames, H, W)) return rc;
     if (D < 1 || D > LV_MAX_D) return gdkvm_fail(GDKVM_ERR_SHAPE, "lv_measure: D=%d outside 1..%d", D, LV_MAX_D);
-    if (cls < 0 || cls > 254) return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure: cls=%d outside 0..254", cls);
+    if (int rc = mask_check_cls("lv_measure", GDKVM_ERR_ARG, cls)) return rc;
     if (frames == 0) return GDKVM_OK;
     if (!mask || !stats || !disks || !geom) return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure: null pointer");
-    if (!gdkvm_aligned16(stats) || !gdkvm_aligned16(disks) || !gdkvm_aligned16(geom))
-        return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure: outputs must be 16-byte aligned");
+    if (int rc = mask_check_aligned16("lv_measure", GDKVM_ERR_ARG, "outputs", {stats, disks, geom})) return rc;
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     LvArgs a{mask, reinterpret_cast<i64*>(stats), reinterpret_cast<i64*>(disks), geom, H * W, W, cls, D};

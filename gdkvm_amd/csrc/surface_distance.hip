@@ -20,7 +20,7 @@
 //   6. the two ranks by bisection on the value: each step is one workgroup-wide count of d2 <= m over the words, 16 bytes per lane and read.
 // Loop bounds: the sweeps count to H, the walks to W, the strided loops to H W / lanes, the bisection to 21 (d2 < 2^21).
 
-#include "gdkvm_device.hpp"
+#include "mask_frame.hpp"
 
 namespace {
 
@@ -41,54 +41,13 @@ struct SdArgs {
 __host__ __device__ inline int sd_plane_words(int HW) { return (HW + 3) & ~3; }
 __host__ __device__ inline int sd_bitmap_words(int HW) { return (((HW + 31) >> 5) + 3) & ~3; }
 
-// The frame's words.  LDS: workgroup-scope relaxed atomics are plain ds instructions; workspace: agent scope, so loads and stores go to L2.
+// The frame's words, and the bitmaps among them
 template <bool LDS>
-struct Words {
-    unsigned* w;
-    static constexpr int SCOPE = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
-    __device__ __forceinline__ unsigned ld(int i) const { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, SCOPE); }
-    __device__ __forceinline__ void st(int i, unsigned v) const { __hip_atomic_store(w + i, v, __ATOMIC_RELAXED, SCOPE); }
-    __device__ __forceinline__ void aor(int i, unsigned v) const { __hip_atomic_fetch_or(w + i, v, __ATOMIC_RELAXED, SCOPE); }
+struct Words : FrameWords<LDS, int> {
+    using FrameWords<LDS, int>::ld;
     // bit p of the bitmap that starts at word `bm`
     __device__ __forceinline__ bool bit(int bm, int p) const { return (ld(bm + (p >> 5)) >> (p & 31)) & 1u; }
 };
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned w = __shfl_xor(v, o); v = w > v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_min(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned w = __shfl_xor(v, o); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o);
-    return v;
-}
-
-// bit e = byte e of the vector equals cls
-__device__ __forceinline__ unsigned match16(const uint4& v, unsigned cls)
-{
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    unsigned m = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m |= (((w[q] >> (8 * e)) & 0xffu) == cls ? 1u : 0u) << (4 * q + e);
-    return m;
-}
 
 // floor(sqrt(d2 * 2^32)): the operand is below 2^53, so the fp64 estimate is off by at most one either way
 __device__ __forceinline__ u64 isqrt_q32(unsigned d2)
@@ -100,25 +59,16 @@ __device__ __forceinline__ u64 isqrt_q32(unsigned d2)
     return r;
 }
 
-// Pass 2 for one frame of bytes at any address: up to 15 head bytes (lane t owns byte t), 16-byte vectors (lane t of NT owns vectors t,
-// t + NT, ...), up to 15 tail bytes.  Bits m of pixels p0 .. p0 + 15 are OR-ed into the bitmap at word bm.
+// Pass 2 for one frame of bytes at any address: bits m of pixels p0 .. p0 + 15 are OR-ed into the bitmap at word bm.
 template <bool LDS, int NT>
-__device__ __forceinline__ void class_bitmap(const Words<LDS>& M, int bm, const uint8_t* base, int HW, unsigned cls)
+__device__ __forceinline__ void class_bitmap(const Words<LDS>& M, int bm, const uint8_t* base, int HW, int W, unsigned cls)
 {
-    const int tid = threadIdx.x;
-    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u);
-    if (head > HW) head = HW;
-    const int nvec = (HW - head) >> 4, tail = HW - head - 16 * nvec;
-    const uint4* body = reinterpret_cast<const uint4*>(base + head);
-    auto put = [&](unsigned m, int p0) {
+    MaskFrame<NT>(base, HW, W, cls).sweep_bits([&](unsigned m, int p0) {
         if (!m) return;
         const int s = p0 & 31;
         M.aor(bm + (p0 >> 5), m << s);
         if (s > 16 && (m >> (32 - s))) M.aor(bm + (p0 >> 5) + 1, m >> (32 - s));
-    };
-    if (tid < head && base[tid] == cls) put(1u, tid);
-    for (int v = tid; v < nvec; v += NT) put(match16(body[v], cls), head + 16 * v);
-    if (tid < tail && base[head + 16 * nvec + tid] == cls) put(1u, head + 16 * nvec + tid);
+    });
 }
 
 // Pass 3 for one set: surface word i from the set's bitmap at `bx` into the bitmap at `bs`; returns the lane's count of surface pixels
@@ -132,7 +82,7 @@ __device__ __forceinline__ unsigned surface_bitmap(const Words<LDS>& M, int bx, 
         if (m) {
             const int p0 = 32 * i;
             int y = p0 / W, x = p0 - y * W, prev = 0;
-            while (m) {                                    // (at most 32 turns)
+            while (m) {                                    // (visit_xy written out: through the helper the registers are allocated differently)
                 const int e = __builtin_ctz(m);
                 m &= m - 1;
                 x += e - prev;
@@ -215,8 +165,8 @@ __global__ __launch_bounds__(NT) void surface_distance_kernel(SdArgs a)
     // pass 1, 2: the bitmaps
     for (int i = tid; i < 4 * BW; i += NT) M.st(PW + i, 0u);
     __syncthreads();
-    class_bitmap<LDS, NT>(M, bA, a.mask + f * (size_t)HW, HW, cls);
-    class_bitmap<LDS, NT>(M, bB, a.target + f * (size_t)HW, HW, cls);
+    class_bitmap<LDS, NT>(M, bA, a.mask + f * (size_t)HW, HW, W, cls);
+    class_bitmap<LDS, NT>(M, bB, a.target + f * (size_t)HW, HW, W, cls);
     __syncthreads();
 
     // pass 3: the surfaces and their sizes
@@ -258,7 +208,7 @@ __global__ __launch_bounds__(NT) void surface_distance_kernel(SdArgs a)
             M.st(p, v);
         }
         hAB = wave_max(hAB); hBA = wave_max(hBA);
-        sAB = wave_sum64(sAB); sBA = wave_sum64(sBA);
+        sAB = wave_sum(sAB); sBA = wave_sum(sBA);
         if (lane == 0) { s_u[1][wv][0] = hAB; s_u[1][wv][1] = hBA; s_s[wv][0] = sAB; s_s[wv][1] = sBA; }
         __syncthreads();
         hAB = hBA = 0;
@@ -325,29 +275,25 @@ __global__ __launch_bounds__(NT) void surface_distance_kernel(SdArgs a)
 
 // words per frame in the workspace: the frame's words rounded up to 128 bytes, so that no two frames share a cache line
 inline size_t sd_stride(int H, int W) { return ((size_t)sd_plane_words(H * W) + 4 * (size_t)sd_bitmap_words(H * W) + 31) & ~(size_t)31; }
-inline bool sd_shape_ok(int frames, int H, int W) { return frames >= 0 && H >= 1 && H <= 1024 && W >= 1 && W <= 1024; }
 
 }  // namespace
 
 extern "C" size_t gdkvm_surface_distance_workspace_bytes(int frames, int H, int W)
 {
-    if (!sd_shape_ok(frames, H, W) || H * W <= SD_LDS_PIX) return 0;
+    if (!mask_shape_ok(frames, H, W) || H * W <= SD_LDS_PIX) return 0;
     return (size_t)frames * sd_stride(H, W) * sizeof(unsigned);
 }
 
 extern "C" int gdkvm_surface_distance(const uint8_t* mask, const uint8_t* target, int64_t* surf, void* workspace, size_t workspace_bytes,
                                       int frames, int H, int W, int cls, void* stream)
 {
-    if (!sd_shape_ok(frames, H, W))
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance: bad shape frames=%d H=%d W=%d (H, W in 1..1024)", frames, H, W);
-    if (cls < 0 || cls > 254) return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance: cls=%d outside 0..254", cls);
+    if (int rc = mask_check_shape("surface_distance", frames, H, W)) return rc;
+    if (int rc = mask_check_cls("surface_distance", GDKVM_ERR_SHAPE, cls)) return rc;
     if (frames == 0) return GDKVM_OK;
     if (!mask || !target || !surf) return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance: null pointer (mask, target and surf are required)");
-    if (!gdkvm_aligned16(surf)) return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance: surf must be 16-byte aligned");
+    if (int rc = mask_check_aligned16("surface_distance", GDKVM_ERR_SHAPE, "surf", {surf})) return rc;
     const size_t need = gdkvm_surface_distance_workspace_bytes(frames, H, W);
-    if (need && (!workspace || workspace_bytes < need || !gdkvm_aligned16(workspace)))
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance: frames of %d x %d need a 16-byte aligned workspace of %zu bytes, got %zu", H, W, need,
-                          workspace ? workspace_bytes : (size_t)0);
+    if (int rc = mask_check_workspace("surface_distance", H, W, need, workspace, workspace_bytes)) return rc;
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     SdArgs a{mask, target, reinterpret_cast<i64*>(surf), static_cast<unsigned*>(workspace), H, W, H * W, (int)sd_stride(H, W), cls};

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from typing import Optional, Tuple
 
@@ -279,6 +280,23 @@ def _channels_last(what: str, *ts, dtype=None, shape: str = "[N,C,H,W]") -> None
 def _u8_target(target: Optional[torch.Tensor], BT: int, H: int, W: int) -> None:
     if target is not None and (target.dtype != torch.uint8 or tuple(target.shape) != (BT, H, W)):
         raise GdkvmError("target must be uint8 [BT,H,W]")
+
+
+def _mask_frames(what: str, mask: torch.Tensor, cls: int, **same):
+    """The per-frame mask kernels' common checks: mask uint8 [..., H, W] with sides in 1..LV_MAX_SIDE, cls in 0..254, and every tensor of
+    `same` (name=tensor; None passes) of mask's dtype and shape.  Returns (lead, frames, H, W): the leading shape and its product."""
+    if mask.dtype != torch.uint8 or mask.dim() < 2:
+        raise GdkvmError(f"{what}: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
+    H, W = mask.shape[-2:]
+    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
+        raise GdkvmError(f"{what}: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
+    if not 0 <= int(cls) <= 254:
+        raise GdkvmError(f"{what}: cls = {cls} outside 0..254")
+    for name, t in same.items():
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != tuple(mask.shape)):
+            raise GdkvmError(f"{what}: {name} must be uint8 {tuple(mask.shape)}, got {t.dtype} {tuple(t.shape)}")
+    lead = tuple(mask.shape[:-2])
+    return lead, math.prod(lead), H, W
 
 
 def _f32_vectors(what: str, c: int, *ts) -> None:
@@ -1893,20 +1911,10 @@ def lv_measure(mask: torch.Tensor, cls: int = 1, disks: int = 20):
     `disks` disks along it and the single-plane method-of-disks volume (definition: include/gdkvm.h; integer-exact up to the disk areas).
     Returns (stats int64 [..., 12] = n sx sy sxx sxy syy Ux Uy tmin tmax Lt 0, disks int64 [..., D], geom float64 [..., 4] = L V cx cy);
     lengths in pixels of the mask's grid, V in pixel^3.  The mask may start at any byte address."""
-    if mask.dtype != torch.uint8 or mask.dim() < 2:
-        raise GdkvmError(f"lv_measure: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
-    H, W = mask.shape[-2:]
-    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
-        raise GdkvmError(f"lv_measure: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
+    lead, frames, H, W = _mask_frames("lv_measure", mask, cls)
     if not 1 <= int(disks) <= LV_MAX_DISKS:
         raise GdkvmError(f"lv_measure: disks = {disks} outside 1..{LV_MAX_DISKS}")
-    if not 0 <= int(cls) <= 254:
-        raise GdkvmError(f"lv_measure: cls = {cls} outside 0..254")
     dev = _dev(mask)
-    lead = tuple(mask.shape[:-2])
-    frames = 1
-    for s in lead:
-        frames *= s
     stats = torch.empty(lead + (12,), dtype=torch.int64, device=dev)
     dk = torch.empty(lead + (int(disks),), dtype=torch.int64, device=dev)
     geom = torch.empty(lead + (4,), dtype=torch.float64, device=dev)
@@ -1965,25 +1973,12 @@ def largest_component(mask: torch.Tensor, cls: int = 1, connectivity: int = 4, f
     output is an exact integer).  Returns (out uint8 like mask, info int32 [..., 8] = components, n, n_kept, label_kept (-1: no pixel of the
     class), removed_hit_cls, removed_hit_fill, 0, 0); the two hit counts say what the removed pixels were in `target` (same shape; 0 without
     one), which is what counts_after_largest needs.  out=mask filters in place; mask, target and out may start at any byte address."""
-    if mask.dtype != torch.uint8 or mask.dim() < 2:
-        raise GdkvmError(f"largest_component: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
-    H, W = mask.shape[-2:]
-    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
-        raise GdkvmError(f"largest_component: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
-    if not 0 <= int(cls) <= 254:
-        raise GdkvmError(f"largest_component: cls = {cls} outside 0..254")
+    lead, frames, H, W = _mask_frames("largest_component", mask, cls, target=target, out=out)
     if int(connectivity) not in (4, 8):
         raise GdkvmError(f"largest_component: connectivity = {connectivity} is neither 4 nor 8")
     if not 0 <= int(fill) <= 255 or int(fill) == int(cls):
         raise GdkvmError(f"largest_component: fill = {fill} must lie in 0..255 and differ from cls = {cls}")
-    for name, t in (("target", target), ("out", out)):
-        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != tuple(mask.shape)):
-            raise GdkvmError(f"largest_component: {name} must be uint8 {tuple(mask.shape)}, got {t.dtype} {tuple(t.shape)}")
     dev = _dev(mask, target, out)
-    lead = tuple(mask.shape[:-2])
-    frames = 1
-    for s in lead:
-        frames *= s
     if out is None:
         out = torch.empty_like(mask)
     info = torch.empty(lead + (8,), dtype=torch.int32, device=dev)
@@ -2024,20 +2019,8 @@ def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> 
     target, the largest squared distance per direction, the per-direction sums of the distances in units of 2^-16 pixel (each rounded down)
     and the two squared distances that enclose the pooled 95th percentile; an empty surface leaves the six other fields 0.  surface_metrics
     turns it into HD, HD95 and ASSD.  mask and target may start at any byte address."""
-    if mask.dtype != torch.uint8 or mask.dim() < 2:
-        raise GdkvmError(f"surface_distance: mask must be uint8 [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
-    if target.dtype != torch.uint8 or tuple(target.shape) != tuple(mask.shape):
-        raise GdkvmError(f"surface_distance: target must be uint8 {tuple(mask.shape)}, got {target.dtype} {tuple(target.shape)}")
-    H, W = mask.shape[-2:]
-    if not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
-        raise GdkvmError(f"surface_distance: H = {H}, W = {W} outside 1..{LV_MAX_SIDE}")
-    if not 0 <= int(cls) <= 254:
-        raise GdkvmError(f"surface_distance: cls = {cls} outside 0..254")
+    lead, frames, H, W = _mask_frames("surface_distance", mask, cls, target=target)
     dev = _dev(mask, target)
-    lead = tuple(mask.shape[:-2])
-    frames = 1
-    for s in lead:
-        frames *= s
     surf = torch.empty(lead + (8,), dtype=torch.int64, device=dev)
     ws = _workspace("gdkvm_surface_distance_workspace_bytes", dev, frames, H, W, floor=16)
     _call("gdkvm_surface_distance", dev, mask, target, surf, _Ws(ws), frames, H, W, int(cls))
