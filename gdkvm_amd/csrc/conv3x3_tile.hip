@@ -17,7 +17,10 @@
 //     with weights packed in fragment order (gdkvm_conv3x3_pack_weights) such a load is one contiguous KiB;
 //   * weights are the A operand, so a lane ends with 4 consecutive output channels of one pixel -- 8 with the channel permutation
 //     ct_channel (16-byte stores / residual loads);
-//   * the same kernel computes the training-mode data gradient (weights packed flipped and transposed).
+//   * the same kernel computes the training-mode data gradient (weights packed flipped and transposed);
+//   * the UP form (gdkvm_conv_upcat_bias_act: the decoder's first convolutions) takes the first C1 input channels as the exact-2x bilinear
+//     enlargement of a low-resolution tensor and builds them in the band itself: the DMA brings the low-resolution rows into a staging
+//     area of LDS, and the chunk iteration expands them into its band buffer before it computes -- the enlarged tensor never exists.
 // Arithmetic: fp32 accumulation over the same 9 C products as a library convolution, one rounding after the epilogue.
 #include <atomic>
 #include "gdkvm_device.hpp"
@@ -46,6 +49,16 @@ struct ConvTileArgs {
     float inv_band, inv_bw, inv_tw, inv_w;   // 1 / (bh bw), 1 / bw, 1 / (th W), 1 / W: index arithmetic without integer division
     int perm;                                // K % 32 == 0: output channels permuted within groups of 32 (ct_channel)
 };
+// The UP form (conv3x3_upcat_kernel): x is lo [N, hl, wl, C1] with H = 2 hl, W = 2 wl, and the first C1 input channels are its bilinear
+// enlargement, built in the band from a staging area of LDS that holds the low-resolution rows a tile needs: per frame of the tile, nlr
+// rows from the tile's first source row on, 128 B (one chunk's channels) per pixel, no padding.
+struct ConvUpArgs : ConvTileArgs {
+    int hl, wl, nlr;                         // low-resolution map; staged rows per frame
+    int stage_px, nstage;                    // fpt nlr wl staged pixels, in nstage 1 KiB DMA pieces (8 pixels each)
+    int stage_off;                           // LDS byte offset of the staging area (behind the two bands and the dump slot)
+    int nrp;                                 // row pairs 2 ip + 1, 2 ip + 2 that cover a band's bh rows: bh / 2 + 1
+    float inv_slr, inv_wl, inv_ncp, inv_nrp; // 1 / (nlr wl), 1 / wl, 1 / (wl + 1), 1 / nrp
+};
 
 // Row j of the 16-channel output tile kt is output channel ct_channel(kt, j).  With K a multiple of 32 the two tiles of a
 // 32-channel group interleave in fours, so that the accumulator rows 4g .. 4g+3 of BOTH tiles of a wave are 8 consecutive
@@ -64,11 +77,13 @@ __host__ __device__ __forceinline__ int ct_channel(int kt, int j, int perm)
 // NWV = 4, MAXMT = 7 (round 4 experiment, variant 4): FOUR waves per workgroup, each with the SAME work as a wave of <4, 2> (seven pixel
 // tiles x two channel tiles), on a tile of half the pixels (112) -- so that TWO workgroups share a CU and drift apart: one's barrier,
 // first-band wait and epilogue overlap the other's MFMAs (what conv3x3_c64 gains from its two workgroups per CU, profiles/r04_v_...).
-template <int NWN, int NTW, bool PK, int NWV = 8, int MAXMT = CT_MAXMT>
-__global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_kernel(ConvTileArgs a)
+// UP (ARGS = ConvUpArgs): the chunks below C1 are enlarged in place from lo -- fetch() brings the low-resolution rows into the staging
+// area with the same PP pieces per wave, and the chunk iteration expands them into its band buffer before it computes (below).
+template <int NWN, int NTW, bool PK, int NWV = 8, int MAXMT = CT_MAXMT, bool UP = false>
+__global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_kernel(std::conditional_t<UP, ConvUpArgs, ConvTileArgs> a)
 {
     constexpr int MW = NWV / NWN, MTW = (MAXMT + MW - 1) / MW;         // pixel-tile groups, pixel tiles per wave
-    extern __shared__ __attribute__((aligned(16))) unsigned char ct_band[];    // [2][npieces * 1024] | 1 KiB dump slot
+    extern __shared__ __attribute__((aligned(16))) unsigned char ct_band[];    // [2][npieces * 1024] | 1 KiB dump slot | UP: [nstage * 1024] staging
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), wn = w % NWN, wm = w / NWN;
     const int H = a.H, W = a.W, C = a.C, K = a.K, BW = a.bw;
@@ -106,35 +121,59 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
         const bool live = j < a.npieces && c < 8 && pix < a.band_px && bx >= 1 && bx <= W && (a.tiles_y > 1 || (by >= 1 && by <= a.th));
         g_off1[u] = live ? (unsigned)(sp * cs1 * 2 + c * 16) : RSRC_DEAD;
         g_off2[u] = live ? (unsigned)(sp * cs2 * 2 + c * 16) : RSRC_DEAD;
+        if constexpr (UP) {
+            // x is never fetched into a band: g_off1 addresses the staging pieces instead.  Slot d = 8 spx + c of staged pixel
+            // spx = (f nlr + lr) wl + lx <- lo pixel (f, lrow0 + lr, lx) of the frame group; lrow0 is the tile's scalar.  A row past the frame
+            // reads the next frame's (never used: the taps clamp) or, past the group, zeros.
+            const int spx = d >> 3, c8 = d & 7;
+            const int sf = idx_div(spx, a.inv_slr), sr = spx - sf * (a.nlr * a.wl), lr = idx_div(sr, a.inv_wl), lx = sr - lr * a.wl;
+            g_off1[u] = j < a.nstage && spx < a.stage_px ? (unsigned)((((sf * a.hl + lr) * a.wl + lx) * cs1 + c8 * 8) * 2) : RSRC_DEAD;
+        }
     }
     const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>(ct_band);
     const int nlive = max(0, (a.npieces - w + NWV - 1) / NWV);         // this wave's pieces u < nlive exist (j = w + NWV u < npieces)
+    int nlive_up = 0, stage_off = 0;                                   // UP: likewise for the staging pieces
+    if constexpr (UP) { nlive_up = max(0, (a.nstage - w + NWV - 1) / NWV); stage_off = a.stage_off; }
     // what a tile's band fetches need of the tile, computed ONCE per tile (scalar): the frame group's first pixel, its pixel count and the
     // tile's first row, in pixels -- the descriptor and the offset scalar of a chunk are a few scalar instructions from these
-    struct Geo { int px0, npx, row0; };
+    struct Geo { int px0, npx, row0, r0, lr0, nfr; };     // (r0, lr0, nfr: UP only -- the tile's first row, its first staged source row, its frames)
     auto geo_of = [&](int tile) __attribute__((always_inline)) {
         const int ty = tile % a.tiles_y, fg = tile / a.tiles_y;          // row tile, frame group
         Geo q;
         q.px0 = fg * a.fpt * H * W;
         q.npx = min(a.fpt, a.N - fg * a.fpt) * H * W;                   // (the frames that exist in the last group)
         q.row0 = ty * a.th * W;
+        q.r0 = q.lr0 = q.nfr = 0;
+        if constexpr (UP) {
+            // output row y >= 1 blends source rows (y - 1) >> 1 and the next one: the band's first row inside the frame is max(r0 - 1, 0)
+            q.r0 = ty * a.th; q.lr0 = max((q.r0 - 2) >> 1, 0); q.nfr = min(a.fpt, a.N - fg * a.fpt);
+        }
         return q;
     };
     auto fetch = [&](const Geo q, int chunk, int buf) __attribute__((always_inline)) {
         const bool second = a.x2 != nullptr && chunk * CT_CK >= a.C1;   // which tensor of a concatenated input holds this chunk
         const int cs = second ? cs2 : cs1;                              // its channel count = pixel pitch
+        const bool up = UP && !second;                                  // a chunk of lo: a quarter of the pixels, into the staging area
         // wave-uniform values only (kernel arguments and scalars of the tile loop): the descriptor lives in SGPRs, no waterfall loop
-        const bf16_t* base = (second ? a.x2 : a.x) + (long long)q.px0 * cs;
-        const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(base, q.npx * cs * 2);
-        const unsigned ts = (unsigned)((q.row0 * cs + chunk * CT_CK - (second ? a.C1 : 0)) * 2);
-        const unsigned dst0 = lds0 + buf * band_bytes + 1024 * w;       // LDS address of this wave's piece 0
+        const bf16_t* base = (second ? a.x2 : a.x) + (long long)(up ? q.px0 >> 2 : q.px0) * cs;
+        const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(base, (up ? q.npx >> 2 : q.npx) * cs * 2);
+        unsigned ts = (unsigned)((q.row0 * cs + chunk * CT_CK - (second ? a.C1 : 0)) * 2);
+        unsigned dst0 = lds0 + buf * band_bytes + 1024 * w;             // LDS address of this wave's piece 0
+        int nl = nlive;
+        if constexpr (UP) {                                             // (selects, not a branch: a branch here put the offset sets in scratch)
+            ts = up ? (unsigned)((q.lr0 * (W >> 1) * cs + chunk * CT_CK) * 2) : ts;
+            dst0 = up ? lds0 + stage_off + 1024 * w : dst0;
+            nl = up ? nlive_up : nlive;
+        }
         // straight-line on purpose (always PP pieces: surplus ones land in a dump slot): the hand-written vmcnt counts of the chunk loop
         // assume exactly PP DMA operations per fetch
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
-            const unsigned dst = u < nlive ? dst0 + 1024 * NWV * u : lds0 + 2 * band_bytes;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, lds_dma_dst(dst), 16,
-                                                     (int)((second ? g_off2[u] : g_off1[u]) + ts), 0, 0, 0);
+            const unsigned dst = u < nl ? dst0 + 1024 * NWV * u : lds0 + 2 * band_bytes;
+            unsigned go;
+            if constexpr (UP) go = g_off1[u] ^ ((g_off1[u] ^ g_off2[u]) & (second ? ~0u : 0u));    // (both sets read: a conditional read of one put them in scratch)
+            else go = second ? g_off2[u] : g_off1[u];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, lds_dma_dst(dst), 16, (int)(go + ts), 0, 0, 0);
         }
     };
 
@@ -209,12 +248,66 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
             // would drain the weight fragments in flight.)
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WD * NTW) : "memory");
             asm volatile("s_barrier" ::: "memory");
+            if constexpr (UP) if (chunk * CT_CK < a.C1) {
+                // An enlarged chunk: what has landed is the staging area.  All waves build band[buf] from it -- exactly what the DMA path would
+                // have delivered from a materialised enlargement: zeros outside the frame (the halo ring, the rows above and below it, also
+                // between the frames of a tile, and the frames a ragged last group lacks), the enlargement's clamped taps inside -- with LDS
+                // reads, fp32 arithmetic and 16-byte LDS writes: no vector-memory operation, so the counts below stay exact.  band[buf] was
+                // last read two chunks ago; the staging area is free for the next fetch behind the second barrier.
+                // (The staging reads are asm, waited for by hand: the compiler answers an LDS read it knows of, behind LDS-DMA it cannot tell
+                // apart, with s_waitcnt vmcnt(0) -- on the weight fragments in flight.)
+                const unsigned stg = lds0 + stage_off;
+                unsigned char* const bandw = ct_band + buf * band_bytes;
+                // One item = the 2 x 2 output pixels that share four source taps (as in upsample_cat_bf16_2x_kernel), 8 channels: rows
+                // 2 ip + 1, 2 ip + 2 and columns 2 jp + 1, 2 jp + 2, for jp = -1 .. wl - 1 (columns -1 .. W: the band's width) and the nrp row
+                // pairs from ip0 on that cover the band's rows r0 - 1 .. r0 + th.  Four reads, 32 conversions and the horizontal blends serve
+                // four output vectors.
+                const int hl = H >> 1, wl = W >> 1, ncp = wl + 1, ip0 = (cur.r0 - 2) >> 1;
+                const int nitems = a.fpt * a.nrp * ncp * 8;
+#pragma unroll 1
+                for (int i = tid; i < nitems; i += 64 * NWV) {
+                    const int c8 = i & 7, t = i >> 3;
+                    const int t2 = idx_div(t, a.inv_ncp), jp = t - t2 * ncp - 1, f = idx_div(t2, a.inv_nrp), ip = ip0 + t2 - f * a.nrp;
+                    const int y0 = 2 * ip + 1, x0o = 2 * jp + 1;                            // the block's first output row / column
+                    const int by0 = y0 - cur.r0 + 1;                                        // its first band row (the columns: bx = x + 1)
+                    const bool vy[2] = {y0 >= 0 && y0 < H, y0 + 1 >= 0 && y0 + 1 < H}, vx[2] = {x0o >= 0, x0o + 1 < W};
+                    u32x4 o[2][2] = {};
+                    if ((vy[0] || vy[1]) && f < cur.nfr) {
+                        const int ra = max(ip, 0) - cur.lr0, rb = min(ip + 1, hl - 1) - cur.lr0;
+                        const int xa_ = max(jp, 0), xb_ = min(jp + 1, wl - 1);
+                        const unsigned s0 = stg + (f * a.nlr + ra) * wl * 128 + c8 * 16, s1 = stg + (f * a.nlr + rb) * wl * 128 + c8 * 16;
+                        u32x4 t00, t01, t10, t11;
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(t00) : "v"(s0 + xa_ * 128) : "memory");
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(t01) : "v"(s0 + xb_ * 128) : "memory");
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(t10) : "v"(s1 + xa_ * 128) : "memory");
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(t11) : "v"(s1 + xb_ * 128) : "memory");
+                        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t00), "+v"(t01), "+v"(t10), "+v"(t11) :: "memory");
+                        // that kernel's row weights: fy = max(y / 2 - 1 / 4, 0): 1/4 on odd rows, 3/4 on even ones, 0 on row 0
+                        const float ly[2] = {0.25f, y0 + 1 == 0 ? 0.f : 0.75f}, hy[2] = {0.75f, 1.f - ly[1]};
+                        bilerp2x_bf16x8(t00, t01, t10, t11, hy, ly, o);
+                    }
+#pragma unroll
+                    for (int ey = 0; ey < 2; ++ey) {
+                        if (by0 + ey < 0 || by0 + ey >= a.bh) continue;                 // (a row pair may reach past the band)
+                        const bool rowin = vy[ey] && f < cur.nfr;
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            const u32x4 z = {0u, 0u, 0u, 0u};
+                            *reinterpret_cast<u32x4*>(bandw + ((f * a.bh + by0 + ey) * BW + x0o + 1 + e) * CT_PIX + c8 * 16) = rowin && vx[e] ? o[ey][e] : z;
+                        }
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                asm volatile("s_barrier" ::: "memory");
+            }
             // the next band streams in behind this chunk's MFMAs: the tile's next chunk, or chunk 0 of the workgroup's next tile
             // (past the last tile: one more band of the last tile, into the buffer nobody reads again)
             {
                 const bool more = chunk + 1 < nchunk;
                 Geo q;                                     // (field by field: a select between the two structs would put them in scratch)
                 q.px0 = more ? cur.px0 : nxt.px0; q.npx = more ? cur.npx : nxt.npx; q.row0 = more ? cur.row0 : nxt.row0;
+                q.r0 = q.lr0 = q.nfr = 0;
+                if constexpr (UP) q.lr0 = more ? cur.lr0 : nxt.lr0;
                 fetch(q, more ? chunk + 1 : 0, buf ^ 1);
             }
             const unsigned char* band = ct_band + buf * band_bytes;
@@ -488,7 +581,78 @@ bool setattr_tile()
     return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_tile_kernel<NWN, NTW, true, NWV, MAXMT>), hipFuncAttributeMaxDynamicSharedMemorySize, 113 * 1024) == hipSuccess
         && hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_tile_kernel<NWN, NTW, false, NWV, MAXMT>), hipFuncAttributeMaxDynamicSharedMemorySize, 113 * 1024) == hipSuccess;
 }
+constexpr size_t CT_UP_LDS = 80 * 1024;                    // the UP forms keep two workgroups per CU (160 KB of LDS)
+template <int NWN, int NTW>
+bool setattr_up()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_tile_kernel<NWN, NTW, true, 4, 7, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT_UP_LDS) == hipSuccess;
+}
+
+// The tile and band geometry of a launch (a.N, a.H, a.W set): frames per tile, rows per tile, band size and DMA pieces, tile count.
+// Returns false when the map does not tile into maxpix pixels under maxpieces pieces.
+bool tile_geometry(ConvTileArgs& a, int maxpix, int maxpieces)
+{
+    const int N = a.N, H = a.H, W = a.W;
+    if (H * W <= maxpix) { a.th = H; a.fpt = maxpix / (H * W); a.tiles_y = 1; if (a.fpt > N) a.fpt = N; }
+    else { a.fpt = 1; a.th = maxpix / W; if (a.th < 1) return false; a.tiles_y = (H + a.th - 1) / a.th; }
+    a.bw = W + 2; a.bh = a.th + 2;
+    // the halo band of a tile must fit the 56 DMA pieces (8 waves x 7) of a chunk: tiny maps take fewer frames, wide ones fewer rows
+    auto pieces = [&]() { a.band_px = a.fpt * a.bh * a.bw; return (a.band_px * CT_SLOTS + 63) / 64; };
+    while (pieces() > maxpieces && a.fpt > 1) --a.fpt;
+    while (pieces() > maxpieces && a.th > 1) { --a.th; a.bh = a.th + 2; a.tiles_y = (H + a.th - 1) / a.th; }
+    a.npieces = pieces();
+    if (a.npieces > maxpieces) return false;
+    a.inv_band = 1.0f / (float)(a.bh * a.bw); a.inv_bw = 1.0f / (float)a.bw;
+    a.inv_tw = 1.0f / (float)(a.th * W); a.inv_w = 1.0f / (float)W;
+    const long long groups = (N + a.fpt - 1) / a.fpt;
+    const long long ntiles = groups * a.tiles_y;
+    if (ntiles <= 0 || ntiles > 0x7fffffffLL) return false;
+    a.ntiles = (int)ntiles;
+    return true;
+}
 }  // namespace
+
+// The UP form: the first C1 of the C input channels are the exact-2x enlargement of lo [N, H/2, W/2, C1], the rest x2 [N, H, W, C - C1];
+// packed weights.  K % 128 == 0 runs <4, 2> on four waves, any other K (a multiple of 16) <2, 2> on four waves.  0 = launched.
+int gdkvm_conv3x3_upcat_launch(const void* lo, const void* x2, int C1, const void* w, const float* bias, const void* residual, void* y,
+                               int N, int C, int H, int W, int K, int relu, hipStream_t st)
+{
+    if (C % CT_CK || K % 16 || W > 64 || W < 2 || H < 2 || (H | W) & 1 || N < 1 || !x2 || C1 <= 0 || C1 >= C || C1 % CT_CK) return 1;
+    ConvUpArgs a;
+    a.x2 = static_cast<const bf16_t*>(x2); a.C1 = C1;
+    a.x = static_cast<const bf16_t*>(lo); a.w = static_cast<const bf16_t*>(w); a.bias = bias;
+    a.res = static_cast<const bf16_t*>(residual); a.y = static_cast<bf16_t*>(y);
+    a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.relu = relu;
+    if (!tile_geometry(a, 16 * 7, 32)) return 1;
+    if ((long long)(a.fpt * H + 2) * W * (C1 > C - C1 ? C1 : C - C1) * 2 >= 0x7fffffffLL) return 1;     // (as gdkvm_conv3x3_tile_launch)
+    a.perm = K % 32 == 0;
+    // staging: a band of bh rows blends at most bh / 2 + 2 source rows (rows (y - 1) >> 1 and the next, over bh consecutive y)
+    a.hl = H / 2; a.wl = W / 2;
+    a.nlr = a.bh / 2 + 2 < a.hl ? a.bh / 2 + 2 : a.hl;
+    a.stage_px = a.fpt * a.nlr * a.wl;
+    a.nstage = (a.stage_px + 7) / 8;
+    if (a.nstage > 32) return 1;                           // (the pieces of one fetch: four waves x 8)
+    a.inv_slr = 1.0f / (float)(a.nlr * a.wl); a.inv_wl = 1.0f / (float)a.wl;
+    a.nrp = a.bh / 2 + 1; a.inv_ncp = 1.0f / (float)(a.wl + 1); a.inv_nrp = 1.0f / (float)a.nrp;
+    a.stage_off = 2 * a.npieces * 1024 + 1024;
+    const size_t lds = (size_t)a.stage_off + (size_t)a.nstage * 1024;
+    if (lds > CT_UP_LDS) return 1;
+    const int kwg = K % 128 == 0 ? 128 : 64;
+    const int gy = (K + kwg - 1) / kwg;
+    int per = 512 / gy; if (per < 1) per = 1;
+    const int gx = a.ntiles < per ? a.ntiles : per;        // persistent: two workgroups per CU
+    static std::atomic<unsigned long long> done_mask{0};   // per device; a lost race only repeats the idempotent call
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 1;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(done_mask.load(std::memory_order_relaxed) & bit)) {
+        if (!setattr_up<4, 2>() || !setattr_up<2, 2>()) return 1;
+        done_mask.fetch_or(bit, std::memory_order_relaxed);
+    }
+    if (kwg == 128) hipLaunchKernelGGL((conv3x3_tile_kernel<4, 2, true, 4, 7, true>), dim3(gx, gy), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((conv3x3_tile_kernel<2, 2, true, 4, 7, true>), dim3(gx, gy), dim3(256), lds, st, a);
+    return 0;
+}
 
 int gdkvm_conv3x3_tile_launch(const void* x, const void* x2, int C1, const void* w, const float* bias, const void* residual, void* y,
                               int N, int C, int H, int W, int K, int relu, int variant, int packed, hipStream_t st)
@@ -515,25 +679,12 @@ int gdkvm_conv3x3_tile_launch(const void* x, const void* x2, int C1, const void*
     a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.relu = relu;
     const int maxpix = half ? 16 * 7 : 16 * CT_MAXMT;
     const int maxpieces = half ? 32 : 56;
-    if (H * W <= maxpix) { a.th = H; a.fpt = maxpix / (H * W); a.tiles_y = 1; if (a.fpt > N) a.fpt = N; }
-    else { a.fpt = 1; a.th = maxpix / W; if (a.th < 1) return 1; a.tiles_y = (H + a.th - 1) / a.th; }
-    a.bw = W + 2; a.bh = a.th + 2;
-    // the halo band of a tile must fit the 56 DMA pieces (8 waves x 7) of a chunk: tiny maps take fewer frames, wide ones fewer rows
-    auto pieces = [&]() { a.band_px = a.fpt * a.bh * a.bw; return (a.band_px * CT_SLOTS + 63) / 64; };
-    while (pieces() > maxpieces && a.fpt > 1) --a.fpt;
-    while (pieces() > maxpieces && a.th > 1) { --a.th; a.bh = a.th + 2; a.tiles_y = (H + a.th - 1) / a.th; }
-    a.npieces = pieces();
-    if (a.npieces > maxpieces) return 1;
+    if (!tile_geometry(a, maxpix, maxpieces)) return 1;
     // a band piece is addressed by a 32-bit byte offset from its frame group's first byte, and offsets from 2^31 on stand for "zeros":
     // a group, the band row below it included, stays below that
     if ((long long)(a.fpt * H + 2) * W * (x2 ? (C1 > C - C1 ? C1 : C - C1) : C) * 2 >= 0x7fffffffLL) return 1;
-    a.inv_band = 1.0f / (float)(a.bh * a.bw); a.inv_bw = 1.0f / (float)a.bw;
-    a.inv_tw = 1.0f / (float)(a.th * W); a.inv_w = 1.0f / (float)W;
     a.perm = K % 32 == 0;
-    const long long groups = (N + a.fpt - 1) / a.fpt;
-    const long long ntiles = groups * a.tiles_y;
-    if (ntiles <= 0 || ntiles > 0x7fffffffLL) return 1;
-    a.ntiles = (int)ntiles;
+    const long long ntiles = a.ntiles;
     // wave grid by output channels (variant 0; 1..4 pick one for tuning): 128 per workgroup where K allows, else 64
     if (variant == 0) variant = K % 128 == 0 ? 2 : CT_VARIANT_64;
     const int kwg = (variant == 2 || variant == 4) ? 128 : 64;   // output channels per workgroup

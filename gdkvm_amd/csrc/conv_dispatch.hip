@@ -10,6 +10,8 @@ int gdkvm_conv3x3_c64_launch(const void* x, const void* w, const float* bias, co
                              int relu, int packed, hipStream_t st);   // conv3x3_c64.hip
 int gdkvm_conv3x3_tile_launch(const void* x, const void* x2, int C1, const void* w, const float* bias, const void* residual, void* y,
                               int N, int C, int H, int W, int K, int relu, int variant, int packed, hipStream_t st);   // conv3x3_tile.hip
+int gdkvm_conv3x3_upcat_launch(const void* lo, const void* x2, int C1, const void* w, const float* bias, const void* residual, void* y,
+                               int N, int C, int H, int W, int K, int relu, hipStream_t st);   // conv3x3_tile.hip
 int gdkvm_conv_igemm_launch(const void* x, const void* wpacked, const float* bias, const void* residual, void* y,
                             int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int relu,
                             const void* w2packed, const float* bias2, void* y2, hipStream_t st);   // conv_igemm.hip
@@ -89,6 +91,33 @@ extern "C" int gdkvm_conv_cat_bias_act(const void* x1, const void* x2, const voi
     if (gdkvm_conv3x3_tile_launch(x1, x2, C1, w, bias, residual, y, N, C1 + C2, H, W, K, relu, kernel >= 10 ? kernel - 6 : (kernel >= 6 ? kernel - 5 : 0), packed ? 1 : 0,
                                   static_cast<hipStream_t>(stream)))
         return gdkvm_fail(GDKVM_ERR_SHAPE, "conv_cat_bias_act: %dx%d is not served (rows of at most 64 pixels)", H, W);
+    GDKVM_LAUNCH_CHECK("conv3x3_tile_kernel");
+    return GDKVM_OK;
+}
+
+// The decoder's  conv(cat(upsample2x(lo), x2))  with neither the concatenated nor the ENLARGED tensor in memory: the first C1 input
+// channels are the exact-2x bilinear enlargement (align_corners = false) of lo [N, H/2, W/2, C1], which the chunked kernel builds in its
+// LDS band from the low-resolution rows (conv3x3_tile.hip, the UP form) with the arithmetic of gdkvm_upsample_cat's 2x kernel.  H, W are
+// the output map.  Packed weights only (kernel = GDKVM_CONV_PACKED_WEIGHTS: the wave grid follows K).
+extern "C" int gdkvm_conv_upcat_bias_act(const void* lo, const void* x2, const void* w, const float* bias, const void* residual, void* y,
+                                         int N, int C1, int C2, int H, int W, int K, int relu, int kernel, int io_dtype, void* stream)
+{
+    if (io_dtype != GDKVM_BF16) return gdkvm_fail(GDKVM_ERR_DTYPE, "conv_upcat_bias_act: only bf16 is implemented");
+    if (kernel != GDKVM_CONV_PACKED_WEIGHTS)
+        return gdkvm_fail(GDKVM_ERR_ARG, "conv_upcat_bias_act: kernel=%d (%d: the gdkvm_conv3x3_pack_weights copy of the weights, wave grid by shape)", kernel, GDKVM_CONV_PACKED_WEIGHTS);
+    if (N < 0 || C1 <= 0 || C2 <= 0 || C1 % 64 || C2 % 64 || H <= 0 || W <= 0 || K <= 0 || K % 16)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "conv_upcat_bias_act: N=%d C1=%d C2=%d H=%d W=%d K=%d (C1, C2 multiples of 64, K of 16)", N, C1, C2, H, W, K);
+    if (H % 2 || W % 2 || W > 64)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "conv_upcat_bias_act: H=%d W=%d (an exact 2x enlargement: both even; rows of at most 64 pixels)", H, W);
+    if (N == 0) return GDKVM_OK;
+    if (!lo || !x2 || !w || !bias || !y) return gdkvm_fail(GDKVM_ERR_ARG, "conv_upcat_bias_act: null pointer");
+    if (!gdkvm_aligned16(lo) || !gdkvm_aligned16(x2) || !gdkvm_aligned16(w) || !gdkvm_aligned16(y) || !gdkvm_aligned16(bias) || (residual && !gdkvm_aligned16(residual)))
+        return gdkvm_fail(GDKVM_ERR_ARG, "conv_upcat_bias_act: pointers must be 16-byte aligned");
+    if ((size_t)N * H * W * (C1 + C2) >= (1ull << 31) || (size_t)N * H * W * K >= (1ull << 31))
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "conv_upcat_bias_act: tensor too large for 32-bit offsets");
+    if (int rc = gdkvm_check_device()) return rc;
+    if (gdkvm_conv3x3_upcat_launch(lo, x2, C1, w, bias, residual, y, N, C1 + C2, H, W, K, relu, static_cast<hipStream_t>(stream)))
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "conv_upcat_bias_act: %dx%d is not served (the band and the staged rows of a tile must fit 80 KB of LDS)", H, W);
     GDKVM_LAUNCH_CHECK("conv3x3_tile_kernel");
     return GDKVM_OK;
 }

@@ -79,3 +79,45 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, int b
 // it with zeros.  Holds because the launchers keep everything one descriptor addresses (frame or frame group, halo rows included) below
 // 2^31 bytes, so offset + scalar stays in [2^31, 2^32).
 constexpr unsigned RSRC_DEAD = 0x80000000u;
+
+// A 2 x 2 block of output vectors (8 channels, 16 bytes each) of the exact-2x bilinear enlargement (align_corners = false): the output
+// rows 2 ip + 1, 2 ip + 2 and columns 2 jp + 1, 2 jp + 2 share the four source taps a, b (row ip: columns jp, jp + 1) and c, d (row
+// ip + 1), as in upsample_cat_bf16_2x_kernel (epilogue.hip).  o[ey][e] = hy[ey] (hx a + lx b) + ly[ey] (hx c + lx d) with (hx, lx) =
+// (3/4, 1/4) for e = 0 and (1/4, 3/4) for e = 1, rounded by pack_bf16x2; hy + ly = 1 are the caller's row weights (1/4 and 3/4 inside,
+// 1 / 0 on output row 0).  Each value goes through EXACTLY the multiply / fused-multiply-add sequence that kernel compiles to for gfx950,
+// which is not the same for every channel: its pairs of packed fp32 instructions take channels 0, 1, 4, 5 of a vector with the products
+// hx a, hx c and hy top rounded on their own and the other three terms inside the fused operations, and channels 2, 3, 6, 7 the other
+// way round.  The horizontal products are exact either way (an 8-bit significand times 1/4 or 3/4); the vertical ones are not, so a
+// consumer that must reproduce that kernel's bits (the convolution that builds the enlarged feature in its LDS band, conv3x3_tile.hip)
+// has to round where it rounds.  Contraction is off in here: every rounding is the one written.
+__device__ __forceinline__ void bilerp2x_bf16x8(const u32x4& a, const u32x4& b, const u32x4& c, const u32x4& d,
+                                                const float (&hy)[2], const float (&ly)[2], u32x4 (&o)[2][2])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float v[2][2][2];                                  // [ey][e][half]
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float A = h ? bf16_hi(a[q]) : bf16_lo(a[q]), B = h ? bf16_hi(b[q]) : bf16_lo(b[q]);
+            const float C = h ? bf16_hi(c[q]) : bf16_lo(c[q]), D = h ? bf16_hi(d[q]) : bf16_lo(d[q]);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float lx = e ? 0.75f : 0.25f, hx = e ? 0.25f : 0.75f;
+                if (q & 1) {
+                    const float top = __fmaf_rn(hx, A, __fmul_rn(lx, B)), bot = __fmaf_rn(hx, C, __fmul_rn(lx, D));
+#pragma unroll
+                    for (int ey = 0; ey < 2; ++ey) v[ey][e][h] = __fmaf_rn(hy[ey], top, __fmul_rn(ly[ey], bot));
+                } else {
+                    const float top = __fmaf_rn(lx, B, __fmul_rn(hx, A)), bot = __fmaf_rn(lx, D, __fmul_rn(hx, C));
+#pragma unroll
+                    for (int ey = 0; ey < 2; ++ey) v[ey][e][h] = __fmaf_rn(ly[ey], bot, __fmul_rn(hy[ey], top));
+                }
+            }
+        }
+#pragma unroll
+        for (int ey = 0; ey < 2; ++ey)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) o[ey][e][q] = pack_bf16x2(v[ey][e][0], v[ey][e][1]);
+    }
+}

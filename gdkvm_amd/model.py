@@ -338,10 +338,14 @@ class UpBlock(nn.Module):
         c = self.conv
         if (isinstance(c[0], FusedConv) and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16
                 and skip.dtype == torch.bfloat16 and c[0].cat_served(x.shape[1], skip.shape[1], skip.shape[-1])):
-            # inference build: only the enlarged feature is written; the first convolution reads it and the skip feature where they
-            # lie (no concatenated copy: 154 MB less traffic per forward at cfg2)
-            u = ops.upsample_bilinear(x.contiguous(memory_format=torch.channels_last), skip.shape[2:])
-            y = c[0].forward_cat(u, skip)
+            # inference build: the first convolution reads the low-resolution feature and the skip feature where they lie and enlarges
+            # the former in its LDS band (no enlarged and no concatenated copy); GDKVM_UPCAT_FUSED=0, or a shape that form does not take:
+            # only the enlarged feature is written first (ops.upsample_bilinear), same bits
+            if c[0].upcat_served(x.shape[1], skip.shape[1], tuple(x.shape[2:]), tuple(skip.shape[2:])):
+                y = c[0].forward_upcat(x, skip)
+            else:
+                u = ops.upsample_bilinear(x.contiguous(memory_format=torch.channels_last), skip.shape[2:])
+                y = c[0].forward_cat(u, skip)
             for m in list(c)[1:]:
                 y = m(y)
             return y
@@ -466,6 +470,18 @@ class FusedConv(nn.Module):
                 and cv.dilation == (1, 1) and cv.stride == (1, 1) and cv.padding == (1, 1) and cv.weight.is_cuda
                 and cv.weight.dtype == torch.bfloat16 and cv.weight.is_contiguous(memory_format=torch.channels_last)
                 and c1 % 64 == 0 and c2 % 64 == 0 and c1 + c2 == cv.in_channels and cv.out_channels % 16 == 0 and width <= 64)
+
+    def upcat_served(self, c1: int, c2: int, lo_size, size) -> bool:
+        """Can forward_upcat run this layer on [2x enlargement of lo (c1 channels, lo_size) ; x2 (c2, size)] (gdkvm_conv_upcat_bias_act)?
+        GDKVM_UPCAT_FUSED=0 (read per call) says no: the A/B switch onto the two-launch path."""
+        return (os.environ.get("GDKVM_UPCAT_FUSED", "1") != "0" and self.cat_served(c1, c2, size[1])
+                and size == (2 * lo_size[0], 2 * lo_size[1]))
+
+    def forward_upcat(self, lo, x2):
+        """forward_cat(ops.upsample_bilinear(lo, x2.shape[2:]), x2) with the enlargement built inside the convolution."""
+        cl = torch.channels_last
+        return ops.conv_upcat_bias_act(lo.contiguous(memory_format=cl), x2.contiguous(memory_format=cl), self.conv.weight, self.epi.bias,
+                                       None, self.relu, self._packed(lo.device))
 
     def forward_cat(self, x1, x2):
         """forward(torch.cat([x1, x2], 1)) with every 64-channel chunk read from the tensor it lies in."""

@@ -93,6 +93,7 @@ SIGNATURES = {
     "gdkvm_conv_igemm_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gdkvm_conv_down_bias_act": (_i, [_vp] * 4 + [_i] + [_vp] * 3 + [_i] * 10 + [_vp]),
     "gdkvm_conv_cat_bias_act": (_i, [_vp] * 6 + [_i] * 9 + [_vp]),
+    "gdkvm_conv_upcat_bias_act": (_i, [_vp] * 6 + [_i] * 9 + [_vp]),
     "gdkvm_conv_s2_dgrad_pack_bytes": (_sz, [_i] * 3),
     "gdkvm_conv_s2_pack_train": (_i, [_vp] * 7 + [_i, _i, _vp]),
     "gdkvm_conv_s2_dgrad": (_i, [_vp] * 4 + [_i] * 7 + [_vp]),
@@ -1407,19 +1408,17 @@ def upsample_bilinear(lo: torch.Tensor, size) -> torch.Tensor:
     return out
 
 
-def conv_cat_bias_act(x1: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
-                      residual: Optional[torch.Tensor] = None, relu: bool = True, tile: int = 0,
-                      packed: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """conv_bias_act(torch.cat([x1, x2], 1), weight, ...) for a 3x3 / stride 1 / pad 1 layer WITHOUT the concatenated tensor
-    (gdkvm_conv_cat_bias_act): channel counts in multiples of 64, same result bit for bit."""
-    _channels_last("conv_cat_bias_act", x1, x2, dtype=torch.bfloat16)
-    n, c1, hh, ww = x1.shape
-    c2 = x2.shape[1]
-    if tuple(x2.shape) != (n, c2, hh, ww):
-        raise GdkvmError("conv_cat_bias_act: x1 and x2 must agree in batch and size")
+def _conv_cat_operands(what: str, x1, x2, size, weight, bias, residual, packed) -> torch.Tensor:
+    """The checks conv_cat_bias_act and conv_upcat_bias_act share (x1 is the tensor whose channels come first; size = x2's map); returns
+    the empty output."""
+    _channels_last(what, x1, x2, dtype=torch.bfloat16)
+    n, c1 = x1.shape[:2]
+    c2, hh, ww = x2.shape[1:]
+    if x2.shape[0] != n or tuple(size) != (hh, ww):
+        raise GdkvmError(f"{what}: the two inputs must agree in batch and size")
     if weight.dim() != 4 or weight.dtype != torch.bfloat16 or tuple(weight.shape[1:]) != (c1 + c2, 3, 3) or \
             not weight.is_contiguous(memory_format=torch.channels_last):
-        raise GdkvmError("conv_cat_bias_act: weight must be channels_last bf16 [K,C1+C2,3,3]")
+        raise GdkvmError(f"{what}: weight must be channels_last bf16 [K,C1+C2,3,3]")
     k = weight.shape[0]
     if bias.dtype != torch.float32 or bias.numel() != k:
         raise GdkvmError("bias must be float32 [K]")
@@ -1427,12 +1426,38 @@ def conv_cat_bias_act(x1: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, 
     if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or
                                  not residual.is_contiguous(memory_format=torch.channels_last)):
         raise GdkvmError("residual must match the output (shape, dtype, channels_last)")
+    if packed is not None and (packed.dtype != torch.bfloat16 or packed.numel() != weight.numel() or packed.device != x1.device):
+        raise GdkvmError(f"{what}: packed must be conv3x3_pack_weights(weight)")
+    return y
+
+
+def conv_cat_bias_act(x1: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                      residual: Optional[torch.Tensor] = None, relu: bool = True, tile: int = 0,
+                      packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_bias_act(torch.cat([x1, x2], 1), weight, ...) for a 3x3 / stride 1 / pad 1 layer WITHOUT the concatenated tensor
+    (gdkvm_conv_cat_bias_act): channel counts in multiples of 64, same result bit for bit."""
+    y = _conv_cat_operands("conv_cat_bias_act", x1, x2, x1.shape[2:] if x1.dim() == 4 else (), weight, bias, residual, packed)
     if packed is not None:
-        if packed.dtype != torch.bfloat16 or packed.numel() != weight.numel() or packed.device != x1.device:
-            raise GdkvmError("conv_cat_bias_act: packed must be conv3x3_pack_weights(weight)")
         tile |= CONV_PACKED_WEIGHTS
+    n, c1, hh, ww = x1.shape
     _call("gdkvm_conv_cat_bias_act", x1.device, x1, x2, packed if packed is not None else weight, bias, residual, y,
-          n, c1, c2, hh, ww, k, int(relu), tile, BF16)
+          n, c1, x2.shape[1], hh, ww, y.shape[1], int(relu), tile, BF16)
+    return y
+
+
+def conv_upcat_bias_act(lo: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                        residual: Optional[torch.Tensor] = None, relu: bool = True,
+                        packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_cat_bias_act(upsample_bilinear(lo, x2.shape[2:]), x2, weight, ...) for an exact 2x enlargement, bit for bit, WITHOUT the
+    enlarged tensor (gdkvm_conv_upcat_bias_act): lo channels_last bf16 [N,C1,H/2,W/2], x2 [N,C2,H,W] with H, W even and W <= 64;
+    packed = conv3x3_pack_weights(weight) (made here when not given: the kernel reads only that form)."""
+    size = (2 * lo.shape[2], 2 * lo.shape[3]) if lo.dim() == 4 else ()
+    y = _conv_cat_operands("conv_upcat_bias_act", lo, x2, size, weight, bias, residual, packed)
+    if packed is None:
+        packed = conv3x3_pack_weights(weight)
+    n, c1 = lo.shape[:2]
+    _call("gdkvm_conv_upcat_bias_act", lo.device, lo, x2, packed, bias, residual, y,
+          n, c1, x2.shape[1], size[0], size[1], y.shape[1], int(relu), CONV_PACKED_WEIGHTS, BF16)
     return y
 
 

@@ -466,6 +466,12 @@ int gdkvm_conv_wgrad_strided(const void* x, const void* dy, float* dw, long long
  * 5..8, 10, 11.  Bit-identical to gdkvm_conv_bias_act on the concatenated tensor. */
 int gdkvm_conv_cat_bias_act(const void* x1, const void* x2, const void* w, const float* bias, const void* residual, void* y,
                             int N, int C1, int C2, int H, int W, int K, int relu, int kernel, int io_dtype, void* stream);
+/* The same with x1 = the exact-2x bilinear enlargement (align_corners = false) of lo [N, H/2, W/2, C1], which is never materialised
+ * either: the kernel builds it in its LDS band from the low-resolution rows.  H, W (both even, W <= 64) are the OUTPUT map; C1, C2
+ * multiples of 64, K of 16; w = the gdkvm_conv3x3_pack_weights copy of [K, 3, 3, C1 + C2] and kernel = GDKVM_CONV_PACKED_WEIGHTS
+ * (anything else: GDKVM_ERR_ARG).  Bit-identical to gdkvm_conv_cat_bias_act on gdkvm_upsample_cat(lo, NULL) and x2. */
+int gdkvm_conv_upcat_bias_act(const void* lo, const void* x2, const void* w, const float* bias, const void* residual, void* y,
+                              int N, int C1, int C2, int H, int W, int K, int relu, int kernel, int io_dtype, void* stream);
 
 /* Row n1, the stem: bias + ReLU + 3x3 / stride 2 / pad 1 max-pool in one pass over the NHWC conv output
  * x [N, H, W, C] -> y [N, (H-1)/2+1, (W-1)/2+1, C]:  y = relu(max_window(x) + bias)  (== max_window(relu(x + bias)), the
