@@ -5,8 +5,9 @@ eval_stage.num_vis, eval_stage.wandb_mode`` -- /root/reference/website/src/pages
 launcher environment variables are torchrun's (``MASTER_PORT`` etc., index.astro:238-239)."""
 from __future__ import annotations
 
+import math
 from dataclasses import asdict, dataclass, field, fields, is_dataclass
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional
 
 import yaml
 
@@ -55,6 +56,14 @@ class AugmentCfg:
 
 
 @dataclass
+class LossCfg:
+    """The training objective beyond cross-entropy + soft Dice.  boundary_weight > 0 adds that many times the boundary loss of Kervadec et al.
+    (train.segmentation_loss; on the GPU ops.seg_loss_boundary over ops.signed_distance).  The weight is a constant of the run."""
+    boundary_weight: float = 0.0
+    boundary_classes: Optional[List[int]] = None                   # null: every class but 0 (the term is not divided by their number)
+
+
+@dataclass
 class RunConfig:
     data_path: str = ""
     batch_size: int = 8
@@ -64,6 +73,7 @@ class RunConfig:
     data: DataCfg = field(default_factory=DataCfg)
     model: ModelCfg = field(default_factory=ModelCfg)
     augment: AugmentCfg = field(default_factory=AugmentCfg)
+    loss: LossCfg = field(default_factory=LossCfg)
     run_dir: str = "outputs"
     save_every: int = 1000
     log_every: int = 20
@@ -109,4 +119,13 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     sc = cfg.data.surface_class
     if isinstance(sc, bool) or not isinstance(sc, int) or not -1 <= sc < cfg.data.num_classes:
         raise ValueError(f"data.surface_class = {sc!r}: -1 (off) or a class in 0..{cfg.data.num_classes - 1}")
+    bw = cfg.loss.boundary_weight
+    if isinstance(bw, bool) or not isinstance(bw, (int, float)) or not math.isfinite(bw) or bw < 0:
+        raise ValueError(f"loss.boundary_weight = {bw!r}: a finite number >= 0 (0 = off)")
+    cfg.loss.boundary_weight = float(bw)
+    bc = cfg.loss.boundary_classes
+    if bc is not None:
+        if not isinstance(bc, list) or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < cfg.data.num_classes for c in bc) \
+                or len(set(bc)) != len(bc):
+            raise ValueError(f"loss.boundary_classes = {bc!r}: null (every class but 0) or distinct integers in 0..{cfg.data.num_classes - 1}")
     return cfg

@@ -145,6 +145,16 @@ struct FrameWords {
     __device__ __forceinline__ void aadd(I i, unsigned v) const { __hip_atomic_fetch_add(w + i, v, __ATOMIC_RELAXED, SCOPE); }
 };
 
+// The same for 16-bit words (signed_distance.hip: a pixel's kind and an 11-bit distance), at half the bytes per pixel: a 256 x 256 plane is
+// 128 KiB and fits one workgroup's LDS.  Loads and stores only.
+template <bool LDS, class I>
+struct FrameHalves {
+    unsigned short* h;
+    static constexpr int SCOPE = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
+    __device__ __forceinline__ unsigned ld(I i) const { return __hip_atomic_load(h + i, __ATOMIC_RELAXED, SCOPE); }
+    __device__ __forceinline__ void st(I i, unsigned v) const { __hip_atomic_store(h + i, (unsigned short)v, __ATOMIC_RELAXED, SCOPE); }
+};
+
 // The launchers' shared argument checks.  Each returns GDKVM_OK or gdkvm_fail(...) with the kernel's name in front of the message; `code`
 // is the kernel's own code for that failure (lv_measure reports a bad cls and misaligned outputs as GDKVM_ERR_ARG, the others as
 // GDKVM_ERR_SHAPE).

@@ -115,6 +115,9 @@ SIGNATURES = {
     "gdkvm_seg_loss_workspace_bytes": (_sz, [_i]),
     "gdkvm_seg_loss_fwd": (_i, [_vp] * 4 + [_sz] + [_i] * 6 + [ctypes.c_float] * 2 + [_i, _i, _vp]),
     "gdkvm_seg_loss_bwd": (_i, [_vp] * 3 + [_sz] + [_vp] * 2 + [_i] * 8 + [_vp]),
+    "gdkvm_seg_loss_boundary_workspace_bytes": (_sz, [_i]),
+    "gdkvm_seg_loss_boundary_fwd": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [ctypes.c_float] * 3 + [ctypes.c_uint, _i, _i, _vp]),
+    "gdkvm_seg_loss_boundary_bwd": (_i, [_vp] * 4 + [_sz] + [_vp] * 2 + [_i] * 6 + [ctypes.c_uint, _i, _i, _vp]),
     "gdkvm_bn_workspace_bytes": (_sz, [_i]),
     "gdkvm_bn_fwd_train": (_i, [_vp] * 9 + [_sz, ctypes.c_longlong, _i, ctypes.c_float, ctypes.c_float, _i, _i, _vp]),
     "gdkvm_bn_bwd": (_i, [_vp] * 10 + [_sz, ctypes.c_longlong, _i, _i, _i, _vp]),
@@ -127,6 +130,8 @@ SIGNATURES = {
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
+    "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
+    "gdkvm_signed_distance": (_i, [_vp] * 3 + [_sz] + [_i] * 4 + [ctypes.c_uint, _vp]),
 }
 
 
@@ -1914,6 +1919,98 @@ def seg_loss(lowres_logits: torch.Tensor, target: torch.Tensor, dice_weight: flo
     """Cross-entropy + soft Dice of bilinear_upsample(lowres_logits -> target's H x W) against integer labels, without the
     full-resolution logits (gdkvm_seg_loss_fwd / _bwd).  lowres_logits [images,C,h,w], target [images,H,W]; scalar loss."""
     return _SegLossFunction.apply(lowres_logits, target, target.shape[-2], target.shape[-1], dice_weight, eps)
+
+
+SIGNED_DISTANCE_MAX_CLASSES = 32
+
+
+def _class_mask(what: str, num_classes: int, classes, default_from: int) -> int:
+    """Bit c = class c takes part.  classes None: every class from `default_from` on; otherwise distinct integers in 0..num_classes - 1."""
+    if classes is None:
+        return ((1 << int(num_classes)) - 1) & ~((1 << default_from) - 1)
+    cl = list(classes)
+    if any(isinstance(c, bool) or int(c) != c or not 0 <= int(c) < num_classes for c in cl) or len({int(c) for c in cl}) != len(cl):
+        raise GdkvmError(f"{what}: classes = {cl} must be distinct integers in 0..{num_classes - 1}")
+    mask = 0
+    for c in cl:
+        mask |= 1 << int(c)
+    return mask
+
+
+def _labels_u8(target: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """uint8 labels for the per-frame mask kernels: uint8 passes, int64 has everything outside [0, num_classes) mapped to 255 before the cast
+    (a plain cast would fold 256 onto class 0)."""
+    if target.dtype == torch.uint8:
+        return target
+    return torch.where((target < 0) | (target >= num_classes), 255, target).to(torch.uint8)
+
+
+def signed_distance(target: torch.Tensor, num_classes: int, classes=None, _mask: Optional[int] = None) -> torch.Tensor:
+    """gdkvm_signed_distance: per frame of target [..., H, W] (uint8, or int64 labels) and class c < num_classes the signed squared Euclidean
+    distance of every pixel to the class's contour -- + the squared distance to the nearest pixel of the class outside it, - the squared
+    distance to the nearest pixel outside the class inside it, 0 everywhere when the frame has no pixel of the class or no other (definition:
+    include/gdkvm.h; every output is an exact integer).  Returns int32 [..., num_classes, H, W]; `classes` (default: all) names the classes that
+    are computed, the planes of the others are zero.  The operand sd2 of seg_loss_boundary."""
+    if target.dtype not in (torch.uint8, torch.int64) or target.dim() < 2:
+        raise GdkvmError(f"signed_distance: target must be uint8 or int64 [..., H, W], got {target.dtype} {tuple(target.shape)}")
+    C = int(num_classes)
+    if not 1 <= C <= SIGNED_DISTANCE_MAX_CLASSES:
+        raise GdkvmError(f"signed_distance: num_classes = {num_classes} outside 1..{SIGNED_DISTANCE_MAX_CLASSES}")
+    mask = _class_mask("signed_distance", C, classes, 0) if _mask is None else _mask
+    dev = _dev(target)
+    t8 = _labels_u8(target, C)
+    lead, frames, H, W = _mask_frames("signed_distance", t8, 0)
+    sd2 = torch.empty(lead + (C, H, W), dtype=torch.int32, device=dev)
+    ws = _workspace("gdkvm_signed_distance_workspace_bytes", dev, frames, C, H, W, floor=16)
+    _call("gdkvm_signed_distance", dev, t8, sd2, _Ws(ws), frames, C, H, W, mask)
+    return sd2
+
+
+class _SegLossBoundaryFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, target, sd2, out, H, W, dice_weight, eps, boundary_weight, mask):
+        if z.dim() != 4 or not z.is_cuda or target.dim() != 3 or target.shape[0] != z.shape[0]:
+            raise GdkvmError("seg_loss_boundary: logits [images,C,h,w] and labels [images,H,W] on the device (no CPU path)")
+        if target.dtype not in (torch.int64, torch.uint8) or tuple(target.shape[1:]) != (H, W):
+            raise GdkvmError("seg_loss_boundary: labels must be int64 or uint8 [images,H,W]")
+        if not (math.isfinite(float(boundary_weight)) and float(boundary_weight) >= 0.0):
+            raise GdkvmError(f"seg_loss_boundary: boundary_weight = {boundary_weight} must be finite and >= 0")
+        z, target = z.contiguous(), target.contiguous()
+        ni, c, h, w = z.shape
+        if sd2 is None:
+            sd2 = signed_distance(target, c, _mask=mask)
+        elif sd2.dtype != torch.int32 or tuple(sd2.shape) != (ni, c, H, W) or sd2.device != z.device or not sd2.is_contiguous():
+            raise GdkvmError(f"seg_loss_boundary: sd2 must be contiguous int32 {(ni, c, H, W)} on the logits' device (ops.signed_distance)")
+        ws = _workspace("gdkvm_seg_loss_boundary_workspace_bytes", z.device, c)
+        tb = 8 if target.dtype == torch.int64 else 1
+        _call("gdkvm_seg_loss_boundary_fwd", z.device, z, target, sd2, out, _Ws(ws), ni, c, h, w, H, W, float(dice_weight), float(eps),
+              float(boundary_weight), mask, _io_dtype(z), tb)
+        ctx.save_for_backward(z, target, sd2, ws)
+        ctx.dims = (ni, c, h, w, H, W, tb, mask)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        z, target, sd2, ws = ctx.saved_tensors
+        ni, c, h, w, H, W, tb, mask = ctx.dims
+        g = g.to(torch.float32).reshape(1).contiguous()
+        dz = torch.empty_like(z)
+        _call("gdkvm_seg_loss_boundary_bwd", z.device, z, target, sd2, _Ws(ws), g, dz, ni, c, h, w, H, W, mask, _io_dtype(z), tb)
+        return (dz,) + (None,) * 9
+
+
+def seg_loss_boundary(lowres_logits: torch.Tensor, target: torch.Tensor, dice_weight: float = 1.0, eps: float = 1.0,
+                      boundary_weight: float = 0.0, classes=None, sd2: Optional[torch.Tensor] = None, terms: bool = False):
+    """seg_loss plus boundary_weight * the boundary loss of Kervadec et al. (gdkvm_seg_loss_boundary_fwd / _bwd; definition: include/gdkvm.h):
+    the mean over the labelled pixels of sum_{c in classes} softmax_c * signed distance to the contour of class c in `target`.  `classes`
+    default: every class but 0; the term is not divided by their number.  sd2: ops.signed_distance(target, C) when the caller has it already
+    (planes outside `classes` are not read); built here otherwise, and kept for the backward either way.  Scalar loss; terms=True: (loss,
+    float32 [4] = loss, CE, Dice term, L_B, detached)."""
+    mask = _class_mask("seg_loss_boundary", lowres_logits.shape[1], classes, 1)
+    out = torch.empty(4, dtype=torch.float32, device=lowres_logits.device)          # (written by the forward; never part of the autograd graph)
+    loss = _SegLossBoundaryFunction.apply(lowres_logits, target, sd2, out, target.shape[-2], target.shape[-1], dice_weight, eps,
+                                          boundary_weight, mask)
+    return (loss, out) if terms else loss
 
 
 def dice_from_counts(counts: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:

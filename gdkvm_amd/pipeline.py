@@ -320,14 +320,16 @@ class SegmentRunner:
 
 
 def make_train_step(model, opt_factory, frames: torch.Tensor, target: torch.Tensor, autocast_dtype, world: int, device,
-                    graph: bool = True, opt_state: Optional[dict] = None):
+                    graph: bool = True, opt_state: Optional[dict] = None, boundary_weight: float = 0.0, boundary_classes=None):
     """The training step train.py runs, in the form bench.py measures: ONE hipGraph replay per step (GraphedTrainStep) over the bare module,
     the gradient all-reduce a node of the graph (FlatGradSync) when world > 1, fused capturable AdamW -- or, loudly, the eager step
     (DistributedDataParallel + the default AdamW) when the capture fails or graph=False.  opt_factory(params, fused: bool, capturable: bool)
     -> optimiser (opt_state: a checkpoint's optimiser state, loaded before the capture).  Returns (step(frames, target) -> loss, optimiser,
     description dict); the shapes are those of `frames` / `target`.  The capture's warm-up runs info["warmup_steps"] REAL optimiser steps on
-    the batch given here: the caller counts them as iterations."""
+    the batch given here: the caller counts them as iterations.  boundary_weight / boundary_classes: the boundary term of the objective
+    (train.segmentation_loss), constants of the run -- the weight is baked into the captured graph."""
     from .train import FlatGradSync, GraphedTrainStep, train_step, wrap_ddp
+    bkw = {"boundary_weight": boundary_weight, "boundary_classes": boundary_classes} if boundary_weight else {}
     info = {"launch": "eager", "grad_sync": "none", "optimizer": "AdamW"}
     if graph:
         sync = None
@@ -338,7 +340,7 @@ def make_train_step(model, opt_factory, frames: torch.Tensor, target: torch.Tens
             opt = opt_factory(model.parameters(), True, True)
             if opt_state is not None:
                 opt.load_state_dict(opt_state)
-            gstep = GraphedTrainStep(model, opt, frames, target, autocast_dtype, warmup=2, grad_sync=sync)
+            gstep = GraphedTrainStep(model, opt, frames, target, autocast_dtype, warmup=2, grad_sync=sync, **bkw)
             info.update(launch="one hipGraph replay per step (GraphedTrainStep)", optimizer="AdamW(fused, capturable)", warmup_steps=gstep.eager_steps,
                         grad_sync="FlatGradSync: one flat-bucket all-reduce, a node of the graph" if sync is not None else "none (one rank)")
             return (lambda f, t: gstep(f, t)), opt, info
@@ -352,4 +354,4 @@ def make_train_step(model, opt_factory, frames: torch.Tensor, target: torch.Tens
     if opt_state is not None:
         opt.load_state_dict(opt_state)
     info.update(grad_sync="DistributedDataParallel" if ddp is not model else "none (one rank)")
-    return (lambda f, t: train_step(ddp, opt, f, t, autocast_dtype)), opt, info
+    return (lambda f, t: train_step(ddp, opt, f, t, autocast_dtype, **bkw)), opt, info

@@ -14,10 +14,55 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
-def segmentation_loss(logits: torch.Tensor, target: torch.Tensor, dice_weight: float = 1.0, eps: float = 1.0) -> torch.Tensor:
+def _dist2_to(S: torch.Tensor) -> torch.Tensor:
+    """int64 [N,H,W]: the squared Euclidean distance of every pixel to the nearest True pixel of its frame of S bool [N,H,W] (at least 2^40
+    where the frame has none).  Exact, separable: columns by running maxima of the last set row, rows by a minimum over the W columns."""
+    N, H, W = S.shape
+    big = 1 << 20
+    ys = torch.arange(H, device=S.device).view(1, H, 1)
+    above = torch.where(S, ys, -big).cummax(1).values                          # the last set row at or above
+    below = torch.where(S, ys, big + H).flip(1).cummin(1).values.flip(1)       # the first set row at or below
+    g = torch.minimum(ys - above, below - ys).clamp(max=big)
+    g2 = g * g
+    xs = torch.arange(W, device=S.device)
+    d2 = torch.full_like(g2, big * big)
+    for x2 in range(W):
+        d2 = torch.minimum(d2, g2[:, :, x2:x2 + 1] + (xs - x2) ** 2)
+    return d2
+
+
+def signed_distance_maps(target: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """The host twin of ops.signed_distance (definition: include/gdkvm.h): int64 [..., num_classes, H, W] signed squared distances of integer
+    labels [..., H, W] -- + to the nearest pixel of the class outside it, - to the nearest pixel outside the class inside it, 0 where the
+    class is absent from the frame or fills it.  Exact integers, plain torch on the labels' device."""
+    H, W = target.shape[-2:]
+    t = target.reshape(-1, 1, H, W).long()
+    A = (t == torch.arange(num_classes, device=t.device).view(1, -1, 1, 1)).reshape(-1, H, W)
+    n = A.sum((1, 2), keepdim=True)
+    s = torch.where(A, -_dist2_to(~A), _dist2_to(A))
+    s = torch.where((n == 0) | (n == H * W), torch.zeros_like(s), s)
+    return s.reshape(*target.shape[:-2], num_classes, H, W)
+
+
+def boundary_class_list(num_classes: int, classes=None) -> list:
+    """The classes of the boundary term: None = every class but 0, else distinct integers in 0..num_classes - 1."""
+    if classes is None:
+        return list(range(1, num_classes))
+    cl = list(classes)
+    if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < num_classes for c in cl) or len(set(cl)) != len(cl):
+        raise ValueError(f"boundary classes = {cl!r}: distinct integers in 0..{num_classes - 1}")
+    return cl
+
+
+def segmentation_loss(logits: torch.Tensor, target: torch.Tensor, dice_weight: float = 1.0, eps: float = 1.0,
+                      boundary_weight: float = 0.0, boundary_classes=None) -> torch.Tensor:
     """Cross-entropy + soft Dice over [B,T,ncls,H,W] logits and [B,T,H,W] integer labels (fp32 math).  Labels outside
     [0, ncls) are unlabelled pixels (EchoNet-Dynamic: every frame but the two traced ones): left out of the cross-entropy mean and of every
-    Dice sum -- intersection, target AND prediction mass (gdkvm_seg_loss_fwd does the same)."""
+    Dice sum -- intersection, target AND prediction mass (gdkvm_seg_loss_fwd does the same).
+    boundary_weight > 0 adds boundary_weight * the boundary loss of Kervadec et al. (gdkvm_seg_loss_boundary_fwd does the same): the mean over
+    the labelled pixels of sum_{c in boundary_classes} softmax_c * phi_c, phi_c the signed distance to the contour of class c in the target
+    (sqrt(s) outside, -(sqrt(-s) - 1) inside, from signed_distance_maps); boundary_classes None = every class but 0, no division by their
+    number."""
     B, T, C, H, W = logits.shape
     lg = logits.reshape(B * T, C, H, W).float()
     tg = target.reshape(B * T, H, W).long()
@@ -31,15 +76,27 @@ def segmentation_loss(logits: torch.Tensor, target: torch.Tensor, dice_weight: f
     oh = (F.one_hot(torch.where(labelled, tg, torch.zeros_like(tg)), C) * labelled.unsqueeze(-1)).permute(0, 3, 1, 2).float()
     inter = (p * oh).sum((0, 2, 3))
     dice = 1.0 - ((2 * inter + eps) / (p.sum((0, 2, 3)) + oh.sum((0, 2, 3)) + eps)).mean()
-    return ce + dice_weight * dice
+    if not boundary_weight:
+        return ce + dice_weight * dice
+    s = signed_distance_maps(tg, C).float()
+    phi = torch.where(s > 0, s.abs().sqrt(), torch.where(s < 0, 1.0 - s.abs().sqrt(), torch.zeros_like(s)))
+    take = torch.zeros(C, dtype=p.dtype, device=p.device)
+    take[boundary_class_list(C, boundary_classes)] = 1.0
+    lb = (p * phi * take.view(1, C, 1, 1)).sum() / labelled.sum().clamp_min(1)
+    return ce + dice_weight * dice + boundary_weight * lb
 
 
-def segmentation_loss_lowres(lowres_logits: torch.Tensor, target: torch.Tensor, dice_weight: float = 1.0, eps: float = 1.0) -> torch.Tensor:
+def segmentation_loss_lowres(lowres_logits: torch.Tensor, target: torch.Tensor, dice_weight: float = 1.0, eps: float = 1.0,
+                             boundary_weight: float = 0.0, boundary_classes=None) -> torch.Tensor:
     """segmentation_loss(bilinear_upsample(lowres_logits -> target size), target) as one fused HIP forward / backward
-    (ops.seg_loss): the full-resolution logits, their softmax and one-hot tensors never exist.  [B,T,ncls,h,w] logits."""
+    (ops.seg_loss): the full-resolution logits, their softmax and one-hot tensors never exist.  [B,T,ncls,h,w] logits.
+    boundary_weight > 0: ops.seg_loss_boundary, which builds the signed distance maps from `target` on the device (ops.signed_distance)."""
     from . import ops
     B, T, C, h, w = lowres_logits.shape
-    return ops.seg_loss(lowres_logits.reshape(B * T, C, h, w), target.reshape(B * T, *target.shape[-2:]), dice_weight, eps)
+    z, t = lowres_logits.reshape(B * T, C, h, w), target.reshape(B * T, *target.shape[-2:])
+    if not boundary_weight:
+        return ops.seg_loss(z, t, dice_weight, eps)
+    return ops.seg_loss_boundary(z, t, dice_weight, eps, boundary_weight, boundary_classes)
 
 
 def wrap_ddp(model: nn.Module, device: Optional[torch.device] = None, bucket_cap_mb: int = 25, force: bool = False) -> nn.Module:
@@ -138,9 +195,10 @@ class FlatGradSync:
 
 
 def train_step(model: nn.Module, opt: torch.optim.Optimizer, frames: torch.Tensor, target: torch.Tensor,
-               autocast_dtype: Optional[torch.dtype] = None, grad_sync=None) -> torch.Tensor:
+               autocast_dtype: Optional[torch.dtype] = None, grad_sync=None, boundary_weight: float = 0.0, boundary_classes=None) -> torch.Tensor:
     """forward -> loss -> backward (HIP backward kernels; DDP all-reduce if wrapped) -> [grad_sync(): FlatGradSync on a bare module] ->
-    optimiser step."""
+    optimiser step.  boundary_weight > 0 adds the boundary term to the objective (segmentation_loss); at 0 the step is the one of before,
+    call for call."""
     opt.zero_grad(set_to_none=True)
     fused = frames.is_cuda                      # GPU: the objective is evaluated on the stride-4 logits by the HIP loss kernels
     kw = {"_lowres": True} if fused else {}
@@ -149,7 +207,11 @@ def train_step(model: nn.Module, opt: torch.optim.Optimizer, frames: torch.Tenso
             logits = model(frames, **kw)
     else:
         logits = model(frames, **kw)
-    loss = segmentation_loss_lowres(logits, target) if fused else segmentation_loss(logits, target)
+    if not boundary_weight:
+        loss = segmentation_loss_lowres(logits, target) if fused else segmentation_loss(logits, target)
+    else:
+        bkw = {"boundary_weight": float(boundary_weight), "boundary_classes": boundary_classes}
+        loss = segmentation_loss_lowres(logits, target, **bkw) if fused else segmentation_loss(logits, target, **bkw)
     loss.backward()
     if grad_sync is not None:
         grad_sync()
@@ -188,11 +250,12 @@ class GraphedTrainStep:
     (a DistributedDataParallel wrapper is refused: its reducer is host logic); shapes are fixed at construction; the optimiser must be
     capturable (torch.optim.AdamW(..., fused=True, capturable=True)).  The first `warmup` steps run eagerly on a side stream (library
     convolutions pick their solvers, the HIP library sets its kernel attributes, the optimiser creates its state), then one step is
-    captured; every call copies the batch into the graph's input buffers and replays -- same arithmetic, same order, same results as
+    captured (with the boundary weight and classes given here, constants of the graph); every call copies the batch into the graph's input buffers and replays -- same arithmetic, same order, same results as
     train_step (tools/graph_step_diag.py prints both loss sequences side by side; tests/test_train_side_gpu.py asserts them equal)."""
 
     def __init__(self, model: nn.Module, opt: torch.optim.Optimizer, frames: torch.Tensor, target: torch.Tensor,
-                 autocast_dtype: Optional[torch.dtype] = None, warmup: int = 3, grad_sync=None):
+                 autocast_dtype: Optional[torch.dtype] = None, warmup: int = 3, grad_sync=None, boundary_weight: float = 0.0,
+                 boundary_classes=None):
         if not frames.is_cuda:
             raise RuntimeError("GraphedTrainStep needs device tensors")
         if isinstance(model, nn.parallel.DistributedDataParallel):
@@ -201,12 +264,14 @@ class GraphedTrainStep:
         self.frames, self.target = frames.clone(), target.clone()
         from .model import _capture_mode, _packs_held, _warm_up
         # (library convolutions pick their solvers, the optimiser creates its state; nothing of that may happen inside the capture)
-        _warm_up(frames.device, warmup, lambda: train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync))
+        # (the boundary weight is a constant of the run: it is baked into the captured launches)
+        bkw = {"boundary_weight": boundary_weight, "boundary_classes": boundary_classes} if boundary_weight else {}
+        _warm_up(frames.device, warmup, lambda: train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync, **bkw))
         self.graph = torch.cuda.CUDAGraph()
         # (a collective in the step is reason enough for the thread-local capture mode, whether or not a process group is up yet)
         mode = _capture_mode(thread_local=grad_sync is not None)
         with torch.cuda.graph(self.graph, **mode):
-            self.loss = train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync)
+            self.loss = train_step(model, opt, self.frames, self.target, autocast_dtype, grad_sync, **bkw)
         self.eager_steps = max(1, warmup)       # optimiser steps taken before the first replay (the capture itself runs no kernel)
         # the captured kernels address the per-weight packs (re-packed by the graph itself every replay) and other buffers the warm-up steps
         # allocated outside the graph's pool: held here, so that GDKVM.invalidate_packed_weights() (an eval() / train() toggle between steps)

@@ -575,6 +575,28 @@ int gdkvm_seg_loss_fwd(const void* z, const void* target, float* out, void* ws, 
 int gdkvm_seg_loss_bwd(const void* z, const void* target, const void* ws, size_t ws_bytes, const float* grad_out, void* dz,
                        int images, int C, int h, int w, int H, int W, int io_dtype, int target_bytes, void* stream);
 
+/* The same objective with the boundary loss of Kervadec et al. (MIDL 2019) as a third term:  loss = CE + dice_weight * Dice + boundary_weight * L_B,
+ *   L_B = (1 / n_lab) sum over the labelled pixels x, sum over c in K, of p_c(x) phi_c(x)
+ * with p the softmax of the upsampled logits as above, n_lab the count of labelled pixels clamped to 1 (the cross-entropy's own denominator; an
+ * unlabelled pixel adds nothing), K the classes whose bit is set in class_mask (bit c = class c; no bit at or above C), and phi_c the signed
+ * distance to the contour of class c as the paper's reference implementation defines it (edt(neg) neg - (edt(pos) - 1) pos), evaluated in fp32
+ * inside the kernels from sd2 [images, C, H, W] int32, the signed squared distances of gdkvm_signed_distance for the SAME target:
+ *   s > 0: phi = sqrt(s);   s < 0: phi = -(sqrt(-s) - 1);   s = 0: phi = 0.
+ * L_B is NOT divided by |K|: boundary_weight absorbs it (a weight tuned for three foreground classes is three times a per-class weight).
+ * The planes of sd2 outside class_mask are never read.  boundary_weight is finite and >= 0.
+ * fwd: out[0] = loss, out[1] = CE, out[2] = Dice term, out[3] = L_B.
+ * bwd: with respect to an upsampled logit the term adds  boundary_weight / n_lab * p_c (psi_c - sum_k p_k psi_k),  psi_c = phi_c for c in K, else 0
+ * -- one more summand of u_c in the gather of gdkvm_seg_loss_bwd; deterministic.  class_mask as in the forward.
+ * ws: gdkvm_seg_loss_boundary_workspace_bytes(C), the SAME buffer for fwd and bwd (one partial sum more than gdkvm_seg_loss_workspace_bytes).
+ * gdkvm_seg_loss_fwd / _bwd are unchanged by these entries. */
+size_t gdkvm_seg_loss_boundary_workspace_bytes(int C);
+int gdkvm_seg_loss_boundary_fwd(const void* z, const void* target, const int32_t* sd2, float* out, void* ws, size_t ws_bytes,
+                                int images, int C, int h, int w, int H, int W, float dice_weight, float eps, float boundary_weight,
+                                unsigned class_mask, int io_dtype, int target_bytes, void* stream);
+int gdkvm_seg_loss_boundary_bwd(const void* z, const void* target, const int32_t* sd2, const void* ws, size_t ws_bytes,
+                                const float* grad_out, void* dz, int images, int C, int h, int w, int H, int W, unsigned class_mask,
+                                int io_dtype, int target_bytes, void* stream);
+
 /* Training-clip augmentation folded into the uint8 -> [0, 1] cast of a batch (gdkvm_amd.pipeline.DevicePrefetcher): one pass, one launch.
  * frames uint8 [B,T,C,H,W]; target [B,T,H,W] (target_bytes = 1: uint8, 8: int64; target and target_out alike, both may be NULL together);
  * params fp32 [B,12] on the device, one row per clip -- every frame of a clip gets the same warp (the memory path needs temporally
@@ -676,6 +698,25 @@ int gdkvm_largest_component(const uint8_t* mask, const uint8_t* target, uint8_t*
 size_t gdkvm_surface_distance_workspace_bytes(int frames, int H, int W);
 int gdkvm_surface_distance(const uint8_t* mask, const uint8_t* target, int64_t* surf, void* workspace, size_t workspace_bytes,
                            int frames, int H, int W, int cls, void* stream);
+
+/* Signed squared distance maps of label frames (the operand of gdkvm_seg_loss_boundary_fwd / _bwd; csrc/signed_distance.hip).  Every output is
+ * an integer that depends on neither the algorithm nor the schedule.  Distances are in pixels of the frame's grid (isotropic pixels assumed).
+ * Per frame t [H, W] uint8 of target [frames, H, W] and class c in [0, C), 1 <= C <= 32, H, W in 1..1024:  A = {x : t(x) == c}; every other
+ * byte, a label outside [0, C) such as 255 included, is not c and belongs to the complement.  sd2 [frames, C, H, W] int32:
+ *   A empty or A = the whole frame:  s_c = 0 everywhere;
+ *   x outside A:  s_c(x) = + min over y in A of |x - y|^2;        x in A:  s_c(x) = - min over y outside A of |x - y|^2.
+ * So s_c(x) = 0 only where the class is absent from the frame or fills it, and |s_c| <= 2 * 1023^2.
+ * The plane of a class whose bit is clear in class_mask (bit c = class c) is zero-filled.
+ * target is contiguous at ANY byte address (frames of H W bytes follow each other); sd2 is 4-byte aligned.  The workspace (16-byte aligned, at
+ * least gdkvm_signed_distance_workspace_bytes(frames, C, H, W) bytes) is scratch: 0 while H W <= 79872 -- a (frame, class) keeps one 16-bit word
+ * per pixel (its kind and the vertical distance to the other kind in its column), which then live in up to 156 KiB of dynamic LDS (a 256 x 256
+ * frame: 128 KiB) -- else those 2 bytes per pixel with each plane rounded up to 128 bytes.  One workgroup per (frame, class); neither entry
+ * allocates or synchronises; no workgroup waits for another; bit-reproducible; every loop of the kernel is bounded by H, W or H W / lanes.  Bad
+ * arguments (shape, C, null or misaligned pointers, a short workspace) are GDKVM_ERR_SHAPE before any device call; frames == 0 is GDKVM_OK
+ * without a launch. */
+size_t gdkvm_signed_distance_workspace_bytes(int frames, int C, int H, int W);
+int gdkvm_signed_distance(const uint8_t* target, int32_t* sd2, void* workspace, size_t workspace_bytes,
+                          int frames, int C, int H, int W, unsigned class_mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -79,9 +79,13 @@ def main(argv=None):
             if train_one is None:
                 # the step in the form bench.py measures: one hipGraph replay (forward + backward + gradient all-reduce node + fused AdamW);
                 # a capture that fails falls back to the eager DistributedDataParallel step, loudly
-                train_one, opt, how = make_train_step(model, adamw, frames, target, amp, world, dev, graph=use_graph, opt_state=opt_state)
+                train_one, opt, how = make_train_step(model, adamw, frames, target, amp, world, dev, graph=use_graph, opt_state=opt_state,
+                                                      boundary_weight=cfg.loss.boundary_weight, boundary_classes=cfg.loss.boundary_classes)
                 if rank == 0:
                     print(f"train step: {how['launch']}; gradient exchange: {how['grad_sync']}; optimiser: {how['optimizer']}", flush=True)
+                    if cfg.loss.boundary_weight:
+                        print(f"objective: CE + Dice + {cfg.loss.boundary_weight} x boundary loss over classes "
+                              f"{cfg.loss.boundary_classes if cfg.loss.boundary_classes is not None else 'all but 0'}", flush=True)
                 step += how.get("warmup_steps", 0)                # (the capture's warm-up steps are real optimiser steps on this batch)
             loss = train_one(frames, target)
             step += 1
