@@ -9,7 +9,9 @@ computed from the unfiltered mask.  With `data.surface_class` >= 0 a `surface` b
 ASSD between predicted mask and target (ops.surface_distance / surface_metrics: pixels of the input grid, over the labelled frames where both
 have a surface).  The surface distances are those of the unfiltered mask, whatever `data.lv_keep_largest` says.
 
-    python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [key=value ...]"""
+--ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
+
+    python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [key=value ...]"""
 from __future__ import annotations
 
 import argparse
@@ -28,6 +30,7 @@ def main(argv=None):
     ap.add_argument("--config", default=os.path.join(ROOT, "config", "config_gdkvm_01.yaml"))
     ap.add_argument("--weights", default="")
     ap.add_argument("--split", default="val")
+    ap.add_argument("--ema", action="store_true", help="evaluate the checkpoint's EMA weights (optim.ema_decay > 0 runs)")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv)
 
@@ -47,8 +50,14 @@ def main(argv=None):
                        value_dim=cfg.model.value_dim, rule=cfg.model.rule,
                        scan_segments=cfg.model.scan_segments, mask_feedback=cfg.model.mask_feedback)
     model = GDKVM(mcfg).eval()
+    if args.ema and not args.weights:
+        raise SystemExit("eval.py: --ema needs --weights (the averaged weights live in a checkpoint)")
     if args.weights:
-        model.load_state_dict(torch.load(args.weights, map_location="cpu")["model"])
+        ck = torch.load(args.weights, map_location="cpu")
+        if args.ema and "ema" not in ck:
+            raise SystemExit(f"eval.py: --ema: {args.weights} holds no averaged weights (no \"ema\" entry): it was trained without "
+                             "optim.kind=native and optim.ema_decay > 0")
+        model.load_state_dict(ck["ema"] if args.ema else ck["model"])
     model = model.fuse_for_inference().to(dev)
     if cfg.precision == "bf16":
         model = model.to(torch.bfloat16)

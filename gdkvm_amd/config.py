@@ -64,6 +64,27 @@ class LossCfg:
 
 
 @dataclass
+class OptimCfg:
+    """The optimiser.  kind: torch = torch.optim.AdamW (fused and capturable in the captured step), the run of before; native = optim.NativeAdamW
+    (csrc/adamw.hip), which alone knows the keys from decay_1d on: under kind: torch they must keep their defaults, nothing is silently ignored.
+    The schedule's total_steps is num_iterations."""
+    kind: str = "torch"
+    weight_decay: float = 0.01                                     # torch.optim.AdamW's own default
+    betas: List[float] = field(default_factory=lambda: [0.9, 0.999])
+    eps: float = 1e-8
+    decay_1d: bool = True                                          # false: parameters with dim <= 1 (BatchNorm scales, every bias) get decay 0
+    clip_norm: float = 0.0                                         # global gradient-norm clipping; 0 = off
+    schedule: str = "constant"                                     # constant | cosine | poly, after warmup_steps of linear warm-up
+    warmup_steps: int = 0
+    min_lr_ratio: float = 0.0                                      # the schedule ends at learning_rate * min_lr_ratio
+    poly_power: float = 0.9
+    ema_decay: float = 0.0                                         # > 0: an EMA of the weights, saved as the checkpoint's "ema" (eval.py --ema)
+
+
+OPTIM_NATIVE_ONLY = ("decay_1d", "clip_norm", "schedule", "warmup_steps", "min_lr_ratio", "poly_power", "ema_decay")
+
+
+@dataclass
 class RunConfig:
     data_path: str = ""
     batch_size: int = 8
@@ -74,6 +95,7 @@ class RunConfig:
     model: ModelCfg = field(default_factory=ModelCfg)
     augment: AugmentCfg = field(default_factory=AugmentCfg)
     loss: LossCfg = field(default_factory=LossCfg)
+    optim: OptimCfg = field(default_factory=OptimCfg)
     run_dir: str = "outputs"
     save_every: int = 1000
     log_every: int = 20
@@ -128,4 +150,42 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
         if not isinstance(bc, list) or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < cfg.data.num_classes for c in bc) \
                 or len(set(bc)) != len(bc):
             raise ValueError(f"loss.boundary_classes = {bc!r}: null (every class but 0) or distinct integers in 0..{cfg.data.num_classes - 1}")
+    _check_optim(cfg.optim)
     return cfg
+
+
+def _check_optim(o: OptimCfg) -> None:
+    num = lambda x: not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x)
+    if o.kind not in ("torch", "native"):
+        raise ValueError(f"optim.kind = {o.kind!r}: torch or native")
+    for key in ("weight_decay", "eps", "clip_norm", "poly_power", "min_lr_ratio", "ema_decay"):      # (YAML 1.1 reads 1e-8, without a dot, as a string)
+        if isinstance(getattr(o, key), str):
+            try:
+                setattr(o, key, float(getattr(o, key)))
+            except ValueError:
+                pass
+    for key in ("weight_decay", "eps", "clip_norm", "poly_power"):
+        if not num(getattr(o, key)) or getattr(o, key) < 0:
+            raise ValueError(f"optim.{key} = {getattr(o, key)!r}: a finite number >= 0")
+        setattr(o, key, float(getattr(o, key)))
+    if not isinstance(o.betas, list) or len(o.betas) != 2 or not all(num(b) and 0 <= b < 1 for b in o.betas):
+        raise ValueError(f"optim.betas = {o.betas!r}: two numbers in [0, 1)")
+    o.betas = [float(b) for b in o.betas]
+    if not isinstance(o.decay_1d, bool):
+        raise ValueError(f"optim.decay_1d = {o.decay_1d!r}: true or false")
+    if o.schedule not in ("constant", "cosine", "poly"):
+        raise ValueError(f"optim.schedule = {o.schedule!r}: constant, cosine or poly")
+    if isinstance(o.warmup_steps, bool) or not isinstance(o.warmup_steps, int) or o.warmup_steps < 0:
+        raise ValueError(f"optim.warmup_steps = {o.warmup_steps!r}: an integer >= 0")
+    if not num(o.min_lr_ratio) or not 0 <= o.min_lr_ratio <= 1:
+        raise ValueError(f"optim.min_lr_ratio = {o.min_lr_ratio!r}: a number in [0, 1]")
+    o.min_lr_ratio = float(o.min_lr_ratio)
+    if not num(o.ema_decay) or not 0 <= o.ema_decay < 1:
+        raise ValueError(f"optim.ema_decay = {o.ema_decay!r}: a number in [0, 1) (0 = off)")
+    o.ema_decay = float(o.ema_decay)
+    if o.kind == "torch":
+        default = OptimCfg()
+        set_ = [k for k in OPTIM_NATIVE_ONLY if getattr(o, k) != getattr(default, k)]
+        if set_:
+            raise ValueError(f"optim.{set_[0]} = {getattr(o, set_[0])!r} needs optim.kind = native: torch.optim.AdamW has no such option "
+                             f"(native-only keys: {', '.join(OPTIM_NATIVE_ONLY)})")

@@ -132,6 +132,8 @@ SIGNATURES = {
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
     "gdkvm_signed_distance": (_i, [_vp] * 3 + [_sz] + [_i] * 4 + [ctypes.c_uint, _vp]),
+    "gdkvm_adamw_workspace_bytes": (_sz, [_i, ctypes.c_longlong]),
+    "gdkvm_adamw_step": (_i, [_vp] * 7 + [_i, _vp, _vp, _sz] + [ctypes.c_double] * 8 + [ctypes.c_longlong] * 2 + [_i, _vp]),
 }
 
 
@@ -2185,3 +2187,44 @@ def surface_stats(sums) -> dict:
     n, one, hd, hd95, assd = (float(v) for v in sums)
     d = n if n >= 1 else 1.0
     return {"frames": int(n), "frames_one_empty": int(one), "hd_mean": hd / d, "hd95_mean": hd95 / d, "assd_mean": assd / d}
+
+
+ADAMW_SCHEDULES = {"constant": 0, "cosine": 1, "poly": 2}      # GDKVM_SCHEDULE_*
+ADAMW_STATE_WORDS = 8                                          # GDKVM_ADAMW_STATE_BYTES / 8
+
+
+def adamw_state(device) -> torch.Tensor:
+    """The persistent state block of adamw_step, zeroed: int64 [8] -- [0] step, [1] skipped, [2:5] viewed as float64 the last gradient norm,
+    clip coefficient and learning rate, the rest private to the kernels."""
+    return torch.zeros(ADAMW_STATE_WORDS, dtype=torch.int64, device=device)
+
+
+def adamw_workspace(device, tensors: int, total_elems: int) -> torch.Tensor:
+    """A workspace for adamw_step over `tensors` tensors of `total_elems` elements in all (one fp32 partial per 4096-element chunk)."""
+    return _workspace("gdkvm_adamw_workspace_bytes", device, int(tensors), int(total_elems), floor=16)
+
+
+def adamw_step(addresses: torch.Tensor, counts: torch.Tensor, decays: torch.Tensor, state: torch.Tensor, workspace: torch.Tensor, *,
+               lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float = 0.0, ema_decay: float = 0.0, schedule: str = "constant",
+               warmup_steps: int = 0, total_steps: int = 0, min_lr_ratio: float = 0.0, poly_power: float = 0.9) -> None:
+    """gdkvm_adamw_step (definition: include/gdkvm.h): one AdamW step with global-norm clipping, the scheduled learning rate, the non-finite
+    guard and the EMA over the tensors whose DEVICE addresses the HOST tensor `addresses` holds -- int64 [5, n] on the CPU, rows: parameter,
+    gradient, exp_avg, exp_avg_sq, EMA copy (0 = none; the row is ignored while ema_decay == 0) -- with `counts` int64 [n] and `decays` fp32 [n]
+    on the CPU too.  All tensors addressed are fp32 on state's device, and gradient / moments / EMA pair with the parameter by address.  `state`
+    (adamw_state) and `workspace` (adamw_workspace) live on the device; three kernels on the current stream, nothing synchronises."""
+    n = int(counts.numel())
+    if (addresses.device.type != "cpu" or addresses.dtype != torch.int64 or tuple(addresses.shape) != (5, n) or not addresses.is_contiguous()
+            or counts.device.type != "cpu" or counts.dtype != torch.int64 or not counts.is_contiguous()
+            or decays.device.type != "cpu" or decays.dtype != torch.float32 or tuple(decays.shape) != (n,) or not decays.is_contiguous()):
+        raise GdkvmError("adamw_step: addresses int64 [5, n], counts int64 [n] and decays fp32 [n] must be contiguous CPU tensors")
+    if schedule not in ADAMW_SCHEDULES:
+        raise GdkvmError(f"adamw_step: schedule = {schedule!r}, one of {sorted(ADAMW_SCHEDULES)}")
+    dev = _dev(state, workspace)
+    if state.dtype != torch.int64 or state.numel() != ADAMW_STATE_WORDS:
+        raise GdkvmError(f"adamw_step: state must be int64 [{ADAMW_STATE_WORDS}] (ops.adamw_state)")
+    if n == 0:
+        return
+    a = addresses
+    _call("gdkvm_adamw_step", dev, a[0], a[1], a[2], a[3], a[4] if ema_decay > 0 else None, counts, decays, n, state, _Ws(workspace),
+          float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_norm), float(ema_decay), float(min_lr_ratio), float(poly_power),
+          int(warmup_steps), int(total_steps), ADAMW_SCHEDULES[schedule])

@@ -319,6 +319,15 @@ class SegmentRunner:
         return self.submit(frames, target).get()
 
 
+def _optimizer_name(opt) -> str:
+    """The optimiser actually built, for make_train_step's description: the class, and for torch's AdamW the form it runs in."""
+    name = type(opt).__name__
+    g = opt.param_groups[0] if opt.param_groups else {}
+    if g.get("fused"):
+        name += "(fused, capturable)" if g.get("capturable") else "(fused)"
+    return name
+
+
 def make_train_step(model, opt_factory, frames: torch.Tensor, target: torch.Tensor, autocast_dtype, world: int, device,
                     graph: bool = True, opt_state: Optional[dict] = None, boundary_weight: float = 0.0, boundary_classes=None):
     """The training step train.py runs, in the form bench.py measures: ONE hipGraph replay per step (GraphedTrainStep) over the bare module,
@@ -341,7 +350,7 @@ def make_train_step(model, opt_factory, frames: torch.Tensor, target: torch.Tens
             if opt_state is not None:
                 opt.load_state_dict(opt_state)
             gstep = GraphedTrainStep(model, opt, frames, target, autocast_dtype, warmup=2, grad_sync=sync, **bkw)
-            info.update(launch="one hipGraph replay per step (GraphedTrainStep)", optimizer="AdamW(fused, capturable)", warmup_steps=gstep.eager_steps,
+            info.update(launch="one hipGraph replay per step (GraphedTrainStep)", optimizer=_optimizer_name(opt), warmup_steps=gstep.eager_steps,
                         grad_sync="FlatGradSync: one flat-bucket all-reduce, a node of the graph" if sync is not None else "none (one rank)")
             return (lambda f, t: gstep(f, t)), opt, info
         except Exception as e:                  # noqa: BLE001
@@ -353,5 +362,5 @@ def make_train_step(model, opt_factory, frames: torch.Tensor, target: torch.Tens
     opt = opt_factory(model.parameters(), False, False)
     if opt_state is not None:
         opt.load_state_dict(opt_state)
-    info.update(grad_sync="DistributedDataParallel" if ddp is not model else "none (one rank)")
+    info.update(grad_sync="DistributedDataParallel" if ddp is not model else "none (one rank)", optimizer=_optimizer_name(opt))
     return (lambda f, t: train_step(ddp, opt, f, t, autocast_dtype, **bkw)), opt, info

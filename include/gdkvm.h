@@ -718,6 +718,40 @@ size_t gdkvm_signed_distance_workspace_bytes(int frames, int C, int H, int W);
 int gdkvm_signed_distance(const uint8_t* target, int32_t* sd2, void* workspace, size_t workspace_bytes,
                           int frames, int C, int H, int W, unsigned class_mask, void* stream);
 
+/* The optimiser step (csrc/adamw.hip): multi-tensor AdamW (decoupled weight decay, torch.optim.AdamW's update) over `tensors` fp32 tensors with
+ * global-norm gradient clipping, a learning-rate schedule, a non-finite guard and an optional EMA of the weights, as three kernels on `stream`.
+ * params, grads, exp_avg, exp_avg_sq, ema are HOST arrays of device addresses (4-byte aligned; 16-byte aligned tensors take 16-byte accesses),
+ * counts / decays HOST arrays of element counts (1 .. 2^31 - 4097) and per-tensor weight decays; element i of a tensor's gradient and moments
+ * belongs to element i of its parameter BY ADDRESS.  ema may be null, and so may single entries of it; it is read only when ema_decay > 0.
+ * The addresses travel to the kernels by value in the kernel arguments (a capture holds them; nothing is copied to the device), at most 76
+ * tensors per launch, longer lists in several launches.
+ *   1. sum of squares: one fp32 partial per 4096-element chunk of a gradient, summed in a fixed order, at the chunk's index over the whole
+ *      list in the workspace (gdkvm_adamw_workspace_bytes(tensors, total elements) bytes, an upper bound; 4-byte aligned).
+ *   2. finalise, in double: S = the partials summed in a fixed order, norm = sqrt(S).  S not finite (a gradient holds inf or NaN, or a square
+ *      overflows fp32): apply = 0, skipped += 1, step stays.  Otherwise t = step + 1 is stored,
+ *        coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1                         (torch.nn.utils.clip_grad_norm_)
+ *        lr(t) = lr t / W  while t <= W = warmup_steps;  past it, with s = min(1, (t - W) / max(1, total_steps - W)), r = min_lr_ratio:
+ *                GDKVM_SCHEDULE_CONSTANT  lr        GDKVM_SCHEDULE_COSINE  lr (r + (1 - r) (1 + cos(pi s)) / 2)
+ *                GDKVM_SCHEDULE_POLY      lr (r + (1 - r) (1 - s)^poly_power)
+ *        bc1 = 1 - beta1^t, bc2 = 1 - beta2^t;  coef, lr(t), lr(t) / bc1 and sqrt(bc2) are rounded once to fp32 for the update.
+ *   3. update (nothing is written when apply = 0), per element in fp32 with g' = coef g:
+ *        m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  p = p (1 - lr(t) wd) - (lr(t) / bc1) m / (sqrt(v) / sqrt(bc2) + eps);
+ *        ema entry present: e = ema_decay e + (1 - ema_decay) p.     The gradient is read, never written: it keeps its unclipped values.
+ * state: GDKVM_ADAMW_STATE_BYTES bytes on the device (8-byte aligned), zeroed by the caller before the first step and kept between steps:
+ *   int64 step, int64 skipped, double grad_norm, double clip_coef, double lr (of the last step; a skipped step stores its norm and coef 0),
+ *   then 24 bytes private to the kernels.  The caller may read it, and may write `step` between calls (a resumed run).
+ * No atomics; no workgroup waits for another; nothing allocates or synchronises; bit-reproducible, and independent of the split into launches
+ * and of the alignment of the tensors.  Bad arguments (null or misaligned addresses, a count outside its range, a short workspace, betas
+ * outside [0, 1), negative or non-finite lr / eps / decay / max_norm / poly_power, ema_decay outside [0, 1), an unknown schedule, min_lr_ratio
+ * outside [0, 1], negative step counts) are GDKVM_ERR_SHAPE before any device call; tensors == 0 is GDKVM_OK without a launch. */
+enum { GDKVM_SCHEDULE_CONSTANT = 0, GDKVM_SCHEDULE_COSINE = 1, GDKVM_SCHEDULE_POLY = 2 };
+#define GDKVM_ADAMW_STATE_BYTES 64
+size_t gdkvm_adamw_workspace_bytes(int tensors, long long total_elems);
+int gdkvm_adamw_step(const uint64_t* params, const uint64_t* grads, const uint64_t* exp_avg, const uint64_t* exp_avg_sq, const uint64_t* ema,
+                     const int64_t* counts, const float* decays, int tensors, void* state, void* workspace, size_t workspace_bytes,
+                     double lr, double beta1, double beta2, double eps, double max_norm, double ema_decay, double min_lr_ratio,
+                     double poly_power, long long warmup_steps, long long total_steps, int schedule, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

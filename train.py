@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training entry point: one process per GPU under torchrun, ONE gradient all-reduce per step over RCCL.
 The step runs in the form bench.py measures -- one hipGraph replay: forward, backward, the flat-bucket all-reduce as a node of the graph,
-fused AdamW (gdkvm_amd.pipeline.make_train_step; GDKVM_TRAIN_GRAPH=0 or a failed capture: the eager DistributedDataParallel step, said
+the optimiser step (fused AdamW, or with optim.kind=native the library's own: gdkvm_amd.pipeline.make_train_step; GDKVM_TRAIN_GRAPH=0 or a failed capture: the eager DistributedDataParallel step, said
 loudly) -- on batches prefetched through pinned memory on a side stream (gdkvm_amd.pipeline.DevicePrefetcher).
 
     python train.py --config config/config_gdkvm_01.yaml [key=value ...]                       # one GPU
@@ -20,6 +20,28 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+
+def optimizer_factory(cfg, model):
+    """opt_factory(params, fused, capturable) for pipeline.make_train_step from the config's optim section.  kind: torch -- torch.optim.AdamW,
+    fused and capturable in the captured step; kind: native -- optim.NativeAdamW over the model's named parameters (its one step serves the
+    captured and the eager form alike), with decay 0 for the parameters of dim <= 1 when decay_1d is off."""
+    o = cfg.optim
+    if o.kind == "torch":
+        return lambda params, fused, capturable: torch.optim.AdamW(params, lr=cfg.learning_rate, betas=tuple(o.betas), eps=o.eps, weight_decay=o.weight_decay,
+                                                                   **({"fused": True, "capturable": capturable} if fused else {}))
+    from gdkvm_amd.optim import NativeAdamW
+
+    def native(params, fused, capturable):
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        flat = [(n, p) for n, p in named if p.dim() <= 1 and not o.decay_1d]
+        groups = [{"params": [(n, p) for n, p in named if not (p.dim() <= 1 and not o.decay_1d)], "weight_decay": o.weight_decay}]
+        if flat:
+            groups.append({"params": flat, "weight_decay": 0.0})
+        return NativeAdamW(groups, lr=cfg.learning_rate, betas=tuple(o.betas), eps=o.eps, weight_decay=o.weight_decay, max_norm=o.clip_norm,
+                           schedule=o.schedule, warmup_steps=o.warmup_steps, total_steps=cfg.num_iterations, min_lr_ratio=o.min_lr_ratio,
+                           poly_power=o.poly_power, ema_decay=o.ema_decay)
+    return native
 
 
 def main(argv=None):
@@ -70,7 +92,7 @@ def main(argv=None):
     step, t_log = step0, time.perf_counter()
     train_one = opt = None                                        # built on the first batch (the graph is captured for its shape)
     use_graph = os.environ.get("GDKVM_TRAIN_GRAPH", "1") != "0"
-    adamw = lambda params, fused, capturable: torch.optim.AdamW(params, lr=cfg.learning_rate, **({"fused": True, "capturable": capturable} if fused else {}))
+    adamw = optimizer_factory(cfg, model)
     while step < cfg.num_iterations:
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -93,12 +115,19 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t_log; t_log = time.perf_counter()
                 fps = world * cfg.batch_size * cfg.data.frames * cfg.log_every / dt
-                run.log(step, loss=float(loss), frames_per_s=fps)
-                print(f"step {step:6d}  loss {float(loss):.4f}  {fps:9.0f} frames/s", flush=True)
+                extra, tail = {}, ""
+                if hasattr(opt, "stats"):                         # the native optimiser: one more read beside the synchronise above
+                    st = opt.stats()
+                    extra = {"grad_norm": st["grad_norm"], "lr": st["lr"], "skipped": st["skipped"]}
+                    tail = f"  grad_norm {st['grad_norm']:.4g}  lr {st['lr']:.3e}  skipped {st['skipped']}"
+                run.log(step, loss=float(loss), frames_per_s=fps, **extra)
+                print(f"step {step:6d}  loss {float(loss):.4f}  {fps:9.0f} frames/s{tail}", flush=True)
             if (step % cfg.save_every == 0 or step >= cfg.num_iterations) and rank == 0:
                 os.makedirs(cfg.run_dir, exist_ok=True)
-                torch.save({"model": model.state_dict(), "optimizer": opt.state_dict(), "step": step, "epoch": epoch, "config": cfg.to_dict()},
-                           os.path.join(cfg.run_dir, f"gdkvm_step{min(step, cfg.num_iterations)}.pth"))
+                ck = {"model": model.state_dict(), "optimizer": opt.state_dict(), "step": step, "epoch": epoch, "config": cfg.to_dict()}
+                if cfg.optim.kind == "native" and cfg.optim.ema_decay > 0:
+                    ck["ema"] = opt.ema_state_dict(model)          # the averaged weights: eval.py --ema
+                torch.save(ck, os.path.join(cfg.run_dir, f"gdkvm_step{min(step, cfg.num_iterations)}.pth"))
             if step >= cfg.num_iterations:
                 break
         epoch += 1
