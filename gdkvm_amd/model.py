@@ -1228,7 +1228,10 @@ def _warm_up(device, warmup: int, step) -> None:
 def _capture_mode(thread_local: bool = False, **kw) -> dict:
     """Keyword arguments of torch.cuda.graph (`kw`: the caller's own, e.g. pool).  With a process group alive its watchdog THREAD may poll
     events of earlier collectives while this thread captures: under the default "global" capture mode its hipEventQuery aborts the process with
-    "operation not permitted when stream is capturing" (measured round 5 in train.GraphedTrainStep) -- so only this thread is policed."""
+    "operation not permitted when stream is capturing" (measured round 5 in train.GraphedTrainStep) -- so only this thread is policed.
+    GraphedSegment always asks for it: eval.py and train.py capture a forward in the middle of an epoch, while the DataLoader's pin-memory
+    THREAD page-locks the next batches (host allocations and event queries of the pinned-memory cache); under the "global" mode such a call
+    now and then invalidated the capture ("operation failed due to a previous error during capture" at the forward's first launch)."""
     if thread_local or (torch.distributed.is_available() and torch.distributed.is_initialized()):
         kw["capture_error_mode"] = "thread_local"
     return kw
@@ -1284,7 +1287,7 @@ class GraphedSegment:
         with torch.no_grad():
             _warm_up(frames.device, warmup, eager)
             self.graph = torch.cuda.CUDAGraph()
-            mode = _capture_mode(pool=pool)
+            mode = _capture_mode(thread_local=True, pool=pool)
             if streams == 1:
                 with torch.cuda.graph(self.graph, **mode):
                     self.out = model.segment(self.frames, self.target, **kw)

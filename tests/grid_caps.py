@@ -63,9 +63,10 @@ def function_body(text, name):
     raise LookupError(name)
 
 
-def source_constant(name, csrc=CSRC):
-    """The value the .hip source gives the constant `name` (products and shifts of integer literals are evaluated)."""
-    _, fname, where, rx = CONSTANTS[name]
+def source_constant(name, csrc=CSRC, table=None):
+    """The value the .hip source gives the constant `name` of `table` (this file's CONSTANTS unless given; products and shifts of integer
+    literals are evaluated)."""
+    _, fname, where, rx = (CONSTANTS if table is None else table)[name]
     with open(os.path.join(csrc, fname)) as f:
         text = f.read()
     scope = text if where is None else function_body(text, where)

@@ -158,7 +158,8 @@ def test_scan_backward_no_state_input(hip):
     assert tq.grad is not None and torch.isfinite(tq.grad).all()
 
 
-@pytest.mark.parametrize("case", [(3, 7, 7, 64, 256, 256), (2, 16, 16, 32, 64, 64), (2, 5, 3, 16, 16, 32)])
+@pytest.mark.parametrize("case", [(3, 7, 7, 64, 256, 256), (2, 16, 16, 32, 64, 64), (2, 5, 3, 16, 16, 32),
+                                  (3, 6, 19, 32, 32, 64), (2, 14, 14, 64, 64, 128)])       # (the last two: column-tiled, row bands with a ragged one)
 def test_kpff_backward_fp32(hip, case):
     from tests.util import make_kpff_inputs
     BT, h, w, Ck, Cv, Cp = case
@@ -175,11 +176,11 @@ def test_kpff_backward_fp32(hip, case):
         assert err <= 2e-4 * max(1.0, np.abs(r).max()), (name, err, np.abs(r).max())
 
 
-def test_kpff_backward_bf16(hip):
+def _kpff_backward_bf16(hip, case, seed):
     from oracle import gdkvm_oracle as O
     from tests.util import make_kpff_inputs
-    BT, h, w, Ck, Cv, Cp = 3, 7, 7, 64, 256, 256
-    arrs = make_kpff_inputs(BT, h, w, Ck, Cv, Cp, seed=51)
+    BT, h, w, Ck, Cv, Cp = case
+    arrs = make_kpff_inputs(BT, h, w, Ck, Cv, Cp, seed=seed)
     dF = O.to_bf16_f32(np.random.default_rng(52).standard_normal((BT, h * w, Cp)).astype(np.float32))
     rnd = [O.to_bf16_f32(x) if i != 4 else x for i, x in enumerate(arrs)]      # features and weights as the bf16 arm sees them
     ts = [torch.from_numpy(x).double().requires_grad_() for x in rnd]
@@ -191,6 +192,16 @@ def test_kpff_backward_bf16(hip):
         err = np.abs(g.grad.float().cpu().numpy() - r)
         scale = np.abs(r).max()
         assert err.max() <= 0.03 * scale + 1e-2 and err.mean() <= 4e-3 * scale + 1e-3, (name, err.max(), err.mean(), scale)
+
+
+def test_kpff_backward_bf16(hip):
+    _kpff_backward_bf16(hip, (3, 7, 7, 64, 256, 256), 51)
+
+
+@pytest.mark.parametrize("case", [(3, 6, 19, 32, 32, 64), (2, 14, 14, 64, 64, 128)])
+def test_kpff_backward_bf16_tiled_grids(hip, case):
+    """The same comparison on a column-tiled grid (w > 16) and on one cut into row bands with a ragged last band."""
+    _kpff_backward_bf16(hip, case, sum(case))
 
 
 @pytest.mark.parametrize("N,Dv,flags,dtype", [(65, 48, 1, torch.float32), (130, 64, 0, torch.float32), (256, 256, 1, torch.float32),

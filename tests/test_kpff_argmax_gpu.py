@@ -439,9 +439,11 @@ def test_stem_reads_the_nchw_frames_itself(hip, case):
     assert one.shape == two.shape and torch.equal(one, two)
 
 
-@pytest.mark.parametrize("case", [(25088, 256, (64, 64, 256)), (1000, 256, (64, 64, 256)), (77, 64, (16, 32)), (5, 512, (48,)), (129, 32, (16, 16, 16))])
+@pytest.mark.parametrize("case", [(25088, 256, (64, 64, 256)), (1000, 256, (64, 64, 256)), (77, 64, (16, 32)), (5, 512, (48,)), (129, 32, (16, 16, 16)),
+                                  (65613, 64, (16, 32))])
 def test_key_query_value_projections_in_one_pass(hip, case):
-    """gdkvm_proj_rows == x W^T + b per projection, fp32 accumulation over the bf16-rounded weights, one rounding."""
+    """gdkvm_proj_rows == x W^T + b per projection, fp32 accumulation over the bf16-rounded weights, one rounding.  (The last case: 128-row
+    tiles, PROJ_TM_SWITCH rows and more, with a ragged last tile -- tests/test_kpff_forms_cpu.py.)"""
     rows, k, widths = case
     torch.manual_seed(rows + k)
     x = torch.randn(rows, k, device="cuda").bfloat16()
