@@ -7,7 +7,11 @@ largest 4- / 8-connected component of that class (fill 0; the target is a tracin
 post-processed one, a `largest_component` block reports what was removed and the class's Dice / IoU after it, and every other key is still
 computed from the unfiltered mask.  With `data.surface_class` >= 0 a `surface` block reports the class's mean Hausdorff distance, HD95 and
 ASSD between predicted mask and target (ops.surface_distance / surface_metrics: pixels of the input grid, over the labelled frames where both
-have a surface).  The surface distances are those of the unfiltered mask, whatever `data.lv_keep_largest` says.
+have a surface).  The surface distances are those of the unfiltered mask, whatever `data.lv_keep_largest` says.  With `data.lv_fill_holes`
+= 4 or 8 (the connectivity of the class's COMPLEMENT) ops.fill_holes then fills the holes of that class in the predicted mask -- after the
+largest-component filter when that is on too, so that the islands' holes never matter; `data.lv_fill_max_area` > 0 fills only the holes of at
+most that many pixels -- and the `lv` block is that of the filled mask; a `fill_holes` block reports the holes, the pixels filled and the
+class's Dice / IoU after it, and every other key, the `largest_component` and `surface` blocks included, is computed as before.
 
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
@@ -72,6 +76,9 @@ def main(argv=None):
     keep = cfg.data.lv_keep_largest if lv_cls >= 0 else 0         # 0 = off: no new call below
     # the filtered mask's counts [ncls, 3], then frames changed and pixels removed: accumulated on the device, read once at the end
     lc_acc = torch.zeros(cfg.data.num_classes * 3 + 2, dtype=torch.int64, device=dev) if keep else None
+    fillc = cfg.data.lv_fill_holes if lv_cls >= 0 else 0          # 0 = off: no new call below
+    # the filled mask's counts of lv_class [3], then frames changed, holes and pixels filled: accumulated on the device, read once at the end
+    fh_acc = torch.zeros(6, dtype=torch.int64, device=dev) if fillc else None
     s_cls = cfg.data.surface_class                                # -1 = off: no new call below
     sd_sums = torch.zeros(5, dtype=torch.float64, device=dev) if s_cls >= 0 else None    # ops.surface_summary, accumulated on the device
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
@@ -86,12 +93,12 @@ def main(argv=None):
         """(mask, counts, target's LV measurement) per batch, one batch behind the submissions: the host queues batch i + 1 (copy, cast, replay)
         before it reads batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time).
         The TARGET is measured right behind the submission, on the stream where the prefetcher handed it out: its slot is recycled once the
-        consumer asks for the next batch, so nothing may read it later -- the largest-component filter of the prediction and its surface
-        distances, one batch behind, want the target and get a copy made here."""
+        consumer asks for the next batch, so nothing may read it later -- the largest-component filter of the prediction, its hole filling and
+        its surface distances, one batch behind, want the target and get a copy made here."""
         pending = None
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
             nxt = runner.submit(frames, target)
-            t_copy = target.clone() if keep or s_cls >= 0 else None
+            t_copy = target.clone() if keep or fillc or s_cls >= 0 else None
             if lv_cls >= 0:
                 t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
                 nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy)
@@ -113,6 +120,10 @@ def main(argv=None):
             removed = (lc[..., 1] - lc[..., 2]).long()
             lc_acc += torch.cat([(ops.counts_after_largest(c, lc, lv_cls, 0) * labelled).sum((0, 1)).long().reshape(-1),
                                  torch.stack([(removed > 0).sum(), removed.sum()])])
+        if fillc:
+            measured, fh = ops.fill_holes(measured, cls=lv_cls, connectivity=fillc, max_area=cfg.data.lv_fill_max_area, target=t_copy)
+            fh_acc += torch.cat([(ops.class_counts_after_fill(fh) * labelled[..., 0]).sum((0, 1)),
+                                 torch.stack([(fh[..., 3] > 0).sum(), fh[..., 0].clamp(min=0).sum(), fh[..., 3].sum()]).long()])
         if lv_cls >= 0:
             # the prediction's volumes at the TARGET's end-diastolic / end-systolic frames (EchoNet-Dynamic: the two traced frames; unlabelled
             # frames hold no pixel of the class and are no candidates); a clip counts when its target has two such frames and a volume
@@ -137,6 +148,8 @@ def main(argv=None):
             torch.distributed.all_reduce(ef_sums)                 # ... and the eight EF sums
         if keep:
             torch.distributed.all_reduce(lc_acc)                  # ... and the filtered mask's counts and removal totals
+        if fillc:
+            torch.distributed.all_reduce(fh_acc)                  # ... and the filled mask's counts and totals
         if s_cls >= 0:
             torch.distributed.all_reduce(sd_sums)                 # ... and the five surface-distance sums
     if rank == 0:
@@ -155,6 +168,11 @@ def main(argv=None):
             res["largest_component"] = {"connectivity": keep, "frames_changed": int(acc[-2]), "pixels_removed": int(acc[-1]),
                                         "dice_lv": round(float(ops.dice_from_counts(lc_counts)[lv_cls]), 5),
                                         "iou_lv": round(float(ops.iou_from_counts(lc_counts)[lv_cls]), 5)}
+        if fillc:
+            acc = fh_acc.cpu()
+            res["fill_holes"] = {"connectivity": fillc, "max_area": cfg.data.lv_fill_max_area, "frames_changed": int(acc[3]), "holes": int(acc[4]),
+                                 "pixels_filled": int(acc[5]), "dice_lv": round(float(ops.dice_from_counts(acc[:3])), 5),
+                                 "iou_lv": round(float(ops.iou_from_counts(acc[:3])), 5)}
         if s_cls >= 0:
             res["surface"] = {"class": s_cls, **{k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.surface_stats(sd_sums.cpu()).items()}}
         print(json.dumps(res), flush=True)

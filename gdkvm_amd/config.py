@@ -27,6 +27,9 @@ class DataCfg:
     lv_class: int = 1                # eval.py: the class whose volumes and ejection fraction are measured (ops.lv_measure / lv_ef); -1 = off
     lv_keep_largest: int = 0         # eval.py: keep the largest connected component of lv_class in the PREDICTED mask before it is measured
                                      # (ops.largest_component, fill = 0); 0 = off, 4 or 8 = the connectivity
+    lv_fill_holes: int = 0           # eval.py: fill the holes of lv_class in the PREDICTED mask (after lv_keep_largest) before it is measured
+                                     # (ops.fill_holes); 0 = off, 4 or 8 = the connectivity of the class's COMPLEMENT
+    lv_fill_max_area: int = 0        # ... only the holes of at most this many pixels; 0 = holes of any size
     surface_class: int = -1          # eval.py: the class whose HD, HD95 and ASSD against the target are measured (ops.surface_distance, pixels of
                                      # the input grid); -1 = off
 
@@ -138,6 +141,11 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     cfg.learning_rate = float(cfg.learning_rate)
     if isinstance(cfg.data.lv_keep_largest, bool) or cfg.data.lv_keep_largest not in (0, 4, 8):
         raise ValueError(f"data.lv_keep_largest = {cfg.data.lv_keep_largest!r}: 0 (off), 4 or 8 (the connectivity)")
+    if isinstance(cfg.data.lv_fill_holes, bool) or cfg.data.lv_fill_holes not in (0, 4, 8):
+        raise ValueError(f"data.lv_fill_holes = {cfg.data.lv_fill_holes!r}: 0 (off), 4 or 8 (the connectivity of the class's complement)")
+    fa = cfg.data.lv_fill_max_area
+    if isinstance(fa, bool) or not isinstance(fa, int) or not 0 <= fa < 2 ** 31:
+        raise ValueError(f"data.lv_fill_max_area = {fa!r}: an integer >= 0 (0 = holes of any size)")
     sc = cfg.data.surface_class
     if isinstance(sc, bool) or not isinstance(sc, int) or not -1 <= sc < cfg.data.num_classes:
         raise ValueError(f"data.surface_class = {sc!r}: -1 (off) or a class in 0..{cfg.data.num_classes - 1}")

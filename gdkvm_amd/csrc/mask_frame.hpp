@@ -1,4 +1,4 @@
-// mask_frame.hpp -- what the per-frame kernels over uint8 label masks share (lv_measure.hip, largest_component.hip, surface_distance.hip):
+// mask_frame.hpp -- what the per-frame kernels over uint8 label masks share (lv_measure.hip, largest_component.hip, surface_distance.hip, fill_holes.hip):
 // ONE workgroup walks one frame [H, W] of bytes at any byte address.  The frame split and its sweeps, the walk over the set bits of a match
 // word, integer wave reductions and the workgroup fold of their per-wave partials, the accessor of a frame's 32-bit words, and the
 // launchers' shared argument checks.  A new per-frame mask kernel starts here.  No floating-point code: a file may include this ahead of
@@ -89,6 +89,25 @@ struct MaskFrame {
     __device__ __forceinline__ void sweep_xy(F&& f) const
     {
         sweep_bits([&](unsigned m, int p0) { visit_xy(m, p0, W, f); });
+    }
+    // The same three sweeps over the COMPLEMENT, the lane's pixels that are NOT of the class (fill_holes.hip labels those)
+    template <class F>
+    __device__ __forceinline__ void sweep_not_bits(F&& f) const
+    {
+        const int tid = threadIdx.x;
+        if (tid < head && base[tid] != cls) f(1u, tid);
+        for (int v = tid; v < nvec; v += NT) f(match16(body[v], cls) ^ 0xffffu, head + 16 * v);
+        if (tid < tail && base[head + nbody + tid] != cls) f(1u, head + nbody + tid);
+    }
+    template <class F>
+    __device__ __forceinline__ void sweep_not_p(F&& f) const
+    {
+        sweep_not_bits([&](unsigned m, int p0) { visit_p(m, p0, f); });
+    }
+    template <class F>
+    __device__ __forceinline__ void sweep_not_xy(F&& f) const
+    {
+        sweep_not_bits([&](unsigned m, int p0) { visit_xy(m, p0, W, f); });
     }
 };
 

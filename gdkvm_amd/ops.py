@@ -128,6 +128,8 @@ SIGNATURES = {
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
     "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
+    "gdkvm_fill_holes_workspace_bytes": (_sz, [_i] * 3),
+    "gdkvm_fill_holes": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
@@ -2134,6 +2136,38 @@ def counts_after_largest(counts: torch.Tensor, info: torch.Tensor, cls: int, fil
         res[..., int(fill), 0] += inf[..., 5]
         res[..., int(fill), 1] += removed
     return res
+
+
+def fill_holes(mask: torch.Tensor, cls: int = 1, connectivity: int = 4, max_area: int = 0, target: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None):
+    """gdkvm_fill_holes: per frame of mask [..., H, W] uint8 write `cls` over the holes of class `cls`: the components of its complement
+    (`connectivity` 4 or 8 is the COMPLEMENT's; 4 is scipy.ndimage.binary_fill_holes' default) that do not reach the frame's border, those of
+    at most `max_area` pixels when max_area > 0 (definition: include/gdkvm.h; every output is an exact integer).  Returns (out uint8 like
+    mask, info int32 [..., 8] = holes, holes_filled, n, filled, largest_hole, hit_before, hit_filled, n_target); the last three count against
+    `target` (same shape; 0 without one) and are what class_counts_after_fill needs.  out=mask fills in place; mask, target and out may
+    start at any byte address."""
+    lead, frames, H, W = _mask_frames("fill_holes", mask, cls, target=target, out=out)
+    if int(connectivity) not in (4, 8):
+        raise GdkvmError(f"fill_holes: connectivity = {connectivity} is neither 4 nor 8")
+    if isinstance(max_area, bool) or not isinstance(max_area, int) or not 0 <= max_area < 2 ** 31:
+        raise GdkvmError(f"fill_holes: max_area = {max_area} must be an integer >= 0 (0 = holes of any size)")
+    dev = _dev(mask, target, out)
+    if out is None:
+        out = torch.empty_like(mask)
+    info = torch.empty(lead + (8,), dtype=torch.int32, device=dev)
+    # (allocated per call like every workspace of this module: under graph capture it comes from the graph's own pool and is replayed with it)
+    ws = _workspace("gdkvm_fill_holes_workspace_bytes", dev, frames, H, W, floor=16)
+    _call("gdkvm_fill_holes", dev, mask, target, out, info, _Ws(ws), frames, H, W, int(cls), int(connectivity), int(max_area))
+    return out, info
+
+
+def class_counts_after_fill(info: torch.Tensor) -> torch.Tensor:
+    """The argmax_dice-style counts int64 [..., 3] = |A n B|, |A|, |B| of class `cls` in the mask fill_holes(mask, cls, target=target) wrote,
+    from that call's info [..., 8]: hit_before + hit_filled, n + filled, n_target.  Pure torch on either device, integer-exact."""
+    if info.dim() < 1 or info.shape[-1] != 8 or torch.is_floating_point(info):
+        raise GdkvmError(f"class_counts_after_fill: info must be integers [..., 8] (ops.fill_holes), got {info.dtype} {tuple(info.shape)}")
+    inf = info.to(torch.int64)
+    return torch.stack([inf[..., 5] + inf[..., 6], inf[..., 2] + inf[..., 3], inf[..., 7]], -1)
 
 
 def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:

@@ -673,6 +673,38 @@ size_t gdkvm_largest_component_workspace_bytes(int frames, int H, int W);
 int gdkvm_largest_component(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, void* workspace, size_t workspace_bytes,
                             int frames, int H, int W, int cls, int connectivity, int fill, void* stream);
 
+/* Fill the holes of one class of label masks (the second clean-up in front of gdkvm_lv_measure, behind gdkvm_largest_component: pixels inside
+ * the cavity that argmax gave to another class; the method of disks squares each disk's area, so a hole costs about twice its pixel share in
+ * volume; csrc/fill_holes.hip).  Every output is an integer that depends on neither the algorithm nor the schedule.
+ * Per frame mask [H, W] uint8, class cls (0..254), connectivity 4 or 8, max_area >= 0, H, W in 1..1024:
+ *   1. P = the pixels with mask[y][x] == cls; every other byte, 255 and every other class included, belongs to the complement Q.
+ *   2. Two pixels of Q in the SAME frame are adjacent when |dx| + |dy| == 1 (connectivity 4) or max(|dx|, |dy|) == 1 (connectivity 8).
+ *      Adjacency is geometric, as for gdkvm_largest_component: (W - 1, y) and (0, y + 1) are no neighbours, nor are pixels of two frames.
+ *      `connectivity` is that of the COMPLEMENT: 4 is scipy.ndimage.binary_fill_holes' default and the dual of an 8-connected class, 8 the
+ *      dual of a 4-connected one.
+ *   3. A component of Q is an equivalence class of the transitive closure of adjacency.  It is OUTSIDE when it holds a pixel with x == 0,
+ *      x == W - 1, y == 0 or y == H - 1; every other component is a HOLE, and its size is its number of pixels.
+ *   4. A hole is FILLED when max_area == 0 or its size is <= max_area (max_area lets the call serve a ring-shaped class: a myocardium whose
+ *      cavity must stay open while speckle holes close).
+ *   5. out[p] = cls for every pixel of a filled hole, out[p] = mask[p] everywhere else.
+ *   6. info [frames, 8] int32 = holes (their number, filled or not), holes_filled, n = |P|, filled (pixels changed), largest_hole (the size of
+ *        the largest hole, filled or not; 0 without holes), hit_before = |{p in P : target[p] == cls}|,
+ *        hit_filled = |{p filled : target[p] == cls}|, n_target = |{p : target[p] == cls}| (the last three 0 when target == NULL).
+ *        The class's three Dice counts of the filled mask are |A n B| = hit_before + hit_filled, |A| = n + filled, |B| = n_target: no second
+ *        pass over the pixels.
+ *   7. P empty, P the whole frame, H <= 2 or W <= 2: every pixel of Q touches the border, holes = 0 and out = mask.
+ * mask, target (optional) and out are [frames, H, W] contiguous at ANY byte address (frames of H W bytes follow each other); out is either
+ * exactly mask (in place) or does not overlap it; info is 16-byte aligned.  The workspace (16-byte aligned, at least
+ * gdkvm_fill_holes_workspace_bytes(frames, H, W) bytes: 0 while H W <= 15360, where the labels live in LDS, else 4 bytes per pixel with each
+ * frame's slice rounded up to 16 bytes) is scratch.  One workgroup per frame; neither entry allocates or synchronises; bit-reproducible.
+ * Every loop of the kernel is bounded by H W or a constant; should a frame ever reach that bound (the derivation in the source says it
+ * cannot), it reports holes = -1, holes_filled = filled = largest_hole = hit_filled = 0 and out = mask.  Bad arguments (shape, cls,
+ * connectivity, max_area < 0, null or misaligned pointers, a short workspace, a partial overlap) are GDKVM_ERR_SHAPE before any device call;
+ * frames == 0 is GDKVM_OK without a launch. */
+size_t gdkvm_fill_holes_workspace_bytes(int frames, int H, int W);
+int gdkvm_fill_holes(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, void* workspace, size_t workspace_bytes,
+                     int frames, int H, int W, int cls, int connectivity, int max_area, void* stream);
+
 /* Surface distances between one class of a predicted mask and of its target (what HD, HD95 and ASSD are made of; csrc/surface_distance.hip).
  * Every output is an integer that depends on neither the algorithm nor the schedule; the three floating-point metrics are a few lines on top
  * (gdkvm_amd.ops.surface_metrics) and not part of this ABI.  Distances are in pixels of the masks' grid (isotropic pixels assumed).

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What the LV measurement, the largest-component filter in front of it and the surface distances cost (profiles/r10_a_lv_probe.txt,
-profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt).
+"""What the LV measurement, the largest-component filter and the hole filling in front of it and the surface distances cost
+(profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt).
 python3 tools/lv_probe.py [--quick] [--no-eval]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
@@ -11,12 +11,18 @@ python3 tools/lv_probe.py [--quick] [--no-eval]
     about a tenth of it (a ventricle); every pixel of the class (the worst case for the per-pixel passes); no pixel of the class.  The floor is
     the bytes read (and, for the mask kernel, written) once over the 6.3 TB/s achievable HBM rate.  gdkvm_largest_component (class 1,
     4-connected, fill 0, out of place, with a target) runs in the same windows on the same three fills, the ellipses with three islands each
-    (discs of radius 1 to 5 % of the side; the kernel removes them), and at 8-connectivity on the first.  gdkvm_surface_distance (class 1)
+    (discs of radius 1 to 5 % of the side; the kernel removes them), and at 8-connectivity on the first.  gdkvm_fill_holes (class 1, complement
+    4-connected, any size, out of place, with a target) runs in the same windows: the ellipses with three holes punched into each (discs of
+    class 0 of radius 1 to 3 % of the side; the kernel fills them), the same at connectivity 8, the ellipse alone (nothing to fill: a copy),
+    every pixel of the class (no complement), no pixel of the class (the whole frame is one outside component, which the kernel knows after
+    its counting pass: nothing can enclose a hole) and ONE pixel of the class in the middle (the labelling's worst case: every other pixel is
+    one outside component, the same amount of labelling as largest_component's "every pixel of the class").  gdkvm_surface_distance (class 1)
     runs in the same windows: ellipse against the next input's ellipse (a prediction close to its target), the ellipse with islands against
     it, a checkerboard against a one-pixel-shifted checkerboard (every pixel of the class is surface) and against the ellipse (every row
     walk of the ellipse's surface ends at once, every walk of the checkerboard's is as long as the ellipse is far), and an empty class.
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
-    data.lv_keep_largest=4 on top of it, with data.surface_class=1 instead, and with data.lv_class=-1, alternated, twice each."""
+    data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.surface_class=1 instead, and with data.lv_class=-1,
+    alternated, twice each."""
 import math
 import os
 import statistics
@@ -60,6 +66,19 @@ def add_islands(masks, seed):
     return out
 
 
+def punch_holes(masks, seed):
+    """Three discs of class 0 per frame, inside the ellipse (centres drawn from its own pixels; one that reaches its rim is a notch, no hole)."""
+    rng = np.random.default_rng(seed)
+    F, S, _ = masks.shape
+    yy, xx = np.mgrid[0:S, 0:S]
+    out = masks.copy()
+    for f in range(F):
+        ys, xs = np.nonzero(masks[f])
+        for k in rng.integers(0, len(ys), 3):
+            out[f][(yy - ys[k]) ** 2 + (xx - xs[k]) ** 2 <= (rng.uniform(0.01, 0.03) * S) ** 2] = 0
+    return out
+
+
 CALLS = 20            # launches per timed window
 
 
@@ -70,10 +89,14 @@ def part_a(dev, F, S, reps, n_in=4):
     masks_np = [ellipse_masks(F, S, s) for s in range(n_in)]
     masks = [torch.from_numpy(m).to(dev) for m in masks_np]
     isl = [torch.from_numpy(add_islands(m, s)).to(dev) for s, m in enumerate(masks_np)]
+    holed = [torch.from_numpy(punch_holes(m, s)).to(dev) for s, m in enumerate(masks_np)]
+    fh_ws = torch.empty(max(16, int(lib.gdkvm_fill_holes_workspace_bytes(F, S, S))), dtype=torch.uint8, device=dev)
     cc_out = torch.empty((F, S, S), dtype=torch.uint8, device=dev)
     cc_info = torch.empty((F, 8), dtype=torch.int32, device=dev)
     cc_ws = torch.empty(max(16, int(lib.gdkvm_largest_component_workspace_bytes(F, S, S))), dtype=torch.uint8, device=dev)
     full = torch.ones((F, S, S), dtype=torch.uint8, device=dev)
+    lone = full.clone()
+    lone[:, S // 2, S // 2] = 2
     board = ((torch.arange(S, device=dev)[:, None] + torch.arange(S, device=dev)[None, :]) % 2 == 0).to(torch.uint8).expand(F, S, S).contiguous()
     board_shifted = (1 - board).contiguous()
     sd_out = torch.empty((F, 8), dtype=torch.int64, device=dev)
@@ -92,6 +115,11 @@ def part_a(dev, F, S, reps, n_in=4):
     def cc(mask, target, cls, conn=4):
         rc = lib.gdkvm_largest_component(mask.data_ptr(), target.data_ptr(), cc_out.data_ptr(), cc_info.data_ptr(), cc_ws.data_ptr(), cc_ws.numel(),
                                          F, S, S, cls, conn, 0, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def fh(mask, target, cls, conn=4):
+        rc = lib.gdkvm_fill_holes(mask.data_ptr(), target.data_ptr(), cc_out.data_ptr(), cc_info.data_ptr(), fh_ws.data_ptr(), fh_ws.numel(),
+                                  F, S, S, cls, conn, 0, st)
         assert rc == 0, lib.gdkvm_last_error()
 
     def sd(mask, target, cls):
@@ -114,6 +142,12 @@ def part_a(dev, F, S, reps, n_in=4):
         "largest_component, ellipse alone (a copy)": (lambda i: cc(masks[i], masks[i], 1), 2 * F * S * S),
         "largest_component, every pixel of the class": (lambda i: cc(full, masks[i], 1), 2 * F * S * S),
         "largest_component, no pixel of the class": (lambda i: cc(full, masks[i], 2), 2 * F * S * S),
+        "fill_holes, ellipse with 3 holes": (lambda i: fh(holed[i], masks[i], 1), 2 * F * S * S),
+        "fill_holes, the same, connectivity 8": (lambda i: fh(holed[i], masks[i], 1, 8), 2 * F * S * S),
+        "fill_holes, ellipse alone (a copy)": (lambda i: fh(masks[i], masks[i], 1), 2 * F * S * S),
+        "fill_holes, every pixel of the class": (lambda i: fh(full, masks[i], 1), 2 * F * S * S),
+        "fill_holes, no pixel of the class": (lambda i: fh(full, masks[i], 2), 2 * F * S * S),
+        "fill_holes, one pixel of the class": (lambda i: fh(lone, masks[i], 2), 2 * F * S * S),
         "surface_distance, ellipse against ellipse": (lambda i: sd(masks[i], masks[(i + 1) % n_in], 1), 2 * F * S * S),
         "surface_distance, ellipse + 3 islands against it": (lambda i: sd(isl[i], masks[i], 1), 2 * F * S * S),
         "surface_distance, checkerboard against shifted": (lambda i: sd(board, board_shifted, 1), 2 * F * S * S),
@@ -125,6 +159,11 @@ def part_a(dev, F, S, reps, n_in=4):
     removed = (cc_info[:, 1] - cc_info[:, 2]).float()
     print(f"    (islands: {float(cc_info[:, 0].float().mean()):.2f} components per frame, {float(removed.mean()):.0f} of {float(cc_info[:, 1].float().mean()):.0f} "
           f"pixels removed; label words in {'LDS' if cc_ws.numel() == 16 else 'the workspace, ' + str(cc_ws.numel() >> 20) + ' MiB'})")
+    fh(holed[0], masks[0], 1)
+    torch.cuda.synchronize()
+    print(f"    (holes: {float(cc_info[:, 0].float().mean()):.2f} per frame, {float(cc_info[:, 3].float().mean()):.0f} pixels filled beside "
+          f"{float(cc_info[:, 2].float().mean()):.0f} of the class, {int((cc_out != masks[0]).any((1, 2)).sum())} of {F} frames differ from the ellipse; "
+          f"label words in {'LDS' if fh_ws.numel() == 16 else 'the workspace, ' + str(fh_ws.numel() >> 20) + ' MiB'})")
     sd(masks[0], masks[1], 1)
     torch.cuda.synchronize()
     met, ok = ops.surface_metrics(sd_out)
@@ -154,6 +193,7 @@ def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
         for keys in (["data.lv_class=1", "data.lv_keep_largest=0"], ["data.lv_class=1", "data.lv_keep_largest=4"],
+                     ["data.lv_class=1", "data.lv_keep_largest=0", "data.lv_fill_holes=4"],
                      ["data.lv_class=1", "data.lv_keep_largest=0", "data.surface_class=1"], ["data.lv_class=-1"]):
             t0 = time.perf_counter()
             out = subprocess.run([sys.executable, os.path.join(ROOT, "eval.py")] + keys + overrides, capture_output=True, text=True, timeout=600)
