@@ -11,7 +11,13 @@ have a surface).  The surface distances are those of the unfiltered mask, whatev
 = 4 or 8 (the connectivity of the class's COMPLEMENT) ops.fill_holes then fills the holes of that class in the predicted mask -- after the
 largest-component filter when that is on too, so that the islands' holes never matter; `data.lv_fill_max_area` > 0 fills only the holes of at
 most that many pixels -- and the `lv` block is that of the filled mask; a `fill_holes` block reports the holes, the pixels filled and the
-class's Dice / IoU after it, and every other key, the `largest_component` and `surface` blocks included, is computed as before.
+class's Dice / IoU after it, and every other key, the `largest_component` and `surface` blocks included, is computed as before.  With
+`data.temporal_vote` = r in 1..7 ops.temporal_vote first smooths the predicted masks of every clip over time (each pixel takes the class most
+of the frames t - r .. t + r have there), so that the unlabelled frames of a clip steady the labelled ones: the voted mask is what enters the
+largest-component filter, the hole filling and the `lv` block, the `largest_component` block's Dice / IoU start from the vote's counts, and a
+`temporal_vote` block reports the frames and pixels changed, the pixels per frame that differ from the previous frame before and after the
+vote (temporal instability) and the voted mask's Dice; `dice_per_class`, `iou_per_class` and the `surface` block are still those of the
+unfiltered mask.
 
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
@@ -79,6 +85,9 @@ def main(argv=None):
     fillc = cfg.data.lv_fill_holes if lv_cls >= 0 else 0          # 0 = off: no new call below
     # the filled mask's counts of lv_class [3], then frames changed, holes and pixels filled: accumulated on the device, read once at the end
     fh_acc = torch.zeros(6, dtype=torch.int64, device=dev) if fillc else None
+    vote = cfg.data.temporal_vote                                 # 0 = off: no new call below
+    # ops.vote_summary: the voted mask's counts [ncls, 3], then pixels changed, frames changed, flips before, flips after, frames
+    tv_acc = torch.zeros(cfg.data.num_classes * 3 + 5, dtype=torch.int64, device=dev) if vote else None
     s_cls = cfg.data.surface_class                                # -1 = off: no new call below
     sd_sums = torch.zeros(5, dtype=torch.float64, device=dev) if s_cls >= 0 else None    # ops.surface_summary, accumulated on the device
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
@@ -93,12 +102,12 @@ def main(argv=None):
         """(mask, counts, target's LV measurement) per batch, one batch behind the submissions: the host queues batch i + 1 (copy, cast, replay)
         before it reads batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time).
         The TARGET is measured right behind the submission, on the stream where the prefetcher handed it out: its slot is recycled once the
-        consumer asks for the next batch, so nothing may read it later -- the largest-component filter of the prediction, its hole filling and
-        its surface distances, one batch behind, want the target and get a copy made here."""
+        consumer asks for the next batch, so nothing may read it later -- the temporal vote of the prediction, its largest-component filter, its
+        hole filling and its surface distances, one batch behind, want the target and get a copy made here."""
         pending = None
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
             nxt = runner.submit(frames, target)
-            t_copy = target.clone() if keep or fillc or s_cls >= 0 else None
+            t_copy = target.clone() if vote or keep or fillc or s_cls >= 0 else None
             if lv_cls >= 0:
                 t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
                 nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy)
@@ -114,11 +123,14 @@ def main(argv=None):
         # only frames that carry labels count (EchoNet-Dynamic: the two traced frames of a clip -- gdkvm_amd.data.IGNORE_LABEL everywhere
         # else, where a predicted pixel must not enter |A|): a labelled frame has a non-empty target in some class
         labelled = (c[..., 2].sum(-1, keepdim=True) > 0).unsqueeze(-1)
-        measured = mask
+        measured, c_meas = mask, c                                # what is post-processed and measured, and its counts
+        if vote:
+            measured, tv, c_meas = ops.temporal_vote(mask, cfg.data.num_classes, vote, target=t_copy)
+            tv_acc += ops.vote_summary(tv, c_meas, labelled[..., 0, 0])
         if keep:
-            measured, lc = ops.largest_component(mask, cls=lv_cls, connectivity=keep, fill=0, target=t_copy)
+            measured, lc = ops.largest_component(measured, cls=lv_cls, connectivity=keep, fill=0, target=t_copy)
             removed = (lc[..., 1] - lc[..., 2]).long()
-            lc_acc += torch.cat([(ops.counts_after_largest(c, lc, lv_cls, 0) * labelled).sum((0, 1)).long().reshape(-1),
+            lc_acc += torch.cat([(ops.counts_after_largest(c_meas, lc, lv_cls, 0) * labelled).sum((0, 1)).long().reshape(-1),
                                  torch.stack([(removed > 0).sum(), removed.sum()])])
         if fillc:
             measured, fh = ops.fill_holes(measured, cls=lv_cls, connectivity=fillc, max_area=cfg.data.lv_fill_max_area, target=t_copy)
@@ -146,6 +158,8 @@ def main(argv=None):
         torch.distributed.all_reduce(counts)                      # the only exchanges: 3 integers per class ...
         if lv_cls >= 0:
             torch.distributed.all_reduce(ef_sums)                 # ... and the eight EF sums
+        if vote:
+            torch.distributed.all_reduce(tv_acc)                  # ... and the voted mask's counts and change totals
         if keep:
             torch.distributed.all_reduce(lc_acc)                  # ... and the filtered mask's counts and removal totals
         if fillc:
@@ -162,6 +176,14 @@ def main(argv=None):
                "mean_foreground_iou": round(sum(iou[1:]) / max(len(iou) - 1, 1), 5)}
         if lv_cls >= 0:
             res["lv"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.ef_stats(ef_sums.cpu()).items()}
+        if vote:
+            acc = tv_acc.cpu()
+            tv_dice = ops.dice_from_counts(acc[:-5].view(cfg.data.num_classes, 3)).tolist()
+            nfr = max(int(acc[-1]), 1)
+            res["temporal_vote"] = {"radius": vote, "frames_changed": int(acc[-4]), "pixels_changed": int(acc[-5]),
+                                    "flips_per_frame_before": round(int(acc[-3]) / nfr, 5), "flips_per_frame_after": round(int(acc[-2]) / nfr, 5),
+                                    "dice_per_class": [round(d, 5) for d in tv_dice],
+                                    "mean_foreground_dice": round(sum(tv_dice[1:]) / max(len(tv_dice) - 1, 1), 5)}
         if keep:
             acc = lc_acc.cpu()
             lc_counts = acc[:-2].view(cfg.data.num_classes, 3)

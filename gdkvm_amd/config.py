@@ -30,6 +30,8 @@ class DataCfg:
     lv_fill_holes: int = 0           # eval.py: fill the holes of lv_class in the PREDICTED mask (after lv_keep_largest) before it is measured
                                      # (ops.fill_holes); 0 = off, 4 or 8 = the connectivity of the class's COMPLEMENT
     lv_fill_max_area: int = 0        # ... only the holes of at most this many pixels; 0 = holes of any size
+    temporal_vote: int = 0           # eval.py: smooth the PREDICTED masks of a clip over time before anything above (ops.temporal_vote: per-pixel
+                                     # majority over the frames t - r .. t + r); 0 = off, 1..7 = the radius r
     surface_class: int = -1          # eval.py: the class whose HD, HD95 and ASSD against the target are measured (ops.surface_distance, pixels of
                                      # the input grid); -1 = off
 
@@ -146,6 +148,11 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     fa = cfg.data.lv_fill_max_area
     if isinstance(fa, bool) or not isinstance(fa, int) or not 0 <= fa < 2 ** 31:
         raise ValueError(f"data.lv_fill_max_area = {fa!r}: an integer >= 0 (0 = holes of any size)")
+    tv = cfg.data.temporal_vote
+    if isinstance(tv, bool) or not isinstance(tv, int) or not 0 <= tv <= 7:
+        raise ValueError(f"data.temporal_vote = {tv!r}: 0 (off) or the radius 1..7 of the vote's window")
+    if tv and not 2 <= cfg.data.num_classes <= 8:
+        raise ValueError(f"data.temporal_vote = {tv}: ops.temporal_vote votes over 2..8 classes, data.num_classes = {cfg.data.num_classes}")
     sc = cfg.data.surface_class
     if isinstance(sc, bool) or not isinstance(sc, int) or not -1 <= sc < cfg.data.num_classes:
         raise ValueError(f"data.surface_class = {sc!r}: -1 (off) or a class in 0..{cfg.data.num_classes - 1}")

@@ -130,6 +130,8 @@ SIGNATURES = {
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_fill_holes_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_fill_holes": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
+    "gdkvm_temporal_vote_workspace_bytes": (_sz, [_i] * 5),
+    "gdkvm_temporal_vote": (_i, [_vp] * 6 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
@@ -2168,6 +2170,64 @@ def class_counts_after_fill(info: torch.Tensor) -> torch.Tensor:
         raise GdkvmError(f"class_counts_after_fill: info must be integers [..., 8] (ops.fill_holes), got {info.dtype} {tuple(info.shape)}")
     inf = info.to(torch.int64)
     return torch.stack([inf[..., 5] + inf[..., 6], inf[..., 2] + inf[..., 3], inf[..., 7]], -1)
+
+
+TEMPORAL_VOTE_MAX_RADIUS = 7
+
+
+def temporal_vote(mask: torch.Tensor, num_classes: int, radius: int = 1, target: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None):
+    """gdkvm_temporal_vote: smooth the label masks of clips over time.  mask [..., T, H, W] uint8 (the leading dimensions are the clips; a
+    3-D mask is one clip): every pixel with a label < num_classes (2..8) takes the class most frames of its window t - radius .. t + radius
+    (0..7; truncated at the clip's ends) have there; ties go to the pixel's own label, else to the smallest class; bytes >= num_classes
+    neither vote nor change (definition: include/gdkvm.h; every output is an exact integer).  Returns (out uint8 like mask, info int32
+    [..., T, 4] = changed, flips_in, flips_out, 0 -- pixels whose label changed, and pixels that differ from the previous frame before and
+    after the vote --, counts int32 [..., T, num_classes, 3] = argmax_dice's counts of `out` against `target` (same shape), or None without
+    a target).  out must not overlap mask; mask, target and out may start at any byte address."""
+    if mask.dim() < 3:
+        raise GdkvmError(f"temporal_vote: mask must be uint8 [..., T, H, W], got {mask.dtype} {tuple(mask.shape)}")
+    lead, frames, H, W = _mask_frames("temporal_vote", mask, 0, target=target, out=out)
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 8:
+        raise GdkvmError(f"temporal_vote: num_classes = {num_classes!r} must be an integer in 2..8")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= TEMPORAL_VOTE_MAX_RADIUS:
+        raise GdkvmError(f"temporal_vote: radius = {radius!r} must be an integer in 0..{TEMPORAL_VOTE_MAX_RADIUS}")
+    T = lead[-1]
+    if T < 1:
+        raise GdkvmError(f"temporal_vote: T = {T} frames per clip, at least 1")
+    dev = _dev(mask, target, out)
+    if out is None:
+        out = torch.empty_like(mask)
+    else:
+        lo, hi = mask.data_ptr(), mask.data_ptr() + mask.numel()
+        if out.data_ptr() < hi and lo < out.data_ptr() + out.numel():
+            raise GdkvmError("temporal_vote: out must not overlap mask (later frames read earlier input)")
+    clips = frames // T
+    info = torch.empty(lead + (4,), dtype=torch.int32, device=dev)
+    counts = torch.empty(lead + (num_classes, 3), dtype=torch.int32, device=dev) if target is not None else None
+    # (allocated per call like every workspace of this module; the kernel asks for none today)
+    ws = _workspace("gdkvm_temporal_vote_workspace_bytes", dev, clips, T, H, W, num_classes, floor=16)
+    _call("gdkvm_temporal_vote", dev, mask, target, out, info, counts, _Ws(ws), clips, T, H, W, num_classes, radius)
+    return out, info, counts
+
+
+def vote_summary(info: torch.Tensor, counts: Optional[torch.Tensor], labelled: torch.Tensor) -> torch.Tensor:
+    """The running sums of an evaluation with temporal_vote, int64 [ncls * 3 + 5] on the inputs' device: the voted mask's counts [ncls, 3]
+    (flattened) over the frames where `labelled` (bool, broadcastable to info[..., 0]), then over ALL frames pixels changed, frames changed,
+    flips_in, flips_out and the number of frames.  counts=None leaves the first part out.  Sums of batches and of ranks add.  Pure torch on
+    either device, integer-exact."""
+    if info.dim() < 2 or info.shape[-1] != 4 or torch.is_floating_point(info):
+        raise GdkvmError(f"vote_summary: info must be integers [..., T, 4] (ops.temporal_vote), got {info.dtype} {tuple(info.shape)}")
+    inf = info.to(torch.int64)
+    tail = torch.stack([inf[..., 0].sum(), (inf[..., 0] > 0).sum(), inf[..., 1].sum(), inf[..., 2].sum(),
+                        torch.tensor(inf[..., 0].numel(), dtype=torch.int64, device=info.device)])
+    if counts is None:
+        return tail
+    if counts.dim() < 2 or counts.shape[-1] != 3 or tuple(counts.shape[:-2]) != tuple(info.shape[:-1]) or torch.is_floating_point(counts):
+        raise GdkvmError(f"vote_summary: counts must be integers [..., T, ncls, 3] beside info {tuple(info.shape)}, got {counts.dtype} "
+                         f"{tuple(counts.shape)}")
+    lab = labelled.to(torch.bool).expand(info.shape[:-1])
+    head = (counts.to(torch.int64) * lab[..., None, None]).reshape(-1, counts.shape[-2] * 3).sum(0)
+    return torch.cat([head, tail])
 
 
 def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:

@@ -705,6 +705,42 @@ size_t gdkvm_fill_holes_workspace_bytes(int frames, int H, int W);
 int gdkvm_fill_holes(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, void* workspace, size_t workspace_bytes,
                      int frames, int H, int W, int cls, int connectivity, int max_area, void* stream);
 
+/* Smooth a clip's label masks over time: a per-pixel majority vote over the frames t - r .. t + r (a temporal mode filter; the clean-up that
+ * runs FIRST in front of gdkvm_lv_measure, ahead of gdkvm_largest_component and gdkvm_fill_holes: a border pixel that flips class from one
+ * frame to the next makes the area curve jitter from which the ED / ES frames are read; csrc/temporal_vote.hip).  Every output is an integer
+ * that depends on neither the algorithm nor the schedule.
+ * mask [clips, T, H, W] uint8, ncls in 2..8, radius r in 0..7, T >= 1, H, W in 1..1024.  For clip b, frame t and pixel p:
+ *   1. The window is the frames max(0, t - r) .. min(T - 1, t + r) of the same clip: truncated at the clip's ends, not padded, and never
+ *      reaching into another clip.
+ *   2. A frame of the window votes for class c at p when its byte at p equals c and c < ncls.  Bytes >= ncls (255 included) do not vote.
+ *   3. If the pixel's own byte is >= ncls, out = mask there (pass-through).
+ *   4. Otherwise out is the class with the most votes.  Among tied classes the pixel's own label wins if it is one of them, else the
+ *      smallest class index.  (The own label always has its own vote: the maximum is at least 1.)
+ *   5. info [clips, T, 4] int32 = changed = |{p : out != mask}|, flips_in = |{p : mask[t][p] != mask[t - 1][p]}| (0 at t = 0; the raw bytes
+ *      are compared), flips_out = the same count on out, 0.
+ *   6. counts [clips, T, ncls, 3] int32 = {|out == c & target == c|, |out == c|, |target == c|}, gdkvm_argmax_dice's definition; written only
+ *      when target (mask's shape, uint8) is given -- without a target counts may be NULL.
+ *   7. radius == 0: out = mask, info and counts still computed.
+ * mask, target and out are contiguous at ANY byte address (frames of H W bytes follow each other, so with H W % 16 != 0 every frame is
+ * aligned differently); out must not overlap mask at all (later frames read earlier input).  info and counts are 16-byte aligned and are
+ * zeroed by the callee, with a kernel.  gdkvm_temporal_vote_workspace_bytes is 0 for every shape (the votes live in registers) and the
+ * workspace may be NULL; the pair is there so that a caller treats every mask kernel alike.  Neither entry allocates or synchronises;
+ * bit-reproducible (the sums are integer atomics).  Bad arguments (shape, ncls, radius, null or misaligned pointers, a target without
+ * counts, a short workspace, any overlap of out with mask, clips * T > 2^30) are GDKVM_ERR_SHAPE before any device call; clips == 0 is
+ * GDKVM_OK without a launch.
+ * Launch geometry, for tests that want shapes on both sides of it: a workgroup (one wave) owns GDKVM_TEMPORAL_VOTE_RUN pixel positions of
+ * one clip, 16 per lane, and walks its frames -- or, while that gives fewer than GDKVM_TEMPORAL_VOTE_NARROW_BELOW (clip, run) pairs,
+ * GDKVM_TEMPORAL_VOTE_NARROW_RUN positions, 4 per lane; a launch has at most GDKVM_TEMPORAL_VOTE_MAX_WG workgroups, which take further
+ * pairs in a grid-stride loop; 16- / 4-byte loads and stores when H W % 16 == 0 and mask, out and target are 16-byte aligned, byte accesses
+ * otherwise; one kernel per ncls. */
+#define GDKVM_TEMPORAL_VOTE_RUN 1024
+#define GDKVM_TEMPORAL_VOTE_NARROW_RUN 256
+#define GDKVM_TEMPORAL_VOTE_NARROW_BELOW 3072
+#define GDKVM_TEMPORAL_VOTE_MAX_WG 4096
+size_t gdkvm_temporal_vote_workspace_bytes(int clips, int T, int H, int W, int ncls);
+int gdkvm_temporal_vote(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, int32_t* counts,
+                        void* workspace, size_t workspace_bytes, int clips, int T, int H, int W, int ncls, int radius, void* stream);
+
 /* Surface distances between one class of a predicted mask and of its target (what HD, HD95 and ASSD are made of; csrc/surface_distance.hip).
  * Every output is an integer that depends on neither the algorithm nor the schedule; the three floating-point metrics are a few lines on top
  * (gdkvm_amd.ops.surface_metrics) and not part of this ABI.  Distances are in pixels of the masks' grid (isotropic pixels assumed).

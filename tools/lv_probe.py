@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""What the LV measurement, the largest-component filter and the hole filling in front of it and the surface distances cost
-(profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt).
-python3 tools/lv_probe.py [--quick] [--no-eval]
+"""What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
+cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
+vote's figures are in DESIGN.md).
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -20,9 +21,16 @@ python3 tools/lv_probe.py [--quick] [--no-eval]
     runs in the same windows: ellipse against the next input's ellipse (a prediction close to its target), the ellipse with islands against
     it, a checkerboard against a one-pixel-shifted checkerboard (every pixel of the class is surface) and against the ellipse (every row
     walk of the ellipse's surface ends at once, every walk of the checkerboard's is as long as the ellipse is far), and an empty class.
+(v) gdkvm_temporal_vote at the cfg2 mask shape, 16 clips of 32 frames of 112^2 with 4 classes (--vote-only: this part alone), radius 1, 2
+    and 7 with a target and radius 1 without, through the C symbol on preallocated outputs, beside two yardsticks in the same alternated
+    windows: the plain torch expression of the same filter (torch_vote: a one-hot, a window sum along T, an argmax with the tie rules; the
+    probe first checks that it computes what the kernel computes) and the byte floor, 2 clips T H W bytes over the copy bandwidth measured
+    here on 512 MiB that no cache holds.  Inputs: clips of an ellipse in a ring that drifts over the frames with 15 % of the pixels
+    re-drawn, four in rotation.  Then 320 clips (two inputs of 128 MB in rotation), where the launcher takes the form with 16 pixels
+    per lane instead of 4, without the torch rows.
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
-    data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.surface_class=1 instead, and with data.lv_class=-1,
-    alternated, twice each."""
+    data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
+    instead, and with data.lv_class=-1, alternated, twice each."""
 import math
 import os
 import statistics
@@ -189,11 +197,102 @@ def part_a(dev, F, S, reps, n_in=4):
     print(flush=True)
 
 
+def drifting_masks(clips, T, S, ncls, seed, dev):
+    """Label clips for the temporal vote: per clip an ellipse of class 1 inside a ring of class 2 that drifts and breathes over the frames,
+    15 % of the pixels re-drawn uniformly over the classes (the flicker the vote removes)."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
+    out = np.zeros((clips, T, S, S), np.uint8)
+    for b in range(clips):
+        cy, cx, dy, dx = S * rng.uniform(0.45, 0.55), S * rng.uniform(0.45, 0.55), S * rng.uniform(-0.003, 0.003), S * rng.uniform(-0.003, 0.003)
+        for t in range(T):
+            s = 1.0 + 0.15 * math.sin(2 * math.pi * t / T)
+            d = ((yy - cy - dy * t) / (0.27 * S * s)) ** 2 + ((xx - cx - dx * t) / (0.13 * S * s)) ** 2
+            out[b, t][d < 1.5] = 2 % ncls
+            out[b, t][d < 1.0] = 1
+    noise = rng.random(out.shape) < 0.15
+    out[noise] = rng.integers(0, ncls, int(noise.sum()), dtype=np.uint8)
+    return torch.from_numpy(out).to(dev)
+
+
+def torch_vote(mask, ncls, r):
+    """The same filter as a plain torch expression (the yardstick): a one-hot, a window sum along T from a running sum, and an argmax over
+    keys 2 votes + (class == own label) -- the first maximum is the smallest class, the own label wins the ties it is part of."""
+    T = mask.shape[1]
+    oh = (mask.unsqueeze(-1) == torch.arange(ncls, dtype=torch.uint8, device=mask.device)).to(torch.int16)       # [clips, T, H, W, ncls]
+    cs = torch.nn.functional.pad(oh.cumsum(1, dtype=torch.int16), (0, 0, 0, 0, 0, 0, 1, 0))
+    t = torch.arange(T, device=mask.device)
+    votes = cs[:, (t + r + 1).clamp(max=T)] - cs[:, (t - r).clamp(min=0)]
+    return torch.where(mask < ncls, (votes * 2 + oh).argmax(-1).to(torch.uint8), mask)
+
+
+def part_v(dev, clips, T, S, ncls, reps, n_in=4, torch_rows=True):
+    """gdkvm_temporal_vote at the cfg2 mask shape beside its two yardsticks, in the same windows: the torch expression of the filter
+    (torch_rows; left out at the large batch, where its one-hots take gigabytes), and the byte floor -- every mask byte read once, every
+    out byte written once -- over the copy bandwidth measured here."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    masks = [drifting_masks(clips, T, S, ncls, s, dev) for s in range(n_in)]
+    out = torch.empty_like(masks[0])
+    info = torch.empty((clips, T, 4), dtype=torch.int32, device=dev)
+    counts = torch.empty((clips, T, ncls, 3), dtype=torch.int32, device=dev)
+    big = [torch.empty(512 << 20, dtype=torch.uint8, device=dev) for _ in range(2)]      # a copy that no cache holds
+    nbytes = 2 * masks[0].numel()
+
+    def tv(i, r, target=True):
+        rc = lib.gdkvm_temporal_vote(masks[i].data_ptr(), masks[(i + 1) % n_in].data_ptr() if target else None, out.data_ptr(), info.data_ptr(),
+                                     counts.data_ptr() if target else None, None, 0, clips, T, S, S, ncls, r, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    for r in (1, 2) if torch_rows else ():                         # the yardstick computes the same filter
+        tv(0, r)
+        assert torch.equal(out, torch_vote(masks[0], ncls, r)), r
+    tv(0, 1)
+    torch.cuda.synchronize()
+    print(f"    (vote, r = 1: {float(info[..., 0].float().mean()):.0f} of {S * S} pixels changed per frame, {float(info[..., 1].float().mean()):.0f} "
+          f"differ from the previous frame before and {float(info[..., 2].float().mean()):.0f} after)")
+    forms = {
+        "temporal_vote, r = 1, with a target": (lambda i: tv(i, 1), CALLS),
+        "temporal_vote, r = 2, with a target": (lambda i: tv(i, 2), CALLS),
+        "temporal_vote, r = 1, without a target": (lambda i: tv(i, 1, False), CALLS),
+        "temporal_vote, r = 7, with a target": (lambda i: tv(i, 7), CALLS),
+        "torch expression, r = 1": (lambda i: torch_vote(masks[i], ncls, 1), 2),
+        "torch expression, r = 2": (lambda i: torch_vote(masks[i], ncls, 2), 2),
+        "copy of the mask (out.copy_)": (lambda i: out.copy_(masks[i]), CALLS),
+        "copy of 512 MiB": (lambda i: big[1].copy_(big[0]), 2),
+    }
+    if not torch_rows:
+        forms = {name: f for name, f in forms.items() if not name.startswith("torch")}
+    times = {name: [] for name in forms}
+    for rep in range(reps + 3):
+        for name, (fn, calls) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn(rep % n_in)
+            e1.record()
+            e1.synchronize()
+            if rep >= 3:
+                times[name].append(e0.elapsed_time(e1) * 1e3 / calls)
+    bw = 2 * big[0].numel() / (statistics.median(times["copy of 512 MiB"]) * 1e-6)
+    floor = nbytes / bw * 1e6
+    print(f"(v) temporal vote, {clips} clips of {T} frames of {S}x{S}, {ncls} classes: us per call, windows of device events, median / minimum of "
+          f"{reps} windows per form (alternated, {n_in} inputs in rotation)")
+    print(f"    copy bandwidth {bw / 1e12:.2f} TB/s (read + write of 512 MiB); byte floor of the vote = {nbytes / 1e6:.1f} MB over it = {floor:.2f} us")
+    print(f"{'form':48s} {'median us':>10s} {'min us':>9s} {'x floor':>9s} {'x torch':>9s}")
+    for name in forms:
+        med = statistics.median(times[name])
+        ref = statistics.median(times["torch expression, r = 2" if "r = 2" in name else "torch expression, r = 1"]) if torch_rows else math.nan
+        print(f"{name:48s} {med:10.1f} {min(times[name]):9.1f} {med / floor:9.1f} {med / ref:9.3f}")
+    print(flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
         for keys in (["data.lv_class=1", "data.lv_keep_largest=0"], ["data.lv_class=1", "data.lv_keep_largest=4"],
                      ["data.lv_class=1", "data.lv_keep_largest=0", "data.lv_fill_holes=4"],
+                     ["data.lv_class=1", "data.lv_keep_largest=0", "data.temporal_vote=1"],
                      ["data.lv_class=1", "data.lv_keep_largest=0", "data.surface_class=1"], ["data.lv_class=-1"]):
             t0 = time.perf_counter()
             out = subprocess.run([sys.executable, os.path.join(ROOT, "eval.py")] + keys + overrides, capture_output=True, text=True, timeout=600)
@@ -208,9 +307,13 @@ def main():
     quick = "--quick" in sys.argv
     ops.require_native()
     dev = torch.device("cuda", torch.cuda.current_device())
-    for S in (112, 256):
-        part_a(dev, 8 if quick else 512, S, 5 if quick else 40)
-    if "--no-eval" not in sys.argv:
+    if "--vote-only" not in sys.argv:
+        for S in (112, 256):
+            part_a(dev, 8 if quick else 512, S, 5 if quick else 40)
+    part_v(dev, 2 if quick else 16, 8 if quick else 32, 112, 4, 5 if quick else 40)
+    if not quick:                                                  # 20 times the clips: the launcher's other form (16 pixels per lane)
+        part_v(dev, 320, 32, 112, 4, 20, n_in=2, torch_rows=False)
+    if "--no-eval" not in sys.argv and "--vote-only" not in sys.argv:
         part_b(1 if quick else 2, ["data.size=64", "data.frames=4", "batch_size=4", "model.value_dim=64"] if quick else [])
 
 
