@@ -1,7 +1,8 @@
 // mask_frame.hpp -- what the per-frame kernels over uint8 label masks share (lv_measure.hip, largest_component.hip, surface_distance.hip, fill_holes.hip):
 // ONE workgroup walks one frame [H, W] of bytes at any byte address.  The frame split and its sweeps, the walk over the set bits of a match
 // word, integer wave reductions and the workgroup fold of their per-wave partials, the accessor of a frame's 32-bit words, and the
-// launchers' shared argument checks.  A new per-frame mask kernel starts here.  No floating-point code: a file may include this ahead of
+// launchers' shared argument checks.  A new per-frame mask kernel starts here (one that labels connected components: from mask_labels.hpp,
+// which builds on this).  No floating-point code: a file may include this ahead of
 // an fp-contract pragma of its own.  Like gdkvm_device.hpp, every device helper is __forceinline__ and written with the exact expression the
 // kernels used before they shared it (tools/isa_equal.py).
 #pragma once
@@ -55,7 +56,6 @@ struct MaskFrame {
     const uint8_t* base; const uint4* body;
     int head, nvec, nbody, tail, W;                        // nbody = 16 nvec, the bytes of the vectors: the tail starts at head + nbody
     unsigned cls;
-    MaskFrame() = default;                                 // (largest_component.hip fills one in place, see there)
     // The split is computed in locals: this function is simplified on its own before it is inlined, and from locals the tail comes out as
     // (HW - head) & 15 as in the kernels that had the split inline.
     __device__ __forceinline__ MaskFrame(const uint8_t* base_, int HW, int W_, unsigned cls_) : base(base_), W(W_), cls(cls_)

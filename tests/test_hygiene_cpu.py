@@ -1,7 +1,7 @@
 """CPU checks of round 6's host-side rules: pack / graph invalidation is per model and only on real changes, a convolution that leaves the
 hand-written path says so (and raises under GDKVM_STRICT=1), the launcher honours the reference guide's CUDA_VISIBLE_DEVICES, the
 flat-gradient exchange refuses a parameter without a gradient, stream groups of a captured segment must keep 16-byte output slabs.  And one rule of the kernel sources: the shared device idioms are
-written once, in csrc/gdkvm_device.hpp, and those of the per-frame mask kernels in csrc/mask_frame.hpp."""
+written once, in csrc/gdkvm_device.hpp, and those of the per-frame mask kernels in csrc/mask_frame.hpp and csrc/mask_labels.hpp."""
 import glob
 import os
 import re
@@ -210,8 +210,9 @@ def test_device_idioms_live_in_one_header():
     assert re.search(r"\bvoid\s+static_for\s*\(", header) and re.search(r"\bidx_div\s*\(\s*int\s+n\s*,\s*float\s+inv\s*\)", header)
 
 
-# The per-frame kernels over uint8 label masks share their frame plumbing through csrc/mask_frame.hpp.
-_MASK_KERNELS = ("lv_measure.hip", "largest_component.hip", "surface_distance.hip")
+# The per-frame kernels over uint8 label masks share their frame plumbing through csrc/mask_frame.hpp, and the two that label connected
+# components share the labelling through csrc/mask_labels.hpp, which builds on it.
+_MASK_KERNELS = ("lv_measure.hip", "largest_component.hip", "surface_distance.hip", "fill_holes.hip", "signed_distance.hip")
 _MASK_IDIOMS = {
     "match16 definition": r"\bmatch16\s*\([^()]*\)\s*\{",
     "wave reduction definition": r"\bwave_(sum|min|max)\w*\s*\([^()]*\)\s*\{",
@@ -221,14 +222,15 @@ _MASK_IDIOMS = {
     "shuffle reduction": r"__shfl_xor",
     "atomic word access": r"__hip_atomic_(load|store)",
 }
+# what mask_labels.hpp holds: the union-find, and the frame rewritten vector by vector (a byte spliced into a 32-bit word of the vector)
+_LABEL_IDIOMS = {
+    "union-find definition": r"\b\w*(find|unite)\s*\([^()]*\)\s*\{",
+    "vector rewrite": r"&\s*~\(\s*0xffu\s*<<\s*\(\s*8\s*\*",
+}
 # Sites left as they were: (file, idiom) -> reason; where the helper changed the file's gfx950 assembly, with the number of differing lines
 _MASK_IDIOM_ALLOWED = {
     ("lv_measure.hip", "shuffle reduction"): "lv_ef_kernel's butterfly carries (volume, frame) pairs, a double compared with an index as the tie-break, "
                                              "beside a count: no integer reduction",
-    ("largest_component.hip", "head split"): "the kernel fills its MaskFrame member by member: the constructor's tail comes out as (HW - head) & 15 "
-                                             "and every sweep's tail test changes with it (2119 assembly lines)",
-    ("largest_component.hip", "shuffle reduction"): "pass 7's 64-bit maximum beside wave_sum: through wave_max the two butterflies are scheduled and "
-                                                    "their registers allocated differently (64 assembly lines)",
     ("surface_distance.hip", "bit walk"): "surface_bitmap's walk over a bitmap word: through visit_xy its registers are allocated differently "
                                           "(164 assembly lines)",
 }
@@ -236,16 +238,22 @@ _MASK_IDIOM_ALLOWED = {
 
 def test_mask_frame_idioms_live_in_one_header():
     csrc = os.path.join(ROOT, "gdkvm_amd", "csrc")
+    with open(os.path.join(csrc, "mask_frame.hpp")) as f:
+        header = f.read()
+    with open(os.path.join(csrc, "mask_labels.hpp")) as f:
+        labels = f.read()
+    assert '#include "mask_frame.hpp"' in labels
+    idioms = {**_MASK_IDIOMS, **_LABEL_IDIOMS}
     found = set()
     for name in _MASK_KERNELS:
         with open(os.path.join(csrc, name)) as f:
             text = f.read()
-        assert '#include "mask_frame.hpp"' in text
-        found |= {(name, idiom) for idiom, rx in _MASK_IDIOMS.items() if re.search(rx, text)}
-    assert found == set(_MASK_IDIOM_ALLOWED), (f"mask-frame idioms outside mask_frame.hpp that are not allowed: {sorted(found - set(_MASK_IDIOM_ALLOWED))}; "
-                                               f"allowed but gone: {sorted(set(_MASK_IDIOM_ALLOWED) - found)}")
-    with open(os.path.join(csrc, "mask_frame.hpp")) as f:
-        header = f.read()
+        assert '#include "mask_frame.hpp"' in text or '#include "mask_labels.hpp"' in text
+        found |= {(name, idiom) for idiom, rx in idioms.items() if re.search(rx, text)}
+    found |= {("mask_labels.hpp", idiom) for idiom, rx in _MASK_IDIOMS.items() if re.search(rx, labels)}     # it builds on the first header
+    assert found == set(_MASK_IDIOM_ALLOWED), (f"mask-frame idioms outside mask_frame.hpp / mask_labels.hpp that are not allowed: "
+                                               f"{sorted(found - set(_MASK_IDIOM_ALLOWED))}; allowed but gone: {sorted(set(_MASK_IDIOM_ALLOWED) - found)}")
     missing = [idiom for idiom, rx in _MASK_IDIOMS.items() if not re.search(rx, header)]
-    assert not missing, f"the patterns do not match the header's own idioms: {missing}"
+    missing += [idiom for idiom, rx in _LABEL_IDIOMS.items() if not re.search(rx, labels)]
+    assert not missing, f"the patterns do not match the headers' own idioms: {missing}"
     assert all(re.search(r"\b" + d + r"\s*\(", header) for d in ("match16", "wave_sum", "wave_min", "wave_max", "visit_xy", "visit_p"))
