@@ -19,6 +19,13 @@ largest-component filter, the hole filling and the `lv` block, the `largest_comp
 vote (temporal instability) and the voted mask's Dice; `dice_per_class`, `iou_per_class` and the `surface` block are still those of the
 unfiltered mask.
 
+With a pixel spacing for every clip (gdkvm_amd.data.clip_spacing_table: the dataset's own, e.g. the spacing.json beside a CAMUS sequence, else
+`data.spacing_um` = [row_um, col_um]) the same masks are measured a second time in physical units: an `lv_mm` block (with `lv_class` >= 0) holds
+the EF statistics computed from the volumes in mL (ops.lv_measure_mm: the long axis is found in the physical plane, and ED / ES are the target's
+frames picked on its mL curve) and the mean absolute error and bias of EDV and ESV in mL; a `surface_mm` block (with `surface_class` >= 0)
+holds the mean HD, HD95 and ASSD in mm (ops.surface_distance_mm / surface_metrics_mm).  Every other key keeps its value; without a spacing for
+every clip neither block appears and nothing new runs.
+
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [key=value ...]"""
@@ -46,7 +53,7 @@ def main(argv=None):
 
     from gdkvm_amd import ops
     from gdkvm_amd.config import load_config
-    from gdkvm_amd.data import build_dataset
+    from gdkvm_amd.data import build_dataset, clip_spacing_table
     from gdkvm_amd.distributed import init_from_env, shard_range
     from gdkvm_amd.model import GDKVM, GDKVMConfig
 
@@ -76,9 +83,17 @@ def main(argv=None):
     from gdkvm_amd.pipeline import DevicePrefetcher, SegmentRunner
     ds = build_dataset(cfg, args.split, as_uint8=True)            # bytes across PCIe; cast and scaled on the GPU
     lo, hi = shard_range(len(ds), world, rank)
+    spacing = clip_spacing_table(ds, cfg)                         # int32 [clips, 2] micrometres per pixel, or None: no mL / mm blocks
+    if spacing is not None:
+        if int(spacing.min()) < 1 or int(spacing.max()) > ops.SPACING_UM_MAX:
+            raise SystemExit(f"eval.py: a pixel spacing outside 1..{ops.SPACING_UM_MAX} micrometres")
+        spacing = spacing.to(dev)
     counts = torch.zeros(cfg.data.num_classes, 3, dtype=torch.int64, device=dev)
     lv_cls = cfg.data.lv_class
-    ef_sums = torch.zeros(8, dtype=torch.float64, device=dev)     # ops.ef_summary, accumulated on the device and read once at the end
+    mm = spacing is not None
+    # ops.ef_summary, accumulated on the device and read once at the end; with a spacing, behind it the same eight sums of the EF, the EDV and
+    # the ESV measured in mL
+    ef_sums = torch.zeros(8 + (24 if mm else 0), dtype=torch.float64, device=dev)
     keep = cfg.data.lv_keep_largest if lv_cls >= 0 else 0         # 0 = off: no new call below
     # the filtered mask's counts [ncls, 3], then frames changed and pixels removed: accumulated on the device, read once at the end
     lc_acc = torch.zeros(cfg.data.num_classes * 3 + 2, dtype=torch.int64, device=dev) if keep else None
@@ -89,7 +104,8 @@ def main(argv=None):
     # ops.vote_summary: the voted mask's counts [ncls, 3], then pixels changed, frames changed, flips before, flips after, frames
     tv_acc = torch.zeros(cfg.data.num_classes * 3 + 5, dtype=torch.int64, device=dev) if vote else None
     s_cls = cfg.data.surface_class                                # -1 = off: no new call below
-    sd_sums = torch.zeros(5, dtype=torch.float64, device=dev) if s_cls >= 0 else None    # ops.surface_summary, accumulated on the device
+    # ops.surface_summary, accumulated on the device; with a spacing, behind it the same five sums in mm
+    sd_sums = torch.zeros(5 + (5 if mm else 0), dtype=torch.float64, device=dev) if s_cls >= 0 else None
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -103,23 +119,29 @@ def main(argv=None):
         before it reads batch i's result, and two forwards are in flight (SegmentRunner(in_flight=2); GDKVM_FWD_IN_FLIGHT=1: one at a time).
         The TARGET is measured right behind the submission, on the stream where the prefetcher handed it out: its slot is recycled once the
         consumer asks for the next batch, so nothing may read it later -- the temporal vote of the prediction, its largest-component filter, its
-        hole filling and its surface distances, one batch behind, want the target and get a copy made here."""
+        hole filling and its surface distances, one batch behind, want the target and get a copy made here.  The last element is the
+        target's volumes in mL (with a spacing and lv_class >= 0): the loader is unshuffled, so the clips of a submission are the next rows
+        of the spacing table."""
         pending = None
+        sub = lo                                                  # the first clip of the batch being submitted
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
             nxt = runner.submit(frames, target)
             t_copy = target.clone() if vote or keep or fillc or s_cls >= 0 else None
             if lv_cls >= 0:
                 t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
-                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy)
+                t_ml = ops.lv_measure_mm(target, spacing[sub:sub + target.shape[0], None], cls=lv_cls)[2][..., 1].contiguous() if mm else None
+                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy, t_ml)
             else:
-                nxt = (nxt, None, None, t_copy)
+                nxt = (nxt, None, None, t_copy, None)
+            sub += target.shape[0]
             if pending is not None:
                 yield pending[0].get() + pending[1:]
             pending = nxt
         if pending is not None:
             yield pending[0].get() + pending[1:]
 
-    for mask, c, t_vol, t_npix, t_copy in batches():
+    for mask, c, t_vol, t_npix, t_copy, t_ml in batches():
+        sp = spacing[i:i + mask.shape[0], None] if mm else None   # [B, 1, 2]: results arrive one batch behind, in order, and i counts them
         # only frames that carry labels count (EchoNet-Dynamic: the two traced frames of a clip -- gdkvm_amd.data.IGNORE_LABEL everywhere
         # else, where a predicted pixel must not enter |A|): a labelled frame has a non-empty target in some class
         labelled = (c[..., 2].sum(-1, keepdim=True) > 0).unsqueeze(-1)
@@ -142,10 +164,20 @@ def main(argv=None):
             p_stats, _, p_geom = ops.lv_measure(measured, cls=lv_cls)
             r_idx, r_val = ops.lv_ef(t_vol, t_npix)
             _, p_val = ops.lv_ef(p_geom[..., 1], p_stats[..., 0], pick_vol=t_vol, pick_npix=t_npix)
-            ef_sums += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
+            ef_sums[:8] += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
+            if mm:
+                # the same post-processed mask and the same rule in mL: ED / ES are the target's frames, picked on the target's mL curve
+                q_stats, _, q_geom = ops.lv_measure_mm(measured, sp, cls=lv_cls)
+                m_idx, m_val = ops.lv_ef(t_ml, t_npix)
+                _, q_val = ops.lv_ef(q_geom[..., 1], q_stats[..., 0], pick_vol=t_ml, pick_npix=t_npix)
+                ok = (m_idx[:, 0] >= 0) & (m_val[:, 0] > 0)
+                ef_sums[8:] += torch.cat([ops.ef_summary(q_val[:, k], m_val[:, k], ok) for k in (2, 0, 1)])
         if s_cls >= 0:
             surf = ops.surface_distance(mask, t_copy, cls=s_cls)
-            sd_sums += ops.surface_summary(*ops.surface_metrics(surf), surf, labelled[..., 0, 0])
+            sd_sums[:5] += ops.surface_summary(*ops.surface_metrics(surf), surf, labelled[..., 0, 0])
+            if mm:
+                surf = ops.surface_distance_mm(mask, t_copy, sp, cls=s_cls)
+                sd_sums[5:] += ops.surface_summary(*ops.surface_metrics_mm(surf), surf, labelled[..., 0, 0])
         counts += (c * labelled).sum((0, 1)).long()
         if vis_left > 0:
             from PIL import Image
@@ -175,7 +207,14 @@ def main(argv=None):
                "iou_per_class": [round(d, 5) for d in iou],
                "mean_foreground_iou": round(sum(iou[1:]) / max(len(iou) - 1, 1), 5)}
         if lv_cls >= 0:
-            res["lv"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.ef_stats(ef_sums.cpu()).items()}
+            res["lv"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.ef_stats(ef_sums[:8].cpu()).items()}
+            if mm:
+                acc = ef_sums.cpu()
+                lv_mm = ops.ef_stats(acc[8:16])
+                for name, sums in (("edv", acc[16:24]), ("esv", acc[24:32])):     # ef_summary's sums: count, sum e, sum |e|, ...
+                    cnt = max(float(sums[0]), 1.0)
+                    lv_mm[f"{name}_mae_ml"], lv_mm[f"{name}_bias_ml"] = float(sums[2]) / cnt, float(sums[1]) / cnt
+                res["lv_mm"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in lv_mm.items()}
         if vote:
             acc = tv_acc.cpu()
             tv_dice = ops.dice_from_counts(acc[:-5].view(cfg.data.num_classes, 3)).tolist()
@@ -196,7 +235,11 @@ def main(argv=None):
                                  "pixels_filled": int(acc[5]), "dice_lv": round(float(ops.dice_from_counts(acc[:3])), 5),
                                  "iou_lv": round(float(ops.iou_from_counts(acc[:3])), 5)}
         if s_cls >= 0:
-            res["surface"] = {"class": s_cls, **{k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.surface_stats(sd_sums.cpu()).items()}}
+            res["surface"] = {"class": s_cls, **{k: (v if isinstance(v, int) else round(v, 5)) for k, v in ops.surface_stats(sd_sums[:5].cpu()).items()}}
+            if mm:
+                st = ops.surface_stats(sd_sums[5:].cpu())
+                res["surface_mm"] = {"frames": st["frames"], "frames_one_empty": st["frames_one_empty"],
+                                     **{k + "_mm": round(st[k], 5) for k in ("hd_mean", "hd95_mean", "assd_mean")}}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

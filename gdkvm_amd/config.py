@@ -34,6 +34,8 @@ class DataCfg:
                                      # majority over the frames t - r .. t + r); 0 = off, 1..7 = the radius r
     surface_class: int = -1          # eval.py: the class whose HD, HD95 and ASSD against the target are measured (ops.surface_distance, pixels of
                                      # the input grid); -1 = off
+    spacing_um: Any = None           # eval.py: [row_um, col_um], the micrometres per pixel of the network grid (integers in 1..4095) for datasets
+                                     # that carry no spacing of their own (data.clip_spacing_table); with a spacing eval.py adds the mL / mm blocks
 
 
 @dataclass
@@ -156,6 +158,10 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     sc = cfg.data.surface_class
     if isinstance(sc, bool) or not isinstance(sc, int) or not -1 <= sc < cfg.data.num_classes:
         raise ValueError(f"data.surface_class = {sc!r}: -1 (off) or a class in 0..{cfg.data.num_classes - 1}")
+    sp = cfg.data.spacing_um
+    if sp is not None and (not isinstance(sp, list) or len(sp) != 2
+                           or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4095 for v in sp)):
+        raise ValueError(f"data.spacing_um = {sp!r}: null or [row_um, col_um], two integers in 1..4095 (micrometres per pixel)")
     bw = cfg.loss.boundary_weight
     if isinstance(bw, bool) or not isinstance(bw, (int, float)) or not math.isfinite(bw) or bw < 0:
         raise ValueError(f"loss.boundary_weight = {bw!r}: a finite number >= 0 (0 = off)")

@@ -173,6 +173,157 @@ __global__ __launch_bounds__(256) void lv_measure_kernel(LvArgs a)
     }
 }
 
+struct LvMmArgs {
+    const uint8_t* mask; const int32_t* spacing; i64* stats; i64* disks; double* geom;
+    int HW, W, cls, D;
+};
+
+// lv_measure_kernel with a pixel spacing per frame (gdkvm_lv_measure_mm): the passes are the ones above, integer for integer, with the axis V
+// of step 3' in place of U and one pixel's extent E along it in place of Q; step 6' turns the integers into mm and mL.  A kernel of its own
+// beside the one above, not a switch inside it: the pixel kernel's code stays what it was.
+template <bool RES>
+__global__ __launch_bounds__(256) void lv_measure_mm_kernel(LvMmArgs a)
+{
+    __shared__ i64 s_red[4][6];
+    __shared__ i64 s_mm[4][2];
+    __shared__ u64 s_w[LV_MAX_D];
+    const int tid = threadIdx.x, wv = tid >> 6, HW = a.HW, W = a.W, D = a.D;
+    const size_t f = blockIdx.x;
+    const unsigned cls = (unsigned)a.cls;
+    i64* st = a.stats + f * 12;
+    i64* dk = a.disks + f * (size_t)D;
+    double* ge = a.geom + f * 6;
+    const int ry = a.spacing[2 * f], rx = a.spacing[2 * f + 1];
+    if (ry < 1 || ry > 4095 || rx < 1 || rx > 4095) {      // (uniform) no error can be returned from here: the outputs say so
+        if (tid < 12) st[tid] = -1;
+        if (tid < D) dk[tid] = -1;
+        if (tid < 6) ge[tid] = -1.0;
+        return;
+    }
+    const uint8_t* base = a.mask + f * (size_t)HW;
+    const MaskFrame<256> fr(base, HW, W, cls);
+    if (tid < LV_MAX_D) s_w[tid] = 0;
+
+    unsigned edge = 0;
+    if (tid < fr.head && base[tid] == cls) edge |= 1u;
+    if (tid < fr.tail && base[fr.head + fr.nbody + tid] == cls) edge |= 2u;
+    unsigned mk[LV_RES];
+    if constexpr (RES) {
+        uint4 r[LV_RES];
+#pragma unroll
+        for (int k = 0; k < LV_RES; ++k) {
+            const int v = tid + 256 * k;
+            r[k] = v < fr.nvec ? fr.body[v] : make_uint4(~0u, ~0u, ~0u, ~0u);      // 255 is no class (cls <= 254)
+        }
+#pragma unroll
+        for (int k = 0; k < LV_RES; ++k) mk[k] = match16(r[k], cls);
+    }
+
+    // pass 1: moments
+    unsigned n32 = 0, sx32 = 0, sy32 = 0;
+    u64 sxx = 0, sxy = 0, syy = 0;
+    sweep<RES>(mk, fr, edge, [&](int, int x, int y) {
+        ++n32; sx32 += (unsigned)x; sy32 += (unsigned)y;
+        sxx += (unsigned)(x * x); sxy += (unsigned)(x * y); syy += (unsigned)(y * y);
+    });
+    {
+        const i64 part[6] = {(i64)n32, (i64)sx32, (i64)sy32, (i64)sxx, (i64)sxy, (i64)syy};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const i64 s = wave_sum(part[i]);
+            if ((tid & 63) == 0) s_red[wv][i] = s;
+        }
+    }
+    __syncthreads();
+    i64 tot[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) tot[i] = wg_sum(s_red, i);
+    const i64 n = tot[0], sx = tot[1], sy = tot[2];
+    if (n == 0) {                                          // (uniform) empty frame: every output is 0
+        if (tid < 12) st[tid] = 0;
+        if (tid < D) dk[tid] = 0;
+        if (tid < 6) ge[tid] = 0.0;
+        return;
+    }
+
+    // pass 2: step 3', the long axis in the physical plane -- every lane, the same operations on the same totals
+    int gc = ry;
+    for (int b = rx; b != 0;) { const int t = gc % b; gc = b; b = t; }        // (uniform; at most 18 turns for 12-bit operands)
+    const int py = ry / gc, px = rx / gc, pm = px > py ? px : py;
+    const i64 A = n * tot[3] - sx * sx, B = n * tot[4] - sx * sy, C = n * tot[5] - sy * sy;
+    const double da = sub_rn(mul_rn((double)(px * px), (double)A), mul_rn((double)(py * py), (double)C));
+    const double db = mul_rn(2.0, mul_rn((double)(px * py), (double)B));
+    const double r = sqrt(add_rn(mul_rn(da, da), mul_rn(db, db)));
+    double vx, vy;
+    if (r == 0.0) { vx = 0.0; vy = 1.0; }
+    else if (da >= 0.0) { vx = add_rn(da, r); vy = db; }
+    else { vx = db; vy = sub_rn(r, da); }
+    const double nrm = sqrt(add_rn(mul_rn(vx, vx), mul_rn(vy, vy)));
+    double ux = vx / nrm, uy = vy / nrm;
+    if (uy < 0.0 || (uy == 0.0 && ux < 0.0)) { ux = -ux; uy = -uy; }
+    const double ex = mul_rn(ux, (double)px), ey = mul_rn(uy, (double)py);
+    const double eh = sqrt(add_rn(mul_rn(ex, ex), mul_rn(ey, ey)));
+    const int Vx = (int)rint(mul_rn(ux, (double)(px * LV_Q)) / (double)pm), Vy = (int)rint(mul_rn(uy, (double)(py * LV_Q)) / (double)pm);
+    const int E = (int)rint(mul_rn(eh, (double)LV_Q) / (double)pm);
+
+    // pass 3: extent of the projections t_p = (n x - sx) Vx + (n y - sy) Vy (|Vx|, |Vy| <= Q: the ranges are those of the pixel kernel)
+    const int n_i = (int)n, sx_i = (int)sx, sy_i = (int)sy;
+    auto proj = [&](int x, int y) -> i64 { return (i64)(n_i * x - sx_i) * Vx + (i64)(n_i * y - sy_i) * Vy; };
+    i64 tmin = 0x7fffffffffffffffLL, tmax = -0x7fffffffffffffffLL - 1;
+    sweep<RES>(mk, fr, edge, [&](int, int x, int y) {
+        const i64 t = proj(x, y);
+        tmin = t < tmin ? t : tmin;
+        tmax = t > tmax ? t : tmax;
+    });
+    tmin = wave_min(tmin);
+    tmax = wave_max(tmax);
+    if ((tid & 63) == 0) { s_mm[wv][0] = tmin; s_mm[wv][1] = tmax; }
+    __syncthreads();                                       // (also orders the zeroing of s_w in front of the atomics below)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        tmin = s_mm[w][0] < tmin ? s_mm[w][0] : tmin;
+        tmax = s_mm[w][1] > tmax ? s_mm[w][1] : tmax;
+    }
+
+    // pass 4: the disks by overlap, P1 = n E (E <= Q)
+    const i64 P1 = n * E, Lt = tmax - tmin + P1, DP1 = (i64)D * P1;
+    const double inv_lt = 1.0 / (double)Lt;
+    sweep<RES>(mk, fr, edge, [&](int, int x, int y) {
+        const i64 lo = (i64)D * (proj(x, y) - tmin), hi = lo + DP1;
+        int j = (int)((double)lo * inv_lt);                // floor(lo / Lt) up to rounding, made exact below
+        j = j < 0 ? 0 : (j > D - 1 ? D - 1 : j);
+        while (j > 0 && (i64)j * Lt > lo) --j;
+        while (j < D - 1 && (i64)(j + 1) * Lt <= lo) ++j;
+        for (; j < D && (i64)j * Lt < hi; ++j) {
+            const i64 d0 = (i64)j * Lt, d1 = d0 + Lt;
+            const i64 ov = (hi < d1 ? hi : d1) - (lo > d0 ? lo : d0);
+            atomicAdd(&s_w[j], (u64)ov);
+        }
+    });
+    __syncthreads();
+
+    // pass 5: the record, and step 6'
+    if (tid < D) dk[tid] = (i64)s_w[tid];
+    if (tid < 6) st[tid] = tot[tid];
+    if (tid == 6) { st[6] = Vx; st[7] = Vy; st[8] = tmin; st[9] = tmax; st[10] = Lt; st[11] = E; }
+    if (tid == 64) {
+        const double k = mul_rn(eh, (double)gc);
+        const double L = mul_rn((double)Lt / (double)P1, k) / 1000.0;
+        const double pix = (double)(ry * rx) / 1e6;
+        double s = 0.0;
+        for (int j = 0; j < D; ++j) {
+            const double aj = mul_rn((double)(i64)s_w[j] / (double)DP1, pix);
+            s = add_rn(s, mul_rn(aj, aj));
+        }
+        ge[0] = L;
+        ge[1] = mul_rn(mul_rn(3.14159265358979323846, (double)D), s) / mul_rn(4.0, L) / 1000.0;
+        ge[2] = mul_rn((double)sx / (double)n, (double)rx) / 1000.0;
+        ge[3] = mul_rn((double)sy / (double)n, (double)ry) / 1000.0;
+        ge[4] = k;
+        ge[5] = (double)(n * (i64)(ry * rx)) / 1e6;
+    }
+}
+
 struct EfArgs {
     const double* vol; const i64* npix; const double* pick_vol; const i64* pick_npix;
     int32_t* idx; double* val;
@@ -237,6 +388,25 @@ extern "C" int gdkvm_lv_measure(const uint8_t* mask, int64_t* stats, int64_t* di
     if (H * W <= LV_RES * 256 * 16) hipLaunchKernelGGL((lv_measure_kernel<true>), dim3((unsigned)frames), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((lv_measure_kernel<false>), dim3((unsigned)frames), dim3(256), 0, st, a);
     GDKVM_LAUNCH_CHECK("lv_measure_kernel");
+    return GDKVM_OK;
+}
+
+extern "C" int gdkvm_lv_measure_mm(const uint8_t* mask, const int32_t* spacing_um, int64_t* stats, int64_t* disks, double* geom,
+                                   int frames, int H, int W, int cls, int D, void* stream)
+{
+    if (int rc = mask_check_shape("lv_measure_mm", frames, H, W)) return rc;
+    if (D < 1 || D > LV_MAX_D) return gdkvm_fail(GDKVM_ERR_SHAPE, "lv_measure_mm: D=%d outside 1..%d", D, LV_MAX_D);
+    if (int rc = mask_check_cls("lv_measure_mm", GDKVM_ERR_ARG, cls)) return rc;
+    if (frames == 0) return GDKVM_OK;
+    if (!mask || !spacing_um || !stats || !disks || !geom) return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure_mm: null pointer");
+    if (reinterpret_cast<uintptr_t>(spacing_um) & 3u) return gdkvm_fail(GDKVM_ERR_ARG, "lv_measure_mm: spacing_um must be 4-byte aligned");
+    if (int rc = mask_check_aligned16("lv_measure_mm", GDKVM_ERR_ARG, "outputs", {stats, disks, geom})) return rc;
+    if (int rc = gdkvm_check_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LvMmArgs a{mask, spacing_um, reinterpret_cast<i64*>(stats), reinterpret_cast<i64*>(disks), geom, H * W, W, cls, D};
+    if (H * W <= LV_RES * 256 * 16) hipLaunchKernelGGL((lv_measure_mm_kernel<true>), dim3((unsigned)frames), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((lv_measure_mm_kernel<false>), dim3((unsigned)frames), dim3(256), 0, st, a);
+    GDKVM_LAUNCH_CHECK("lv_measure_mm_kernel");
     return GDKVM_OK;
 }
 

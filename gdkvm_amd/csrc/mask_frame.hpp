@@ -1,6 +1,6 @@
 // mask_frame.hpp -- what the per-frame kernels over uint8 label masks share (lv_measure.hip, largest_component.hip, surface_distance.hip, fill_holes.hip):
 // ONE workgroup walks one frame [H, W] of bytes at any byte address.  The frame split and its sweeps, the walk over the set bits of a match
-// word, integer wave reductions and the workgroup fold of their per-wave partials, the accessor of a frame's 32-bit words, and the
+// word, integer wave reductions and the workgroup fold of their per-wave partials, the accessors of a frame's 32-, 16- and 64-bit words, and the
 // launchers' shared argument checks.  A new per-frame mask kernel starts here (one that labels connected components: from mask_labels.hpp,
 // which builds on this).  No floating-point code: a file may include this ahead of
 // an fp-contract pragma of its own.  Like gdkvm_device.hpp, every device helper is __forceinline__ and written with the exact expression the
@@ -172,6 +172,16 @@ struct FrameHalves {
     static constexpr int SCOPE = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
     __device__ __forceinline__ unsigned ld(I i) const { return __hip_atomic_load(h + i, __ATOMIC_RELAXED, SCOPE); }
     __device__ __forceinline__ void st(I i, unsigned v) const { __hip_atomic_store(h + i, (unsigned short)v, __ATOMIC_RELAXED, SCOPE); }
+};
+
+// The same for 64-bit words (surface_distance.hip in micrometres: an 11-bit row count beside a 45-bit squared distance), 8-byte aligned.
+// Loads and stores only.
+template <bool LDS, class I>
+struct FrameWords64 {
+    unsigned long long* w;
+    static constexpr int SCOPE = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
+    __device__ __forceinline__ unsigned long long ld(I i) const { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, SCOPE); }
+    __device__ __forceinline__ void st(I i, unsigned long long v) const { __hip_atomic_store(w + i, v, __ATOMIC_RELAXED, SCOPE); }
 };
 
 // The launchers' shared argument checks.  Each returns GDKVM_OK or gdkvm_fail(...) with the kernel's name in front of the message; `code`

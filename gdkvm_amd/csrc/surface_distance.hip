@@ -19,8 +19,11 @@
 //   5. maxima, the fixed-point sums, and every word becomes multiplicity (0, 1 or 2 surfaces) << 21 | d2.
 //   6. the two ranks by bisection on the value: each step is one workgroup-wide count of d2 <= m over the words, 16 bytes per lane and read.
 // Loop bounds: the sweeps count to H, the walks to W, the strided loops to H W / lanes, the bisection to 21 (d2 < 2^21).
+// gdkvm_surface_distance_mm, further down, is the same measurement with a pixel spacing per frame (micrometres; 64-bit words per pixel).
 
 #include "mask_frame.hpp"
+
+#include <atomic>
 
 namespace {
 
@@ -276,6 +279,221 @@ __global__ __launch_bounds__(NT) void surface_distance_kernel(SdArgs a)
 // words per frame in the workspace: the frame's words rounded up to 128 bytes, so that no two frames share a cache line
 inline size_t sd_stride(int H, int W) { return ((size_t)sd_plane_words(H * W) + 4 * (size_t)sd_bitmap_words(H * W) + 31) & ~(size_t)31; }
 
+// ---- the same with a pixel spacing: gdkvm_surface_distance_mm ---------------------------------------------------------------------------------
+// Every frame brings its pixel's height ry and width rx in micrometres (1..4095), and a squared distance is (ry dy)^2 + (rx dx)^2 um^2, below
+// 2^45.  The bitmaps, the surfaces and the passes are those above; what changes is the pixel's word, now 64 bits: g in the low 11 bits as
+// before (a count of ROWS: the column sweep is unchanged), d2 in the 45 bits above them, and from pass 5 on d2 in the low 45 bits with the
+// multiplicity above.  A frame keeps 8.5 bytes per pixel: the 64-bit plane first (whole 16-byte vectors), then the four bitmaps.  They live in
+// dynamic LDS while the frame has at most GDKVM_SURFACE_MM_LDS_PIXELS pixels (153 KiB of the workgroup's 160 KiB; a 112 x 112 frame takes
+// 104 KiB; SDU_LDS_NT lanes), otherwise in the frame's slice of the workspace (1024 lanes).  NONE is tested for, not squared: with ry = 1
+// its square is below real distances.  Loop bounds: as above, and the bisection counts to 45.
+constexpr int SDU_LDS_PIX = GDKVM_SURFACE_MM_LDS_PIXELS;
+constexpr int SDU_LDS_NT = 1024;               // lanes of the LDS form: a 112 x 112 frame's 104 KiB leave room for ONE workgroup per CU, so it is a wide one
+constexpr unsigned SDU_D2BITS = 45;
+constexpr u64 SDU_D2MASK = (1ull << SDU_D2BITS) - 1;
+constexpr u64 SDU_INF = ~0ull;                 // no pixel of the other surface met yet
+
+struct SdUmArgs {
+    const uint8_t* mask; const uint8_t* target; const int32_t* spacing; i64* surf; u64* ws;
+    int H, W, HW, cls;
+    size_t stride;                             // 64-bit words per frame of the workspace
+};
+
+__host__ __device__ inline int sdu_plane_words(int HW) { return (HW + 1) & ~1; }          // 64-bit words: whole 16-byte vectors
+inline size_t sdu_frame_bytes(int HW) { return 8 * (size_t)sdu_plane_words(HW) + 16 * (size_t)sd_bitmap_words(HW); }
+inline size_t sdu_stride(int H, int W) { return ((sdu_frame_bytes(H * W) + 127) & ~(size_t)127) / 8; }
+
+// floor(sqrt(d2 * 2^16)): the operand is below 2^61 and its root below 2^31, so the fp64 estimate is off by at most one either way
+__device__ __forceinline__ u64 isqrt_q16(u64 d2)
+{
+    const u64 n = d2 << 16;
+    u64 r = (u64)sqrt((double)n);
+    if (r * r > n) --r;
+    if ((r + 1) * (r + 1) <= n) ++r;
+    return r;
+}
+
+// Pass 4 for one direction, as directed_distance: B holds the bitmaps, P the plane; ry2, rx2 = the squared spacings
+template <bool LDS, int NT>
+__device__ __forceinline__ void directed_distance_um(const Words<LDS>& B, const FrameWords64<LDS, int>& P, int bt, int bo, int H, int W, int HW,
+                                                     u64 ry2, u64 rx2, bool first)
+{
+    const int tid = threadIdx.x;
+    for (int x = tid; x < W; x += NT) {
+        unsigned d = SD_NONE;
+        for (int y = 0, p = x; y < H; ++y, p += W) {
+            if (B.bit(bo, p)) d = 0;
+            else if (d != SD_NONE) ++d;
+            P.st(p, (first ? 0ull : (P.ld(p) & ~(u64)SD_NONE)) | d);
+        }
+        d = SD_NONE;
+        for (int y = H - 1, p = (H - 1) * W + x; y >= 0; --y, p -= W) {
+            if (B.bit(bo, p)) d = 0;
+            else if (d != SD_NONE) ++d;
+            const u64 w = P.ld(p);
+            if (d < ((unsigned)w & SD_NONE)) P.st(p, (w & ~(u64)SD_NONE) | d);
+        }
+    }
+    __syncthreads();
+    // while a lane replaces the d2 bits of its own word, other lanes read that word's g bits, which the (single, 64-bit) store leaves as they are
+    for (int p = tid; p < HW; p += NT) {
+        if (!B.bit(bt, p)) continue;
+        const int y = p / W, x = p - y * W, row = p - x;
+        const unsigned g0 = (unsigned)P.ld(p) & SD_NONE;
+        u64 best = g0 == SD_NONE ? SDU_INF : (u64)(g0 * g0) * ry2;
+        const int kmax = x > W - 1 - x ? x : W - 1 - x;
+        for (int k = 1; k <= kmax; ++k) {
+            const u64 kk = (u64)(unsigned)(k * k) * rx2;     // (< 2^20 * 2^24)
+            if (kk >= best) break;
+            if (x - k >= 0) {
+                const unsigned g = (unsigned)P.ld(row + x - k) & SD_NONE;
+                const u64 c = kk + (u64)(g * g) * ry2;
+                best = (g != SD_NONE && c < best) ? c : best;
+            }
+            if (x + k < W) {
+                const unsigned g = (unsigned)P.ld(row + x + k) & SD_NONE;
+                const u64 c = kk + (u64)(g * g) * ry2;
+                best = (g != SD_NONE && c < best) ? c : best;
+            }
+        }
+        P.st(p, (best << SD_GBITS) | g0);                   // (the other surface is not empty: best < 2^45)
+    }
+    __syncthreads();
+}
+
+template <bool LDS, int NT>
+__global__ __launch_bounds__(NT) void surface_distance_mm_kernel(SdUmArgs a)
+{
+    constexpr int NW = NT / 64;
+    extern __shared__ uint4 sdu_mem[];
+    __shared__ unsigned s_n[NW][2];
+    __shared__ u64 s_h[NW][2];
+    __shared__ u64 s_s[NW][2];
+    __shared__ u64 s_c[2][NW][2];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, H = a.H, W = a.W, HW = a.HW;
+    const size_t f = blockIdx.x;
+    const unsigned cls = (unsigned)a.cls;
+    const int PW = sdu_plane_words(HW), BW = sd_bitmap_words(HW);
+    const int bA = 0, bB = BW, bSA = 2 * BW, bSB = 3 * BW;
+    i64* out = a.surf + f * 8;
+    const int ry = a.spacing[2 * f], rx = a.spacing[2 * f + 1];
+    if (ry < 1 || ry > 4095 || rx < 1 || rx > 4095) {      // (uniform) no error can be returned from here: the record says so
+        if (tid < 8) out[tid] = -1;
+        return;
+    }
+    const u64 ry2 = (u64)(ry * ry), rx2 = (u64)(rx * rx);
+    FrameWords64<LDS, int> P;
+    if constexpr (LDS) P.w = reinterpret_cast<u64*>(sdu_mem);
+    else P.w = a.ws + f * a.stride;
+    Words<LDS> M;
+    M.w = reinterpret_cast<unsigned*>(P.w + PW);
+
+    // pass 1, 2: the bitmaps
+    for (int i = tid; i < 4 * BW; i += NT) M.st(i, 0u);
+    __syncthreads();
+    class_bitmap<LDS, NT>(M, bA, a.mask + f * (size_t)HW, HW, W, cls);
+    class_bitmap<LDS, NT>(M, bB, a.target + f * (size_t)HW, HW, W, cls);
+    __syncthreads();
+
+    // pass 3: the surfaces and their sizes
+    {
+        const unsigned ca = wave_sum(surface_bitmap<LDS, NT>(M, bA, bSA, H, W, HW));
+        const unsigned cb = wave_sum(surface_bitmap<LDS, NT>(M, bB, bSB, H, W, HW));
+        if (lane == 0) { s_n[wv][0] = ca; s_n[wv][1] = cb; }
+        __syncthreads();
+    }
+    const unsigned nA = wg_sum(s_n, 0), nB = wg_sum(s_n, 1);
+    if (nA == 0 || nB == 0) {                              // (uniform) no surface distance
+        if (tid < 8) out[tid] = tid == 0 ? (i64)nA : tid == 1 ? (i64)nB : 0;
+        return;
+    }
+
+    // pass 4: both directions
+    directed_distance_um<LDS, NT>(M, P, bSA, bSB, H, W, HW, ry2, rx2, true);
+    directed_distance_um<LDS, NT>(M, P, bSB, bSA, H, W, HW, ry2, rx2, false);
+
+    // pass 5: maxima, sums, and the words of the bisection (the word past an odd H W counts nothing)
+    u64 hAB = 0, hBA = 0;
+    {
+        u64 sAB = 0, sBA = 0;
+        for (int p = tid; p < PW; p += NT) {
+            u64 v = 0;
+            if (p < HW) {
+                const bool ina = M.bit(bSA, p), inb = M.bit(bSB, p);
+                if (ina || inb) {
+                    const u64 d2 = P.ld(p) >> SD_GBITS;
+                    const u64 r = isqrt_q16(d2);
+                    if (ina) { hAB = d2 > hAB ? d2 : hAB; sAB += r; }
+                    if (inb) { hBA = d2 > hBA ? d2 : hBA; sBA += r; }
+                    v = ((u64)((ina ? 1u : 0u) + (inb ? 1u : 0u)) << SDU_D2BITS) | d2;
+                }
+            }
+            P.st(p, v);
+        }
+        hAB = wave_max(hAB); hBA = wave_max(hBA);
+        sAB = wave_sum(sAB); sBA = wave_sum(sBA);
+        if (lane == 0) { s_h[wv][0] = hAB; s_h[wv][1] = hBA; s_s[wv][0] = sAB; s_s[wv][1] = sBA; }
+        __syncthreads();
+        hAB = hBA = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            hAB = s_h[w][0] > hAB ? s_h[w][0] : hAB;
+            hBA = s_h[w][1] > hBA ? s_h[w][1] : hBA;
+        }
+    }
+
+    // pass 6: the ranks, as above: the slots of s_c alternate, one barrier per count
+    int turn = 0;
+    auto count = [&](u64 m, u64& above) -> unsigned {
+        unsigned c = 0;
+        u64 mn = SDU_INF;
+        for (int i = tid; i < PW / 2; i += NT) {
+            u64 w[2];
+            if constexpr (LDS) {
+                const uint4 q = sdu_mem[i];
+                w[0] = ((u64)q.y << 32) | q.x; w[1] = ((u64)q.w << 32) | q.z;
+            } else {
+                w[0] = P.ld(2 * i); w[1] = P.ld(2 * i + 1);
+            }
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const u64 d2 = w[e] & SDU_D2MASK;
+                const unsigned mult = (unsigned)(w[e] >> SDU_D2BITS);
+                c += d2 <= m ? mult : 0u;
+                mn = (mult && d2 > m && d2 < mn) ? d2 : mn;
+            }
+        }
+        c = wave_sum(c);
+        mn = wave_min(mn);
+        if (lane == 0) { s_c[turn][wv][0] = c; s_c[turn][wv][1] = mn; }
+        __syncthreads();
+        c = 0; mn = SDU_INF;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            c += (unsigned)s_c[turn][w][0];
+            mn = s_c[turn][w][1] < mn ? s_c[turn][w][1] : mn;
+        }
+        turn ^= 1;
+        above = mn;
+        return c;
+    };
+    const unsigned n = nA + nB, lo = (unsigned)((95ull * (n - 1)) / 100ull), hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
+    u64 vlo = 0, vhi = hAB > hBA ? hAB : hBA, above;
+    for (int it = 0; it < (int)SDU_D2BITS && vlo < vhi; ++it) {     // (uniform) the smallest v with count(v) > lo
+        const u64 mid = (vlo + vhi) >> 1;
+        if (count(mid, above) > lo) vhi = mid;
+        else vlo = mid + 1;
+    }
+    const u64 q_lo = vlo;
+    const unsigned c_lo = count(q_lo, above);
+    const u64 q_hi = c_lo > hi ? q_lo : above;             // (c_lo <= hi <= n - 1: a pooled value above q_lo exists)
+
+    if (tid == 0) {
+        out[0] = (i64)nA; out[1] = (i64)nB; out[2] = (i64)hAB; out[3] = (i64)hBA;
+        out[4] = (i64)wg_sum(s_s, 0); out[5] = (i64)wg_sum(s_s, 1); out[6] = (i64)q_lo; out[7] = (i64)q_hi;
+    }
+}
+
 }  // namespace
 
 extern "C" size_t gdkvm_surface_distance_workspace_bytes(int frames, int H, int W)
@@ -300,5 +518,48 @@ extern "C" int gdkvm_surface_distance(const uint8_t* mask, const uint8_t* target
     if (!need) hipLaunchKernelGGL((surface_distance_kernel<true, 256>), dim3((unsigned)frames), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((surface_distance_kernel<false, 1024>), dim3((unsigned)frames), dim3(1024), 0, st, a);
     GDKVM_LAUNCH_CHECK("surface_distance_kernel");
+    return GDKVM_OK;
+}
+
+extern "C" size_t gdkvm_surface_distance_mm_workspace_bytes(int frames, int H, int W)
+{
+    if (!mask_shape_ok(frames, H, W) || H * W <= SDU_LDS_PIX) return 0;
+    return (size_t)frames * sdu_stride(H, W) * sizeof(u64);
+}
+
+extern "C" int gdkvm_surface_distance_mm(const uint8_t* mask, const uint8_t* target, const int32_t* spacing_um, int64_t* surf, void* workspace,
+                                         size_t workspace_bytes, int frames, int H, int W, int cls, void* stream)
+{
+    if (int rc = mask_check_shape("surface_distance_mm", frames, H, W)) return rc;
+    if (int rc = mask_check_cls("surface_distance_mm", GDKVM_ERR_SHAPE, cls)) return rc;
+    if (frames == 0) return GDKVM_OK;
+    if (!mask || !target || !spacing_um || !surf)
+        return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance_mm: null pointer (mask, target, spacing_um and surf are required)");
+    if (reinterpret_cast<uintptr_t>(spacing_um) & 3u) return gdkvm_fail(GDKVM_ERR_SHAPE, "surface_distance_mm: spacing_um must be 4-byte aligned");
+    if (int rc = mask_check_aligned16("surface_distance_mm", GDKVM_ERR_SHAPE, "surf", {surf})) return rc;
+    const size_t need = gdkvm_surface_distance_mm_workspace_bytes(frames, H, W);
+    if (int rc = mask_check_workspace("surface_distance_mm", H, W, need, workspace, workspace_bytes)) return rc;
+    if (int rc = gdkvm_check_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SdUmArgs a{mask, target, spacing_um, reinterpret_cast<i64*>(surf), static_cast<u64*>(workspace), H, W, H * W, cls, sdu_stride(H, W)};
+    if (!need) {
+        const size_t lds = sdu_frame_bytes(H * W);
+        if (lds > 32 * 1024) {                           // a large frame needs the opt-in once per device
+            static std::atomic<unsigned long long> done_mask{0};
+            int dev = 0;
+            if (hipGetDevice(&dev) != hipSuccess) return gdkvm_fail(GDKVM_ERR_LAUNCH, "surface_distance_mm: hipGetDevice");
+            const unsigned long long bit = 1ull << (dev & 63);
+            if (!(done_mask.load(std::memory_order_relaxed) & bit)) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(surface_distance_mm_kernel<true, SDU_LDS_NT>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)sdu_frame_bytes(SDU_LDS_PIX));
+                if (e != hipSuccess) return gdkvm_fail(GDKVM_ERR_LAUNCH, "surface_distance_mm: LDS attribute: %s", hipGetErrorString(e));
+                done_mask.fetch_or(bit, std::memory_order_relaxed);
+            }
+        }
+        hipLaunchKernelGGL((surface_distance_mm_kernel<true, SDU_LDS_NT>), dim3((unsigned)frames), dim3(SDU_LDS_NT), lds, st, a);
+    } else {
+        hipLaunchKernelGGL((surface_distance_mm_kernel<false, 1024>), dim3((unsigned)frames), dim3(1024), 0, st, a);
+    }
+    GDKVM_LAUNCH_CHECK("surface_distance_mm_kernel");
     return GDKVM_OK;
 }

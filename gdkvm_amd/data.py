@@ -8,17 +8,38 @@ so the default is a seeded synthetic echo-like clip generator; two on-disk forma
                UNLABELLED (label 255, which the loss leaves out: gdkvm_amd.train.segmentation_loss, gdkvm_seg_loss_fwd)
   camus_png    <root>/<split>/<patient>/<view>/frame_XXX.png + mask_XXX.png, view in {2CH, 4CH}, masks 0 bg / 1 LV / 2 myocardium / 3 LA --
                what tools/convert_camus.py writes from the CAMUS NIfTI release (guide: index.astro:221); the reference's own processed
-               "camus_png256x256_10f" tree is not documented beyond its name (index.astro:217,246), so this layout is the builder's
+               "camus_png256x256_10f" tree is not documented beyond its name (index.astro:217,246), so this layout is the builder's;
+               beside the PNGs an optional spacing.json {"spacing_um": [row_um, col_um], "native_hw": [H, W]}: the pixel spacing of the
+               RESIZED grid in micrometres, from the NIfTI pixdim
+
+A dataset's spacing_um(i) is clip i's pixel spacing (row_um, col_um) in integer micrometres per pixel of the grid its masks are on, or None;
+clip_spacing_table gathers them for eval.py, which then reports volumes in mL and surface distances in mm.  Samples stay (frames, target).
 """
 from __future__ import annotations
 
 import glob
+import json
 import os
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 from torch.utils.data import Dataset
+
+
+SPACING_UM_MAX = 4095
+
+
+def _spacing_pair(v) -> Optional[Tuple[int, int]]:
+    """(row_um, col_um) when v holds two integers in 1..SPACING_UM_MAX, else None."""
+    try:
+        a = np.asarray(v)
+        if a.shape != (2,) or not np.issubdtype(a.dtype, np.integer):
+            return None
+        ry, rx = int(a[0]), int(a[1])
+    except (TypeError, ValueError):
+        return None
+    return (ry, rx) if 1 <= ry <= SPACING_UM_MAX and 1 <= rx <= SPACING_UM_MAX else None
 
 
 class SyntheticEchoClips(Dataset):
@@ -30,6 +51,9 @@ class SyntheticEchoClips(Dataset):
 
     def __len__(self):
         return self.n
+
+    def spacing_um(self, i):
+        return None                                               # a drawing has no physical size
 
     def __getitem__(self, i) -> Tuple[torch.Tensor, torch.Tensor]:
         rng = np.random.default_rng(self.seed * 1_000_003 + i)
@@ -205,6 +229,9 @@ class EchoNetNpz(Dataset):
     def __len__(self):
         return len(self.files)
 
+    def spacing_um(self, i):
+        return None                                               # EchoNet-Dynamic ships no pixel spacing
+
     def __getitem__(self, i):
         z = np.load(self.files[i])
         video, traced, masks = z["video"], z["traced"], z["masks"]
@@ -226,6 +253,11 @@ class NpzClips(Dataset):
 
     def __len__(self):
         return len(self.files)
+
+    def spacing_um(self, i):
+        """The clip's optional `spacing_um` array [row_um, col_um]; None without it or when it is no pair of integers in 1..4095."""
+        with np.load(self.files[i]) as z:
+            return _spacing_pair(z["spacing_um"]) if "spacing_um" in z.files else None
 
     def __getitem__(self, i):
         z = np.load(self.files[i])
@@ -259,6 +291,18 @@ class CamusPng(Dataset):
     def view(self, i) -> str:
         return os.path.basename(self.seqs[i])
 
+    def spacing_um(self, i):
+        """The sequence's spacing.json "spacing_um" [row_um, col_um] (tools/convert_camus.py, from the NIfTI pixdim and the resize); None
+        without the file or when it holds no pair of integers in 1..4095."""
+        p = os.path.join(self.seqs[i], "spacing.json")
+        if not os.path.exists(p):
+            return None
+        try:
+            with open(p) as f:
+                return _spacing_pair(json.load(f).get("spacing_um"))
+        except (ValueError, AttributeError):
+            return None
+
     def __getitem__(self, i):
         from PIL import Image
         fr = sorted(glob.glob(os.path.join(self.seqs[i], "frame_*.png")))
@@ -274,6 +318,21 @@ class CamusPng(Dataset):
             xs.append(img)
             ys.append(np.asarray(Image.open(mk), ldt) if os.path.exists(mk) else np.full(img.shape[:2], IGNORE_LABEL, ldt))
         return torch.from_numpy(np.stack(xs)).permute(0, 3, 1, 2).contiguous(), torch.from_numpy(np.stack(ys))
+
+
+def clip_spacing_table(ds, cfg) -> Optional[torch.Tensor]:
+    """int32 [len(ds), 2] (host) = every clip's (row_um, col_um): the dataset's own spacing_um(i), else cfg.data.spacing_um; None as soon as
+    one clip has neither (then nothing is measured in mm: a table with holes would average over a different set of clips)."""
+    fallback = _spacing_pair(cfg.data.spacing_um) if cfg.data.spacing_um is not None else None
+    own = getattr(ds, "spacing_um", None)
+    rows = []
+    for i in range(len(ds)):
+        sp = own(i) if own is not None else None
+        sp = sp if sp is not None else fallback
+        if sp is None:
+            return None
+        rows.append(sp)
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2)
 
 
 def build_dataset(cfg, split: str = "train", n_synthetic: int = 256, as_uint8: bool = False) -> Dataset:

@@ -125,6 +125,7 @@ SIGNATURES = {
     "gdkvm_bn_pool_bwd": (_i, [_vp] * 9 + [_sz] + [_i] * 5 + [_vp]),
     "gdkvm_augment_clips": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
     "gdkvm_lv_measure": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "gdkvm_lv_measure_mm": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
     "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
@@ -134,6 +135,8 @@ SIGNATURES = {
     "gdkvm_temporal_vote": (_i, [_vp] * 6 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
+    "gdkvm_surface_distance_mm_workspace_bytes": (_sz, [_i] * 3),
+    "gdkvm_surface_distance_mm": (_i, [_vp] * 5 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
     "gdkvm_signed_distance": (_i, [_vp] * 3 + [_sz] + [_i] * 4 + [ctypes.c_uint, _vp]),
     "gdkvm_adamw_workspace_bytes": (_sz, [_i, ctypes.c_longlong]),
@@ -2050,6 +2053,46 @@ def lv_measure(mask: torch.Tensor, cls: int = 1, disks: int = 20):
     return stats, dk, geom
 
 
+SPACING_UM_MAX = 4095           # a pixel spacing is (row_um, col_um), integers in 1..SPACING_UM_MAX micrometres
+SURFACE_MM_LDS_PIXELS = 18432   # GDKVM_SURFACE_MM_LDS_PIXELS: frames of up to this many pixels need no workspace in surface_distance_mm
+
+
+def _spacing_frames(what: str, spacing_um: torch.Tensor, lead, dev) -> torch.Tensor:
+    """spacing_um int32 [..., 2] broadcast over the mask's leading shape `lead` -> a contiguous int32 [*lead, 2] on `dev`.  A CPU tensor is
+    range-checked here and copied; a device tensor is trusted (the kernels answer an out-of-range frame with -1 everywhere)."""
+    if not isinstance(spacing_um, torch.Tensor) or spacing_um.dtype != torch.int32 or spacing_um.dim() < 1 or spacing_um.shape[-1] != 2:
+        raise GdkvmError(f"{what}: spacing_um must be an int32 tensor [..., 2] = (row_um, col_um), got "
+                         f"{getattr(spacing_um, 'dtype', type(spacing_um))} {tuple(getattr(spacing_um, 'shape', ()))}")
+    if not spacing_um.is_cuda:
+        if spacing_um.numel() and (int(spacing_um.min()) < 1 or int(spacing_um.max()) > SPACING_UM_MAX):
+            raise GdkvmError(f"{what}: spacing_um outside 1..{SPACING_UM_MAX} micrometres")
+        spacing_um = spacing_um.to(dev)
+    elif spacing_um.device != dev:
+        raise GdkvmError("tensors on different devices")
+    try:
+        return spacing_um.expand(tuple(lead) + (2,)).contiguous()
+    except RuntimeError:
+        raise GdkvmError(f"{what}: spacing_um {tuple(spacing_um.shape)} does not broadcast over the mask's leading shape {tuple(lead)}") from None
+
+
+def lv_measure_mm(mask: torch.Tensor, spacing_um: torch.Tensor, cls: int = 1, disks: int = 20):
+    """gdkvm_lv_measure_mm: lv_measure with a pixel spacing -- spacing_um int32 [..., 2] = (row_um, col_um) micrometres per pixel, broadcast
+    over mask's leading dimensions ([B, 1, 2] against [B, T, H, W]); the long axis is found in the physical plane (definition:
+    include/gdkvm.h).  Returns (stats int64 [..., 12] = n sx sy sxx sxy syy Vx Vy tmin tmax Lt E, disks int64 [..., D], geom float64
+    [..., 6] = L in mm, V in mL, cx, cy in mm, k = um per pixel extent along the axis, area in mm^2).  A frame whose spacing (a device
+    tensor's: a host tensor is refused) is outside 1..4095 holds -1 everywhere."""
+    lead, frames, H, W = _mask_frames("lv_measure_mm", mask, cls)
+    if not 1 <= int(disks) <= LV_MAX_DISKS:
+        raise GdkvmError(f"lv_measure_mm: disks = {disks} outside 1..{LV_MAX_DISKS}")
+    dev = _dev(mask)
+    sp = _spacing_frames("lv_measure_mm", spacing_um, lead, dev)
+    stats = torch.empty(lead + (12,), dtype=torch.int64, device=dev)
+    dk = torch.empty(lead + (int(disks),), dtype=torch.int64, device=dev)
+    geom = torch.empty(lead + (6,), dtype=torch.float64, device=dev)
+    _call("gdkvm_lv_measure_mm", dev, mask, sp, stats, dk, geom, frames, H, W, int(cls), int(disks))
+    return stats, dk, geom
+
+
 def lv_ef(vol: torch.Tensor, npix: torch.Tensor, pick_vol: Optional[torch.Tensor] = None, pick_npix: Optional[torch.Tensor] = None,
           min_pixels: int = 1):
     """gdkvm_lv_ef: per clip the end-diastolic / end-systolic frames and the ejection fraction from vol float64 [B, T] and npix int64 [B, T]
@@ -2261,6 +2304,39 @@ def surface_metrics(surf: torch.Tensor):
     frac = ((95 * (nA + nB - 1).clamp(min=0)) % 100).to(torch.float64) / 100.0
     hd95 = a + (b - a) * frac
     assd = (d[..., 4] / d[..., 0].clamp(min=1.0) + d[..., 5] / d[..., 1].clamp(min=1.0)) / 2.0 / 65536.0
+    metrics = torch.stack([hd, hd95, assd], -1) * valid.unsqueeze(-1).to(torch.float64)
+    return metrics, valid
+
+
+def surface_distance_mm(mask: torch.Tensor, target: torch.Tensor, spacing_um: torch.Tensor, cls: int = 1) -> torch.Tensor:
+    """gdkvm_surface_distance_mm: surface_distance with a pixel spacing -- spacing_um int32 [..., 2] = (row_um, col_um) micrometres per pixel,
+    broadcast over mask's leading dimensions.  Returns surf int64 [..., 8] = nA, nB, hAB, hBA (um^2), sAB, sBA (sums of the distances in
+    units of 2^-8 um, each rounded down), q_lo, q_hi (um^2); a frame whose spacing (a device tensor's: a host tensor is refused) is outside
+    1..4095 holds eight -1.  surface_metrics_mm turns it into HD, HD95 and ASSD in mm."""
+    lead, frames, H, W = _mask_frames("surface_distance_mm", mask, cls, target=target)
+    dev = _dev(mask, target)
+    sp = _spacing_frames("surface_distance_mm", spacing_um, lead, dev)
+    surf = torch.empty(lead + (8,), dtype=torch.int64, device=dev)
+    ws = _workspace("gdkvm_surface_distance_mm_workspace_bytes", dev, frames, H, W, floor=16)
+    _call("gdkvm_surface_distance_mm", dev, mask, target, sp, surf, _Ws(ws), frames, H, W, int(cls))
+    return surf
+
+
+def surface_metrics_mm(surf: torch.Tensor):
+    """(metrics float64 [..., 3] = HD, HD95, ASSD in mm, valid bool [...]) from surface_distance_mm's surf [..., 8]: surface_metrics'
+    formulas with sqrt(.) / 1000 for the squared distances (um^2) and / 256 / 1000 for the sums (2^-8 um).  A record of -1 (a spacing out
+    of range) is invalid, like one with an empty surface; the metrics of an invalid frame are 0."""
+    if surf.shape[-1] != 8 or torch.is_floating_point(surf):
+        raise GdkvmError(f"surface_metrics_mm: surf must be integers [..., 8], got {surf.dtype} {tuple(surf.shape)}")
+    s = surf.to(torch.int64)
+    nA, nB = s[..., 0], s[..., 1]
+    valid = (nA > 0) & (nB > 0)
+    d = s.clamp(min=0).to(torch.float64)
+    hd = torch.maximum(d[..., 2], d[..., 3]).sqrt() / 1000.0
+    a, b = d[..., 6].sqrt() / 1000.0, d[..., 7].sqrt() / 1000.0
+    frac = ((95 * (nA + nB - 1).clamp(min=0)) % 100).to(torch.float64) / 100.0
+    hd95 = a + (b - a) * frac
+    assd = (d[..., 4] / d[..., 0].clamp(min=1.0) + d[..., 5] / d[..., 1].clamp(min=1.0)) / 2.0 / 256.0 / 1000.0
     metrics = torch.stack([hd, hd95, assd], -1) * valid.unsqueeze(-1).to(torch.float64)
     return metrics, valid
 

@@ -640,6 +640,28 @@ int gdkvm_augment_clips(const uint8_t* frames, const void* target, const float* 
  * One workgroup per frame, integer sums only: bit-reproducible.  frames == 0 is GDKVM_OK without a launch. */
 int gdkvm_lv_measure(const uint8_t* mask, int64_t* stats, int64_t* disks, double* geom,
                      int frames, int H, int W, int cls, int D, void* stream);
+/* The same with a pixel spacing: lengths in mm, volumes in mL, the long axis found in the PHYSICAL plane (a CAMUS sequence squeezed to a square
+ * grid has pixels of about 0.33 x 0.47 mm: in pixel units its ventricle is distorted).  spacing_um [frames, 2] int32 on the DEVICE (4-byte
+ * aligned) holds, per frame, ry = the micrometres per pixel down the rows (y) and rx = along the columns (x), each in 1..4095.
+ * Steps 1, 2, 4 and 5 are those above, integer for integer, with (Vx, Vy) in place of (Ux, Uy) and P1 = n E.  What is new:
+ *   3'. axis (fp64, every operation rounded once, no fused multiply-add)   g = gcd(ry, rx), py = ry / g, px = rx / g, pm = max(px, py);
+ *        a = (double)(px px) (double)A - (double)(py py) (double)C,  b = 2 ((double)(px py) (double)B)   (the central moments of the
+ *        physical positions (x rx, y ry), over g^2);  r and the unit vector (ux, uy) with its sign rule exactly as in step 3: the long axis
+ *        in the physical plane;
+ *        ex = ux (double)px, ey = uy (double)py, e = sqrt(ex ex + ey ey);
+ *        Vx = rint((ux (double)(px Q)) / (double)pm), Vy = rint((uy (double)(py Q)) / (double)pm), E = rint((e (double)Q) / (double)pm).
+ *        (x, y) -> x Vx + y Vy is the projection of the physical position on the axis in units of g pm / Q um, and E one pixel's extent
+ *        along the axis in the same units.  |Vx|, |Vy| <= Q and 16 <= E <= Q, so the integer ranges of steps 4 and 5 stand.  Isotropic
+ *        spacing gives px = py = 1 and E = Q, and V is U up to the +-1 of a moved rint tie.
+ *   6'. geometry (fp64)   k = e (double)g (um per pixel extent along the axis);  L = ((Lt / P1) k) / 1000 (mm);
+ *        a_j = (W_j / (D P1)) ((double)(ry rx) / 1e6) (mm^2 in disk j);  V = ((pi D) sum_j a_j^2) / (4 L) / 1000 (mL), the sum in ascending j;
+ *        cx = ((sx / n) (double)rx) / 1000, cy = ((sy / n) (double)ry) / 1000 (mm);  area = (double)(n ry rx) / 1e6 (mm^2).
+ * Outputs (16-byte aligned):  stats [frames, 12] = n, sx, sy, sxx, sxy, syy, Vx, Vy, tmin, tmax, Lt, E;   disks [frames, D] = W_j;
+ *   geom [frames, 6] = L, V, cx, cy, k, area.   n == 0: every output of the frame is 0.  A frame whose ry or rx is outside 1..4095: every
+ * output of the frame is -1 (the kernel cannot return an error; gdkvm_amd.ops checks a host tensor before it is copied).  gdkvm_lv_ef takes
+ * the mL curve (geom[..., 1]) as it is.  Everything else as for gdkvm_lv_measure. */
+int gdkvm_lv_measure_mm(const uint8_t* mask, const int32_t* spacing_um, int64_t* stats, int64_t* disks, double* geom,
+                        int frames, int H, int W, int cls, int D, void* stream);
 /* Clip level: vol, npix [B, T] (geom[..., 1] and stats[..., 0] of gdkvm_lv_measure, made contiguous; 8-byte aligned), optional pick_vol /
  * pick_npix [B, T] (both or neither; e.g. the target's, so that the prediction's volumes are read at the annotated frames).  Frame t is valid
  * when pick_npix[b][t] >= min_pixels (npix without pick arrays); ED = the valid frame of the largest pick volume, ES = of the smallest, ties ->
@@ -766,6 +788,25 @@ int gdkvm_temporal_vote(const uint8_t* mask, const uint8_t* target, uint8_t* out
 size_t gdkvm_surface_distance_workspace_bytes(int frames, int H, int W);
 int gdkvm_surface_distance(const uint8_t* mask, const uint8_t* target, int64_t* surf, void* workspace, size_t workspace_bytes,
                            int frames, int H, int W, int cls, void* stream);
+/* The same with a pixel spacing: distances in micrometres, so that HD, HD95 and ASSD come out in mm whatever the pixels' aspect (a CAMUS
+ * sequence squeezed to a square grid has pixels of about 0.33 x 0.47 mm).  spacing_um [frames, 2] int32 on the DEVICE (4-byte aligned) holds,
+ * per frame, ry = the micrometres per pixel down the rows (y) and rx = along the columns (x), each in 1..4095.
+ *   1, 2. A, B and the surfaces are those of gdkvm_surface_distance: the erosion is topological and knows no spacing (what medpy does with
+ *      `voxelspacing`).
+ *   3. d2(p, q) = (ry (py - qy))^2 + (rx (px - qx))^2 in um^2, an exact integer below 2 (1023 * 4095)^2 < 2^45.
+ *   4. surf [frames, 8] int64 = nA, nB, hAB, hBA (the largest d2 per direction), sAB = sum over S(A) of isqrt(d2_AB(p) 2^16), sBA likewise
+ *      (every term a distance in units of 2^-8 um, rounded down; the operand is below 2^61, a sum below 2^51), q_lo, q_hi by rule 5 above.
+ *   5. nA == 0 or nB == 0: the six other fields are 0.   A frame whose ry or rx is outside 1..4095: all eight fields are -1 (the kernel
+ *      cannot return an error; gdkvm_amd.ops checks a host tensor before it is copied).
+ * The workspace is 0 bytes while H W <= GDKVM_SURFACE_MM_LDS_PIXELS -- a frame's 8.5 bytes per pixel (one 64-bit word per pixel: 11 bits of
+ * row count, 45 of d2, 2 of multiplicity; and the four bitmaps) then live in up to 153 KiB of dynamic LDS, 104 KiB for a 112 x 112 frame --
+ * else those 8.5 bytes per pixel with each frame's slice rounded up to 128 bytes.  Everything else (alignment, one workgroup per frame, no
+ * allocation, bit-reproducible, bounded loops -- the bisection takes at most 45 steps --, GDKVM_ERR_SHAPE for bad arguments, a null
+ * spacing_um included) is as for gdkvm_surface_distance. */
+#define GDKVM_SURFACE_MM_LDS_PIXELS 18432
+size_t gdkvm_surface_distance_mm_workspace_bytes(int frames, int H, int W);
+int gdkvm_surface_distance_mm(const uint8_t* mask, const uint8_t* target, const int32_t* spacing_um, int64_t* surf, void* workspace,
+                              size_t workspace_bytes, int frames, int H, int W, int cls, void* stream);
 
 /* Signed squared distance maps of label frames (the operand of gdkvm_seg_loss_boundary_fwd / _bwd; csrc/signed_distance.hip).  Every output is
  * an integer that depends on neither the algorithm nor the schedule.  Distances are in pixels of the frame's grid (isotropic pixels assumed).

@@ -8,6 +8,11 @@ The dataset as published (the "raw data" link of the reference's guide, /root/re
 Written (what the reference calls "camus_png256x256_10f": 256 x 256, 10 frames per sequence -- index.astro:217,246):
     <dst>/<split>/patientXXXX/<2CH|4CH>/frame_000.png ... mask_000.png ...   `--frames` frames evenly spread over the sequence, resized
     to `--size` (images bilinear, labels nearest)
+    <dst>/<split>/patientXXXX/<2CH|4CH>/spacing.json   {"spacing_um": [row_um, col_um], "native_hw": [H, W]}: the micrometres per pixel of
+    the RESIZED grid, down the rows and along the columns, from the header's pixdim (pixdim[1] belongs to the stored x = width, pixdim[2] to
+    y = height): row_um = rint(1000 pixdim_y_mm H / size), col_um likewise with W.  A 549 x 778 sequence squeezed to 256 x 256 has pixels of
+    about 0.33 x 0.47 mm; eval.py measures volumes in mL and surface distances in mm with it.  No file (and a log line) when a pixdim is not
+    finite or not positive, or a result falls outside 1..4095.
 
 NIfTI-1 is read here directly (a 348-byte header + a raw array, gzip around it): no nibabel in this image.  Nothing touches a GPU.
 
@@ -16,6 +21,8 @@ NIfTI-1 is read here directly (a 348-byte header + a raw array, gzip around it):
 import argparse
 import glob
 import gzip
+import json
+import math
 import os
 import struct
 
@@ -46,14 +53,46 @@ def read_nifti(path: str) -> np.ndarray:
     return arr
 
 
-def write_nifti(path: str, arr: np.ndarray) -> None:
-    """A minimal NIfTI-1 writer (tests build tiny CAMUS-shaped trees with it)."""
+_UNIT_MM = {0: 1.0, 1: 1000.0, 2: 1.0, 3: 0.001}                # xyzt_units & 7 -> millimetres per unit (0 = unknown is read as mm)
+SPACING_UM_MAX = 4095
+
+
+def read_nifti_pixdim_mm(path: str):
+    """(dx, dy) in mm from a NIfTI-1 header: pixdim[1] (the stored x = width) and pixdim[2] (y = height), float32 at byte 76 + 4 i, scaled
+    by the spatial unit in the low 3 bits of xyzt_units (byte 123).  The values are returned as they are: the caller checks them."""
+    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+        raw = f.read(352)
+    if len(raw) < 348:
+        raise ValueError(f"{path}: too short for a NIfTI-1 header")
+    end = "<" if struct.unpack("<i", raw[:4])[0] == 348 else ">"
+    dx, dy = struct.unpack(end + "2f", raw[80:88])
+    unit = _UNIT_MM.get(raw[123] & 7, 1.0)
+    return float(dx) * unit, float(dy) * unit
+
+
+def spacing_um(dx_mm: float, dy_mm: float, native_h: int, native_w: int, size: int):
+    """[row_um, col_um] of a native_h x native_w frame with pixels of dy_mm x dx_mm resized to size x size, or None when a pixdim is not
+    finite or not positive or a result falls outside 1..SPACING_UM_MAX."""
+    if not (math.isfinite(dx_mm) and math.isfinite(dy_mm) and dx_mm > 0 and dy_mm > 0):
+        return None
+    row, col = float(np.rint(1000.0 * dy_mm * native_h / size)), float(np.rint(1000.0 * dx_mm * native_w / size))
+    if not (1 <= row <= SPACING_UM_MAX and 1 <= col <= SPACING_UM_MAX):
+        return None
+    return [int(row), int(col)]
+
+
+def write_nifti(path: str, arr: np.ndarray, pixdim=None) -> None:
+    """A minimal NIfTI-1 writer (tests build tiny CAMUS-shaped trees with it).  pixdim = (dx, dy) in mm goes to pixdim[1..2] with the spatial
+    unit set to mm; without it those header bytes stay zero, as before."""
     code = {np.dtype(v): k for k, v in _DTYPES.items()}[arr.dtype]
     hdr = bytearray(352)
     struct.pack_into("<i", hdr, 0, 348)
     struct.pack_into("<8h", hdr, 40, arr.ndim, *(list(arr.shape) + [1] * (7 - arr.ndim)))
     struct.pack_into("<h", hdr, 70, code)
     struct.pack_into("<h", hdr, 72, arr.dtype.itemsize * 8)
+    if pixdim is not None:
+        struct.pack_into("<2f", hdr, 80, float(pixdim[0]), float(pixdim[1]))
+        hdr[123] = 2
     struct.pack_into("<f", hdr, 108, 352.0)
     struct.pack_into("<2f", hdr, 112, 1.0, 0.0)
     hdr[344:348] = b"n+1\0"
@@ -122,6 +161,13 @@ def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = 
                 hi = float(a.max()) or 1.0
                 Image.fromarray(np.clip(a * (255.0 / hi if hi > 255.0 else 1.0), 0, 255).astype(np.uint8)).save(os.path.join(out, f"frame_{j:03d}.png"))
                 Image.fromarray(m.astype(np.uint8)).save(os.path.join(out, f"mask_{j:03d}.png"))
+            dx_mm, dy_mm = read_nifti_pixdim_mm(seq[0])
+            sp = spacing_um(dx_mm, dy_mm, img.shape[1], img.shape[0], size)
+            if sp is None:
+                log(f"  {pid} {view}: no usable pixel spacing (pixdim {dx_mm} x {dy_mm} mm, native {img.shape[1]} x {img.shape[0]}): no spacing.json")
+            else:
+                with open(os.path.join(out, "spacing.json"), "w") as f:
+                    json.dump({"spacing_um": sp, "native_hw": [int(img.shape[1]), int(img.shape[0])]}, f)
             done += 1
     log(f"converted {done} sequences")
     return {"sequences": done}

@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -21,6 +21,9 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only]
     runs in the same windows: ellipse against the next input's ellipse (a prediction close to its target), the ellipse with islands against
     it, a checkerboard against a one-pixel-shifted checkerboard (every pixel of the class is surface) and against the ellipse (every row
     walk of the ellipse's surface ends at once, every walk of the checkerboard's is as long as the ellipse is far), and an empty class.
+    gdkvm_lv_measure_mm and gdkvm_surface_distance_mm (a spacing of 330 x 468 um for every frame) run in the same windows on the same inputs
+    as the pixel kernels' rows, so that each mm row reads against its pixel row of the same run (--mm-only: part (a) with the lv_measure and
+    surface_distance rows alone, pixel and mm, and nothing else).
 (v) gdkvm_temporal_vote at the cfg2 mask shape, 16 clips of 32 frames of 112^2 with 4 classes (--vote-only: this part alone), radius 1, 2
     and 7 with a target and radius 1 without, through the C symbol on preallocated outputs, beside two yardsticks in the same alternated
     windows: the plain torch expression of the same filter (torch_vote: a one-hot, a window sum along T, an argmax with the tie rules; the
@@ -90,7 +93,7 @@ def punch_holes(masks, seed):
 CALLS = 20            # launches per timed window
 
 
-def part_a(dev, F, S, reps, n_in=4):
+def part_a(dev, F, S, reps, n_in=4, only=()):
     lib = ops.load()
     st = torch.cuda.current_stream(dev).cuda_stream
     g = torch.Generator().manual_seed(S)
@@ -115,9 +118,21 @@ def part_a(dev, F, S, reps, n_in=4):
     stats = torch.empty((F, 12), dtype=torch.int64, device=dev)
     disks = torch.empty((F, 20), dtype=torch.int64, device=dev)
     geom = torch.empty((F, 4), dtype=torch.float64, device=dev)
+    geom_mm = torch.empty((F, 6), dtype=torch.float64, device=dev)
+    spacing = torch.tensor([330, 468], dtype=torch.int32, device=dev).expand(F, 2).contiguous()
+    sdm_ws = torch.empty(max(16, int(lib.gdkvm_surface_distance_mm_workspace_bytes(F, S, S))), dtype=torch.uint8, device=dev)
 
     def lv(mask, cls):
         rc = lib.gdkvm_lv_measure(mask.data_ptr(), stats.data_ptr(), disks.data_ptr(), geom.data_ptr(), F, S, S, cls, 20, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def lv_mm(mask, cls):
+        rc = lib.gdkvm_lv_measure_mm(mask.data_ptr(), spacing.data_ptr(), stats.data_ptr(), disks.data_ptr(), geom_mm.data_ptr(), F, S, S, cls, 20, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def sd_mm(mask, target, cls):
+        rc = lib.gdkvm_surface_distance_mm(mask.data_ptr(), target.data_ptr(), spacing.data_ptr(), sd_out.data_ptr(), sdm_ws.data_ptr(), sdm_ws.numel(),
+                                           F, S, S, cls, st)
         assert rc == 0, lib.gdkvm_last_error()
 
     def cc(mask, target, cls, conn=4):
@@ -161,7 +176,17 @@ def part_a(dev, F, S, reps, n_in=4):
         "surface_distance, checkerboard against shifted": (lambda i: sd(board, board_shifted, 1), 2 * F * S * S),
         "surface_distance, checkerboard against ellipse": (lambda i: sd(board, masks[i], 1), 2 * F * S * S),
         "surface_distance, no pixel of the class": (lambda i: sd(full, masks[i], 2), 2 * F * S * S),
+        "lv_measure_mm, ellipse": (lambda i: lv_mm(masks[i], 1), F * S * S),
+        "lv_measure_mm, every pixel of the class": (lambda i: lv_mm(full, 1), F * S * S),
+        "lv_measure_mm, no pixel of the class": (lambda i: lv_mm(full, 2), F * S * S),
+        "surface_distance_mm, ellipse against ellipse": (lambda i: sd_mm(masks[i], masks[(i + 1) % n_in], 1), 2 * F * S * S),
+        "surface_distance_mm, ellipse + 3 islands against it": (lambda i: sd_mm(isl[i], masks[i], 1), 2 * F * S * S),
+        "surface_distance_mm, checkerboard against shifted": (lambda i: sd_mm(board, board_shifted, 1), 2 * F * S * S),
+        "surface_distance_mm, checkerboard against ellipse": (lambda i: sd_mm(board, masks[i], 1), 2 * F * S * S),
+        "surface_distance_mm, no pixel of the class": (lambda i: sd_mm(full, masks[i], 2), 2 * F * S * S),
     }
+    if only:
+        forms = {name: f for name, f in forms.items() if name.startswith(only)}
     cc(isl[0], masks[0], 1)
     torch.cuda.synchronize()
     removed = (cc_info[:, 1] - cc_info[:, 2]).float()
@@ -178,6 +203,11 @@ def part_a(dev, F, S, reps, n_in=4):
     print(f"    (ellipse against ellipse: {float(sd_out[:, :2].float().mean()):.0f} surface pixels per set, mean HD {float(met[:, 0].mean()):.2f}, HD95 "
           f"{float(met[:, 1].mean()):.2f}, ASSD {float(met[:, 2].mean()):.2f} pixels over {int(ok.sum())} frames; the frame's words in "
           f"{'LDS' if sd_ws.numel() == 16 else 'the workspace, ' + str(sd_ws.numel() >> 20) + ' MiB'})")
+    sd_mm(masks[0], masks[1], 1)
+    torch.cuda.synchronize()
+    met, ok = ops.surface_metrics_mm(sd_out)
+    print(f"    (the same at 330 x 468 um: mean HD {float(met[:, 0].mean()):.2f}, HD95 {float(met[:, 1].mean()):.2f}, ASSD {float(met[:, 2].mean()):.2f} mm "
+          f"over {int(ok.sum())} frames; the frame's words in {'LDS' if sdm_ws.numel() == 16 else 'the workspace, ' + str(sdm_ws.numel() >> 20) + ' MiB'})")
     times = {name: [] for name in forms}
     for r in range(reps + 3):
         for name, (fn, _) in forms.items():
@@ -307,6 +337,10 @@ def main():
     quick = "--quick" in sys.argv
     ops.require_native()
     dev = torch.device("cuda", torch.cuda.current_device())
+    if "--mm-only" in sys.argv:
+        for S in (112, 256):
+            part_a(dev, 8 if quick else 512, S, 5 if quick else 40, only=("lv_measure", "surface_distance"))
+        return
     if "--vote-only" not in sys.argv:
         for S in (112, 256):
             part_a(dev, 8 if quick else 512, S, 5 if quick else 40)
