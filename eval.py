@@ -26,6 +26,14 @@ frames picked on its mL curve) and the mean absolute error and bias of EDV and E
 holds the mean HD, HD95 and ASSD in mm (ops.surface_distance_mm / surface_metrics_mm).  Every other key keeps its value; without a spacing for
 every clip neither block appears and nothing new runs.
 
+With `data.lv_beats` (and `lv_class` >= 0) the clip is also read beat by beat (ops.lv_beats on the area curve of the post-processed predicted
+masks and on their volume curve, mL with a spacing, else pixel^3; `data.beat_distance`, `data.beat_prominence`; only the frames a clip's
+dataset calls its own count, gdkvm_amd.data.clip_length_table): a `beats` block holds `clips`, `beats_per_clip` and `mean_cycle_frames` over
+the clips whose class never vanished, `clips_dropped_below_min` (those where it did: a vanished class is a false systole), and, against the
+target's own curves where the target labels every valid frame of a clip, `clips_with_target`, `ef_mae`, `ef_bias`, `ef_pearson_r` of the mean
+beat EF and `systole_count_agreement`; where the dataset knows an EF per file (EchoNetNpz.file_ef), the same EF statistics against it as
+`vs_file_ef`.  Every other key keeps its value; the `lv` block's one ED / ES / EF per clip is right for clips of one beat only.
+
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [key=value ...]"""
@@ -52,8 +60,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     from gdkvm_amd import ops
-    from gdkvm_amd.config import load_config
-    from gdkvm_amd.data import build_dataset, clip_spacing_table
+    from gdkvm_amd.config import beat_prominence_permille, load_config
+    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table
     from gdkvm_amd.distributed import init_from_env, shard_range
     from gdkvm_amd.model import GDKVM, GDKVMConfig
 
@@ -106,6 +114,16 @@ def main(argv=None):
     s_cls = cfg.data.surface_class                                # -1 = off: no new call below
     # ops.surface_summary, accumulated on the device; with a spacing, behind it the same five sums in mm
     sd_sums = torch.zeros(5 + (5 if mm else 0), dtype=torch.float64, device=dev) if s_cls >= 0 else None
+    beats_on = cfg.data.lv_beats and lv_cls >= 0                  # off: no new call below
+    if beats_on:
+        # clips, dropped, kept, their beats, clips with a cycle, the cycles; ops.beats_summary against the target [11]; ops.ef_summary against
+        # the files' EF [8]: accumulated on the device, read once at the end
+        bt_acc = torch.zeros(6 + 11 + 8, dtype=torch.float64, device=dev)
+        bt_len = clip_length_table(ds).to(dev)
+        bt_args = dict(distance=cfg.data.beat_distance, prominence_permille=beat_prominence_permille(cfg))
+        file_ef = getattr(ds, "file_ef", None)
+        if file_ef is not None:                                   # per cent per clip, NaN where a file has none
+            file_ef = torch.tensor([float("nan") if (v := file_ef(k)) is None else float(v) for k in range(len(ds))], dtype=torch.float64).to(dev)
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -172,6 +190,20 @@ def main(argv=None):
                 _, q_val = ops.lv_ef(q_geom[..., 1], q_stats[..., 0], pick_vol=t_ml, pick_npix=t_npix)
                 ok = (m_idx[:, 0] >= 0) & (m_val[:, 0] > 0)
                 ef_sums[8:] += torch.cat([ops.ef_summary(q_val[:, k], m_val[:, k], ok) for k in (2, 0, 1)])
+        if beats_on:
+            # beat by beat, on the curves of the same post-processed mask: the prediction's, and the target's where it labels every valid frame
+            ln = bt_len[i:i + mask.shape[0]]
+            _, _, b_info, b_summ = ops.lv_beats(p_stats[..., 0], (q_geom if mm else p_geom)[..., 1], ln, **bt_args)
+            _, _, r_info, r_summ = ops.lv_beats(t_npix, t_ml if mm else t_vol, ln, **bt_args)
+            full = (labelled[..., 0, 0] | (torch.arange(mask.shape[1], device=dev) >= ln[:, None])).all(1)
+            kept = b_info[:, 2] == 0
+            cyc = kept & (b_info[:, 1] >= 2)
+            bt_acc[:6] += torch.stack([torch.ones_like(kept).sum(), (~kept).sum(), kept.sum(), (b_info[:, 0] * kept).sum(), cyc.sum(),
+                                       (b_summ[:, 3] * cyc).sum()]).to(torch.float64)
+            bt_acc[6:17] += ops.beats_summary(b_summ, b_info, r_summ, r_info, ok=full)
+            if file_ef is not None:
+                fe = file_ef[i:i + mask.shape[0]]
+                bt_acc[17:] += ops.ef_summary(b_summ[:, 0], torch.nan_to_num(fe) / 100.0, kept & (b_info[:, 0] >= 1) & ~torch.isnan(fe))
         if s_cls >= 0:
             surf = ops.surface_distance(mask, t_copy, cls=s_cls)
             sd_sums[:5] += ops.surface_summary(*ops.surface_metrics(surf), surf, labelled[..., 0, 0])
@@ -198,6 +230,8 @@ def main(argv=None):
             torch.distributed.all_reduce(fh_acc)                  # ... and the filled mask's counts and totals
         if s_cls >= 0:
             torch.distributed.all_reduce(sd_sums)                 # ... and the five surface-distance sums
+        if beats_on:
+            torch.distributed.all_reduce(bt_acc)                  # ... and the beat-by-beat sums
     if rank == 0:
         dice = ops.dice_from_counts(counts).tolist()
         iou = ops.iou_from_counts(counts).tolist()
@@ -240,6 +274,18 @@ def main(argv=None):
                 st = ops.surface_stats(sd_sums[5:].cpu())
                 res["surface_mm"] = {"frames": st["frames"], "frames_one_empty": st["frames_one_empty"],
                                      **{k + "_mm": round(st[k], 5) for k in ("hd_mean", "hd95_mean", "assd_mean")}}
+        if beats_on:
+            acc = bt_acc.cpu()
+            r5 = lambda v: round(float(v), 5)
+            vs_t = ops.beats_stats(acc[6:17])
+            res["beats"] = {"clips": int(acc[0]), "beats_per_clip": r5(acc[3] / max(float(acc[2]), 1.0)),
+                            "mean_cycle_frames": r5(acc[5] / max(float(acc[4]), 1.0)), "clips_dropped_below_min": int(acc[1]),
+                            "clips_with_target": vs_t["clips"], "ef_mae": r5(vs_t["ef_mae"]), "ef_bias": r5(vs_t["ef_bias"]),
+                            "ef_pearson_r": r5(vs_t["ef_pearson_r"]), "systole_count_agreement": r5(vs_t["systole_count_agreement"])}
+            if file_ef is not None:
+                vs_f = ops.ef_stats(acc[17:])
+                res["beats"]["vs_file_ef"] = {k: (v if isinstance(v, int) else r5(v)) for k, v in vs_f.items()
+                                              if k in ("clips_with_ef", "ef_mae", "ef_bias", "ef_pearson_r")}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

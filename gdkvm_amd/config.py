@@ -36,6 +36,11 @@ class DataCfg:
                                      # the input grid); -1 = off
     spacing_um: Any = None           # eval.py: [row_um, col_um], the micrometres per pixel of the network grid (integers in 1..4095) for datasets
                                      # that carry no spacing of their own (data.clip_spacing_table); with a spacing eval.py adds the mL / mm blocks
+    lv_beats: bool = False           # eval.py: beat-by-beat EF of lv_class from the whole clip's area curve (ops.lv_beats): a `beats` block
+    beat_distance: int = 20          # ... the fewest frames between two end-systoles, 1..4096 (find_peaks' distance=; EchoNet-Dynamic: 20 at 50 fps)
+    beat_prominence: float = 0.5     # ... the prominence an end-systole needs, as a fraction 0..1 of the curve's range (handed on in per mille)
+    synthetic_beats: float = 1.0     # the synthetic clips' heart beats per clip (> 0; 1.0: the clips of before, bit for bit)
+    whole_video: bool = False        # echonet_npz only: a clip is the video's first `frames` frames (several beats), not the window around ED / ES
 
 
 @dataclass
@@ -162,6 +167,21 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     if sp is not None and (not isinstance(sp, list) or len(sp) != 2
                            or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4095 for v in sp)):
         raise ValueError(f"data.spacing_um = {sp!r}: null or [row_um, col_um], two integers in 1..4095 (micrometres per pixel)")
+    d = cfg.data
+    if not isinstance(d.lv_beats, bool) or not isinstance(d.whole_video, bool):
+        raise ValueError(f"data.lv_beats = {d.lv_beats!r}, data.whole_video = {d.whole_video!r}: true or false")
+    if d.whole_video and d.kind != "echonet_npz":
+        raise ValueError(f"data.whole_video is for data.kind = echonet_npz, not {d.kind!r}")
+    if isinstance(d.beat_distance, bool) or not isinstance(d.beat_distance, int) or not 1 <= d.beat_distance <= 4096:
+        raise ValueError(f"data.beat_distance = {d.beat_distance!r}: an integer in 1..4096 (frames between two end-systoles)")
+    bp = d.beat_prominence
+    if isinstance(bp, bool) or not isinstance(bp, (int, float)) or not 0 <= bp <= 1:
+        raise ValueError(f"data.beat_prominence = {bp!r}: a number in 0..1 (a fraction of the area curve's range)")
+    d.beat_prominence = float(bp)
+    sb = d.synthetic_beats
+    if isinstance(sb, bool) or not isinstance(sb, (int, float)) or not math.isfinite(sb) or not sb > 0:
+        raise ValueError(f"data.synthetic_beats = {sb!r}: a finite number > 0 (heart beats per synthetic clip)")
+    d.synthetic_beats = float(sb)
     bw = cfg.loss.boundary_weight
     if isinstance(bw, bool) or not isinstance(bw, (int, float)) or not math.isfinite(bw) or bw < 0:
         raise ValueError(f"loss.boundary_weight = {bw!r}: a finite number >= 0 (0 = off)")
@@ -173,6 +193,11 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
             raise ValueError(f"loss.boundary_classes = {bc!r}: null (every class but 0) or distinct integers in 0..{cfg.data.num_classes - 1}")
     _check_optim(cfg.optim)
     return cfg
+
+
+def beat_prominence_permille(cfg: RunConfig) -> int:
+    """data.beat_prominence as the per-mille integer ops.lv_beats takes."""
+    return int(round(cfg.data.beat_prominence * 1000))
 
 
 def _check_optim(o: OptimCfg) -> None:

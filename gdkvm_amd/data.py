@@ -5,7 +5,9 @@ so the default is a seeded synthetic echo-like clip generator; two on-disk forma
   echonet_npz  what tools/convert_echonet.py writes from an EchoNet-Dynamic download (Videos/*.avi, FileList.csv, VolumeTracings.csv --
                the "raw data" link of the reference's guide, website reprod/index.astro:222): one .npz per video with the WHOLE video and
                the two traced frames' masks; EchoNetNpz cuts a T-frame clip around the traced frames and marks every other frame
-               UNLABELLED (label 255, which the loss leaves out: gdkvm_amd.train.segmentation_loss, gdkvm_seg_loss_fwd)
+               UNLABELLED (label 255, which the loss leaves out: gdkvm_amd.train.segmentation_loss, gdkvm_seg_loss_fwd); with
+               data.whole_video the clip is the video's first T frames instead (several heart beats: what ops.lv_beats is for), and the
+               optional scalars `ef` (FileList.csv's EF in per cent) and `fps` serve as a second reference
   camus_png    <root>/<split>/<patient>/<view>/frame_XXX.png + mask_XXX.png, view in {2CH, 4CH}, masks 0 bg / 1 LV / 2 myocardium / 3 LA --
                what tools/convert_camus.py writes from the CAMUS NIfTI release (guide: index.astro:221); the reference's own processed
                "camus_png256x256_10f" tree is not documented beyond its name (index.astro:217,246), so this layout is the builder's;
@@ -13,7 +15,9 @@ so the default is a seeded synthetic echo-like clip generator; two on-disk forma
                RESIZED grid in micrometres, from the NIfTI pixdim
 
 A dataset's spacing_um(i) is clip i's pixel spacing (row_um, col_um) in integer micrometres per pixel of the grid its masks are on, or None;
-clip_spacing_table gathers them for eval.py, which then reports volumes in mL and surface distances in mm.  Samples stay (frames, target).
+clip_spacing_table gathers them for eval.py, which then reports volumes in mL and surface distances in mm.  A dataset's length(i), where it has
+one, is the number of clip i's frames that come from the video (the rest repeats the last frame); clip_length_table gathers those for
+ops.lv_beats.  Samples stay (frames, target).
 """
 from __future__ import annotations
 
@@ -44,10 +48,17 @@ def _spacing_pair(v) -> Optional[Tuple[int, int]]:
 
 class SyntheticEchoClips(Dataset):
     """Speckled clips with a pulsating ellipse ("ventricle") and, for >2 classes, concentric wall / atrium regions.
-    Deterministic per index, so ranks and epochs are reproducible."""
+    Deterministic per index, so ranks and epochs are reproducible.  A clip holds `beats` periods of the pulsation (1.0: exactly one, the
+    clips of before bit for bit).  With a whole number of beats >= 2 the clip is meant to SHOW that many beats: the phase is drawn so that
+    every period's smallest area keeps 0.3 periods from both ends of the clip -- a minimum nearer than a quarter period to an end has less than
+    half the curve's range beside it and is no end-systole for ops.lv_beats (nor a peak for scipy.signal.find_peaks) at the usual prominence
+    of 0.5.  Every other value of `beats` keeps the free phase."""
 
-    def __init__(self, n_clips: int, frames: int, size: int, num_classes: int = 2, seed: int = 0, as_uint8: bool = False):
+    def __init__(self, n_clips: int, frames: int, size: int, num_classes: int = 2, seed: int = 0, as_uint8: bool = False, beats: float = 1.0):
+        if not float(beats) > 0:
+            raise ValueError(f"SyntheticEchoClips: beats = {beats!r} must be > 0")
         self.n, self.T, self.S, self.C, self.seed, self.as_uint8 = n_clips, frames, size, num_classes, seed, as_uint8
+        self.beats = float(beats)
 
     def __len__(self):
         return self.n
@@ -61,7 +72,13 @@ class SyntheticEchoClips(Dataset):
         yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
         cy, cx = S * (0.45 + 0.1 * rng.random()), S * (0.45 + 0.1 * rng.random())
         ry0, rx0 = S * (0.22 + 0.06 * rng.random()), S * (0.15 + 0.05 * rng.random())
-        phase, rate = rng.random() * 2 * np.pi, 2 * np.pi / max(T, 2)
+        u = rng.random()
+        phase, rate = u * 2 * np.pi, 2 * np.pi * self.beats / max(T, 2)
+        if self.beats >= 2 and self.beats == int(self.beats):
+            # the minima are where phase + rate t = 3 pi / 2 (mod 2 pi): the first at t0 in [0.3 P, 0.7 P - 1], P = the period in frames, so
+            # that the last, t0 + (beats - 1) P, ends 0.3 P in front of frame T - 1
+            period = max(T, 2) / self.beats
+            phase = 1.5 * np.pi - rate * (0.3 * period + u * max(0.4 * period - 1.0, 0.0))
         frames = np.empty((T, 3, S, S), np.float32)
         masks = np.zeros((T, S, S), np.uint8)
         for t in range(T):
@@ -218,13 +235,15 @@ def clip_indices(n_frames: int, labelled, T: int, pad: int = 2) -> np.ndarray:
 class EchoNetNpz(Dataset):
     """EchoNet-Dynamic as tools/convert_echonet.py leaves it: <root>/<split>/<FileName>.npz with `video` [F,H,W] uint8 (grey),
     `traced` [2] frame indices and `masks` [2,H,W] uint8 (0 background, 1 left ventricle).  A sample is a T-frame clip around the two
-    traced frames: frames [T,3,H,W] float in [0,1], labels [T,H,W] int64 with IGNORE_LABEL on every untraced frame."""
+    traced frames: frames [T,3,H,W] float in [0,1], labels [T,H,W] int64 with IGNORE_LABEL on every untraced frame.  whole=True: the clip
+    is frames 0 .. T - 1 of the video instead (a shorter video repeats its last frame; length(i) = min(F, T) says how many are its own), and a
+    traced frame at or beyond T is not part of it.  Files may carry the scalars `ef` (per cent) and `fps` (file_ef, file_fps)."""
 
-    def __init__(self, root: str, split: str, frames: int, as_uint8: bool = False):
+    def __init__(self, root: str, split: str, frames: int, as_uint8: bool = False, whole: bool = False):
         self.files = sorted(glob.glob(os.path.join(root, split, "*.npz")))
         if not self.files:
             raise FileNotFoundError(f"no converted EchoNet videos (.npz) under {os.path.join(root, split)}: run tools/convert_echonet.py")
-        self.T, self.as_uint8 = frames, as_uint8
+        self.T, self.as_uint8, self.whole = frames, as_uint8, bool(whole)
 
     def __len__(self):
         return len(self.files)
@@ -232,15 +251,39 @@ class EchoNetNpz(Dataset):
     def spacing_um(self, i):
         return None                                               # EchoNet-Dynamic ships no pixel spacing
 
+    def _scalar(self, i, key) -> Optional[float]:
+        with np.load(self.files[i]) as z:
+            if key not in z.files:
+                return None
+            v = float(np.asarray(z[key]).reshape(-1)[0])
+        return v if np.isfinite(v) else None
+
+    def file_ef(self, i) -> Optional[float]:
+        """FileList.csv's EF of video i in per cent, or None for a file converted without it."""
+        return self._scalar(i, "ef")
+
+    def file_fps(self, i) -> Optional[float]:
+        return self._scalar(i, "fps")
+
+    def length(self, i) -> int:
+        """The frames of clip i that are the video's own: T for a window around the tracings (it may repeat frames, but holds one beat by
+        construction), min(F, T) for a whole video (its last frame repeats behind that)."""
+        if not self.whole:
+            return self.T
+        with np.load(self.files[i]) as z:
+            return min(int(z["video"].shape[0]), self.T)
+
     def __getitem__(self, i):
         z = np.load(self.files[i])
         video, traced, masks = z["video"], z["traced"], z["masks"]
-        idx = clip_indices(video.shape[0], traced, self.T)
+        idx = np.minimum(np.arange(self.T), video.shape[0] - 1) if self.whole else clip_indices(video.shape[0], traced, self.T)
         clip = np.ascontiguousarray(video[idx])
         x = torch.from_numpy(clip if self.as_uint8 else clip.astype(np.float32) / 255.0).unsqueeze(1).expand(-1, 3, -1, -1).contiguous()
         y = torch.full((self.T,) + video.shape[1:], IGNORE_LABEL, dtype=torch.uint8 if self.as_uint8 else torch.int64)
         for f, m in zip(traced, masks):
-            y[int(np.nonzero(idx == int(f))[0][0])] = torch.from_numpy(m.astype(np.uint8 if self.as_uint8 else np.int64))
+            if self.whole and int(f) >= self.T:                   # behind the cut: not part of this clip
+                continue
+            y[int(f) if self.whole else int(np.nonzero(idx == int(f))[0][0])] = torch.from_numpy(m.astype(np.uint8 if self.as_uint8 else np.int64))
         return x, y
 
 
@@ -335,6 +378,13 @@ def clip_spacing_table(ds, cfg) -> Optional[torch.Tensor]:
     return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2)
 
 
+def clip_length_table(ds) -> torch.Tensor:
+    """int32 [len(ds)] (host) = every clip's number of valid frames for ops.lv_beats: the dataset's own length(i) where it has one, else its
+    clip length `frames` (attribute T)."""
+    own = getattr(ds, "length", None)
+    return torch.tensor([int(own(i)) if own is not None else int(ds.T) for i in range(len(ds))], dtype=torch.int32).reshape(len(ds))
+
+
 def build_dataset(cfg, split: str = "train", n_synthetic: int = 256, as_uint8: bool = False) -> Dataset:
     """as_uint8: frames as uint8 [T,3,H,W] (0..255: what the files hold) and labels as uint8 (IGNORE_LABEL = 255 fits) instead of float32 in
     [0,1] and int64 -- a fifth of the bytes per batch across PCIe (EchoNet shape, 16 clips: 26 MB instead of 128 MB); the entry points ask for
@@ -342,11 +392,11 @@ def build_dataset(cfg, split: str = "train", n_synthetic: int = 256, as_uint8: b
     d = cfg.data
     if d.kind == "synthetic" or not cfg.data_path:
         return SyntheticEchoClips(n_synthetic if split == "train" else max(8, n_synthetic // 8), d.frames, d.size,
-                                  d.num_classes, seed=cfg.seed + (0 if split == "train" else 7919), as_uint8=as_uint8)
+                                  d.num_classes, seed=cfg.seed + (0 if split == "train" else 7919), as_uint8=as_uint8, beats=d.synthetic_beats)
     if d.kind == "npy_clips":
         return NpzClips(cfg.data_path, split, d.frames, as_uint8=as_uint8)
     if d.kind == "echonet_npz":
-        return EchoNetNpz(cfg.data_path, split, d.frames, as_uint8=as_uint8)
+        return EchoNetNpz(cfg.data_path, split, d.frames, as_uint8=as_uint8, whole=d.whole_video)
     if d.kind == "camus_png":
         return CamusPng(cfg.data_path, split, d.frames, as_uint8=as_uint8)
     raise ValueError(f"unknown data.kind {d.kind!r}")

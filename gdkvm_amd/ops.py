@@ -127,6 +127,7 @@ SIGNATURES = {
     "gdkvm_lv_measure": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
     "gdkvm_lv_measure_mm": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
+    "gdkvm_lv_beats": (_i, [_vp] * 7 + [_i] * 5 + [ctypes.c_int64, _vp]),
     "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_fill_holes_workspace_bytes": (_sz, [_i] * 3),
@@ -2135,6 +2136,65 @@ def ef_stats(sums) -> dict:
     vp, vg, cov = n * spp - sp * sp, n * sgg - sg * sg, n * spg - sp * sg
     r = cov / (vp * vg) ** 0.5 if n >= 2 and vp > 0 and vg > 0 else 0.0
     return {"clips_with_ef": int(n), "ef_mae": sae / n, "ef_bias": se / n, "ef_pearson_r": r, "mean_ref_ef": sg / n, "mean_pred_ef": sp / n}
+
+
+LV_BEATS_MAX_T, LV_BEATS_MAX_BEATS = 4096, 64
+
+
+def lv_beats(area: torch.Tensor, vol: torch.Tensor, length: Optional[torch.Tensor] = None, max_beats: int = 16, distance: int = 20,
+             prominence_permille: int = 500, min_pixels: int = 1):
+    """gdkvm_lv_beats: per clip the heart beats of the curves area int64 [B, T] and vol float64 [B, T] (lv_measure's stats[..., 0] and
+    geom[..., 1]; non-contiguous views are copied): the end-systoles are the strict local minima of `area` that scipy.signal.find_peaks(-area,
+    distance=distance, prominence=prominence_permille / 1000 * range) keeps, each beat's end-diastole the largest area in front of its
+    end-systole, one EF per beat (definition: include/gdkvm.h; integer-exact up to the EF).  length int32 [B] on the same device: only the
+    frames 0 .. length[b] - 1 of clip b count (None: all T).  Returns (beats int32 [B, max_beats, 2] = ed, es or -1, beat_val float64
+    [B, max_beats, 3] = EDV, ESV, EF, info int32 [B, 4] = n_beats, end-systoles, frames below min_pixels, last - first end-systole, summ
+    float64 [B, 4] = mean, smallest, largest beat EF, mean cycle in frames)."""
+    if area.dim() != 2 or not 1 <= area.shape[1] <= LV_BEATS_MAX_T:
+        raise GdkvmError(f"lv_beats: area must be [B, T] with T in 1..{LV_BEATS_MAX_T}, got {tuple(area.shape)}")
+    for name, t, dt in (("area", area, torch.int64), ("vol", vol, torch.float64)):
+        if t.dtype != dt or tuple(t.shape) != tuple(area.shape):
+            raise GdkvmError(f"lv_beats: {name} must be {dt} {tuple(area.shape)}, got {t.dtype} {tuple(t.shape)}")
+    B, T = area.shape
+    if length is not None and (length.dtype != torch.int32 or tuple(length.shape) != (B,)):
+        raise GdkvmError(f"lv_beats: length must be int32 [{B}], got {length.dtype} {tuple(length.shape)}")
+    if not 1 <= int(max_beats) <= LV_BEATS_MAX_BEATS:
+        raise GdkvmError(f"lv_beats: max_beats = {max_beats} outside 1..{LV_BEATS_MAX_BEATS}")
+    if not 1 <= int(distance) <= LV_BEATS_MAX_T:
+        raise GdkvmError(f"lv_beats: distance = {distance} outside 1..{LV_BEATS_MAX_T}")
+    if not 0 <= int(prominence_permille) <= 1000:
+        raise GdkvmError(f"lv_beats: prominence_permille = {prominence_permille} outside 0..1000")
+    area, vol, length = (None if t is None else t.contiguous() for t in (area, vol, length))
+    dev = _dev(area, vol, length)
+    beats = torch.empty((B, int(max_beats), 2), dtype=torch.int32, device=dev)
+    beat_val = torch.empty((B, int(max_beats), 3), dtype=torch.float64, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    summ = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    _call("gdkvm_lv_beats", dev, area, vol, length, beats, beat_val, info, summ, B, T, int(max_beats), int(distance), int(prominence_permille),
+          int(min_pixels))
+    return beats, beat_val, info, summ
+
+
+def beats_summary(pred_summ: torch.Tensor, pred_info: torch.Tensor, ref_summ: torch.Tensor, ref_info: torch.Tensor,
+                  ok: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The running sums of a beat-by-beat comparison of lv_beats' (summ, info) of a prediction and of a reference (float64 [11], on the
+    inputs' device; sums of batches and of ranks add): ef_summary's eight sums of the mean beat EF over the clips where both sides have
+    n_beats >= 1 and n_below == 0, then the clips compared, the clips whose end-systole counts agree, and the sum of |m_pred - m_ref|.
+    ok bool [B] (optional): the clips where it is False are not compared at all (a reference that does not cover the clip)."""
+    use = torch.ones_like(pred_info[:, 0], dtype=torch.bool) if ok is None else ok.to(torch.bool)
+    both = use & (pred_info[:, 0] >= 1) & (pred_info[:, 2] == 0) & (ref_info[:, 0] >= 1) & (ref_info[:, 2] == 0)
+    dm = (pred_info[:, 1] - ref_info[:, 1]).abs() * use
+    return torch.cat([ef_summary(pred_summ[:, 0], ref_summ[:, 0], both),
+                      torch.stack([use.sum(), ((dm == 0) & use).sum(), dm.sum()]).to(torch.float64)])
+
+
+def beats_stats(sums) -> dict:
+    """{ef_stats' keys over the clips with a beat EF on both sides, clips, systole_count_agreement, systole_count_mae} from beats_summary's
+    sums (host numbers; 0 when no clip was compared)."""
+    st = ef_stats(sums[:8])
+    n, agree, dm = (float(v) for v in sums[8:11])
+    st.update(clips=int(n), systole_count_agreement=agree / n if n >= 1 else 0.0, systole_count_mae=dm / n if n >= 1 else 0.0)
+    return st
 
 
 def largest_component(mask: torch.Tensor, cls: int = 1, connectivity: int = 4, fill: int = 0, target: Optional[torch.Tensor] = None,

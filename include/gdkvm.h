@@ -669,6 +669,38 @@ int gdkvm_lv_measure_mm(const uint8_t* mask, const int32_t* spacing_um, int64_t*
  * EDV = ESV = EF = 0.  ed_es_nvalid int32 [B, 3], edv_esv_ef fp64 [B, 3] (16-byte aligned).  B == 0 is GDKVM_OK without a launch. */
 int gdkvm_lv_ef(const double* vol, const int64_t* npix, const double* pick_vol, const int64_t* pick_npix,
                 int32_t* ed_es_nvalid, double* edv_esv_ef, int B, int T, int64_t min_pixels, void* stream);
+/* Clip level, beat by beat (csrc/lv_beats.hip): gdkvm_lv_ef's global maximum and minimum belong to different beats as soon as a clip holds more
+ * than one, and the EF they give is biased upwards.  area int64 [B, T] (stats[..., 0] of gdkvm_lv_measure; values in 0 .. 2^50), vol fp64
+ * [B, T] (geom[..., 1], pixel^3 or mL: only read at the beats' frames), both 8-byte aligned; length int32 [B] on the device (4-byte aligned) or
+ * NULL = T.  Per clip only the frames 0 .. len - 1 count, len = length[b] clamped to 0 .. T; the padding behind len is never read.  With a =
+ * area[b], all integer arithmetic up to the per-beat EF:
+ *   1. candidates   the strict local minima of a.  Frame p, 0 < p < len - 1, starts a plateau p .. r of equal values when a[p - 1] > a[p] and
+ *        a[r + 1] > a[p] (r + 1 <= len - 1); the candidate is frame (p + r) / 2, integer division (scipy.signal.find_peaks' rule).  The
+ *        first and the last valid frame are never candidates.
+ *   2. distance     candidates are ordered by priority, smaller area first and the lower frame on a tie (a strict total order); a candidate
+ *        is kept exactly when no kept candidate of higher priority lies closer than `distance` frames (|p - q| < distance): find_peaks'
+ *        distance= rule, the greedy pass in priority order.  (Its result is the unique fixed point of "keep when every rival in range is
+ *        dropped or of lower priority, drop when one rival in range is kept", which is what the kernel iterates.)
+ *   3. prominence   for a kept candidate p: walk left from p while a[j] >= a[p], to a frame of strictly smaller area or to frame 0; lmax =
+ *        the largest area met, a[p] included; rmax the same towards len - 1 (the walks are over ALL frames, as in scipy).  p is an
+ *        END-SYSTOLE when (min(lmax, rmax) - a[p]) 1000 >= prominence_permille (max a - min a), both extremes over the valid frames.
+ *   4. beats        end-systoles e_0 < .. < e_(m-1); beat j has ES = e_j and ED = the frame of the largest area in e_(j-1) + 1 .. e_j - 1
+ *        (e_(-1) = -1), the lowest frame on a tie.  Beat 0 COUNTS only when its ED is not frame 0 (the clip started inside that beat: its true
+ *        ED is unknown); every later beat counts.  Per counted beat, fp64, every operation rounded once, no fused multiply-add:
+ *        EDV = vol[ed], ESV = vol[es], EF = (EDV - ESV) / EDV (0 when EDV == 0).
+ * Outputs (16-byte aligned):
+ *   beats int32 [B, max_beats, 2] = (ed, es) of the first max_beats counted beats, the rest -1;   beat_val fp64 [B, max_beats, 3] = EDV, ESV,
+ *   EF, the rest 0;   info int32 [B, 4] = n_beats (ALL counted beats: it may exceed max_beats), m, n_below = the valid frames with area <
+ *   min_pixels, e_(m-1) - e_0 (0 when m < 2);   summ fp64 [B, 4] = the mean EF over all counted beats (added in ascending beat order, then
+ *   divided by n_beats), the smallest EF, the largest EF, the mean cycle in frames (double)(e_(m-1) - e_0) / (double)(m - 1) (0 when m < 2);
+ *   all four 0 when no beat counts.
+ * n_below > 0 drops nothing: a frame where the class vanished is a false systole, and what to do with such a clip is the caller's decision.
+ * 1 <= T <= 4096, 1 <= max_beats <= 64, 1 <= distance <= 4096, 0 <= prominence_permille <= 1000, B >= 0: anything else is GDKVM_ERR_SHAPE, a
+ * null or misaligned pointer GDKVM_ERR_ARG, both before any device call; B == 0 is GDKVM_OK without a launch.  One workgroup per clip, the curve
+ * in LDS; no allocation, no synchronisation, no global atomics: capturable beside gdkvm_lv_measure; bit-reproducible. */
+int gdkvm_lv_beats(const int64_t* area, const double* vol, const int32_t* length,
+                   int32_t* beats, double* beat_val, int32_t* info, double* summ,
+                   int B, int T, int max_beats, int distance, int prominence_permille, int64_t min_pixels, void* stream);
 
 /* Keep the largest connected component of one class of label masks (the clean-up in front of gdkvm_lv_measure: an argmax mask is no tracing,
  * and a false-positive island far from the ventricle enters tmin / tmax, the long axis and the disks; csrc/largest_component.hip).  Every

@@ -7,7 +7,8 @@ The dataset as published (the "raw data" link of the reference's guide, /root/re
     <src>/VolumeTracings.csv             FileName, X1, Y1, X2, Y2, Frame -- 21 rows per traced frame (long axis + 20 chords), two traced
                                          frames per video (end-diastole, end-systole)
 Written:
-    <dst>/<train|val|test>/<FileName>.npz   video [F,H,W] uint8, traced [2] int (frame indices, video order), masks [2,H,W] uint8 (0 / 1)
+    <dst>/<train|val|test>/<FileName>.npz   video [F,H,W] uint8, traced [2] int (frame indices, video order), masks [2,H,W] uint8 (0 / 1),
+                                            ef and fps (float64 scalars: FileList.csv's EF in per cent and FPS; NaN where the cell is no number)
 
 Decoding an .avi needs OpenCV (cv2); this image has none, so run the converter where the dataset was downloaded.  For videos already
 decoded by other means, <src>/Videos/<FileName>.npy ([F,H,W] or [F,H,W,3] uint8) is taken instead of the .avi -- which is also how the
@@ -62,6 +63,13 @@ def read_tracings(path: str):
     return out
 
 
+def _number(cell) -> float:
+    try:
+        return float(cell)
+    except (TypeError, ValueError):
+        return float("nan")
+
+
 def convert(src: str, dst: str, limit: int = 0, log=print) -> dict:
     from gdkvm_amd.data import echonet_tracing_polygon, polygon_mask
     tracings = read_tracings(os.path.join(src, "VolumeTracings.csv"))
@@ -88,7 +96,8 @@ def convert(src: str, dst: str, limit: int = 0, log=print) -> dict:
         h, w = video.shape[1:]
         masks = np.stack([polygon_mask(*echonet_tracing_polygon(tr[t]), h, w) for t in traced])
         os.makedirs(os.path.join(dst, split), exist_ok=True)
-        np.savez_compressed(os.path.join(dst, split, name + ".npz"), video=video, traced=np.asarray(traced, np.int64), masks=masks)
+        np.savez_compressed(os.path.join(dst, split, name + ".npz"), video=video, traced=np.asarray(traced, np.int64), masks=masks,
+                            ef=np.float64(_number(row.get("EF"))), fps=np.float64(_number(row.get("FPS"))))
         done[split] += 1
     log(f"converted {dict(done)}; skipped {len(skipped)}")
     for n, why in skipped[:20]:

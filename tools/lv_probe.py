@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -31,6 +31,12 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only]
     here on 512 MiB that no cache holds.  Inputs: clips of an ellipse in a ring that drifts over the frames with 15 % of the pixels
     re-drawn, four in rotation.  Then 320 clips (two inputs of 128 MB in rotation), where the launcher takes the form with 16 pixels
     per lane instead of 4, without the torch rows.
+(e) --beats (this part alone): gdkvm_lv_beats (distance 20, prominence 500 per mille, 16 beats listed) on 16 clips of 512 frames and on 2 clips
+    of 4096, on curves of the synthetic kind (the area and the volume of a pulsating ellipse with one beat per 40 frames and a few per cent of
+    noise, samples made pairwise distinct, the last eighth of every second clip padding), through the C symbol on preallocated outputs in windows of device events; beside
+    it what a user does without it: the same curves, already on the device as lv_measure left them, through .cpu() into
+    scipy.signal.find_peaks and a host loop over the beats, timed on the host's clock around the whole round trip.  A device call against a
+    host round trip, not kernel against kernel.
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
     data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
     instead, and with data.lv_class=-1, alternated, twice each."""
@@ -317,6 +323,81 @@ def part_v(dev, clips, T, S, ncls, reps, n_in=4, torch_rows=True):
     print(flush=True)
 
 
+def beat_curves(clips, T, seed, dev):
+    """area int64 [clips, T], vol float64 [clips, T], length int32 [clips]: a pulsating ellipse's pixel count and its volume, one beat per
+    40 frames, a random phase and noise; every second clip ends in padding (zeros) behind 7/8 of its frames.  The areas are made pairwise
+    distinct (times 8192, plus a permutation of the frame numbers): among equal minima scipy's choice is that of an unstable sort, and the
+    yardstick has to find the beats the kernel finds."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(T)
+    k = 1.0 + 0.18 * np.sin(rng.uniform(0, 2 * np.pi, (clips, 1)) + 2 * np.pi * t / 40.0) + rng.normal(0, 0.006, (clips, T))
+    area = np.round(1200.0 * k * k).astype(np.int64) * 8192 + np.stack([rng.permutation(T) for _ in range(clips)])
+    vol = 30000.0 * k ** 3
+    length = np.full(clips, T, np.int32)
+    length[1::2] = T - T // 8
+    for b in range(clips):
+        area[b, length[b]:], vol[b, length[b]:] = 0, 0.0
+    return torch.from_numpy(area).to(dev), torch.from_numpy(vol).to(dev), torch.from_numpy(length).to(dev)
+
+
+def part_e(dev, clips, T, reps, n_in=4):
+    from scipy.signal import find_peaks
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ins = [beat_curves(clips, T, s, dev) for s in range(n_in)]
+    beats = torch.empty((clips, 16, 2), dtype=torch.int32, device=dev)
+    val = torch.empty((clips, 16, 3), dtype=torch.float64, device=dev)
+    info = torch.empty((clips, 4), dtype=torch.int32, device=dev)
+    summ = torch.empty((clips, 4), dtype=torch.float64, device=dev)
+
+    def kernel(i):
+        a, v, ln = ins[i]
+        rc = lib.gdkvm_lv_beats(a.data_ptr(), v.data_ptr(), ln.data_ptr(), beats.data_ptr(), val.data_ptr(), info.data_ptr(), summ.data_ptr(),
+                                clips, T, 16, 20, 500, 1, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def host(i):
+        a, v, ln = (x.cpu().numpy() for x in ins[i])
+        out = []
+        for b in range(clips):
+            ab, vb = a[b, :ln[b]], v[b, :ln[b]]
+            es, _ = find_peaks(-ab.astype(np.float64), distance=20, prominence=0.5 * float(ab.max() - ab.min()))
+            efs, prev = [], -1
+            for j, e in enumerate(es):
+                ed = prev + 1 + int(np.argmax(ab[prev + 1:e]))
+                if not (j == 0 and ed == 0):
+                    efs.append((vb[ed] - vb[e]) / vb[ed] if vb[ed] else 0.0)
+                prev = int(e)
+            out.append((len(es), float(np.mean(efs)) if efs else 0.0))
+        return out
+
+    kernel(0)
+    torch.cuda.synchronize()
+    want = host(0)                                                 # the yardstick computes the same beats (no ties on these curves)
+    assert [w[0] for w in want] == info[:, 1].tolist(), (want, info[:, 1].tolist())
+    assert np.allclose([w[1] for w in want], summ[:, 0].cpu().numpy(), rtol=1e-12, atol=0.0)
+    t_k, t_h = [], []
+    for r in range(reps + 3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(CALLS):
+            kernel(r % n_in)
+        e1.record()
+        e1.synchronize()
+        t0 = time.perf_counter()
+        host(r % n_in)
+        dt = time.perf_counter() - t0
+        if r >= 3:
+            t_k.append(e0.elapsed_time(e1) * 1e3 / CALLS)
+            t_h.append(dt * 1e6)
+    print(f"(e) lv_beats, {clips} clips of {T} frames ({float(info[:, 1].float().mean()):.1f} end-systoles, {float(info[:, 0].float().mean()):.1f} counted beats "
+          f"per clip): us per call, median / minimum of {reps} windows ({n_in} inputs in rotation)")
+    print(f"{'form':64s} {'median us':>10s} {'min us':>9s}")
+    print(f"{'gdkvm_lv_beats (' + str(CALLS) + ' launches per window of device events)':64s} {statistics.median(t_k):10.1f} {min(t_k):9.1f}")
+    print(f"{'.cpu() + scipy.signal.find_peaks + host loop (host clock)':64s} {statistics.median(t_h):10.1f} {min(t_h):9.1f}")
+    print(flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
@@ -337,6 +418,10 @@ def main():
     quick = "--quick" in sys.argv
     ops.require_native()
     dev = torch.device("cuda", torch.cuda.current_device())
+    if "--beats" in sys.argv:
+        part_e(dev, 16, 512, 5 if quick else 40)
+        part_e(dev, 2, 4096, 5 if quick else 40)
+        return
     if "--mm-only" in sys.argv:
         for S in (112, 256):
             part_a(dev, 8 if quick else 512, S, 5 if quick else 40, only=("lv_measure", "surface_distance"))
