@@ -150,12 +150,27 @@ def test_scan_backward_bf16_io(hip):
 
 
 def test_scan_backward_no_state_input(hip):
+    """No state input and a loss on the read-out alone (no d_s_in; the state's gradient arrives as zeros): all five gradients against
+    fp64 autograd -- on this test's first inputs, and as the first of the "which gradients are asked for" cases of
+    tests/test_scan_backward_forms_gpu.py (shape, bound and reference of tests/scan_bwd_forms.py) in fp32 and bf16."""
+    from tests import scan_bwd_forms as F
     q, k, v, a, b = make_scan_inputs(1, 2, 9, 1, 64, 16, seed=46)
     dev = lambda x: torch.from_numpy(x).cuda()
-    tq = dev(q).requires_grad_()
-    R, S = hip.scan(tq, dev(k), dev(v), dev(a), dev(b))
+    ts = [dev(x).requires_grad_() for x in (q, k, v, a, b)]
+    R, S = hip.scan(*ts)
     R.sum().backward()
-    assert tq.grad is not None and torch.isfinite(tq.grad).all()
+    assert ts[0].grad is not None and torch.isfinite(ts[0].grad).all()
+    rs = [torch.from_numpy(x).double().requires_grad_() for x in (q, k, v, a, b)]
+    TR.scan(*rs)[0].sum().backward()
+    for name, g, r in zip("q k v alpha beta".split(), ts, rs):
+        err, ref = np.abs(g.grad.cpu().numpy() - r.grad.numpy()).max(), np.abs(r.grad.numpy()).max()
+        print(f"no state input, first inputs: d_{name} err {err:.3e} max|ref| {ref:.3e}")
+        assert g.grad is not None and err <= 1e-4 * max(1.0, ref), (name, err, ref)
+    for dtype in ("fp32", "bf16"):
+        inp = F.make_inputs(F._c(F.ASKED_SHAPE, dtype=dtype))
+        w = F.worst(F.hip_grads(hip, inp, "R", with_s0=False), F.ref_grads(inp, "R", with_s0=False), inp.bf16)
+        print(f"no state input, {F.ASKED_SHAPE} {dtype}: err / allowed " + " ".join(f"d_{n} {x:.4f}" for n, x in w.items()))
+        assert set(w) == {"q", "k", "v", "alpha", "beta"} and all(x <= 1.0 for x in w.values()), (dtype, w)
 
 
 @pytest.mark.parametrize("case", [(3, 7, 7, 64, 256, 256), (2, 16, 16, 32, 64, 64), (2, 5, 3, 16, 16, 32),
