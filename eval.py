@@ -34,6 +34,18 @@ target's own curves where the target labels every valid frame of a clip, `clips_
 beat EF and `systole_count_agreement`; where the dataset knows an EF per file (EchoNetNpz.file_ef), the same EF statistics against it as
 `vs_file_ef`.  Every other key keeps its value; the `lv` block's one ED / ES / EF per clip is right for clips of one beat only.
 
+With `data.lv_biplane` (and `lv_class` >= 0, a spacing for every clip and a dataset that names every clip's patient and view: camus_png) the
+2CH and the 4CH clip of a patient are combined into ONE volume per frame by the bi-plane method of disks (ops.lv_biplane on the records
+ops.lv_measure_mm left of the post-processed prediction and of the target, kept for the whole split in device tables and summed over the ranks:
+a pair may straddle batches and shards) -- the quantity CAMUS states per patient.  A `biplane` block, behind every other key, holds `pairs`,
+`patients_single_view`, `pairs_with_target` (the target's bi-plane curve has two frames and an EDV; ED / ES are picked on it and the
+prediction is read there), the EF statistics of prediction against target, `edv_mae_ml`, `edv_bias_ml`, `esv_mae_ml`, `esv_bias_ml`,
+`length_mismatch_mean` and `pairs_length_mismatch_over_10pct` (how far the prediction's two long axes are apart at ED, as a fraction of the
+longer) and, where the dataset knows what the files state (CamusPng.info: the 2CH view's value, else the 4CH view's), a `vs_file` block:
+`pairs_with_ef`, EF MAE / bias / r of the prediction against the file, `target_ef_mae` (how well this method on the tracings reproduces the
+file) and the same for EDV and ESV in mL.  Disk j of both views must count from the same end of the ventricle: both views apex up, as CAMUS
+stores them.  Every other key keeps its value.
+
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [key=value ...]"""
@@ -61,7 +73,7 @@ def main(argv=None):
 
     from gdkvm_amd import ops
     from gdkvm_amd.config import beat_prominence_permille, load_config
-    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table
+    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table, view_pair_table
     from gdkvm_amd.distributed import init_from_env, shard_range
     from gdkvm_amd.model import GDKVM, GDKVMConfig
 
@@ -124,6 +136,19 @@ def main(argv=None):
         file_ef = getattr(ds, "file_ef", None)
         if file_ef is not None:                                   # per cent per clip, NaN where a file has none
             file_ef = torch.tensor([float("nan") if (v := file_ef(k)) is None else float(v) for k in range(len(ds))], dtype=torch.float64).to(dev)
+    bp_on = cfg.data.lv_biplane                                   # off: no new call below
+    if bp_on:
+        pair_tab = view_pair_table(ds)
+        missing = [what for what, absent in (("data.lv_class >= 0", lv_cls < 0), ("a pixel spacing for every clip", not mm),
+                                             ("a dataset that names every clip's patient and view", pair_tab is None)) if absent]
+        if missing:
+            raise SystemExit(f"eval.py: data.lv_biplane needs {' and '.join(missing)}")
+        bp_pairs, bp_single = pair_tab                            # host int32 [P, 2] = (2CH clip, 4CH clip), patients with one view only
+        # ops.lv_measure_mm's three records (stats, disks, geom) of EVERY clip of the split, of the post-processed prediction and of the
+        # target: zeros until the clip's own batch writes its rows (a rank writes its shard's rows only, and a row of zeros is an empty frame)
+        bp_rows = lambda: [torch.zeros(len(ds), cfg.data.frames, w, dtype=dt, device=dev)
+                           for w, dt in ((12, torch.int64), (20, torch.int64), (6, torch.float64))]
+        bp_pred, bp_tgt = bp_rows(), bp_rows()
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -147,7 +172,11 @@ def main(argv=None):
             t_copy = target.clone() if vote or keep or fillc or s_cls >= 0 else None
             if lv_cls >= 0:
                 t_stats, _, t_geom = ops.lv_measure(target, cls=lv_cls)
-                t_ml = ops.lv_measure_mm(target, spacing[sub:sub + target.shape[0], None], cls=lv_cls)[2][..., 1].contiguous() if mm else None
+                t_rec = ops.lv_measure_mm(target, spacing[sub:sub + target.shape[0], None], cls=lv_cls) if mm else None
+                t_ml = t_rec[2][..., 1].contiguous() if mm else None
+                if bp_on:                                         # the target's records at the clips' own rows
+                    for tab, rec in zip(bp_tgt, t_rec):
+                        tab[sub:sub + target.shape[0]] = rec
                 nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy, t_ml)
             else:
                 nxt = (nxt, None, None, t_copy, None)
@@ -185,7 +214,10 @@ def main(argv=None):
             ef_sums[:8] += ops.ef_summary(p_val[:, 2], r_val[:, 2], (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
             if mm:
                 # the same post-processed mask and the same rule in mL: ED / ES are the target's frames, picked on the target's mL curve
-                q_stats, _, q_geom = ops.lv_measure_mm(measured, sp, cls=lv_cls)
+                q_stats, q_disks, q_geom = ops.lv_measure_mm(measured, sp, cls=lv_cls)
+                if bp_on:                                         # the prediction's records at the clips' own rows
+                    for tab, rec in zip(bp_pred, (q_stats, q_disks, q_geom)):
+                        tab[i:i + mask.shape[0]] = rec
                 m_idx, m_val = ops.lv_ef(t_ml, t_npix)
                 _, q_val = ops.lv_ef(q_geom[..., 1], q_stats[..., 0], pick_vol=t_ml, pick_npix=t_npix)
                 ok = (m_idx[:, 0] >= 0) & (m_val[:, 0] > 0)
@@ -232,6 +264,9 @@ def main(argv=None):
             torch.distributed.all_reduce(sd_sums)                 # ... and the five surface-distance sums
         if beats_on:
             torch.distributed.all_reduce(bt_acc)                  # ... and the beat-by-beat sums
+        if bp_on:
+            for tab in bp_pred + bp_tgt:                          # ... and the record tables: every row was written by one rank and is 0 on
+                torch.distributed.all_reduce(tab)                 # the others, and integer and fp64 sums with zeros are exact
     if rank == 0:
         dice = ops.dice_from_counts(counts).tolist()
         iou = ops.iou_from_counts(counts).tolist()
@@ -286,6 +321,56 @@ def main(argv=None):
                 vs_f = ops.ef_stats(acc[17:])
                 res["beats"]["vs_file_ef"] = {k: (v if isinstance(v, int) else r5(v)) for k, v in vs_f.items()
                                               if k in ("clips_with_ef", "ef_mae", "ef_bias", "ef_pearson_r")}
+        if bp_on:
+            # one launch per side over the whole split's tables; ED / ES are the target's frames, picked on its bi-plane curve
+            rnd = lambda v: v if isinstance(v, int) else round(float(v), 5)
+            g_out, g_npix = ops.lv_biplane(*bp_tgt, spacing[:, None], bp_pairs)
+            p_out, p_npix = ops.lv_biplane(*bp_pred, spacing[:, None], bp_pairs)
+            g_vol = g_out[..., 0].contiguous()
+            g_idx, g_val = ops.lv_ef(g_vol, g_npix)
+            _, p_val = ops.lv_ef(p_out[..., 0].contiguous(), p_npix, pick_vol=g_vol, pick_npix=g_npix)
+            ok = (g_idx[:, 0] >= 0) & (g_val[:, 0] > 0)           # the pairs with a target: two valid frames and an EDV
+            # sums of (predicted - reference) and of its magnitude over the pairs where `use`, as MAE and bias
+            def mae_bias(p, g, use):
+                s = ops.ef_summary(p, g, use).cpu()
+                cnt = max(float(s[0]), 1.0)
+                return float(s[2]) / cnt, float(s[1]) / cnt
+            blk = {"pairs": int(bp_pairs.shape[0]), "patients_single_view": int(bp_single), "pairs_with_target": int(ok.sum()),
+                   **ops.ef_stats(ops.ef_summary(p_val[:, 2], g_val[:, 2], ok).cpu())}
+            for name, k in (("edv", 0), ("esv", 1)):
+                blk[f"{name}_mae_ml"], blk[f"{name}_bias_ml"] = mae_bias(p_val[:, k], g_val[:, k], ok)
+            # the two long axes of the PREDICTION at end-diastole: the guidelines want them within 10 % of each other
+            mism = p_out[..., 2].gather(1, g_idx[:, :1].clamp(min=0).long())[:, 0] * ok
+            blk["length_mismatch_mean"] = float(mism.sum()) / max(int(ok.sum()), 1)
+            blk["pairs_length_mismatch_over_10pct"] = int((mism > 0.1).sum())
+            info = getattr(ds, "info", None)
+            if info is not None:
+                # what the files state per patient (CAMUS: bi-plane Simpson values), from the 2CH view's info, else the 4CH view's
+                def stated(key, scale):
+                    vals = []
+                    for a, b in bp_pairs.tolist():
+                        got = [v for v in ((info(c) or {}).get(key) for c in (a, b))
+                               if isinstance(v, (int, float)) and not isinstance(v, bool) and v == v and abs(v) != float("inf")]
+                        if len(got) == 2 and got[0] != got[1]:
+                            print(f"eval.py: biplane: {key} of clips {a} (2CH) and {b} (4CH) differ: {got[0]} and {got[1]}; the 2CH value is used",
+                                  file=sys.stderr, flush=True)
+                        vals.append(float(got[0]) * scale if got else float("nan"))
+                    return torch.tensor(vals, dtype=torch.float64).reshape(len(vals)).to(dev)
+                f_ef = stated("ef_percent", 0.01)
+                have = ok & ~torch.isnan(f_ef)
+                f_ef = torch.nan_to_num(f_ef)
+                vs = {"pairs_with_ef": int(have.sum()),
+                      **{k: v for k, v in ops.ef_stats(ops.ef_summary(p_val[:, 2], f_ef, have).cpu()).items() if k in ("ef_mae", "ef_bias", "ef_pearson_r")},
+                      "target_ef_mae": mae_bias(g_val[:, 2], f_ef, have)[0]}
+                for name, k in (("edv", 0), ("esv", 1)):
+                    f_v = stated(f"{name}_ml", 1.0)
+                    have = ok & ~torch.isnan(f_v)
+                    f_v = torch.nan_to_num(f_v)
+                    vs[f"pairs_with_{name}"] = int(have.sum())
+                    vs[f"{name}_mae_ml"], vs[f"{name}_bias_ml"] = mae_bias(p_val[:, k], f_v, have)
+                    vs[f"target_{name}_mae_ml"] = mae_bias(g_val[:, k], f_v, have)[0]
+                blk["vs_file"] = {k: rnd(v) for k, v in vs.items()}
+            res["biplane"] = {k: (v if isinstance(v, dict) else rnd(v)) for k, v in blk.items()}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

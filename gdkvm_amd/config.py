@@ -39,6 +39,8 @@ class DataCfg:
     lv_beats: bool = False           # eval.py: beat-by-beat EF of lv_class from the whole clip's area curve (ops.lv_beats): a `beats` block
     beat_distance: int = 20          # ... the fewest frames between two end-systoles, 1..4096 (find_peaks' distance=; EchoNet-Dynamic: 20 at 50 fps)
     beat_prominence: float = 0.5     # ... the prominence an end-systole needs, as a fraction 0..1 of the curve's range (handed on in per mille)
+    lv_biplane: bool = False         # eval.py: bi-plane Simpson volumes and EF per patient from its 2CH and 4CH clips (ops.lv_biplane): a `biplane`
+                                     # block; needs lv_class >= 0, a spacing for every clip and a dataset with patient / view (camus_png)
     synthetic_beats: float = 1.0     # the synthetic clips' heart beats per clip (> 0; 1.0: the clips of before, bit for bit)
     whole_video: bool = False        # echonet_npz only: a clip is the video's first `frames` frames (several beats), not the window around ED / ES
 
@@ -170,6 +172,8 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     d = cfg.data
     if not isinstance(d.lv_beats, bool) or not isinstance(d.whole_video, bool):
         raise ValueError(f"data.lv_beats = {d.lv_beats!r}, data.whole_video = {d.whole_video!r}: true or false")
+    if not isinstance(d.lv_biplane, bool):
+        raise ValueError(f"data.lv_biplane = {d.lv_biplane!r}: true or false")
     if d.whole_video and d.kind != "echonet_npz":
         raise ValueError(f"data.whole_video is for data.kind = echonet_npz, not {d.kind!r}")
     if isinstance(d.beat_distance, bool) or not isinstance(d.beat_distance, int) or not 1 <= d.beat_distance <= 4096:

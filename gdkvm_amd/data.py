@@ -12,7 +12,8 @@ so the default is a seeded synthetic echo-like clip generator; two on-disk forma
                what tools/convert_camus.py writes from the CAMUS NIfTI release (guide: index.astro:221); the reference's own processed
                "camus_png256x256_10f" tree is not documented beyond its name (index.astro:217,246), so this layout is the builder's;
                beside the PNGs an optional spacing.json {"spacing_um": [row_um, col_um], "native_hw": [H, W]}: the pixel spacing of the
-               RESIZED grid in micrometres, from the NIfTI pixdim
+               RESIZED grid in micrometres, from the NIfTI pixdim, and an optional info.json with the EF and volumes the release states for
+               the patient (CamusPng.info); view_pair_table pairs a patient's two views for the bi-plane volume (ops.lv_biplane)
 
 A dataset's spacing_um(i) is clip i's pixel spacing (row_um, col_um) in integer micrometres per pixel of the grid its masks are on, or None;
 clip_spacing_table gathers them for eval.py, which then reports volumes in mL and surface distances in mm.  A dataset's length(i), where it has
@@ -334,6 +335,24 @@ class CamusPng(Dataset):
     def view(self, i) -> str:
         return os.path.basename(self.seqs[i])
 
+    def patient(self, i) -> str:
+        """The name of the patient folder sequence i lies in: the 2CH and the 4CH sequence of a patient share it (view_pair_table)."""
+        return os.path.basename(os.path.dirname(self.seqs[i]))
+
+    def info(self, i) -> Optional[dict]:
+        """The sequence's info.json (tools/convert_camus.py, from the release's Info_<view>.cfg): a dict with ef_percent, edv_ml, esv_ml (the
+        dataset's bi-plane Simpson values of the patient), ed_frame, es_frame, nb_frame, frame_rate, each a number or None; None without the
+        file or when it holds no JSON object."""
+        p = os.path.join(self.seqs[i], "info.json")
+        if not os.path.exists(p):
+            return None
+        try:
+            with open(p) as f:
+                d = json.load(f)
+        except ValueError:
+            return None
+        return d if isinstance(d, dict) else None
+
     def spacing_um(self, i):
         """The sequence's spacing.json "spacing_um" [row_um, col_um] (tools/convert_camus.py, from the NIfTI pixdim and the resize); None
         without the file or when it holds no pair of integers in 1..4095."""
@@ -383,6 +402,21 @@ def clip_length_table(ds) -> torch.Tensor:
     clip length `frames` (attribute T)."""
     own = getattr(ds, "length", None)
     return torch.tensor([int(own(i)) if own is not None else int(ds.T) for i in range(len(ds))], dtype=torch.int32).reshape(len(ds))
+
+
+def view_pair_table(ds):
+    """(pairs int32 [P, 2] (host) = the clip indices of the 2CH and of the 4CH view of every patient that has both, in the order the patients
+    first appear; the number of patients with one of the two views only) for ops.lv_biplane; None for a dataset without patient(i) / view(i).
+    A patient's first sequence of a view counts."""
+    patient, view = getattr(ds, "patient", None), getattr(ds, "view", None)
+    if patient is None or view is None:
+        return None
+    seen = {}
+    for i in range(len(ds)):
+        seen.setdefault(patient(i), {}).setdefault(view(i), i)
+    rows = [(v["2CH"], v["4CH"]) for v in seen.values() if "2CH" in v and "4CH" in v]
+    single = sum(1 for v in seen.values() if ("2CH" in v) != ("4CH" in v))
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2), single
 
 
 def build_dataset(cfg, split: str = "train", n_synthetic: int = 256, as_uint8: bool = False) -> Dataset:

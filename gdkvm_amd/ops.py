@@ -128,6 +128,7 @@ SIGNATURES = {
     "gdkvm_lv_measure_mm": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
     "gdkvm_lv_beats": (_i, [_vp] * 7 + [_i] * 5 + [ctypes.c_int64, _vp]),
+    "gdkvm_lv_biplane": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
     "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_fill_holes_workspace_bytes": (_sz, [_i] * 3),
@@ -2173,6 +2174,44 @@ def lv_beats(area: torch.Tensor, vol: torch.Tensor, length: Optional[torch.Tenso
     _call("gdkvm_lv_beats", dev, area, vol, length, beats, beat_val, info, summ, B, T, int(max_beats), int(distance), int(prominence_permille),
           int(min_pixels))
     return beats, beat_val, info, summ
+
+
+def lv_biplane(stats: torch.Tensor, disks: torch.Tensor, geom: torch.Tensor, spacing_um: torch.Tensor, pairs: torch.Tensor):
+    """gdkvm_lv_biplane: the bi-plane Simpson volume of every frame from the records of two views.  stats int64 [C, T, 12], disks int64
+    [C, T, D] and geom float64 [C, T, 6] are lv_measure_mm's outputs for C clips of T frames (non-contiguous views are copied), spacing_um the
+    int32 [..., 2] that call was given, broadcast over [C, T] as there; pairs a HOST int32 [P, 2] tensor whose rows are the clip indices of
+    view a and view b (eval.py: the 2CH and the 4CH clip of a patient, gdkvm_amd.data.view_pair_table) -- it is range-checked against C here,
+    before anything is copied, and a device tensor is refused.  Disk j of both views must count from the same end of the ventricle
+    (definition and the assumption: include/gdkvm.h).  Returns (out float64 [P, T, 3] = V in mL, L in mm, the long axes' mismatch (L - the
+    shorter) / L; npix int64 [P, T] = the smaller view's pixels, 0 where either view is empty or has a -1 record, and then out is 0 too);
+    lv_ef(out[..., 0], npix) gives ED / ES / EF per pair."""
+    for name, t, dt, last in (("stats", stats, torch.int64, 12), ("disks", disks, torch.int64, None), ("geom", geom, torch.float64, 6)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or (last is not None and t.shape[2] != last):
+            raise GdkvmError(f"lv_biplane: {name} must be {dt} [C, T, {last or 'D'}], got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    C, T = int(stats.shape[0]), int(stats.shape[1])
+    D = int(disks.shape[2])
+    if tuple(disks.shape[:2]) != (C, T) or tuple(geom.shape[:2]) != (C, T):
+        raise GdkvmError(f"lv_biplane: stats {tuple(stats.shape)}, disks {tuple(disks.shape)} and geom {tuple(geom.shape)} are not records of "
+                         "the same [C, T] frames")
+    if not 1 <= D <= LV_MAX_DISKS:
+        raise GdkvmError(f"lv_biplane: disks = {D} outside 1..{LV_MAX_DISKS}")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise GdkvmError(f"lv_biplane: pairs must be an int32 tensor [P, 2] = (clip of view a, clip of view b), got "
+                         f"{getattr(pairs, 'dtype', type(pairs))} {tuple(getattr(pairs, 'shape', ()))}")
+    if pairs.device.type != "cpu":
+        raise GdkvmError("lv_biplane: pairs must be a host tensor (it is range-checked before it is copied)")
+    if pairs.numel() and (int(pairs.min()) < 0 or int(pairs.max()) >= C):
+        raise GdkvmError(f"lv_biplane: a pair names a clip outside 0..{C - 1}")
+    stats, disks, geom = stats.contiguous(), disks.contiguous(), geom.contiguous()
+    dev = _dev(stats, disks, geom)
+    sp = _spacing_frames("lv_biplane", spacing_um, (C, T), dev)
+    P = int(pairs.shape[0])
+    pr = pairs.contiguous().to(dev)
+    out = torch.empty((P, T, 3), dtype=torch.float64, device=dev)
+    npix = torch.empty((P, T), dtype=torch.int64, device=dev)
+    _call("gdkvm_lv_biplane", dev, stats, disks, geom, sp, pr, out, npix, C, T, D, P)
+    return out, npix
 
 
 def beats_summary(pred_summ: torch.Tensor, pred_info: torch.Tensor, ref_summ: torch.Tensor, ref_info: torch.Tensor,

@@ -701,6 +701,33 @@ int gdkvm_lv_ef(const double* vol, const int64_t* npix, const double* pick_vol, 
 int gdkvm_lv_beats(const int64_t* area, const double* vol, const int32_t* length,
                    int32_t* beats, double* beat_val, int32_t* info, double* summ,
                    int B, int T, int max_beats, int distance, int prominence_permille, int64_t min_pixels, void* stream);
+/* Bi-plane Simpson volume from two views of one ventricle (csrc/lv_biplane.hip): the apical two-chamber and four-chamber clips of a patient
+ * combined into one volume per frame, the method of disks the echo guidelines prescribe and the quantity CAMUS states per patient.  Inputs are
+ * the records exactly as gdkvm_lv_measure_mm wrote them for C clips of T frames, on the device: stats int64 [C, T, 12], disks int64 [C, T, D],
+ * geom fp64 [C, T, 6] (8-byte aligned), spacing_um int32 [C, T, 2] (the table that call read), and pairs int32 [P, 2] (4-byte aligned): row p
+ * holds the clip index of view a and of view b.  Per (pair, frame), for view v in {a, b}: n_v = stats[0], E_v = stats[11], L_v = geom[0], W_j^v =
+ * disks[j], (ry, rx) = that frame's spacing.  fp64, every operation rounded once, no fused multiply-add:
+ *   pix_v = (double)(ry rx) / 1e6
+ *   a_j^v = ((double)W_j^v / (double)(D n_v E_v)) pix_v        (step 6' of gdkvm_lv_measure_mm, operation for operation: mm^2 in disk j)
+ *   w_j^v = (a_j^v (double)D) / L_v                            (the mean width of disk j in mm)
+ *   L     = max(L_a, L_b)
+ *   s     = sum over j ascending, from 0.0, of w_j^a w_j^b
+ *   V     = (((3.14159265358979323846 / 4.0) s) (L / (double)D)) / 1000.0      (mL: D elliptic disks of height L / D and axes w_j^a, w_j^b)
+ *   mism  = (L - min(L_a, L_b)) / L                            (the guidelines ask for long axes within 10 % of each other)
+ *   npix  = min(n_a, n_b)
+ * With a = b this is the single-plane V of gdkvm_lv_measure_mm up to the order of its operations.  ASSUMPTION: disk j of both views counts from
+ * the same end of the ventricle.  Disk 0 lies at tmin, and step 3's sign rule turns the axis towards growing y (down the image), so disk 0 is
+ * the uppermost end of the ventricle in both views whenever both show the apex up, as CAMUS does; a view stored apex down must be flipped by
+ * the caller.  The two views may differ in spacing, frame size and axis; they share D and T, and frame t of one is paired with frame t of the
+ * other.
+ * Outputs (16-byte aligned):  out fp64 [P, T, 3] = V, L, mism;   npix int64 [P, T].  If n_a <= 0 or n_b <= 0 (an empty frame, or the -1 record
+ * of a spacing out of range): V = L = mism = 0 and npix = 0.  The kernel never reads outside the tables: a pair index outside 0 .. C - 1
+ * gives the pair's rows as all 0 and npix 0 (gdkvm_amd.ops refuses such a table on the host before it is copied).
+ * 1 <= D <= 64, C, T, P >= 0, P T and C T below 2^31: anything else is GDKVM_ERR_SHAPE, a null or misaligned pointer GDKVM_ERR_ARG, both before
+ * any device call; P == 0 or T == 0 is GDKVM_OK without a launch.  One wave per (pair, frame): lanes j < D form the products, which are added
+ * in ascending j; no allocation, no atomics, no synchronisation with the host: capturable; bit-reproducible. */
+int gdkvm_lv_biplane(const int64_t* stats, const int64_t* disks, const double* geom, const int32_t* spacing_um, const int32_t* pairs,
+                     double* out, int64_t* npix, int C, int T, int D, int P, void* stream);
 
 /* Keep the largest connected component of one class of label masks (the clean-up in front of gdkvm_lv_measure: an argmax mask is no tracing,
  * and a false-positive island far from the ventricle enters tmin / tmax, the long axis and the disks; csrc/largest_component.hip).  Every

@@ -13,6 +13,11 @@ Written (what the reference calls "camus_png256x256_10f": 256 x 256, 10 frames p
     y = height): row_um = rint(1000 pixdim_y_mm H / size), col_um likewise with W.  A 549 x 778 sequence squeezed to 256 x 256 has pixels of
     about 0.33 x 0.47 mm; eval.py measures volumes in mL and surface distances in mm with it.  No file (and a log line) when a pixdim is not
     finite or not positive, or a result falls outside 1..4095.
+    <dst>/<split>/patientXXXX/<2CH|4CH>/info.json   when <src>/patientXXXX/Info_<2CH|4CH>.cfg exists: {"ef_percent", "edv_ml", "esv_ml",
+    "ed_frame", "es_frame", "nb_frame", "frame_rate"} from its `key: value` lines (LVef or EF, LVedv, LVesv, ED, ES, NbFrame, FrameRate), null
+    where a key is absent or holds no number.  The volumes and the EF there are the dataset's bi-plane Simpson values, stated per patient in
+    both views' files; eval.py's `biplane` block compares against them.  The key names are written down from the two public CAMUS releases
+    WITHOUT a copy at hand to check them: the parser takes keys in any letter case, ignores what it does not know and never fails on a line.
 
 NIfTI-1 is read here directly (a 348-byte header + a raw array, gzip around it): no nibabel in this image.  Nothing touches a GPU.
 
@@ -81,6 +86,37 @@ def spacing_um(dx_mm: float, dy_mm: float, native_h: int, native_w: int, size: i
     return [int(row), int(col)]
 
 
+# info.json's fields and the cfg keys (lower case) each is read from, the first present one that parses wins
+_INFO_KEYS = (("ef_percent", ("lvef", "ef"), float), ("edv_ml", ("lvedv",), float), ("esv_ml", ("lvesv",), float),
+              ("ed_frame", ("ed", "ed_frame"), int), ("es_frame", ("es", "es_frame"), int), ("nb_frame", ("nbframe", "nb_frame"), int),
+              ("frame_rate", ("framerate", "frame_rate"), float))
+
+
+def parse_info_cfg(text: str) -> dict:
+    """The fields of info.json from the text of a CAMUS Info_<view>.cfg: `key: value` lines, keys in any letter case, unknown keys and lines
+    without a colon ignored; a field is None where none of its keys is present with a finite number (an integer field takes a whole number
+    only).  The key names (LVef / EF, LVedv, LVesv, ED, ES, NbFrame, FrameRate) are from memory of the two public releases and could not be
+    checked against a copy: hence the tolerance, and None rather than an error for anything unexpected."""
+    seen = {}
+    for line in text.splitlines():
+        key, sep, val = line.partition(":")
+        if sep and key.strip():
+            seen.setdefault(key.strip().lower(), val.strip())
+    out = {}
+    for field, keys, kind in _INFO_KEYS:
+        out[field] = None
+        for k in keys:
+            try:
+                v = float(seen[k])
+            except (KeyError, ValueError):
+                continue
+            if not math.isfinite(v) or (kind is int and v != int(v)):
+                continue
+            out[field] = int(v) if kind is int else v
+            break
+    return out
+
+
 def write_nifti(path: str, arr: np.ndarray, pixdim=None) -> None:
     """A minimal NIfTI-1 writer (tests build tiny CAMUS-shaped trees with it).  pixdim = (dx, dy) in mm goes to pixdim[1..2] with the spatial
     unit set to mm; without it those header bytes stay zero, as before."""
@@ -140,7 +176,7 @@ class defaultdict_const(dict):
 def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = "train", log=print) -> dict:
     from PIL import Image
     splits = _splits(src, split)
-    done = 0
+    done = infos = 0
     for pdir in sorted(glob.glob(os.path.join(src, "patient*"))):
         pid = os.path.basename(pdir)
         for view in ("2CH", "4CH"):
@@ -168,8 +204,15 @@ def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = 
             else:
                 with open(os.path.join(out, "spacing.json"), "w") as f:
                     json.dump({"spacing_um": sp, "native_hw": [int(img.shape[1]), int(img.shape[0])]}, f)
+            cfg = os.path.join(pdir, f"Info_{view}.cfg")
+            if os.path.exists(cfg):
+                with open(cfg, errors="replace") as f:
+                    info = parse_info_cfg(f.read())
+                with open(os.path.join(out, "info.json"), "w") as f:
+                    json.dump(info, f)
+                infos += 1
             done += 1
-    log(f"converted {done} sequences")
+    log(f"converted {done} sequences ({infos} with an info.json)")
     return {"sequences": done}
 
 

@@ -23,7 +23,8 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     walk of the ellipse's surface ends at once, every walk of the checkerboard's is as long as the ellipse is far), and an empty class.
     gdkvm_lv_measure_mm and gdkvm_surface_distance_mm (a spacing of 330 x 468 um for every frame) run in the same windows on the same inputs
     as the pixel kernels' rows, so that each mm row reads against its pixel row of the same run (--mm-only: part (a) with the lv_measure and
-    surface_distance rows alone, pixel and mm, and nothing else).
+    surface_distance rows alone, pixel and mm, and nothing else).  gdkvm_lv_biplane runs beside lv_measure_mm on the ellipse's records: the
+    frames as clips of one frame, each paired with the next.
 (v) gdkvm_temporal_vote at the cfg2 mask shape, 16 clips of 32 frames of 112^2 with 4 classes (--vote-only: this part alone), radius 1, 2
     and 7 with a target and radius 1 without, through the C symbol on preallocated outputs, beside two yardsticks in the same alternated
     windows: the plain torch expression of the same filter (torch_vote: a one-hot, a window sum along T, an argmax with the tie rules; the
@@ -160,6 +161,18 @@ def part_a(dev, F, S, reps, n_in=4, only=()):
                                             ops.BF16, st)
         assert rc == 0, lib.gdkvm_last_error()
 
+    # gdkvm_lv_biplane on records of their own (the ellipse's, written once): the F frames as F clips of one frame, each paired with the next
+    lv_mm(masks[0], 1)
+    bp_rec = [t.clone() for t in (stats, disks, geom_mm)]
+    bp_pairs = torch.stack([torch.arange(F), (torch.arange(F) + 1) % F], 1).to(torch.int32).to(dev)
+    bp_out = torch.empty((F, 1, 3), dtype=torch.float64, device=dev)
+    bp_npix = torch.empty((F, 1), dtype=torch.int64, device=dev)
+
+    def bp():
+        rc = lib.gdkvm_lv_biplane(bp_rec[0].data_ptr(), bp_rec[1].data_ptr(), bp_rec[2].data_ptr(), spacing.data_ptr(), bp_pairs.data_ptr(),
+                                  bp_out.data_ptr(), bp_npix.data_ptr(), F, 1, 20, F, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
     frac = float(masks[0].float().mean())
     forms = {
         f"lv_measure, ellipse ({100 * frac:.0f} % of the frame)": (lambda i: lv(masks[i], 1), F * S * S),
@@ -185,6 +198,7 @@ def part_a(dev, F, S, reps, n_in=4, only=()):
         "lv_measure_mm, ellipse": (lambda i: lv_mm(masks[i], 1), F * S * S),
         "lv_measure_mm, every pixel of the class": (lambda i: lv_mm(full, 1), F * S * S),
         "lv_measure_mm, no pixel of the class": (lambda i: lv_mm(full, 2), F * S * S),
+        "lv_measure_mm records -> lv_biplane, F pairs": (lambda i: bp(), F * (2 * 8 * (20 + 4) + 32)),
         "surface_distance_mm, ellipse against ellipse": (lambda i: sd_mm(masks[i], masks[(i + 1) % n_in], 1), 2 * F * S * S),
         "surface_distance_mm, ellipse + 3 islands against it": (lambda i: sd_mm(isl[i], masks[i], 1), 2 * F * S * S),
         "surface_distance_mm, checkerboard against shifted": (lambda i: sd_mm(board, board_shifted, 1), 2 * F * S * S),
