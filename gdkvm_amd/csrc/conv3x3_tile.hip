@@ -11,6 +11,14 @@
 //     streams in while chunk c computes; the input may be the channel concatenation of TWO tensors (x2 / C1), fetched in place;
 //     the DMA goes through a buffer descriptor over the tile's frames, whose range check zero-fills the pixels above and below the
 //     frame; the padding slots and the left / right halo columns carry an offset that is always out of range;
+//   * the four-wave forms (112-pixel tiles, two workgroups per CU) cut the maps whose rows tile 112 pixels but whose frames do not -- 14 x 14
+//     (196 pixels in two tiles of 8 and 6 rows) and 7 x 7 (two frames, 98 pixels, per tile) -- ACROSS frame boundaries: 4 (16) frames
+//     are one stacked image of seven full tiles where whole rows of one frame group made eight, an eighth of them padded pixel slots that
+//     cost their LDS reads and MFMAs in every k-step.  A tile's band holds its 8 (16) rows frame segment by segment, ONE zero row between
+//     two consecutive frames (the lower halo of one, the upper of the next), and a row above and below that holds data where it lies in the
+//     same frame: <= 11 rows x 16 pixels (28 pieces, 57 KB of LDS per workgroup) and <= 21 x 9 (30 pieces, 61 KB) where the row tiles
+//     took 10 x 16 (25 pieces, 51 KB) and 18 x 9 (26 pieces, 53 KB).  The layout depends only on the tile's phase (tile % 7) and the grid is
+//     a multiple of 7, so a workgroup computes it once like any other geometry; the UP form keeps the row tiles;
 //   * the nine taps are nine SHIFTED READS of that image; the weights never touch LDS: a wave owns one or two 16-channel output
 //     tiles and streams their weight fragments (one 16-byte load each per k-step, three k-steps ahead, straight from L2) -- each
 //     is used for all the wave's pixel tiles (7 MFMAs per load);
@@ -48,6 +56,10 @@ struct ConvTileArgs {
     int relu;
     float inv_band, inv_bw, inv_tw, inv_w;   // 1 / (bh bw), 1 / bw, 1 / (th W), 1 / W: index arithmetic without integer division
     int perm;                                // K % 32 == 0: output channels permuted within groups of 32 (ct_channel)
+    // Frame-stacked tiling (four-wave forms, not UP; stk = 0: off).  A group of sg frames is ONE image of sg H rows, cut into stk tiles of
+    // th = 112 / W rows that run across frame boundaries (fpt = 1, tiles_y = 1; bh = the tallest band of the stk phases): no padded pixel.
+    int stk, sg;                             // tiles per frame group, frames per group: stk th W = sg H W
+    float inv_hw, inv_h1;                    // 1 / (H W), 1 / (H + 1)
 };
 // The UP form (conv3x3_upcat_kernel): x is lo [N, hl, wl, C1] with H = 2 hl, W = 2 wl, and the first C1 input channels are its bilinear
 // enlargement, built in the band from a staging area of LDS that holds the low-resolution rows a tile needs: per frame of the tile, nlr
@@ -90,6 +102,15 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     const int band_bytes = a.npieces * 1024, nchunk = C / CT_CK;
     const int tpix = a.fpt * a.th * W;                     // output pixels of a full tile
     const int co0 = blockIdx.y * (16 * NTW * NWN) + 16 * NTW * wn;     // this wave's output channels co0 .. co0 + 16 NTW - 1
+    // Frame-stacked tiling: a workgroup's tiles are gridDim.x apart and the launcher keeps gridDim.x a multiple of stk (or gives every workgroup
+    // one tile), so ALL its tiles share the phase ph = tile % stk -- and with it the band layout, which is computed once below like the
+    // row-tile geometry.  The tile starts at stacked row s0 = row m0 of the group's frame f0.  Pixel p of the tile is pixel poff + p of the
+    // group; its frame f and row py give band row f rmul + py - rsub for tap (0, 0): (H + 1) rows per frame, ONE zero row between two frames.
+    const bool stk = NWV == 4 && !UP && a.stk != 0;
+    const int ph = stk ? (int)(blockIdx.x % (unsigned)a.stk) : 0, s0 = ph * a.th, f0 = stk ? s0 / H : 0, m0 = s0 - f0 * H;
+    const int poff = stk ? ph * tpix : 0, pper = stk ? H * W : a.th * W, rmul = stk ? H + 1 : a.bh, rsub = stk ? s0 + f0 : 0;
+    const float inv_pper = stk ? a.inv_hw : a.inv_tw;
+    const int tdiv = stk ? a.stk : a.tiles_y, fpg = stk ? a.sg : a.fpt;           // tiles per frame group, frames per group
 
     // bias of this lane's output channels: asm loads, first thing, waited for with the first band (they are older than its pieces).  A load
     // the compiler sees would be "pending" to it at the bias's first use in EVERY iteration of the tile loop -- it cannot count across the
@@ -117,8 +138,14 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     for (int u = 0; u < PP; ++u) {
         const int j = w + NWV * u, d = 64 * j + lane, pix = d / CT_SLOTS, c = d - CT_SLOTS * pix;
         const int f = idx_div(pix, a.inv_band), r = pix - f * (a.bh * BW), by = idx_div(r, a.inv_bw), bx = r - by * BW;
-        const int sp = (f * H + by - 1) * W + bx - 1;      // source pixel, from the group's first, of a tile that starts at row 0
-        const bool live = j < a.npieces && c < 8 && pix < a.band_px && bx >= 1 && bx <= W && (a.tiles_y > 1 || (by >= 1 && by <= a.th));
+        // stacked: band row by is row rr of frame f0 + k in a layout of H + 1 rows per frame that starts at frame f0's row 1 - m0; rr = H is
+        // the zero row two frames share; the band ends with the row below the tile where that lies in the same frame (rr != 0)
+        const int uu = by - 1 + m0, k = idx_div(max(uu, 0), a.inv_h1), rr = uu - k * (H + 1), srow = s0 - m0 + k * H + rr;
+        const bool srow_live = uu >= 0 && rr < H && (srow < s0 + a.th || (srow == s0 + a.th && rr != 0));
+        // source pixel, from the group's first (unstacked: of a tile that starts at row 0)
+        const int sp = ((stk ? srow : f * H + by - 1)) * W + bx - 1;
+        const bool row_live = stk ? srow_live : a.tiles_y > 1 || (by >= 1 && by <= a.th);
+        const bool live = j < a.npieces && c < 8 && pix < a.band_px && bx >= 1 && bx <= W && row_live;
         g_off1[u] = live ? (unsigned)(sp * cs1 * 2 + c * 16) : RSRC_DEAD;
         g_off2[u] = live ? (unsigned)(sp * cs2 * 2 + c * 16) : RSRC_DEAD;
         if constexpr (UP) {
@@ -138,11 +165,11 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     // tile's first row, in pixels -- the descriptor and the offset scalar of a chunk are a few scalar instructions from these
     struct Geo { int px0, npx, row0, r0, lr0, nfr; };     // (r0, lr0, nfr: UP only -- the tile's first row, its first staged source row, its frames)
     auto geo_of = [&](int tile) __attribute__((always_inline)) {
-        const int ty = tile % a.tiles_y, fg = tile / a.tiles_y;          // row tile, frame group
+        const int ty = tile % tdiv, fg = tile / tdiv;                    // row tile (stacked: the phase), frame group
         Geo q;
-        q.px0 = fg * a.fpt * H * W;
-        q.npx = min(a.fpt, a.N - fg * a.fpt) * H * W;                   // (the frames that exist in the last group)
-        q.row0 = ty * a.th * W;
+        q.px0 = fg * fpg * H * W;
+        q.npx = min(fpg, a.N - fg * fpg) * H * W;                       // (the frames that exist in the last group)
+        q.row0 = stk ? 0 : ty * a.th * W;                               // (stacked: the phase's rows are in the lanes' offsets)
         q.r0 = q.lr0 = q.nfr = 0;
         if constexpr (UP) {
             // output row y >= 1 blends source rows (y - 1) >> 1 and the next one: the band's first row inside the frame is max(r0 - 1, 0)
@@ -187,9 +214,9 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
     unsigned pbase[MTW];
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
-        const int p = min(16 * (wm + MW * m) + li, tpix - 1);
-        const int f = idx_div(p, a.inv_tw), r = p - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
-        pbase[m] = (unsigned)(((f * a.bh + py) * BW + px) * CT_PIX + g * 16);
+        const int p = poff + min(16 * (wm + MW * m) + li, tpix - 1);
+        const int f = idx_div(p, inv_pper), r = p - f * pper, py = idx_div(r, a.inv_w), px = r - py * W;
+        pbase[m] = (unsigned)(((f * rmul + py - rsub) * BW + px) * CT_PIX + g * 16);
     }
     const bf16_t* wrow[NTW];                               // weights [K][3][3][C]: A operand rows of output tile nt
 #pragma unroll
@@ -351,7 +378,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
         }
         // epilogue: lane (li, g) holds rows 4g .. 4g+3 of each of the wave's output tiles for pixel 16 (wm + MW m) + li
         {
-            const int ty = tile % a.tiles_y, fg = tile / a.tiles_y;
+            const int fg = tile / tdiv, y0 = stk ? 0 : (tile - fg * tdiv) * a.th, n0 = fg * fpg;     // (stacked: frame and row come from the pixel)
             const float lo = a.relu ? 0.f : -INFINITY;
             if (NTW == 2 && a.perm) {                      // 8 consecutive channels 32G + 8g .. +7 (co0 and K are multiples of 32)
                 if (co0 < K) {
@@ -361,9 +388,9 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
 #pragma unroll
                     for (int m = 0; m < MTW; ++m) {
                         const int p = 16 * (wm + MW * m) + li;
-                        const int pc = min(p, tpix - 1);
-                        const int f = idx_div(pc, a.inv_tw), r = pc - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
-                        const int n = fg * a.fpt + f, yy = ty * a.th + py;
+                        const int pc = poff + min(p, tpix - 1);
+                        const int f = idx_div(pc, inv_pper), r = pc - f * pper, py = idx_div(r, a.inv_w), px = r - py * W;
+                        const int n = n0 + f, yy = y0 + py;
                         o[m] = p < tpix && n < a.N && yy < H ? (unsigned)(((n * H + yy) * W + px) * K + co0 + 8 * g) : ~0u;
                     }
                     // The epilogue's loads and stores are asm, invisible to the compiler's wait-count pass: while LDS-DMA (the next band) and the
@@ -419,8 +446,9 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 4 ? 2 : 1)) void conv3x3_tile_ker
                 for (int m = 0; m < MTW; ++m) {
                     const int p = 16 * (wm + MW * m) + li;
                     if (p >= tpix) continue;
-                    const int f = idx_div(p, a.inv_tw), r = p - f * (a.th * W), py = idx_div(r, a.inv_w), px = r - py * W;
-                    const int n = fg * a.fpt + f, yy = ty * a.th + py;
+                    const int pc = poff + p;
+                    const int f = idx_div(pc, inv_pper), r = pc - f * pper, py = idx_div(r, a.inv_w), px = r - py * W;
+                    const int n = n0 + f, yy = y0 + py;
                     if (n >= a.N || yy >= H) continue;
                     const size_t opix = (((size_t)n * H + yy) * W + px) * K;
 #pragma unroll
@@ -590,9 +618,37 @@ bool setattr_up()
 
 // The tile and band geometry of a launch (a.N, a.H, a.W set): frames per tile, rows per tile, band size and DMA pieces, tile count.
 // Returns false when the map does not tile into maxpix pixels under maxpieces pieces.
+// Frame-stacked tiling of the four-wave forms (maxpix = 112 pixels, a multiple of the map's width): frames per group and tiles per group are
+// the smallest with sg H W = stk maxpix, a tile is th = maxpix / W stacked rows (14 x 14: 4 frames, 7 tiles of 8 rows; 7 x 7: 16 frames, 7
+// tiles of 16 rows).  The band holds th + 2 rows and one zero row per frame boundary inside the tile; bh is the tallest of the stk phases.
+// A ragged last group ends with its last tile that has a row.  Returns false when a band does not fit the pieces.
+bool stacked_geometry(ConvTileArgs& a, int maxpix, int maxpieces, int maxgrid)
+{
+    const int N = a.N, H = a.H, W = a.W, hw = H * W;
+    int gcd = hw, b = maxpix;
+    while (b) { const int t = gcd % b; gcd = b; b = t; }
+    a.stk = hw / gcd; a.sg = maxpix / gcd;
+    if (a.stk > maxgrid) return false;
+    a.fpt = 1; a.tiles_y = 1; a.th = maxpix / W; a.bw = W + 2;
+    int cross = 0;
+    for (int ph = 0; ph < a.stk; ++ph) { const int s0 = ph * a.th, c = (s0 + a.th - 1) / H - s0 / H; if (c > cross) cross = c; }
+    a.bh = a.th + 2 + cross;
+    a.band_px = a.bh * a.bw;
+    a.npieces = (a.band_px * CT_SLOTS + 63) / 64;
+    if (a.npieces > maxpieces) return false;
+    a.inv_band = 1.0f / (float)(a.bh * a.bw); a.inv_bw = 1.0f / (float)a.bw;
+    a.inv_tw = 1.0f / (float)(a.th * W); a.inv_w = 1.0f / (float)W;
+    a.inv_hw = 1.0f / (float)hw; a.inv_h1 = 1.0f / (float)(H + 1);
+    const long long ntiles = (long long)(N / a.sg) * a.stk + ((long long)(N % a.sg) * H + a.th - 1) / a.th;
+    if (ntiles <= 0 || ntiles > 0x7fffffffLL) return false;
+    a.ntiles = (int)ntiles;
+    return true;
+}
+
 bool tile_geometry(ConvTileArgs& a, int maxpix, int maxpieces)
 {
     const int N = a.N, H = a.H, W = a.W;
+    a.stk = 0; a.sg = 0; a.inv_hw = a.inv_h1 = 0.f;
     if (H * W <= maxpix) { a.th = H; a.fpt = maxpix / (H * W); a.tiles_y = 1; if (a.fpt > N) a.fpt = N; }
     else { a.fpt = 1; a.th = maxpix / W; if (a.th < 1) return false; a.tiles_y = (H + a.th - 1) / a.th; }
     a.bw = W + 2; a.bh = a.th + 2;
@@ -679,18 +735,22 @@ int gdkvm_conv3x3_tile_launch(const void* x, const void* x2, int C1, const void*
     a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.relu = relu;
     const int maxpix = half ? 16 * 7 : 16 * CT_MAXMT;
     const int maxpieces = half ? 32 : 56;
-    if (!tile_geometry(a, maxpix, maxpieces)) return 1;
-    // a band piece is addressed by a 32-bit byte offset from its frame group's first byte, and offsets from 2^31 on stand for "zeros":
-    // a group, the band row below it included, stays below that
-    if ((long long)(a.fpt * H + 2) * W * (x2 ? (C1 > C - C1 ? C1 : C - C1) : C) * 2 >= 0x7fffffffLL) return 1;
-    a.perm = K % 32 == 0;
-    const long long ntiles = a.ntiles;
     // wave grid by output channels (variant 0; 1..4 pick one for tuning): 128 per workgroup where K allows, else 64
     if (variant == 0) variant = K % 128 == 0 ? 2 : CT_VARIANT_64;
     const int kwg = (variant == 2 || variant == 4) ? 128 : 64;   // output channels per workgroup
     const int gy = (K + kwg - 1) / kwg;
+    int per = (half ? 512 : 256) / gy; if (per < 1) per = 1;     // workgroup slots per channel group
+    // the four-wave forms stack frames where the map's rows tile 112 pixels but whole rows of ONE frame group leave padded pixel slots
+    // (7 x 7: 98 of 112, 14 x 14: 196 of 224); a map that tiles exactly (28 x 28) or whose width does not divide 112 keeps the row tiles
+    const bool padded = H * W <= maxpix ? maxpix % (H * W) != 0 : H % (maxpix / W) != 0;
+    if (!(half && maxpix % W == 0 && padded && stacked_geometry(a, maxpix, maxpieces, per)) && !tile_geometry(a, maxpix, maxpieces)) return 1;
+    // a band piece is addressed by a 32-bit byte offset from its frame group's first byte, and offsets from 2^31 on stand for "zeros":
+    // a group, the band row below it included, stays below that
+    if ((long long)((a.stk ? a.sg : a.fpt) * H + 2) * W * (x2 ? (C1 > C - C1 ? C1 : C - C1) : C) * 2 >= 0x7fffffffLL) return 1;
+    a.perm = K % 32 == 0;
+    const long long ntiles = a.ntiles;
     const size_t lds = (size_t)2 * a.npieces * 1024 + 1024;
-    int per = (half ? 512 : 256) / gy; if (per < 1) per = 1;
+    if (a.stk) per -= per % a.stk;                         // stacked: a workgroup's tiles, gridDim.x apart, share one phase
     const int gx = (int)(ntiles < per ? ntiles : per);     // persistent: one workgroup per CU
     static std::atomic<unsigned long long> done_mask{0};   // per device; a lost race only repeats the idempotent call
     int dev = 0;
