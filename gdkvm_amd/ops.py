@@ -2044,15 +2044,7 @@ def lv_measure(mask: torch.Tensor, cls: int = 1, disks: int = 20):
     `disks` disks along it and the single-plane method-of-disks volume (definition: include/gdkvm.h; integer-exact up to the disk areas).
     Returns (stats int64 [..., 12] = n sx sy sxx sxy syy Ux Uy tmin tmax Lt 0, disks int64 [..., D], geom float64 [..., 4] = L V cx cy);
     lengths in pixels of the mask's grid, V in pixel^3.  The mask may start at any byte address."""
-    lead, frames, H, W = _mask_frames("lv_measure", mask, cls)
-    if not 1 <= int(disks) <= LV_MAX_DISKS:
-        raise GdkvmError(f"lv_measure: disks = {disks} outside 1..{LV_MAX_DISKS}")
-    dev = _dev(mask)
-    stats = torch.empty(lead + (12,), dtype=torch.int64, device=dev)
-    dk = torch.empty(lead + (int(disks),), dtype=torch.int64, device=dev)
-    geom = torch.empty(lead + (4,), dtype=torch.float64, device=dev)
-    _call("gdkvm_lv_measure", dev, mask, stats, dk, geom, frames, H, W, int(cls), int(disks))
-    return stats, dk, geom
+    return _lv_measure("gdkvm_lv_measure", mask, None, cls, disks)
 
 
 SPACING_UM_MAX = 4095           # a pixel spacing is (row_um, col_um), integers in 1..SPACING_UM_MAX micrometres
@@ -2083,15 +2075,21 @@ def lv_measure_mm(mask: torch.Tensor, spacing_um: torch.Tensor, cls: int = 1, di
     include/gdkvm.h).  Returns (stats int64 [..., 12] = n sx sy sxx sxy syy Vx Vy tmin tmax Lt E, disks int64 [..., D], geom float64
     [..., 6] = L in mm, V in mL, cx, cy in mm, k = um per pixel extent along the axis, area in mm^2).  A frame whose spacing (a device
     tensor's: a host tensor is refused) is outside 1..4095 holds -1 everywhere."""
-    lead, frames, H, W = _mask_frames("lv_measure_mm", mask, cls)
+    return _lv_measure("gdkvm_lv_measure_mm", mask, spacing_um, cls, disks)
+
+
+def _lv_measure(entry: str, mask, spacing_um, cls, disks):
+    """lv_measure (spacing_um None) and lv_measure_mm behind their entry point: the spacing in front of the outputs, geom 4 or 6 wide"""
+    what = entry[len("gdkvm_"):]
+    lead, frames, H, W = _mask_frames(what, mask, cls)
     if not 1 <= int(disks) <= LV_MAX_DISKS:
-        raise GdkvmError(f"lv_measure_mm: disks = {disks} outside 1..{LV_MAX_DISKS}")
+        raise GdkvmError(f"{what}: disks = {disks} outside 1..{LV_MAX_DISKS}")
     dev = _dev(mask)
-    sp = _spacing_frames("lv_measure_mm", spacing_um, lead, dev)
+    sp = () if spacing_um is None else (_spacing_frames(what, spacing_um, lead, dev),)
     stats = torch.empty(lead + (12,), dtype=torch.int64, device=dev)
     dk = torch.empty(lead + (int(disks),), dtype=torch.int64, device=dev)
-    geom = torch.empty(lead + (6,), dtype=torch.float64, device=dev)
-    _call("gdkvm_lv_measure_mm", dev, mask, sp, stats, dk, geom, frames, H, W, int(cls), int(disks))
+    geom = torch.empty(lead + (6 if sp else 4,), dtype=torch.float64, device=dev)
+    _call(entry, dev, mask, *sp, stats, dk, geom, frames, H, W, int(cls), int(disks))
     return stats, dk, geom
 
 
@@ -2379,12 +2377,7 @@ def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> 
     target, the largest squared distance per direction, the per-direction sums of the distances in units of 2^-16 pixel (each rounded down)
     and the two squared distances that enclose the pooled 95th percentile; an empty surface leaves the six other fields 0.  surface_metrics
     turns it into HD, HD95 and ASSD.  mask and target may start at any byte address."""
-    lead, frames, H, W = _mask_frames("surface_distance", mask, cls, target=target)
-    dev = _dev(mask, target)
-    surf = torch.empty(lead + (8,), dtype=torch.int64, device=dev)
-    ws = _workspace("gdkvm_surface_distance_workspace_bytes", dev, frames, H, W, floor=16)
-    _call("gdkvm_surface_distance", dev, mask, target, surf, _Ws(ws), frames, H, W, int(cls))
-    return surf
+    return _surface_distance("gdkvm_surface_distance", mask, target, None, cls)
 
 
 def surface_metrics(surf: torch.Tensor):
@@ -2392,19 +2385,7 @@ def surface_metrics(surf: torch.Tensor):
     have pixels, and the metrics of an invalid frame are 0.  HD = sqrt(max(hAB, hBA)); HD95 = a + (b - a) (95 (n - 1) mod 100) / 100 with
     a = sqrt(q_lo), b = sqrt(q_hi), n = nA + nB -- the linearly interpolated 95th percentile of the pooled distances (sorting d^2 sorts d);
     ASSD = (sAB / nA + sBA / nB) / 2 / 65536 (at most 2^-16 pixel below the mean of the unrounded distances).  Pure torch on either device."""
-    if surf.shape[-1] != 8 or torch.is_floating_point(surf):
-        raise GdkvmError(f"surface_metrics: surf must be integers [..., 8], got {surf.dtype} {tuple(surf.shape)}")
-    s = surf.to(torch.int64)
-    nA, nB = s[..., 0], s[..., 1]
-    valid = (nA > 0) & (nB > 0)
-    d = s.to(torch.float64)
-    hd = torch.maximum(d[..., 2], d[..., 3]).sqrt()
-    a, b = d[..., 6].sqrt(), d[..., 7].sqrt()
-    frac = ((95 * (nA + nB - 1).clamp(min=0)) % 100).to(torch.float64) / 100.0
-    hd95 = a + (b - a) * frac
-    assd = (d[..., 4] / d[..., 0].clamp(min=1.0) + d[..., 5] / d[..., 1].clamp(min=1.0)) / 2.0 / 65536.0
-    metrics = torch.stack([hd, hd95, assd], -1) * valid.unsqueeze(-1).to(torch.float64)
-    return metrics, valid
+    return _surface_metrics("surface_metrics", surf, 1.0, 65536.0)
 
 
 def surface_distance_mm(mask: torch.Tensor, target: torch.Tensor, spacing_um: torch.Tensor, cls: int = 1) -> torch.Tensor:
@@ -2412,12 +2393,18 @@ def surface_distance_mm(mask: torch.Tensor, target: torch.Tensor, spacing_um: to
     broadcast over mask's leading dimensions.  Returns surf int64 [..., 8] = nA, nB, hAB, hBA (um^2), sAB, sBA (sums of the distances in
     units of 2^-8 um, each rounded down), q_lo, q_hi (um^2); a frame whose spacing (a device tensor's: a host tensor is refused) is outside
     1..4095 holds eight -1.  surface_metrics_mm turns it into HD, HD95 and ASSD in mm."""
-    lead, frames, H, W = _mask_frames("surface_distance_mm", mask, cls, target=target)
+    return _surface_distance("gdkvm_surface_distance_mm", mask, target, spacing_um, cls)
+
+
+def _surface_distance(entry: str, mask, target, spacing_um, cls):
+    """surface_distance (spacing_um None) and surface_distance_mm behind their entry point and its workspace query: the spacing in front of surf"""
+    what = entry[len("gdkvm_"):]
+    lead, frames, H, W = _mask_frames(what, mask, cls, target=target)
     dev = _dev(mask, target)
-    sp = _spacing_frames("surface_distance_mm", spacing_um, lead, dev)
+    sp = () if spacing_um is None else (_spacing_frames(what, spacing_um, lead, dev),)
     surf = torch.empty(lead + (8,), dtype=torch.int64, device=dev)
-    ws = _workspace("gdkvm_surface_distance_mm_workspace_bytes", dev, frames, H, W, floor=16)
-    _call("gdkvm_surface_distance_mm", dev, mask, target, sp, surf, _Ws(ws), frames, H, W, int(cls))
+    ws = _workspace(entry + "_workspace_bytes", dev, frames, H, W, floor=16)
+    _call(entry, dev, mask, target, *sp, surf, _Ws(ws), frames, H, W, int(cls))
     return surf
 
 
@@ -2425,17 +2412,23 @@ def surface_metrics_mm(surf: torch.Tensor):
     """(metrics float64 [..., 3] = HD, HD95, ASSD in mm, valid bool [...]) from surface_distance_mm's surf [..., 8]: surface_metrics'
     formulas with sqrt(.) / 1000 for the squared distances (um^2) and / 256 / 1000 for the sums (2^-8 um).  A record of -1 (a spacing out
     of range) is invalid, like one with an empty surface; the metrics of an invalid frame are 0."""
+    return _surface_metrics("surface_metrics_mm", surf, 1000.0, 256.0)
+
+
+def _surface_metrics(what: str, surf, unit: float, sum_scale: float):
+    """surface_metrics (unit 1: pixels, sums in 2^-16) and surface_metrics_mm (unit 1000: um -> mm, sums in 2^-8; negative fields, the -1
+    record, count as 0): one formula, distances / unit and sums / sum_scale / unit (a division by 1.0 changes no bit)"""
     if surf.shape[-1] != 8 or torch.is_floating_point(surf):
-        raise GdkvmError(f"surface_metrics_mm: surf must be integers [..., 8], got {surf.dtype} {tuple(surf.shape)}")
+        raise GdkvmError(f"{what}: surf must be integers [..., 8], got {surf.dtype} {tuple(surf.shape)}")
     s = surf.to(torch.int64)
     nA, nB = s[..., 0], s[..., 1]
     valid = (nA > 0) & (nB > 0)
-    d = s.clamp(min=0).to(torch.float64)
-    hd = torch.maximum(d[..., 2], d[..., 3]).sqrt() / 1000.0
-    a, b = d[..., 6].sqrt() / 1000.0, d[..., 7].sqrt() / 1000.0
+    d = (s if unit == 1.0 else s.clamp(min=0)).to(torch.float64)
+    hd = torch.maximum(d[..., 2], d[..., 3]).sqrt() / unit
+    a, b = d[..., 6].sqrt() / unit, d[..., 7].sqrt() / unit
     frac = ((95 * (nA + nB - 1).clamp(min=0)) % 100).to(torch.float64) / 100.0
     hd95 = a + (b - a) * frac
-    assd = (d[..., 4] / d[..., 0].clamp(min=1.0) + d[..., 5] / d[..., 1].clamp(min=1.0)) / 2.0 / 256.0 / 1000.0
+    assd = (d[..., 4] / d[..., 0].clamp(min=1.0) + d[..., 5] / d[..., 1].clamp(min=1.0)) / 2.0 / sum_scale / unit
     metrics = torch.stack([hd, hd95, assd], -1) * valid.unsqueeze(-1).to(torch.float64)
     return metrics, valid
 
