@@ -46,6 +46,16 @@ longer) and, where the dataset knows what the files state (CamusPng.info: the 2C
 file) and the same for EDV and ESV in mL.  Disk j of both views must count from the same end of the ventricle: both views apex up, as CAMUS
 stores them.  Every other key keeps its value.
 
+With `data.native_eval` (and a dataset that has a native target for every clip, gdkvm_amd.data.native_target_table: camus_png trees written by
+tools/convert_camus.py --native-masks, npy_clips with a `native_target` array) the predicted masks are also compared with the tracing as the
+dataset stores it, at every clip's OWN frame size -- the Dice a published figure is computed with, which the keys above, measured on the
+network's grid against a nearest-neighbour down-sampled tracing, are not.  ops.mask_to_native takes the raw predicted mask to the native size
+(half-pixel-centre bilinear on the one-hot planes, exact integers) and counts it against the native target in the same pass; a frame counts
+when its native target has a pixel of some class.  A `native` block holds `dice_per_class`, `mean_foreground_dice`, `iou_per_class`,
+`mean_foreground_iou` (the grid's formulas and rounding), `pixels` (the native pixels compared) and `frames`; with any of `temporal_vote`,
+`lv_keep_largest`, `lv_fill_holes` on, `native.post` holds the same keys for the post-processed mask.  The surface distances and the volumes
+stay on the grid.  Every other key keeps its value; with the key off nothing new runs.
+
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [key=value ...]"""
@@ -73,7 +83,7 @@ def main(argv=None):
 
     from gdkvm_amd import ops
     from gdkvm_amd.config import beat_prominence_permille, load_config
-    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table, view_pair_table
+    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table, native_target_table, view_pair_table
     from gdkvm_amd.distributed import init_from_env, shard_range
     from gdkvm_amd.model import GDKVM, GDKVMConfig
 
@@ -149,6 +159,15 @@ def main(argv=None):
         bp_rows = lambda: [torch.zeros(len(ds), cfg.data.frames, w, dtype=dt, device=dev)
                            for w, dt in ((12, torch.int64), (20, torch.int64), (6, torch.float64))]
         bp_pred, bp_tgt = bp_rows(), bp_rows()
+    nat_on = cfg.data.native_eval                                 # off: no new call below
+    if nat_on:
+        nat_sizes = native_target_table(ds)                       # host int32 [clips, 2] = (h0, w0)
+        if nat_sizes is None:
+            raise SystemExit("eval.py: data.native_eval needs a dataset with a native target for every clip (camus_png written with "
+                             "tools/convert_camus.py --native-masks, or npy_clips with a native_target array), each side in 1..2048")
+        nat_post = bool(vote or keep or fillc)                    # a second set of sums for the post-processed mask
+        nat_k = cfg.data.num_classes * 3 + 2                      # native counts [ncls, 3], then the pixels compared and the labelled frames
+        nat_acc = torch.zeros((2 if nat_post else 1) * nat_k, dtype=torch.int64, device=dev)
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -205,6 +224,20 @@ def main(argv=None):
             measured, fh = ops.fill_holes(measured, cls=lv_cls, connectivity=fillc, max_area=cfg.data.lv_fill_max_area, target=t_copy)
             fh_acc += torch.cat([(ops.class_counts_after_fill(fh) * labelled[..., 0]).sum((0, 1)),
                                  torch.stack([(fh[..., 3] > 0).sum(), fh[..., 0].clamp(min=0).sum(), fh[..., 3].sum()]).long()])
+        if nat_on:
+            # this batch's native targets, packed on the host (results arrive one batch behind, in order, and i counts them) and counted against
+            # the raw mask -- and the post-processed one -- at every clip's own size; a frame counts when its native target has a class pixel
+            nb = mask.shape[0]
+            n_flat, n_sz = ops.pack_native([ds.native_target(k) for k in range(i, i + nb)])
+            if n_sz != [tuple(r) for r in nat_sizes[i:i + nb].tolist()]:
+                raise SystemExit(f"eval.py: the native targets of clips {i}..{i + nb - 1} do not have the sizes the dataset states")
+            n_flat = n_flat.to(dev)
+            n_px = torch.tensor([h0 * w0 for h0, w0 in n_sz], dtype=torch.int64, device=dev)
+            for slot, pm in enumerate((mask, measured) if nat_post else (mask,)):
+                _, n_c, _ = ops.mask_to_native(pm, n_sz, cfg.data.num_classes, target=n_flat, want_out=False)
+                n_lab = n_c[..., 2].sum(-1) > 0                   # [B, T]
+                nat_acc[slot * nat_k:(slot + 1) * nat_k] += torch.cat([(n_c * n_lab[..., None, None]).sum((0, 1)).long().reshape(-1),
+                                                                       torch.stack([(n_lab.sum(1) * n_px).sum(), n_lab.sum()])])
         if lv_cls >= 0:
             # the prediction's volumes at the TARGET's end-diastolic / end-systolic frames (EchoNet-Dynamic: the two traced frames; unlabelled
             # frames hold no pixel of the class and are no candidates); a clip counts when its target has two such frames and a volume
@@ -264,6 +297,8 @@ def main(argv=None):
             torch.distributed.all_reduce(sd_sums)                 # ... and the five surface-distance sums
         if beats_on:
             torch.distributed.all_reduce(bt_acc)                  # ... and the beat-by-beat sums
+        if nat_on:
+            torch.distributed.all_reduce(nat_acc)                 # ... and the native counts, pixels and frames
         if bp_on:
             for tab in bp_pred + bp_tgt:                          # ... and the record tables: every row was written by one rank and is 0 on
                 torch.distributed.all_reduce(tab)                 # the others, and integer and fp64 sums with zeros are exact
@@ -371,6 +406,19 @@ def main(argv=None):
                     vs[f"target_{name}_mae_ml"] = mae_bias(g_val[:, k], f_v, have)[0]
                 blk["vs_file"] = {k: rnd(v) for k, v in vs.items()}
             res["biplane"] = {k: (v if isinstance(v, dict) else rnd(v)) for k, v in blk.items()}
+        if nat_on:
+            def nat_block(acc):
+                n_counts = acc[:-2].view(cfg.data.num_classes, 3)
+                n_dice, n_iou = ops.dice_from_counts(n_counts).tolist(), ops.iou_from_counts(n_counts).tolist()
+                return {"dice_per_class": [round(d, 5) for d in n_dice],
+                        "mean_foreground_dice": round(sum(n_dice[1:]) / max(len(n_dice) - 1, 1), 5),
+                        "iou_per_class": [round(d, 5) for d in n_iou],
+                        "mean_foreground_iou": round(sum(n_iou[1:]) / max(len(n_iou) - 1, 1), 5),
+                        "pixels": int(acc[-2]), "frames": int(acc[-1])}
+            acc = nat_acc.cpu()
+            res["native"] = nat_block(acc[:nat_k])
+            if nat_post:
+                res["native"]["post"] = nat_block(acc[nat_k:])
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

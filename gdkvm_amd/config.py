@@ -41,6 +41,8 @@ class DataCfg:
     beat_prominence: float = 0.5     # ... the prominence an end-systole needs, as a fraction 0..1 of the curve's range (handed on in per mille)
     lv_biplane: bool = False         # eval.py: bi-plane Simpson volumes and EF per patient from its 2CH and 4CH clips (ops.lv_biplane): a `biplane`
                                      # block; needs lv_class >= 0, a spacing for every clip and a dataset with patient / view (camus_png)
+    native_eval: bool = False        # eval.py: Dice / IoU at every clip's NATIVE frame size against the tracing as stored (ops.mask_to_native): a
+                                     # `native` block; needs a dataset with a native target for every clip (data.native_target_table)
     synthetic_beats: float = 1.0     # the synthetic clips' heart beats per clip (> 0; 1.0: the clips of before, bit for bit)
     whole_video: bool = False        # echonet_npz only: a clip is the video's first `frames` frames (several beats), not the window around ED / ES
 
@@ -174,6 +176,10 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
         raise ValueError(f"data.lv_beats = {d.lv_beats!r}, data.whole_video = {d.whole_video!r}: true or false")
     if not isinstance(d.lv_biplane, bool):
         raise ValueError(f"data.lv_biplane = {d.lv_biplane!r}: true or false")
+    if not isinstance(d.native_eval, bool):
+        raise ValueError(f"data.native_eval = {d.native_eval!r}: true or false")
+    if d.native_eval and not 2 <= d.num_classes <= 8:
+        raise ValueError(f"data.native_eval: ops.mask_to_native votes over 2..8 classes, data.num_classes = {d.num_classes}")
     if d.whole_video and d.kind != "echonet_npz":
         raise ValueError(f"data.whole_video is for data.kind = echonet_npz, not {d.kind!r}")
     if isinstance(d.beat_distance, bool) or not isinstance(d.beat_distance, int) or not 1 <= d.beat_distance <= 4096:

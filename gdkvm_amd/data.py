@@ -18,7 +18,9 @@ so the default is a seeded synthetic echo-like clip generator; two on-disk forma
 A dataset's spacing_um(i) is clip i's pixel spacing (row_um, col_um) in integer micrometres per pixel of the grid its masks are on, or None;
 clip_spacing_table gathers them for eval.py, which then reports volumes in mL and surface distances in mm.  A dataset's length(i), where it has
 one, is the number of clip i's frames that come from the video (the rest repeats the last frame); clip_length_table gathers those for
-ops.lv_beats.  Samples stay (frames, target).
+ops.lv_beats.  A dataset's native_hw(i) / native_target(i), where it has them (npy_clips: an optional `native_target` array [T, h0, w0] in the
+.npz; camus_png: the native_mask_XXX.png of tools/convert_camus.py --native-masks), are clip i's labels at the clip's OWN frame size, untouched
+by any resize; native_target_table gathers the sizes for eval.py's `native` block (data.native_eval).  Samples stay (frames, target).
 """
 from __future__ import annotations
 
@@ -303,6 +305,22 @@ class NpzClips(Dataset):
         with np.load(self.files[i]) as z:
             return _spacing_pair(z["spacing_um"]) if "spacing_um" in z.files else None
 
+    def native_hw(self, i) -> Optional[Tuple[int, int]]:
+        """(h0, w0) of the clip's optional `native_target` array [T, h0, w0]; None without it."""
+        t = self.native_target(i)
+        return None if t is None else (int(t.shape[1]), int(t.shape[2]))
+
+    def native_target(self, i) -> Optional[torch.Tensor]:
+        """The clip's optional `native_target` array, uint8 [T, h0, w0] (its first T frames): the labels at the clip's own size, 255 =
+        unlabelled; None without it or when it is no 3-D array of at least T frames."""
+        with np.load(self.files[i]) as z:
+            if "native_target" not in z.files:
+                return None
+            a = z["native_target"]
+        if a.ndim != 3 or a.shape[0] < self.T or not np.issubdtype(a.dtype, np.integer):
+            return None
+        return torch.from_numpy(np.ascontiguousarray(a[: self.T], dtype=np.uint8))
+
     def __getitem__(self, i):
         z = np.load(self.files[i])
         fr, mk = z["frames"][: self.T], z["masks"][: self.T]
@@ -365,13 +383,47 @@ class CamusPng(Dataset):
         except (ValueError, AttributeError):
             return None
 
-    def __getitem__(self, i):
-        from PIL import Image
+    def _picked(self, i):
+        """The frame files of sequence i that make its clip, in order (one pick for __getitem__ and native_target)"""
         fr = sorted(glob.glob(os.path.join(self.seqs[i], "frame_*.png")))
         if not fr:
             raise FileNotFoundError(f"{self.seqs[i]} holds no frame_*.png")
         pick = np.round(np.linspace(0, len(fr) - 1, self.T)).astype(int) if len(fr) >= self.T else \
             np.minimum(np.arange(self.T), len(fr) - 1)
+        return fr, pick
+
+    def native_hw(self, i) -> Optional[Tuple[int, int]]:
+        """(h0, w0) of sequence i's native label frames (tools/convert_camus.py --native-masks: native_mask_XXX.png, all of one size), or None
+        for a tree written without them."""
+        nm = sorted(glob.glob(os.path.join(self.seqs[i], "native_mask_*.png")))
+        if not nm:
+            return None
+        from PIL import Image
+        with Image.open(nm[0]) as im:
+            w0, h0 = im.size
+        return int(h0), int(w0)
+
+    def native_target(self, i) -> Optional[torch.Tensor]:
+        """uint8 [T, h0, w0]: the labels of clip i's frames as the dataset stores them, untouched by any resize -- the same frame pick as
+        __getitem__, IGNORE_LABEL on a frame without a native_mask file; None for a tree without native masks."""
+        hw = self.native_hw(i)
+        if hw is None:
+            return None
+        from PIL import Image
+        fr, pick = self._picked(i)
+        out = np.full((self.T,) + hw, IGNORE_LABEL, np.uint8)
+        for t, j in enumerate(pick):
+            p = os.path.join(os.path.dirname(fr[j]), os.path.basename(fr[j]).replace("frame_", "native_mask_"))
+            if os.path.exists(p):
+                m = np.asarray(Image.open(p), np.uint8)
+                if m.shape != hw:
+                    raise ValueError(f"{p}: {m.shape[0]} x {m.shape[1]} among native masks of {hw[0]} x {hw[1]}")
+                out[t] = m
+        return torch.from_numpy(out)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        fr, pick = self._picked(i)
         xs, ys = [], []
         for j in pick:
             img = np.asarray(Image.open(fr[j]).convert("RGB"), np.uint8) if self.as_uint8 else np.asarray(Image.open(fr[j]).convert("RGB"), np.float32) / 255.0
@@ -394,6 +446,25 @@ def clip_spacing_table(ds, cfg) -> Optional[torch.Tensor]:
         if sp is None:
             return None
         rows.append(sp)
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2)
+
+
+NATIVE_MAX_SIDE = 2048
+
+
+def native_target_table(ds) -> Optional[torch.Tensor]:
+    """int32 [len(ds), 2] (host) = every clip's native (h0, w0), the size of its native_target(i); None as soon as one clip has none or a side
+    outside 1..NATIVE_MAX_SIDE, and for a dataset without native_hw(i) (then nothing is evaluated at native resolution: a table with holes
+    would average over a different set of clips)."""
+    own = getattr(ds, "native_hw", None)
+    if own is None or getattr(ds, "native_target", None) is None:
+        return None
+    rows = []
+    for i in range(len(ds)):
+        hw = own(i)
+        if hw is None or not (1 <= hw[0] <= NATIVE_MAX_SIDE and 1 <= hw[1] <= NATIVE_MAX_SIDE):
+            return None
+        rows.append((int(hw[0]), int(hw[1])))
     return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2)
 
 

@@ -135,6 +135,8 @@ SIGNATURES = {
     "gdkvm_fill_holes": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_temporal_vote_workspace_bytes": (_sz, [_i] * 5),
     "gdkvm_temporal_vote": (_i, [_vp] * 6 + [_sz] + [_i] * 6 + [_vp]),
+    "gdkvm_mask_to_native_workspace_bytes": (_sz, [_i] * 5),
+    "gdkvm_mask_to_native": (_i, [_vp] * 5 + [_sz, _vp, _sz] + [_i] * 5 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_surface_distance_mm_workspace_bytes": (_sz, [_i] * 3),
@@ -2368,6 +2370,172 @@ def vote_summary(info: torch.Tensor, counts: Optional[torch.Tensor], labelled: t
     lab = labelled.to(torch.bool).expand(info.shape[:-1])
     head = (counts.to(torch.int64) * lab[..., None, None]).reshape(-1, counts.shape[-2] * 3).sum(0)
     return torch.cat([head, tail])
+
+
+# GDKVM_MASK_TO_NATIVE_*: the launch geometry of mask_to_native, for tests that want shapes on both sides of it
+MASK_TO_NATIVE_MAX_SIDE = 2048
+MASK_TO_NATIVE_RUN, MASK_TO_NATIVE_BAND_PIXELS, MASK_TO_NATIVE_MAX_WG, MASK_TO_NATIVE_CLIPS = 16, 4096, 4096, 64
+
+
+def _native_sizes(what: str, sizes, clips: Optional[int] = None) -> list:
+    """[(h0, w0), ...] as Python integers from a sequence of pairs or a HOST integer tensor [clips, 2]; every side in
+    1..MASK_TO_NATIVE_MAX_SIDE.  A device tensor is refused: the sizes decide where every byte goes, so they are validated on the host."""
+    if isinstance(sizes, torch.Tensor):
+        if sizes.device.type != "cpu":
+            raise GdkvmError(f"{what}: sizes must be host integers (a sequence of (h0, w0) or a CPU tensor [clips, 2]): they are validated and "
+                             "turned into byte offsets before anything is launched, and a device tensor would have to be copied back first")
+        if sizes.dim() != 2 or sizes.shape[1] != 2 or torch.is_floating_point(sizes) or sizes.dtype == torch.bool:
+            raise GdkvmError(f"{what}: sizes must be an integer tensor [clips, 2] = (h0, w0), got {sizes.dtype} {tuple(sizes.shape)}")
+        rows = sizes.tolist()
+    else:
+        try:
+            rows = [tuple(r) for r in sizes]
+        except TypeError:
+            raise GdkvmError(f"{what}: sizes must be a sequence of (h0, w0) or a CPU tensor [clips, 2], got {type(sizes).__name__}") from None
+    out = []
+    for b, r in enumerate(rows):
+        if len(r) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in r):
+            raise GdkvmError(f"{what}: sizes[{b}] = {r!r} is no pair of integers (h0, w0)")
+        if not (1 <= r[0] <= MASK_TO_NATIVE_MAX_SIDE and 1 <= r[1] <= MASK_TO_NATIVE_MAX_SIDE):
+            raise GdkvmError(f"{what}: sizes[{b}] = {r[0]} x {r[1]} outside 1..{MASK_TO_NATIVE_MAX_SIDE}")
+        out.append((r[0], r[1]))
+    if clips is not None and len(out) != clips:
+        raise GdkvmError(f"{what}: {len(out)} sizes for {clips} clips")
+    return out
+
+
+def _native_offsets(sizes, T: int):
+    """(every clip's first byte, the bytes of all): clip b holds T frames of h0 w0 bytes and follows clip b - 1"""
+    offs, total = [], 0
+    for h0, w0 in sizes:
+        offs.append(total)
+        total += T * h0 * w0
+    return offs, total
+
+
+def _native_axis(n_out: int, n_in: int):
+    """The rule's two source indices and weights per native index, int64: (i0, i1, w0, w1) with w0 + w1 = 2 n_out"""
+    o = torch.arange(n_out, dtype=torch.int64)
+    num, den = (2 * o + 1) * n_in - n_out, 2 * n_out
+    i0 = torch.div(num, den, rounding_mode="floor")
+    f = num - i0 * den
+    return i0.clamp(0, n_in - 1), (i0 + 1).clamp(0, n_in - 1), den - f, f
+
+
+def _mask_to_native_host(m: torch.Tensor, h0: int, w0: int, ncls: int) -> torch.Tensor:
+    """The rule of gdkvm_mask_to_native for the frames m [T, H, W] (uint8, CPU) of one clip, in int64: uint8 [T, h0, w0]"""
+    ya, yb, wya, wyb = _native_axis(h0, m.shape[-2])
+    xa, xb, wxa, wxb = _native_axis(w0, m.shape[-1])
+    votes = torch.zeros((m.shape[0], ncls, h0, w0), dtype=torch.int64)
+    for ys, wy in ((ya, wya), (yb, wyb)):
+        for xs, wx in ((xa, wxa), (xb, wxb)):
+            src = m[:, ys][:, :, xs].to(torch.int64)
+            w = wy[:, None] * wx[None, :]
+            for c in range(ncls):
+                votes[:, c] += w * (src == c)
+    # the most votes, the smallest class among equals (votes <= 2^24), 255 where nothing voted
+    key = (votes * 8 + (7 - torch.arange(ncls, dtype=torch.int64))[None, :, None, None]).amax(1)
+    return torch.where(key >= 8, 7 - key % 8, torch.full_like(key, 255)).to(torch.uint8)
+
+
+def mask_to_native(mask: torch.Tensor, sizes, num_classes: int, target: Optional[torch.Tensor] = None, want_out: bool = True,
+                   out: Optional[torch.Tensor] = None):
+    """gdkvm_mask_to_native: take the label masks of clips from the network's grid to every clip's own frame size and count them against the
+    native tracing in the same pass.  mask [..., T, H, W] uint8 (the leading dimensions are the clips; a 3-D mask is one clip); sizes the
+    clips' native (h0, w0), each in 1..2048: a sequence of pairs of Python integers or a HOST integer tensor [clips, 2] (a device tensor is
+    refused).  Every native pixel takes the class with the largest bilinear weight among its four source pixels (half-pixel centres, as
+    F.interpolate(align_corners=False) on the one-hot planes; exact integers; ties go to the smallest class, bytes >= num_classes (2..8) do
+    not vote, 255 where nothing votes; definition: include/gdkvm.h).  The native masks are RAGGED: flat uint8 tensors in which clip b's T
+    frames of h0 w0 bytes follow each other and clip b + 1 follows clip b (pack_native builds one, native_frames views one clip of it).
+    Returns (out flat uint8, or None with want_out=False; counts int32 [..., T, num_classes, 3] = argmax_dice's counts of out against
+    `target` (flat, 255 = unlabelled), or None without a target; offsets = the host list of every clip's first byte).  `out`: a flat uint8
+    tensor to write into.  At least one of out / target.  CPU tensors take the same rule in torch, so the wrapper works without a GPU."""
+    what = "mask_to_native"
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() < 3:
+        raise GdkvmError(f"{what}: mask must be uint8 [..., T, H, W], got {getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    lead, frames, H, W = _mask_frames(what, mask, 0)
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 8:
+        raise GdkvmError(f"{what}: num_classes = {num_classes!r} must be an integer in 2..8")
+    T = lead[-1]
+    if T < 1:
+        raise GdkvmError(f"{what}: T = {T} frames per clip, at least 1")
+    clips = frames // T
+    sz = _native_sizes(what, sizes, clips)
+    offsets, total = _native_offsets(sz, T)
+    if target is None and not want_out:
+        raise GdkvmError(f"{what}: neither out (want_out=False) nor a target: nothing to do")
+    if out is not None and not want_out:
+        raise GdkvmError(f"{what}: an out tensor with want_out=False")
+    for name, t in (("target", target), ("out", out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < total):
+            raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {total} bytes (the clips' T h0 w0 in turn), got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t is not None and t.device != mask.device:
+            raise GdkvmError("tensors on different devices")
+    if not mask.is_cuda:
+        # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
+        if not mask.is_contiguous() or any(t is not None and not t.is_contiguous() for t in (target, out)):
+            raise GdkvmError("GDKVM ops need contiguous tensors")
+        m = mask.reshape(clips, T, H, W)
+        res = (torch.empty(total, dtype=torch.uint8) if out is None else out) if want_out else None
+        counts = torch.zeros((clips, T, num_classes, 3), dtype=torch.int32) if target is not None else None
+        cls = torch.arange(num_classes, dtype=torch.uint8)[None, :, None]
+        for b, (h0, w0) in enumerate(sz):
+            o = _mask_to_native_host(m[b], h0, w0, num_classes)
+            if res is not None:
+                res[offsets[b]:offsets[b] + T * h0 * w0] = o.reshape(-1)
+            if target is not None:
+                eo = o.reshape(T, 1, -1) == cls
+                et = target[offsets[b]:offsets[b] + T * h0 * w0].reshape(T, 1, -1) == cls
+                counts[b] = torch.stack([(eo & et).sum(-1), eo.sum(-1), et.sum(-1)], -1).to(torch.int32)
+        return res, (None if counts is None else counts.reshape(lead + (num_classes, 3))), offsets
+    dev = _dev(mask, target, out)
+    if want_out:
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        spans = [(mask.data_ptr(), mask.numel(), "mask")] + ([(target.data_ptr(), total, "target")] if target is not None else [])
+        for lo, n, name in spans:
+            if out.data_ptr() < lo + n and lo < out.data_ptr() + total:
+                raise GdkvmError(f"{what}: out must not overlap {name}")
+    counts = torch.empty(lead + (num_classes, 3), dtype=torch.int32, device=dev) if target is not None else None
+    if clips == 0:
+        return out, counts, offsets
+    host = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
+    # (allocated per call like every workspace of this module; the kernel asks for none today)
+    ws = _workspace("gdkvm_mask_to_native_workspace_bytes", dev, clips, T, H, W, num_classes, floor=16)
+    _call("gdkvm_mask_to_native", dev, mask, host, target, out, counts, total, _Ws(ws), clips, T, H, W, num_classes)
+    return out, counts, offsets
+
+
+def native_frames(flat: torch.Tensor, sizes, T: int, b: int) -> torch.Tensor:
+    """Clip b of a ragged native buffer (mask_to_native's out, pack_native's flat) as a [T, h0, w0] view."""
+    sz = _native_sizes("native_frames", sizes)
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"native_frames: T = {T!r} must be an integer >= 1")
+    if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < len(sz):
+        raise GdkvmError(f"native_frames: clip {b!r} is none of the {len(sz)} clips")
+    offsets, total = _native_offsets(sz, T)
+    if not isinstance(flat, torch.Tensor) or flat.dim() != 1 or flat.numel() < total:
+        raise GdkvmError(f"native_frames: flat must be a 1-D tensor of at least {total} elements, got {tuple(getattr(flat, 'shape', ()))}")
+    h0, w0 = sz[b]
+    return flat[offsets[b]:offsets[b] + T * h0 * w0].view(T, h0, w0)
+
+
+def pack_native(clips) -> Tuple[torch.Tensor, list]:
+    """(flat uint8, sizes) from a list of [T, h0, w0] uint8 tensors with one T, on the tensors' device: the ragged layout mask_to_native
+    takes as `target`."""
+    clips = list(clips)
+    if not clips:
+        raise GdkvmError("pack_native: no clips")
+    T = clips[0].shape[0] if isinstance(clips[0], torch.Tensor) and clips[0].dim() == 3 else None
+    for b, c in enumerate(clips):
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 3 or c.shape[0] != T:
+            raise GdkvmError(f"pack_native: clip {b} must be uint8 [T, h0, w0] with T = {T}, got {getattr(c, 'dtype', type(c))} "
+                             f"{tuple(getattr(c, 'shape', ()))}")
+        if c.device != clips[0].device:
+            raise GdkvmError("tensors on different devices")
+    sizes = _native_sizes("pack_native", [(int(c.shape[1]), int(c.shape[2])) for c in clips])
+    return torch.cat([c.reshape(-1) for c in clips]), sizes
 
 
 def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:

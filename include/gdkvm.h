@@ -822,6 +822,43 @@ size_t gdkvm_temporal_vote_workspace_bytes(int clips, int T, int H, int W, int n
 int gdkvm_temporal_vote(const uint8_t* mask, const uint8_t* target, uint8_t* out, int32_t* info, int32_t* counts,
                         void* workspace, size_t workspace_bytes, int clips, int T, int H, int W, int ncls, int radius, void* stream);
 
+/* Take a clip's label masks from the network's grid to the clip's NATIVE frame size and count them against the native tracing in the same
+ * pass (what a Dice that can be set beside a published one is made of; csrc/mask_to_native.hip).  Every output is an integer that depends on
+ * neither the algorithm nor the schedule.
+ * mask [clips, T, H, W] uint8, H, W in 1..1024, T >= 1, ncls in 2..8; clip b has the native size (h0, w0) = sizes[b], each in 1..2048.  The
+ * sampling is the half-pixel-centre bilinear one of F.interpolate(align_corners = False), applied to the one-hot planes of the labels, in
+ * integers.  For frame m [H, W] of clip b and native row y:
+ *   1. ny = (2 y + 1) H - h0, d = 2 h0, y0 = floor(ny / d) (floor division: -1 in the top half-pixel), fy = ny - y0 d in [0, d).  Row
+ *      clamp(y0) has the weight d - fy and row clamp(y0 + 1) the weight fy; clamp clamps to 0 .. H - 1.  Columns likewise with W, w0.
+ *   2. The four source pixels have the weights wy wx, which add up to 4 h0 w0 <= 2^24.  A source byte c < ncls votes its weight for class
+ *      c; bytes >= ncls (255 included) do not vote.
+ *   3. out = the class with the most votes; ties go to the smallest class index; 255 if no class has a vote.
+ *   4. counts [clips, T, ncls, 3] int32 = {|out == c & target == c|, |out == c|, |target == c|}, gdkvm_argmax_dice's definition, over the
+ *      frame's h0 w0 native pixels; written only when target is given (required then), and zeroed by the callee, with a kernel.
+ * So with (h0, w0) == (H, W) out is mask with every byte >= ncls turned into 255, and the votes of a pixel add up to a constant per frame.
+ * out and target are RAGGED: clip b's T frames of h0 w0 bytes follow each other, and clip b + 1 follows clip b; both optional, at least one
+ * of them; 255 in target is unlabelled.  Frames start at ANY byte address.  native_bytes = the bytes out and target each hold; it must
+ * cover the sum over the clips of T h0 w0.  out must overlap neither mask nor target.
+ * sizes is a HOST int32 [clips, 2]: the entry validates every size, computes every clip's offset itself and hands them to the kernel by
+ * value in the kernel arguments, GDKVM_MASK_TO_NATIVE_CLIPS clips per launch, longer batches in several launches; nothing is copied to the
+ * device, nothing allocated, nothing synchronised (a capture holds the sizes).  counts is 16-byte aligned.
+ * gdkvm_mask_to_native_workspace_bytes is 0 for every shape and the workspace may be NULL; the pair is there so that a caller treats every
+ * mask kernel alike.  Bit-reproducible (the sums are integer atomics).  Bad arguments (shape, ncls, a size outside 1..2048, null mask or
+ * sizes, null or misaligned counts with a target, neither out nor target, native_bytes short of the sum, out overlapping mask or target,
+ * clips * T > 2^30) are GDKVM_ERR_SHAPE before any device call; clips == 0 is GDKVM_OK without a launch.
+ * Launch geometry, for tests that want shapes on both sides of it: a workgroup owns a band of whole native rows of one (clip, frame), the
+ * fewest with at least GDKVM_MASK_TO_NATIVE_BAND_PIXELS pixels, and cuts its bytes into runs of GDKVM_MASK_TO_NATIVE_RUN on the 16-byte
+ * grid of out's addresses (a head of up to 15 bytes, 16-byte stores and loads, a ragged tail); a launch has at most
+ * GDKVM_MASK_TO_NATIVE_MAX_WG workgroups, which take further (clip, frame, band) items in a grid-stride loop; one kernel per ncls. */
+#define GDKVM_MASK_TO_NATIVE_RUN 16
+#define GDKVM_MASK_TO_NATIVE_BAND_PIXELS 4096
+#define GDKVM_MASK_TO_NATIVE_MAX_WG 4096
+#define GDKVM_MASK_TO_NATIVE_CLIPS 64
+size_t gdkvm_mask_to_native_workspace_bytes(int clips, int T, int H, int W, int ncls);
+int gdkvm_mask_to_native(const uint8_t* mask, const int32_t* sizes, const uint8_t* target, uint8_t* out, int32_t* counts,
+                         size_t native_bytes, void* workspace, size_t workspace_bytes, int clips, int T, int H, int W, int ncls,
+                         void* stream);
+
 /* Surface distances between one class of a predicted mask and of its target (what HD, HD95 and ASSD are made of; csrc/surface_distance.hip).
  * Every output is an integer that depends on neither the algorithm nor the schedule; the three floating-point metrics are a few lines on top
  * (gdkvm_amd.ops.surface_metrics) and not part of this ABI.  Distances are in pixels of the masks' grid (isotropic pixels assumed).

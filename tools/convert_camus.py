@@ -19,9 +19,14 @@ Written (what the reference calls "camus_png256x256_10f": 256 x 256, 10 frames p
     both views' files; eval.py's `biplane` block compares against them.  The key names are written down from the two public CAMUS releases
     WITHOUT a copy at hand to check them: the parser takes keys in any letter case, ignores what it does not know and never fails on a line.
 
+With --native-masks (off by default: the tree written without it is byte for byte the one above) every picked frame also gets
+    <dst>/<split>/patientXXXX/<2CH|4CH>/native_mask_000.png ...   the label frame exactly as stored, transposed to rows = y, [H, W] uint8,
+    untouched by any resize: the tracing as the experts drew it, which eval.py's `native` block (data.native_eval) compares the prediction
+    with at the sequence's own size (CamusPng.native_target; spacing.json's "native_hw" is that size).
+
 NIfTI-1 is read here directly (a 348-byte header + a raw array, gzip around it): no nibabel in this image.  Nothing touches a GPU.
 
-    python tools/convert_camus.py <src> <dst> [--size 256] [--frames 10] [--split train]
+    python tools/convert_camus.py <src> <dst> [--size 256] [--frames 10] [--split train] [--native-masks]
 """
 import argparse
 import glob
@@ -173,7 +178,7 @@ class defaultdict_const(dict):
         return self.v
 
 
-def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = "train", log=print) -> dict:
+def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = "train", log=print, native_masks: bool = False) -> dict:
     from PIL import Image
     splits = _splits(src, split)
     done = infos = 0
@@ -197,6 +202,8 @@ def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = 
                 hi = float(a.max()) or 1.0
                 Image.fromarray(np.clip(a * (255.0 / hi if hi > 255.0 else 1.0), 0, 255).astype(np.uint8)).save(os.path.join(out, f"frame_{j:03d}.png"))
                 Image.fromarray(m.astype(np.uint8)).save(os.path.join(out, f"mask_{j:03d}.png"))
+                if native_masks:                                              # the labels as stored: no resize of any kind
+                    Image.fromarray(np.ascontiguousarray(np.asarray(lab[:, :, f]).T).astype(np.uint8)).save(os.path.join(out, f"native_mask_{j:03d}.png"))
             dx_mm, dy_mm = read_nifti_pixdim_mm(seq[0])
             sp = spacing_um(dx_mm, dy_mm, img.shape[1], img.shape[0], size)
             if sp is None:
@@ -223,5 +230,6 @@ if __name__ == "__main__":
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--split", default="train")
+    ap.add_argument("--native-masks", action="store_true", help="also write every picked label frame at its own size (native_mask_XXX.png)")
     a = ap.parse_args()
-    convert(a.src, a.dst, a.size, a.frames, a.split)
+    convert(a.src, a.dst, a.size, a.frames, a.split, native_masks=a.native_masks)

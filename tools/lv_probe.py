@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -38,6 +38,10 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     it what a user does without it: the same curves, already on the device as lv_measure left them, through .cpu() into
     scipy.signal.find_peaks and a host loop over the beats, timed on the host's clock around the whole round trip.  A device call against a
     host round trip, not kernel against kernel.
+(n) --native (this part alone): gdkvm_mask_to_native on 16 clips of 10 frames of 256^2 with 4 classes taken to 549 x 778 each and to mixed
+    CAMUS-like sizes, with a native target (out and counts, counts only, out only), beside the torch expression of the same thing (one-hot,
+    F.interpolate, argmax, counts) and the byte floor: source + native out + native target bytes over the HBM rate above
+    (profiles/native_probe.txt; DESIGN.md).
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
     data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
     instead, and with data.lv_class=-1, alternated, twice each."""
@@ -412,6 +416,83 @@ def part_e(dev, clips, T, reps, n_in=4):
     print(flush=True)
 
 
+def torch_native(mask, sizes, ncls, target, offsets):
+    """ops.mask_to_native as a plain torch expression (the yardstick): per clip a one-hot, F.interpolate (bilinear, half-pixel centres), an
+    argmax and the three counts per class and frame.  fp32 planes: it answers differently where the votes tie or nearly do."""
+    T = mask.shape[1]
+    cls = torch.arange(ncls, dtype=torch.uint8, device=mask.device)
+    outs, counts = [], []
+    for b, (h0, w0) in enumerate(sizes):
+        oh = (mask[b].unsqueeze(1) == cls[None, :, None, None]).to(torch.float32)                    # [T, ncls, H, W]
+        o = torch.nn.functional.interpolate(oh, size=(h0, w0), mode="bilinear", align_corners=False).argmax(1).to(torch.uint8)
+        g = target[offsets[b]:offsets[b] + T * h0 * w0].view(T, 1, h0, w0)
+        eo, et = o.unsqueeze(1) == cls[None, :, None, None], g == cls[None, :, None, None]
+        counts.append(torch.stack([(eo & et).sum((2, 3)), eo.sum((2, 3)), et.sum((2, 3))], -1))
+        outs.append(o.reshape(-1))
+    return torch.cat(outs), torch.stack(counts)
+
+
+def part_n(dev, clips, T, S, ncls, reps, n_in=2):
+    """(n) gdkvm_mask_to_native: `clips` clips of T frames of S x S with ncls classes taken to 549 x 778 each, and to mixed CAMUS-like
+    sizes, with a native target, through the C symbol on preallocated outputs, beside two yardsticks in the same alternated windows: the
+    torch expression of the same resize and counts, and the byte floor -- the source read, the native masks written and the native target
+    read once each -- over the HBM rate this probe quotes everywhere."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    mixed = [(549, 778), (1181, 972), (843, 512), (300, 400), (487, 823), (708, 1050), (584, 439), (967, 601)]
+    for label, sizes in (("549 x 778", [(549, 778)] * clips), ("mixed sizes", [mixed[b % len(mixed)] for b in range(clips)])):
+        masks = [drifting_masks(clips, T, S, ncls, s, dev) for s in range(n_in)]
+        for m in masks:                                            # (the vote's flicker is no prediction: keep the drawing, drop the noise)
+            m.copy_(ops.temporal_vote(m, ncls, 2)[0])
+        host = torch.tensor(sizes, dtype=torch.int32)
+        offsets, total = [], 0
+        for h0, w0 in sizes:
+            offsets.append(total)
+            total += T * h0 * w0
+        # the target: the next input's masks at the native size, so that prediction and tracing are close to each other
+        targets = [ops.mask_to_native(masks[(i + 1) % n_in], sizes, ncls)[0] for i in range(n_in)]
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        counts = torch.empty((clips, T, ncls, 3), dtype=torch.int32, device=dev)
+
+        def mn(i, want_out=True, target=True):
+            rc = lib.gdkvm_mask_to_native(masks[i].data_ptr(), host.data_ptr(), targets[i].data_ptr() if target else None,
+                                          out.data_ptr() if want_out else None, counts.data_ptr() if target else None, total, None, 0,
+                                          clips, T, S, S, ncls, st)
+            assert rc == 0, lib.gdkvm_last_error()
+
+        mn(0)
+        t_out, t_counts = torch_native(masks[0], sizes, ncls, targets[0], offsets)
+        torch.cuda.synchronize()
+        differ = int((t_out != out).sum())
+        print(f"    ({label}: the torch expression differs from the kernel in {differ} of {total} pixels (fp32 planes against exact votes); "
+              f"counts {'equal' if torch.equal(t_counts.to(torch.int32), counts) else 'differ accordingly'})")
+        src = masks[0].numel()
+        forms = {
+            "mask_to_native, out and counts": (lambda i: mn(i), CALLS, src + 2 * total),
+            "mask_to_native, counts only": (lambda i: mn(i, want_out=False), CALLS, src + total),
+            "mask_to_native, out only": (lambda i: mn(i, target=False), CALLS, src + total),
+            "torch expression (one-hot, interpolate, argmax)": (lambda i: torch_native(masks[i], sizes, ncls, targets[i], offsets), 1, src + 2 * total),
+        }
+        times = {name: [] for name in forms}
+        for rep in range(reps + 3):
+            for name, (fn, calls, _) in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    fn(rep % n_in)
+                e1.record()
+                e1.synchronize()
+                if rep >= 3:
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / calls)
+        print(f"(n) mask_to_native, {clips} clips of {T} frames of {S}x{S} to {label}, {ncls} classes, {total / 1e6:.1f} MB of native labels: us per call, "
+              f"windows of device events, median / minimum of {reps} windows per form (alternated, {n_in} inputs in rotation)")
+        print(f"{'form':52s} {'median us':>10s} {'min us':>9s} {'MB':>8s} {'floor us':>9s} {'x floor':>8s}")
+        for name, (_, _, nbytes) in forms.items():
+            med, floor = statistics.median(times[name]), nbytes / HBM * 1e6
+            print(f"{name:52s} {med:10.1f} {min(times[name]):9.1f} {nbytes / 1e6:8.1f} {floor:9.2f} {med / floor:8.1f}")
+        print(flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
@@ -435,6 +516,9 @@ def main():
     if "--beats" in sys.argv:
         part_e(dev, 16, 512, 5 if quick else 40)
         part_e(dev, 2, 4096, 5 if quick else 40)
+        return
+    if "--native" in sys.argv:
+        part_n(dev, 2 if quick else 16, 3 if quick else 10, 256, 4, 5 if quick else 40)
         return
     if "--mm-only" in sys.argv:
         for S in (112, 256):
