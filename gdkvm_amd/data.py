@@ -20,7 +20,9 @@ clip_spacing_table gathers them for eval.py, which then reports volumes in mL an
 one, is the number of clip i's frames that come from the video (the rest repeats the last frame); clip_length_table gathers those for
 ops.lv_beats.  A dataset's native_hw(i) / native_target(i), where it has them (npy_clips: an optional `native_target` array [T, h0, w0] in the
 .npz; camus_png: the native_mask_XXX.png of tools/convert_camus.py --native-masks), are clip i's labels at the clip's OWN frame size, untouched
-by any resize; native_target_table gathers the sizes for eval.py's `native` block (data.native_eval).  Samples stay (frames, target).
+by any resize; native_target_table gathers the sizes for eval.py's `native` block (data.native_eval).  native_frames(i) likewise hands out the
+clip's grey IMAGE frames at their own size (npy_clips: an optional `native_frames` array; camus_png: the native_frame_XXX.png of
+tools/convert_camus.py --native-frames), what ops.frames_from_native and predict.py take.  Samples stay (frames, target).
 """
 from __future__ import annotations
 
@@ -321,6 +323,17 @@ class NpzClips(Dataset):
             return None
         return torch.from_numpy(np.ascontiguousarray(a[: self.T], dtype=np.uint8))
 
+    def native_frames(self, i) -> Optional[torch.Tensor]:
+        """The clip's optional `native_frames` array, uint8 [T, h0, w0] (its first T frames): the grey image frames at the clip's own size
+        (what ops.frames_from_native and predict.py take); None without it or when it is no 3-D uint8 array of at least T frames."""
+        with np.load(self.files[i]) as z:
+            if "native_frames" not in z.files:
+                return None
+            a = z["native_frames"]
+        if a.ndim != 3 or a.shape[0] < self.T or a.dtype != np.uint8:
+            return None
+        return torch.from_numpy(np.ascontiguousarray(a[: self.T]))
+
     def __getitem__(self, i):
         z = np.load(self.files[i])
         fr, mk = z["frames"][: self.T], z["masks"][: self.T]
@@ -420,6 +433,23 @@ class CamusPng(Dataset):
                     raise ValueError(f"{p}: {m.shape[0]} x {m.shape[1]} among native masks of {hw[0]} x {hw[1]}")
                 out[t] = m
         return torch.from_numpy(out)
+
+    def native_frames(self, i) -> Optional[torch.Tensor]:
+        """uint8 [T, h0, w0]: the image frames of clip i at the sequence's own size (tools/convert_camus.py --native-frames:
+        native_frame_XXX.png, grey, all of one size) -- the same frame pick as __getitem__; what ops.frames_from_native and predict.py take.
+        None for a tree without them, or when a picked frame has no such file."""
+        from PIL import Image
+        fr, pick = self._picked(i)
+        out = []
+        for j in pick:
+            p = os.path.join(os.path.dirname(fr[j]), "native_" + os.path.basename(fr[j]))
+            if not os.path.exists(p):
+                return None
+            a = np.asarray(Image.open(p).convert("L"), np.uint8)
+            if out and a.shape != out[0].shape:
+                raise ValueError(f"{p}: {a.shape[0]} x {a.shape[1]} among native frames of {out[0].shape[0]} x {out[0].shape[1]}")
+            out.append(a)
+        return torch.from_numpy(np.stack(out))
 
     def __getitem__(self, i):
         from PIL import Image

@@ -137,6 +137,8 @@ SIGNATURES = {
     "gdkvm_temporal_vote": (_i, [_vp] * 6 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_mask_to_native_workspace_bytes": (_sz, [_i] * 5),
     "gdkvm_mask_to_native": (_i, [_vp] * 5 + [_sz, _vp, _sz] + [_i] * 5 + [_vp]),
+    "gdkvm_frames_from_native_workspace_bytes": (_sz, [_i] * 6),
+    "gdkvm_frames_from_native": (_i, [_vp] * 3 + [_sz, _vp, _sz] + [_i] * 6 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_surface_distance_mm_workspace_bytes": (_sz, [_i] * 3),
@@ -2536,6 +2538,91 @@ def pack_native(clips) -> Tuple[torch.Tensor, list]:
             raise GdkvmError("tensors on different devices")
     sizes = _native_sizes("pack_native", [(int(c.shape[1]), int(c.shape[2])) for c in clips])
     return torch.cat([c.reshape(-1) for c in clips]), sizes
+
+
+# GDKVM_FRAMES_FROM_NATIVE_*: the launch geometry of frames_from_native, for tests that want shapes on both sides of it, and its out_dtype codes
+FRAMES_FROM_NATIVE_CHUNK_BYTES, FRAMES_FROM_NATIVE_HS_WORDS, FRAMES_FROM_NATIVE_ACC_WORDS = 16368, 5120, 2048
+FRAMES_FROM_NATIVE_PART, FRAMES_FROM_NATIVE_BAND_ROWS, FRAMES_FROM_NATIVE_MAX_WG, FRAMES_FROM_NATIVE_CLIPS = 16, 256, 4096, 64
+_FRAMES_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}
+
+
+def _area_weights(n_grid: int, n_native: int) -> torch.Tensor:
+    """The rule's overlap weights of one axis, int64 [n_grid, n_native]: max(0, min((i + 1) n0, (k + 1) n) - max(i n0, k n))"""
+    i = torch.arange(n_grid, dtype=torch.int64)[:, None]
+    k = torch.arange(n_native, dtype=torch.int64)[None, :]
+    return (torch.minimum((i + 1) * n_native, (k + 1) * n_grid) - torch.maximum(i * n_native, k * n_grid)).clamp_(min=0)
+
+
+def _frames_from_native_host(v: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """The rule of gdkvm_frames_from_native for the frames v [T, h0, w0] (uint8, CPU) of one clip, in int64: the bytes q, uint8 [T, H, W]"""
+    h0, w0 = v.shape[-2:]
+    n = _area_weights(H, h0) @ v.to(torch.int64) @ _area_weights(W, w0).t()
+    return torch.div(2 * n + h0 * w0, 2 * h0 * w0, rounding_mode="floor").to(torch.uint8)
+
+
+def frames_from_native(flat: torch.Tensor, sizes, T: int, grid=None, channels: int = 3, dtype: torch.dtype = torch.float32,
+                       out: Optional[torch.Tensor] = None):
+    """gdkvm_frames_from_native: take a ragged batch of native-size uint8 clips to the network's grid by an exact-integer area (box) average
+    and cast them to the model's input dtype in the same pass.  flat: a flat uint8 tensor in which clip b's T frames of h0 w0 bytes follow
+    each other and clip b + 1 follows clip b (pack_native builds one, native_frames views one clip of it); sizes the clips' native (h0, w0),
+    each in 1..2048: a sequence of pairs of Python integers or a HOST integer tensor [clips, 2] (a device tensor is refused); grid = (H, W),
+    each in 1..1024, any ratio; channels 1..4, every plane the same value; dtype uint8 (the byte q = the box mean rounded half up), float32
+    (float(q) * (1 / 255)) or bfloat16 (that rounded once): torch.mul(q, 1 / 255, out=...) bit for bit (definition: include/gdkvm.h).
+    Returns (out [clips, T, channels, H, W], offsets = the host list of every clip's first byte in flat).  `out`: a contiguous tensor of
+    that shape and dtype to write into.  CPU tensors take the same rule in torch int64, so the wrapper works without a GPU."""
+    what = "frames_from_native"
+    if not isinstance(flat, torch.Tensor) or flat.dtype != torch.uint8 or flat.dim() != 1:
+        raise GdkvmError(f"{what}: flat must be a flat uint8 tensor (the clips' T h0 w0 bytes in turn), got {getattr(flat, 'dtype', type(flat))} "
+                         f"{tuple(getattr(flat, 'shape', ()))}")
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    try:
+        H, W = grid
+    except (TypeError, ValueError):
+        raise GdkvmError(f"{what}: grid = {grid!r} must be a pair (H, W)") from None
+    if any(isinstance(n, bool) or not isinstance(n, int) for n in (H, W)) or not (1 <= H <= LV_MAX_SIDE and 1 <= W <= LV_MAX_SIDE):
+        raise GdkvmError(f"{what}: grid = {grid!r} must be integers (H, W), each in 1..{LV_MAX_SIDE}")
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 4:
+        raise GdkvmError(f"{what}: channels = {channels!r} must be an integer in 1..4")
+    if dtype not in _FRAMES_DTYPES:
+        raise GdkvmError(f"{what}: dtype {dtype} is none of uint8, float32, bfloat16")
+    sz = _native_sizes(what, sizes)
+    clips = len(sz)
+    offsets, total = _native_offsets(sz, T)
+    if flat.numel() < total:
+        raise GdkvmError(f"{what}: the native frames of these sizes take {total} bytes, flat holds {flat.numel()}")
+    shape = (clips, T, channels, H, W)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape:
+            raise GdkvmError(f"{what}: out must be {dtype} {shape}, got {getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+        if out.device != flat.device:
+            raise GdkvmError("tensors on different devices")
+    if not flat.is_cuda:
+        # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
+        if not flat.is_contiguous() or (out is not None and not out.is_contiguous()):
+            raise GdkvmError("GDKVM ops need contiguous tensors")
+        res = torch.empty(shape, dtype=dtype) if out is None else out
+        for b, (h0, w0) in enumerate(sz):
+            q = _frames_from_native_host(flat[offsets[b]:offsets[b] + T * h0 * w0].view(T, h0, w0), H, W)[:, None].expand(T, channels, H, W)
+            if dtype == torch.uint8:
+                res[b] = q
+            else:
+                torch.mul(q, 1.0 / 255.0, out=res[b])
+        return res, offsets
+    dev = _dev(flat, out)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    if out.data_ptr() % 16:
+        raise GdkvmError(f"{what}: out must be 16-byte aligned")
+    if out.data_ptr() < flat.data_ptr() + total and flat.data_ptr() < out.data_ptr() + out.numel() * out.element_size():
+        raise GdkvmError(f"{what}: out must not overlap flat")
+    if clips == 0:
+        return out, offsets
+    host = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
+    # (allocated per call like every workspace of this module; the kernel asks for none today)
+    ws = _workspace("gdkvm_frames_from_native_workspace_bytes", dev, clips, T, channels, H, W, _FRAMES_DTYPES[dtype], floor=16)
+    _call("gdkvm_frames_from_native", dev, flat, host, out, total, _Ws(ws), clips, T, channels, H, W, _FRAMES_DTYPES[dtype])
+    return out, offsets
 
 
 def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:

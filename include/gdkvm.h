@@ -859,6 +859,58 @@ int gdkvm_mask_to_native(const uint8_t* mask, const int32_t* sizes, const uint8_
                          size_t native_bytes, void* workspace, size_t workspace_bytes, int clips, int T, int H, int W, int ncls,
                          void* stream);
 
+/* Take a ragged batch of NATIVE-size uint8 clips to the network's grid by an area (box) average and cast them to the model's input dtype in
+ * the same pass (the front end of predict.py, and what tools/convert_camus.py --resample area writes; csrc/frames_from_native.hip).  Every
+ * output is a function of integers that depends on neither the algorithm nor the schedule.
+ * A native frame v [h0, w0] is uint8 with one plane; clip b has the native size (h0, w0) = sizes[b], each in 1..2048.  The grid is (H, W),
+ * each in 1..1024; any ratio on either axis, enlarging included.  The rule is the box integral of the piecewise-constant image, in integers.
+ * For grid row i and native row k, grid column j and native column l:
+ *   1. wy(i, k) = max(0, min((i + 1) h0, (k + 1) H) - max(i h0, k H)), and wx(j, l) the same with w0 and W: the overlap of the two pixels
+ *      in units of 1 / (h0 H).  Sum over k of wy(i, k) = h0 for every i; sum over i of wy(i, k) = H for every k; the non-zero k of a row i
+ *      are the contiguous range floor(i h0 / H) .. ceil((i + 1) h0 / H) - 1.
+ *   2. N(i, j) = sum over k, l of wy(i, k) wx(j, l) v(k, l) <= 255 h0 w0 <= 255 * 2^22 < 2^30.
+ *   3. q(i, j) = floor((2 N + h0 w0) / (2 h0 w0)): the mean rounded half up.  2 N + h0 w0 < 2^32, so unsigned 32-bit words suffice
+ *      everywhere; the kernel has no floating point in front of the final cast, and what it puts in the division's place is exact for
+ *      every numerator below 2^32.
+ *   4. out [clips, T, C, H, W], C in 1..4; every plane of a frame holds the same value (the datasets' frames are grey and the model is
+ *      handed the grey value in every plane).  out_dtype GDKVM_FRAMES_U8: q itself; GDKVM_FRAMES_F32: float(q) * (1.0f / 255.0f);
+ *      GDKVM_FRAMES_BF16: that fp32 value rounded once, to nearest even.  The float forms are torch.mul(bytes, 1 / 255, out = ...) of the
+ *      bytes q, bit for bit.
+ * So (h0, w0) == (H, W) is the identity, a constant frame stays constant, the sum over i, j of N(i, j) is H W times the sum of v, and with
+ * h0 % H == 0 and w0 % W == 0 q is the rounded mean of each h0 / H x w0 / W block.
+ * native is RAGGED, the layout of gdkvm_mask_to_native's target: clip b's T frames of h0 w0 bytes follow each other, and clip b + 1 follows
+ * clip b.  Frames start at ANY byte address.  native_bytes = the bytes native holds; it must cover the sum over the clips of T h0 w0.  out is
+ * contiguous and 16-byte aligned (a misaligned out is refused, not served) and must not overlap native.
+ * sizes is a HOST int32 [clips, 2]: the entry validates every size, computes every clip's offset and band geometry itself and hands them to
+ * the kernel by value in the kernel arguments, GDKVM_FRAMES_FROM_NATIVE_CLIPS clips per launch, longer batches in several launches;
+ * nothing is copied to the device, nothing allocated, nothing synchronised (a capture holds the sizes).
+ * gdkvm_frames_from_native_workspace_bytes is 0 for every shape and the workspace may be NULL; the pair is there so that a caller treats
+ * every kernel of this family alike.  Bit-reproducible: there are no atomics at all, every sum is an integer sum in a lane's own words.  Bad
+ * arguments (shape, C outside 1..4, an unknown out_dtype, a size outside 1..2048, null native, sizes or out, a misaligned out,
+ * native_bytes short of the sum, out overlapping native, clips * T > 2^30) are GDKVM_ERR_SHAPE before any device call; clips == 0 is
+ * GDKVM_OK without a launch.
+ * Launch geometry, for tests that want shapes on both sides of it: a workgroup owns a band of grid rows of one (clip, frame) and streams
+ * the native rows the band covers through LDS in chunks of at most GDKVM_FRAMES_FROM_NATIVE_CHUNK_BYTES bytes (whole native rows, 16-byte
+ * loads on the grid of their addresses, a head of up to 15 bytes and a ragged tail) whose per-column sums take at most
+ * GDKVM_FRAMES_FROM_NATIVE_HS_WORDS words; a band is as many grid rows as one chunk covers, at most
+ * GDKVM_FRAMES_FROM_NATIVE_BAND_ROWS of them and GDKVM_FRAMES_FROM_NATIVE_ACC_WORDS accumulators.  A grid column with more than GDKVM_FRAMES_FROM_NATIVE_PART native columns is cut into
+ * 2, 4, ... parts that different lanes sum, and so is a grid row with more than that many native rows.  A launch has at most
+ * GDKVM_FRAMES_FROM_NATIVE_MAX_WG workgroups, which take further (clip, frame, band) items in a grid-stride loop; one kernel per
+ * out_dtype. */
+#define GDKVM_FRAMES_U8 0
+#define GDKVM_FRAMES_F32 1
+#define GDKVM_FRAMES_BF16 2
+#define GDKVM_FRAMES_FROM_NATIVE_CHUNK_BYTES 16368
+#define GDKVM_FRAMES_FROM_NATIVE_HS_WORDS 5120
+#define GDKVM_FRAMES_FROM_NATIVE_ACC_WORDS 2048
+#define GDKVM_FRAMES_FROM_NATIVE_PART 16
+#define GDKVM_FRAMES_FROM_NATIVE_BAND_ROWS 256
+#define GDKVM_FRAMES_FROM_NATIVE_MAX_WG 4096
+#define GDKVM_FRAMES_FROM_NATIVE_CLIPS 64
+size_t gdkvm_frames_from_native_workspace_bytes(int clips, int T, int C, int H, int W, int out_dtype);
+int gdkvm_frames_from_native(const uint8_t* native, const int32_t* sizes, void* out, size_t native_bytes, void* workspace,
+                             size_t workspace_bytes, int clips, int T, int C, int H, int W, int out_dtype, void* stream);
+
 /* Surface distances between one class of a predicted mask and of its target (what HD, HD95 and ASSD are made of; csrc/surface_distance.hip).
  * Every output is an integer that depends on neither the algorithm nor the schedule; the three floating-point metrics are a few lines on top
  * (gdkvm_amd.ops.surface_metrics) and not part of this ABI.  Distances are in pixels of the masks' grid (isotropic pixels assumed).

@@ -1,0 +1,20 @@
+#!/usr/bin/env python3
+"""Prediction entry point: native-size clips in, masks at every clip's own frame size and one JSON report out (gdkvm_amd.predict).
+
+An input is a .npy file (uint8 [T, h0, w0]), a .npz file (`frames`, optional `spacing_um` = the native micrometres per pixel, rows then
+columns) or a directory of native_frame_*.png / frame_*.png (tools/convert_camus.py --native-frames; its spacing.json is rescaled back to the
+native pixel).  The frames are area-averaged onto the network's grid on the GPU (ops.frames_from_native), segmented as eval.py segments,
+post-processed as the configuration says (data.temporal_vote, data.lv_keep_largest, data.lv_fill_holes), taken back to the native size
+(ops.mask_to_native) and, with data.lv_class >= 0, measured: ED / ES frames, volumes and EF per clip, beat by beat with data.lv_beats, in mL
+with a spacing.  Written: <out>/<name>/mask_XXX.png (class indices, native size) and <out>/report.json, which is also printed.
+
+    python predict.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] --out DIR INPUT... [key=value ...]"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+if __name__ == "__main__":
+    from gdkvm_amd.predict import main
+    main()

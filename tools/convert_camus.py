@@ -24,9 +24,18 @@ With --native-masks (off by default: the tree written without it is byte for byt
     untouched by any resize: the tracing as the experts drew it, which eval.py's `native` block (data.native_eval) compares the prediction
     with at the sequence's own size (CamusPng.native_target; spacing.json's "native_hw" is that size).
 
+With --native-frames (off by default) every picked frame also gets
+    <dst>/<split>/patientXXXX/<2CH|4CH>/native_frame_000.png ...   the image frame at its stored size, [H, W] uint8, by the same 255 / max
+    scaling and clipping the resized frames get, applied to the un-resized frame: what predict.py and ops.frames_from_native take
+    (CamusPng.native_frames).
+With --resample area (the default is bilinear: the tree of before) frame_XXX.png is the exact-integer area (box) average of that native
+    byte frame (the rule of gdkvm_frames_from_native in include/gdkvm.h) instead of the point-sampled bilinear resize: a tree converted this
+    way holds exactly the bytes ops.frames_from_native produces from native_frame_XXX.png, so a model trained on it sees at prediction
+    time what it saw in training.  Labels stay nearest.
+
 NIfTI-1 is read here directly (a 348-byte header + a raw array, gzip around it): no nibabel in this image.  Nothing touches a GPU.
 
-    python tools/convert_camus.py <src> <dst> [--size 256] [--frames 10] [--split train] [--native-masks]
+    python tools/convert_camus.py <src> <dst> [--size 256] [--frames 10] [--split train] [--native-masks] [--native-frames] [--resample area]
 """
 import argparse
 import glob
@@ -158,6 +167,31 @@ def resize(img: np.ndarray, size: int, nearest: bool) -> np.ndarray:
     return top * (1 - fy) + bot * fy
 
 
+def native_bytes(img: np.ndarray) -> np.ndarray:
+    """[H, W] of any dtype -> uint8 [H, W]: the scaling and clipping the resized frames get (255 / max when the maximum exceeds 255),
+    applied to the frame at its stored size."""
+    a = img.astype(np.float32)
+    hi = float(a.max()) or 1.0
+    return np.clip(a * (255.0 / hi if hi > 255.0 else 1.0), 0, 255).astype(np.uint8)
+
+
+def _area_weights(n_grid: int, n_native: int) -> np.ndarray:
+    i = np.arange(n_grid, dtype=np.int64)[:, None]
+    k = np.arange(n_native, dtype=np.int64)[None, :]
+    return np.maximum(0, np.minimum((i + 1) * n_native, (k + 1) * n_grid) - np.maximum(i * n_native, k * n_grid))
+
+
+def resize_area(v: np.ndarray, size: int) -> np.ndarray:
+    """uint8 [H, W] -> uint8 [size, size] by the exact-integer area (box) average of gdkvm_frames_from_native (include/gdkvm.h): the
+    overlap weights of the two pixel lattices, N = Wy v Wx^T in int64, q = floor((2 N + H W) / (2 H W)) -- the bytes
+    ops.frames_from_native produces from the same frame."""
+    if v.dtype != np.uint8 or v.ndim != 2:
+        raise ValueError(f"resize_area takes a uint8 [H, W] frame, got {v.dtype} {v.shape}")
+    h, w = v.shape
+    n = _area_weights(size, h) @ v.astype(np.int64) @ _area_weights(size, w).T
+    return ((2 * n + h * w) // (2 * h * w)).astype(np.uint8)
+
+
 def _splits(src: str, default: str) -> dict:
     out = {}
     for name, split in (("training", "train"), ("validation", "val"), ("testing", "test")):
@@ -178,8 +212,11 @@ class defaultdict_const(dict):
         return self.v
 
 
-def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = "train", log=print, native_masks: bool = False) -> dict:
+def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = "train", log=print, native_masks: bool = False,
+            native_frames: bool = False, resample: str = "bilinear") -> dict:
     from PIL import Image
+    if resample not in ("bilinear", "area"):
+        raise ValueError(f"resample = {resample!r} is neither 'bilinear' nor 'area'")
     splits = _splits(src, split)
     done = infos = 0
     for pdir in sorted(glob.glob(os.path.join(src, "patient*"))):
@@ -200,7 +237,14 @@ def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = 
                 a = resize(np.asarray(img[:, :, f]).T, size, False)           # stored [x, y] -> rows = y
                 m = resize(np.asarray(lab[:, :, f]).T.astype(np.int64), size, True)
                 hi = float(a.max()) or 1.0
-                Image.fromarray(np.clip(a * (255.0 / hi if hi > 255.0 else 1.0), 0, 255).astype(np.uint8)).save(os.path.join(out, f"frame_{j:03d}.png"))
+                fr = np.clip(a * (255.0 / hi if hi > 255.0 else 1.0), 0, 255).astype(np.uint8)
+                if native_frames or resample == "area":
+                    nb = native_bytes(np.asarray(img[:, :, f]).T)             # the image frame at its stored size, as bytes
+                    if resample == "area":                                    # the bytes ops.frames_from_native makes of native_frame_XXX.png
+                        fr = resize_area(nb, size)
+                    if native_frames:
+                        Image.fromarray(np.ascontiguousarray(nb)).save(os.path.join(out, f"native_frame_{j:03d}.png"))
+                Image.fromarray(fr).save(os.path.join(out, f"frame_{j:03d}.png"))
                 Image.fromarray(m.astype(np.uint8)).save(os.path.join(out, f"mask_{j:03d}.png"))
                 if native_masks:                                              # the labels as stored: no resize of any kind
                     Image.fromarray(np.ascontiguousarray(np.asarray(lab[:, :, f]).T).astype(np.uint8)).save(os.path.join(out, f"native_mask_{j:03d}.png"))
@@ -231,5 +275,8 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--split", default="train")
     ap.add_argument("--native-masks", action="store_true", help="also write every picked label frame at its own size (native_mask_XXX.png)")
+    ap.add_argument("--native-frames", action="store_true", help="also write every picked image frame at its own size as bytes (native_frame_XXX.png)")
+    ap.add_argument("--resample", choices=("bilinear", "area"), default="bilinear",
+                    help="how frame_XXX.png is made: point-sampled bilinear (the default), or the exact area average of ops.frames_from_native")
     a = ap.parse_args()
-    convert(a.src, a.dst, a.size, a.frames, a.split, native_masks=a.native_masks)
+    convert(a.src, a.dst, a.size, a.frames, a.split, native_masks=a.native_masks, native_frames=a.native_frames, resample=a.resample)

@@ -42,6 +42,11 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     CAMUS-like sizes, with a native target (out and counts, counts only, out only), beside the torch expression of the same thing (one-hot,
     F.interpolate, argmax, counts) and the byte floor: source + native out + native target bytes over the HBM rate above
     (profiles/native_probe.txt; DESIGN.md).
+(i) --native-input (this part alone): gdkvm_frames_from_native on 16 clips of 10 frames of 549 x 778 (and of mixed CAMUS-like sizes) taken to
+    256^2, three planes, bf16 (and uint8), beside F.adaptive_avg_pool2d + cast on the same data -- the nearest torch expression, NOT the
+    same rule at ratios that are no whole number (it averages the pixels a window touches with equal weights; the rule weighs them by
+    their overlap) -- and the byte floor: native bytes read plus output bytes written over the HBM rate above
+    (profiles/native_input_probe.txt; DESIGN.md).
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
     data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
     instead, and with data.lv_class=-1, alternated, twice each."""
@@ -493,6 +498,71 @@ def part_n(dev, clips, T, S, ncls, reps, n_in=2):
         print(flush=True)
 
 
+def torch_area(flat, sizes, offsets, T, S, dtype):
+    """The nearest torch expression of ops.frames_from_native: per clip F.adaptive_avg_pool2d of the float frames to S x S, rounded to bytes,
+    scaled by 1 / 255 into three planes of `dtype`.  Not the same rule at ratios that are no whole number: a window's pixels count equally."""
+    out = torch.empty((len(sizes), T, 3, S, S), dtype=dtype, device=flat.device)
+    for b, (h0, w0) in enumerate(sizes):
+        v = flat[offsets[b]:offsets[b] + T * h0 * w0].view(T, 1, h0, w0).to(torch.float32)
+        q = torch.floor(torch.nn.functional.adaptive_avg_pool2d(v, (S, S)) + 0.5)
+        out[b] = (q * (1.0 / 255.0)).expand(T, 3, S, S)
+    return out
+
+
+def part_i(dev, clips, T, S, reps, n_in=2):
+    """(i) gdkvm_frames_from_native: `clips` clips of T frames of 549 x 778 each, and of mixed CAMUS-like sizes, taken to S x S in three planes,
+    through the C symbol on preallocated outputs, beside the torch expression above in the same alternated windows and the byte floor -- the
+    native bytes read and the output written once each -- over the HBM rate this probe quotes everywhere."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    mixed = [(549, 778), (1181, 972), (843, 512), (300, 400), (487, 823), (708, 1050), (584, 439), (967, 601)]
+    for label, sizes in (("549 x 778", [(549, 778)] * clips), ("mixed sizes", [mixed[b % len(mixed)] for b in range(clips)])):
+        host = torch.tensor(sizes, dtype=torch.int32)
+        offsets, total = [], 0
+        for h0, w0 in sizes:
+            offsets.append(total)
+            total += T * h0 * w0
+        gen = torch.Generator(device=dev).manual_seed(7)
+        flats = [torch.randint(0, 256, (total,), dtype=torch.uint8, device=dev, generator=gen) for _ in range(n_in)]
+        outs = {dt: torch.empty((clips, T, 3, S, S), dtype=dt, device=dev) for dt in (torch.bfloat16, torch.uint8)}
+        code = {torch.uint8: 0, torch.bfloat16: 2}
+
+        def fn(i, dt):
+            rc = lib.gdkvm_frames_from_native(flats[i].data_ptr(), host.data_ptr(), outs[dt].data_ptr(), total, None, 0, clips, T, 3, S, S, code[dt], st)
+            assert rc == 0, lib.gdkvm_last_error()
+
+        fn(0, torch.uint8)
+        t_out = torch_area(flats[0], sizes, offsets, T, S, torch.float32)
+        torch.cuda.synchronize()
+        differ = int(((t_out * 255.0).round().to(torch.uint8) != outs[torch.uint8]).sum())
+        print(f"    ({label}: the torch expression differs from the kernel in {differ} of {outs[torch.uint8].numel()} bytes: adaptive_avg_pool2d is "
+              f"not the area rule at ratios that are no whole number)")
+        n_out = clips * T * 3 * S * S
+        forms = {
+            "frames_from_native, 3 planes bf16": (lambda i: fn(i, torch.bfloat16), CALLS, total + 2 * n_out),
+            "frames_from_native, 3 planes uint8": (lambda i: fn(i, torch.uint8), CALLS, total + n_out),
+            "torch expression (adaptive_avg_pool2d, cast), bf16": (lambda i: torch_area(flats[i], sizes, offsets, T, S, torch.bfloat16), 1, total + 2 * n_out),
+        }
+        times = {name: [] for name in forms}
+        for rep in range(reps + 3):
+            for name, (f, calls, _) in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    f(rep % n_in)
+                e1.record()
+                e1.synchronize()
+                if rep >= 3:
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / calls)
+        print(f"(i) frames_from_native, {clips} clips of {T} frames of {label} to {S}x{S}, {total / 1e6:.1f} MB of native bytes: us per call, "
+              f"windows of device events, median / minimum of {reps} windows per form (alternated, {n_in} inputs in rotation)")
+        print(f"{'form':52s} {'median us':>10s} {'min us':>9s} {'MB':>8s} {'floor us':>9s} {'x floor':>8s}")
+        for name, (_, _, nbytes) in forms.items():
+            med, floor = statistics.median(times[name]), nbytes / HBM * 1e6
+            print(f"{name:52s} {med:10.1f} {min(times[name]):9.1f} {nbytes / 1e6:8.1f} {floor:9.2f} {med / floor:8.1f}")
+        print(flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
@@ -519,6 +589,9 @@ def main():
         return
     if "--native" in sys.argv:
         part_n(dev, 2 if quick else 16, 3 if quick else 10, 256, 4, 5 if quick else 40)
+        return
+    if "--native-input" in sys.argv:
+        part_i(dev, 2 if quick else 16, 3 if quick else 10, 256, 5 if quick else 40)
         return
     if "--mm-only" in sys.argv:
         for S in (112, 256):
