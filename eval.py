@@ -281,6 +281,14 @@ def main(argv=None):
             os.makedirs(os.path.join(cfg.run_dir, "vis"), exist_ok=True)
             scale = 255 // max(cfg.data.num_classes - 1, 1)
             Image.fromarray((mask[0, 0].cpu().numpy() * scale).astype("uint8")).save(os.path.join(cfg.run_dir, "vis", f"mask_{i:05d}.png"))
+            if cfg.eval_stage.vis_overlay:
+                # clip i once more from the dataset (bytes: as_uint8; no prefetcher slot is held): plane 0 of its frames under the
+                # post-processed mask, the target's contour as reference, every frame
+                from gdkvm_amd.predict import overlay_clip
+                v_frames, v_target = ds[i]
+                pictures = overlay_clip(v_frames[:, 0].contiguous(), measured[0], cfg, reference=v_target).cpu().numpy()
+                for t, pic in enumerate(pictures):
+                    Image.fromarray(pic).save(os.path.join(cfg.run_dir, "vis", f"overlay_{i:05d}_{t:03d}.png"))
             vis_left -= 1
         i += mask.shape[0]
     if world > 1:

@@ -16,6 +16,8 @@ import yaml
 class EvalStage:
     num_vis: int = 0
     wandb_mode: str = "offline"
+    vis_overlay: bool = False        # eval.py: beside every vis/mask_XXXXX.png, vis/overlay_XXXXX_TTT.png of every frame of that clip: the
+                                     # post-processed mask over the frame, the target's contour as reference (predict.overlay_clip)
 
 
 @dataclass
@@ -97,6 +99,15 @@ class OptimCfg:
     ema_decay: float = 0.0                                         # > 0: an EMA of the weights, saved as the checkpoint's "ema" (eval.py --ema)
 
 
+@dataclass
+class OverlayCfg:
+    """How ops.overlay_native draws a mask over its frame (predict.py --overlay, eval_stage.vis_overlay)."""
+    alpha: int = 96                                                # the class tint's weight out of 256: 0 = contours only, 256 = solid
+    width: int = 2                                                 # the contour's width in pixels, 1..3
+    palette: Optional[List[List[int]]] = None                      # null (ops.OVERLAY_PALETTE) or data.num_classes entries [r, g, b] in 0..255
+    reference_palette: Optional[List[List[int]]] = None            # the same for a reference mask's contour (ops.OVERLAY_REFERENCE_PALETTE)
+
+
 OPTIM_NATIVE_ONLY = ("decay_1d", "clip_norm", "schedule", "warmup_steps", "min_lr_ratio", "poly_power", "ema_decay")
 
 
@@ -112,6 +123,7 @@ class RunConfig:
     augment: AugmentCfg = field(default_factory=AugmentCfg)
     loss: LossCfg = field(default_factory=LossCfg)
     optim: OptimCfg = field(default_factory=OptimCfg)
+    overlay: OverlayCfg = field(default_factory=OverlayCfg)
     run_dir: str = "outputs"
     save_every: int = 1000
     log_every: int = 20
@@ -202,7 +214,28 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
                 or len(set(bc)) != len(bc):
             raise ValueError(f"loss.boundary_classes = {bc!r}: null (every class but 0) or distinct integers in 0..{cfg.data.num_classes - 1}")
     _check_optim(cfg.optim)
+    if not isinstance(cfg.eval_stage.vis_overlay, bool):
+        raise ValueError(f"eval_stage.vis_overlay = {cfg.eval_stage.vis_overlay!r}: true or false")
+    if cfg.eval_stage.vis_overlay and not 2 <= d.num_classes <= 8:
+        raise ValueError(f"eval_stage.vis_overlay: ops.overlay_native draws 2..8 classes, data.num_classes = {d.num_classes}")
+    _check_overlay(cfg.overlay, d.num_classes)
     return cfg
+
+
+def _check_overlay(o: OverlayCfg, num_classes: int) -> None:
+    if isinstance(o.alpha, bool) or not isinstance(o.alpha, int) or not 0 <= o.alpha <= 256:
+        raise ValueError(f"overlay.alpha = {o.alpha!r}: an integer in 0..256 (the tint's weight out of 256)")
+    if isinstance(o.width, bool) or not isinstance(o.width, int) or not 1 <= o.width <= 3:
+        raise ValueError(f"overlay.width = {o.width!r}: an integer in 1..3 (the contour's width in pixels)")
+    for key in ("palette", "reference_palette"):
+        pal = getattr(o, key)
+        if pal is None:
+            continue
+        if not isinstance(pal, list) or any(not isinstance(c, list) or len(c) != 3 or any(isinstance(v, bool) or not isinstance(v, int)
+                                                                                           or not 0 <= v <= 255 for v in c) for c in pal):
+            raise ValueError(f"overlay.{key} = {pal!r}: null or a list of [r, g, b], integers in 0..255")
+        if len(pal) != num_classes:
+            raise ValueError(f"overlay.{key} has {len(pal)} colours, data.num_classes = {num_classes}: one [r, g, b] per class")
 
 
 def beat_prominence_permille(cfg: RunConfig) -> int:

@@ -139,6 +139,8 @@ SIGNATURES = {
     "gdkvm_mask_to_native": (_i, [_vp] * 5 + [_sz, _vp, _sz] + [_i] * 5 + [_vp]),
     "gdkvm_frames_from_native_workspace_bytes": (_sz, [_i] * 6),
     "gdkvm_frames_from_native": (_i, [_vp] * 3 + [_sz, _vp, _sz] + [_i] * 6 + [_vp]),
+    "gdkvm_overlay_native_workspace_bytes": (_sz, [_i] * 4),
+    "gdkvm_overlay_native": (_i, [_vp] * 7 + [_sz, _vp, _sz] + [_i] * 5 + [_vp]),
     "gdkvm_surface_distance_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_surface_distance_mm_workspace_bytes": (_sz, [_i] * 3),
@@ -2623,6 +2625,147 @@ def frames_from_native(flat: torch.Tensor, sizes, T: int, grid=None, channels: i
     ws = _workspace("gdkvm_frames_from_native_workspace_bytes", dev, clips, T, channels, H, W, _FRAMES_DTYPES[dtype], floor=16)
     _call("gdkvm_frames_from_native", dev, flat, host, out, total, _Ws(ws), clips, T, channels, H, W, _FRAMES_DTYPES[dtype])
     return out, offsets
+
+
+# GDKVM_OVERLAY_NATIVE_*: the launch geometry of overlay_native, for tests that want shapes on both sides of it
+OVERLAY_NATIVE_RUN, OVERLAY_NATIVE_BAND_RUNS, OVERLAY_NATIVE_BAND_ROWS, OVERLAY_NATIVE_MAX_WG, OVERLAY_NATIVE_CLIPS = 16, 512, 64, 4096, 64
+OVERLAY_MAX_WIDTH = 3
+# The default colours (R, G, B) of the classes 0..7; class 0 is never drawn.  The prediction's are saturated and far apart, the reference's
+# near white, so that a tracing reads as "the light line" whatever class it belongs to.
+OVERLAY_PALETTE = ((0, 0, 0), (255, 48, 48), (48, 220, 48), (64, 128, 255), (255, 200, 0), (255, 0, 255), (0, 230, 230), (255, 128, 0))
+OVERLAY_REFERENCE_PALETTE = ((0, 0, 0), (255, 255, 255), (255, 255, 190), (200, 255, 255), (255, 215, 255), (225, 225, 225), (215, 255, 215),
+                             (255, 235, 215))
+
+
+def _overlay_palette(what: str, name: str, pal, ncls: int, default) -> torch.Tensor:
+    """A palette as a HOST uint8 tensor [ncls, 3]: None is the first ncls colours of `default`; otherwise ncls entries (r, g, b) of integers
+    in 0..255, a sequence or a CPU integer tensor.  A device tensor is refused: the colours travel in the kernel arguments."""
+    if pal is None:
+        pal = default[:ncls]
+    if isinstance(pal, torch.Tensor):
+        if pal.device.type != "cpu":
+            raise GdkvmError(f"{what}: {name} must be host values (a sequence of (r, g, b) or a CPU tensor [num_classes, 3]): the colours are "
+                             "validated and handed to the kernel by value")
+        if torch.is_floating_point(pal) or pal.dtype == torch.bool:
+            raise GdkvmError(f"{what}: {name} must hold integers, got {pal.dtype}")
+        pal = pal.tolist()
+    try:
+        rows = [tuple(r) for r in pal]
+    except TypeError:
+        raise GdkvmError(f"{what}: {name} must be a sequence of (r, g, b) or a CPU tensor [num_classes, 3], got {type(pal).__name__}") from None
+    if len(rows) != ncls:
+        raise GdkvmError(f"{what}: {name} has {len(rows)} colours for {ncls} classes")
+    for k, r in enumerate(rows):
+        if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for v in r):
+            raise GdkvmError(f"{what}: {name}[{k}] = {r!r} is no (r, g, b) of integers in 0..255")
+    return torch.tensor(rows, dtype=torch.uint8).reshape(ncls, 3)
+
+
+def _overlay_contour_host(m: torch.Tensor, ncls: int, width: int) -> torch.Tensor:
+    """The rule's contour pixels of the frames m [T, h0, w0] (uint8, CPU): bool [T, h0, w0].  The frame is padded with class 0, which differs
+    from every class byte, as the outside of the frame does."""
+    T, h0, w0 = m.shape
+    p = torch.zeros((T, h0 + 2 * width, w0 + 2 * width), dtype=torch.uint8)
+    p[:, width:width + h0, width:width + w0] = m
+    same = torch.ones(m.shape, dtype=torch.bool)
+    for dy in range(-width, width + 1):
+        r = width - abs(dy)
+        for dx in range(-r, r + 1):
+            same &= p[:, width + dy:width + dy + h0, width + dx:width + dx + w0] == m
+    return (m >= 1) & (m < ncls) & ~same
+
+
+def _overlay_native_host(g, m, r, ncls: int, width: int, alpha: int, pal, rpal) -> torch.Tensor:
+    """The rule of gdkvm_overlay_native for the frames g, m (and r or None) [T, h0, w0] (uint8, CPU) of one clip, in int64: uint8 [T, h0, w0, 3]"""
+    g3 = g.to(torch.int64)[..., None].expand(g.shape + (3,))
+    cls = (m >= 1) & (m < ncls)
+    k = torch.where(cls, m, torch.zeros_like(m)).to(torch.int64)
+    colour = pal.to(torch.int64)[k]
+    out = torch.where(cls[..., None], (g3 * (256 - alpha) + colour * alpha + 128) >> 8, g3)
+    if r is not None:
+        on_r = _overlay_contour_host(r, ncls, width)
+        kr = torch.where(on_r, r, torch.zeros_like(r)).to(torch.int64)
+        out = torch.where(on_r[..., None], rpal.to(torch.int64)[kr], out)
+    out = torch.where(_overlay_contour_host(m, ncls, width)[..., None], colour, out)
+    return out.to(torch.uint8)
+
+
+def overlay_native(grey: torch.Tensor, mask: torch.Tensor, sizes, T: int, num_classes: int, reference: Optional[torch.Tensor] = None,
+                   width: int = 2, alpha: int = 96, palette=None, reference_palette=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gdkvm_overlay_native: the picture of a segmentation at every clip's own frame size -- the grey frame, the mask's classes tinted
+    (alpha / 256 of the class colour; 0 draws contours only, 256 paints the class solid), the mask's contour opaque in the class colour and,
+    with `reference`, that mask's contour in the reference colours where the mask's own contour does not cover it.  A contour pixel of a
+    mask holds a class byte k (1 <= k < num_classes, 2..8) and has a pixel within the 4-neighbour distance `width` (1..3) that holds another
+    byte or lies outside the frame (definition: include/gdkvm.h).  grey, mask and reference are RAGGED flat uint8 tensors, clip b's T frames
+    of h0 w0 bytes in turn (pack_native builds one, mask_to_native returns one, native_frames views one clip); sizes the clips' native
+    (h0, w0), each in 1..2048, HOST integers (a device tensor is refused), and so are the palettes: num_classes entries (r, g, b), None for
+    OVERLAY_PALETTE / OVERLAY_REFERENCE_PALETTE.  Returns the flat uint8 RGB buffer, three bytes per pixel in the same order
+    (native_rgb_frames views one clip of it as [T, h0, w0, 3]); `out`: a flat uint8 tensor of at least three times the pixels to write
+    into, overlapping no input.  CPU tensors take the same rule in torch integers, so the wrapper works without a GPU."""
+    what = "overlay_native"
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 8:
+        raise GdkvmError(f"{what}: num_classes = {num_classes!r} must be an integer in 2..8")
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= OVERLAY_MAX_WIDTH:
+        raise GdkvmError(f"{what}: width = {width!r} must be an integer in 1..{OVERLAY_MAX_WIDTH}")
+    if isinstance(alpha, bool) or not isinstance(alpha, int) or not 0 <= alpha <= 256:
+        raise GdkvmError(f"{what}: alpha = {alpha!r} must be an integer in 0..256")
+    sz = _native_sizes(what, sizes)
+    clips = len(sz)
+    offsets, total = _native_offsets(sz, T)
+    pal = _overlay_palette(what, "palette", palette, num_classes, OVERLAY_PALETTE)
+    rpal = _overlay_palette(what, "reference_palette", reference_palette, num_classes, OVERLAY_REFERENCE_PALETTE)
+    if not isinstance(grey, torch.Tensor):
+        raise GdkvmError(f"{what}: grey must be a flat uint8 tensor, got {type(grey).__name__}")
+    for name, t, n in (("grey", grey, total), ("mask", mask, total), ("reference", reference, total), ("out", out, 3 * total)):
+        if name in ("reference", "out") and t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < n:
+            raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {n} bytes (the clips' T h0 w0 in turn"
+                             f"{', three bytes per pixel' if name == 'out' else ''}), got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+        if t.device != grey.device:
+            raise GdkvmError("tensors on different devices")
+        if not t.is_contiguous():
+            raise GdkvmError("GDKVM ops need contiguous tensors")
+    if out is None:
+        out = torch.empty(3 * total, dtype=torch.uint8, device=grey.device)
+    for name, t in (("grey", grey), ("mask", mask), ("reference", reference)):
+        if t is not None and total and out.data_ptr() < t.data_ptr() + total and t.data_ptr() < out.data_ptr() + 3 * total:
+            raise GdkvmError(f"{what}: out must not overlap {name}")
+    if clips == 0:
+        return out
+    if not grey.is_cuda:
+        # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
+        for b, (h0, w0) in enumerate(sz):
+            lo, hi = offsets[b], offsets[b] + T * h0 * w0
+            r = None if reference is None else reference[lo:hi].view(T, h0, w0)
+            o = _overlay_native_host(grey[lo:hi].view(T, h0, w0), mask[lo:hi].view(T, h0, w0), r, num_classes, width, alpha, pal, rpal)
+            out[3 * lo:3 * hi] = o.reshape(-1)
+        return out
+    dev = _dev(grey, mask, reference, out)
+    host = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
+    # (allocated per call like every workspace of this module; the kernel asks for none today)
+    ws = _workspace("gdkvm_overlay_native_workspace_bytes", dev, clips, T, num_classes, width, floor=16)
+    _call("gdkvm_overlay_native", dev, grey, mask, reference, host, pal, rpal if reference is not None else None, out, total, _Ws(ws),
+          clips, T, num_classes, width, alpha)
+    return out
+
+
+def native_rgb_frames(flat: torch.Tensor, sizes, T: int, b: int) -> torch.Tensor:
+    """Clip b of a ragged native RGB buffer (overlay_native's result) as a [T, h0, w0, 3] view: native_frames with three bytes per pixel."""
+    sz = _native_sizes("native_rgb_frames", sizes)
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"native_rgb_frames: T = {T!r} must be an integer >= 1")
+    if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < len(sz):
+        raise GdkvmError(f"native_rgb_frames: clip {b!r} is none of the {len(sz)} clips")
+    offsets, total = _native_offsets(sz, T)
+    if not isinstance(flat, torch.Tensor) or flat.dim() != 1 or flat.numel() < 3 * total:
+        raise GdkvmError(f"native_rgb_frames: flat must be a 1-D tensor of at least {3 * total} elements, got "
+                         f"{tuple(getattr(flat, 'shape', ()))}")
+    h0, w0 = sz[b]
+    return flat[3 * offsets[b]:3 * (offsets[b] + T * h0 * w0)].view(T, h0, w0, 3)
 
 
 def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:

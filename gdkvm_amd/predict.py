@@ -12,7 +12,10 @@ size) through
 and, with data.lv_class >= 0, measures the class on the grid per clip: ops.lv_measure / lv_ef (pixel^3; EF is a ratio), ops.lv_beats with
 data.lv_beats, and with a native pixel spacing (row_um, col_um) ops.lv_measure_mm at the grid spacing (rint(row_um h0 / H),
 rint(col_um w0 / W)) -- tools/convert_camus.py's spacing_um formula; the mL keys are left out, with the reason, when that falls outside
-1..4095.  Everything after the copy runs on the device: there is no CPU path for the forward, and a CPU model is refused.
+1..4095.  With overlay=True it also draws what a person looks at, ops.overlay_native of the native frames under those native masks (the
+configuration's `overlay:` section); overlay_clip draws one clip with an optional reference mask, which is what eval.py's
+eval_stage.vis_overlay writes.  Everything after the copy runs on the device: there is no CPU path for the forward, and a CPU model is
+refused.
 
 load_input reads what predict.py's command line names: a .npy file ([T, h0, w0] uint8), a .npz file (`frames`, optional `spacing_um` =
 the NATIVE micrometres per pixel) or a directory of native_frame_*.png (else frame_*.png), where a spacing.json with "native_hw" (the
@@ -52,11 +55,36 @@ def make_runner(model):
     return SegmentRunner(model, graph=os.environ.get("GDKVM_FWD_GRAPH", "1") != "0", in_flight=int(os.environ.get("GDKVM_FWD_IN_FLIGHT", "2")))
 
 
-def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, runner=None) -> dict:
+def _overlay_args(cfg) -> dict:
+    """The `overlay:` section of the configuration as ops.overlay_native's keyword arguments"""
+    o = cfg.overlay
+    return dict(width=o.width, alpha=o.alpha, palette=o.palette, reference_palette=o.reference_palette)
+
+
+def overlay_clip(frames_u8: torch.Tensor, mask: torch.Tensor, cfg, reference: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One clip's overlay pictures, uint8 [T, h, w, 3] on the mask's device: frames_u8 [T, h, w] uint8 grey frames, mask [T, h, w] uint8
+    labels and optionally a reference mask of that shape whose contour is drawn too (eval.py: the target), through ops.overlay_native with the
+    configuration's `overlay:` section and data.num_classes.  frames_u8 and reference may live on the host: they are copied to the mask's
+    device."""
+    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 3 for t in (frames_u8, mask)) \
+            or frames_u8.shape != mask.shape or (reference is not None and (not isinstance(reference, torch.Tensor) or reference.dtype != torch.uint8
+                                                                            or reference.shape != mask.shape)):
+        raise ops.GdkvmError("overlay_clip: frames_u8, mask and reference must be uint8 [T, h, w] tensors of one shape")
+    T, h, w = (int(n) for n in mask.shape)
+    dev = mask.device
+    flat = lambda t: t.to(dev).contiguous().reshape(-1)
+    rgb = ops.overlay_native(flat(frames_u8), flat(mask), [(h, w)], T, cfg.data.num_classes,
+                             reference=None if reference is None else flat(reference), **_overlay_args(cfg))
+    return ops.native_rgb_frames(rgb, [(h, w)], T, 0)
+
+
+def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, runner=None, overlay: bool = False) -> dict:
     """See the module's head.  clips: uint8 [T, h0, w0] tensors with one T (host or device); spacing_um: None or, per clip, None or the native
     (row_um, col_um); runner: make_runner(model) kept by the caller over several calls (None: one is made for this call).  Returns
     {"masks": [uint8 [T, h0, w0] per clip, on the model's device], "grid_mask": uint8 [clips, T, H, W] (post-processed), "frames": the
-    network's input [clips, T, 3, H, W], "sizes": [(h0, w0), ...], "report": {"clips", "frames", "grid", "forward", "per_clip": [...]}}."""
+    network's input [clips, T, 3, H, W], "sizes": [(h0, w0), ...], "report": {"clips", "frames", "grid", "forward", "per_clip": [...]}}.
+    overlay=True keeps the device copy of the packed native bytes and adds "overlay": [uint8 [T, h0, w0, 3] per clip], ops.overlay_native of
+    the native frames and the post-processed native masks with the configuration's `overlay:` section (no reference)."""
     clips = list(clips)
     flat, sizes = ops.pack_native([c.cpu() if isinstance(c, torch.Tensor) and c.is_cuda else c for c in clips])
     T = int(clips[0].shape[0])
@@ -70,7 +98,8 @@ def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, r
     H = W = int(d.size)
     ncls, lv_cls = d.num_classes, d.lv_class
     fdt = torch.bfloat16 if cfg.precision == "bf16" else torch.float32
-    frames, _ = ops.frames_from_native(flat.to(dev), sizes, T, grid=(H, W), channels=3, dtype=fdt)
+    flat_dev = flat.to(dev)
+    frames, _ = ops.frames_from_native(flat_dev, sizes, T, grid=(H, W), channels=3, dtype=fdt)
     if runner is None:
         runner = make_runner(model)
     mask, _ = runner(frames, None)
@@ -90,6 +119,10 @@ def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, r
         post["fill_holes"] = fh
     native, _, _ = ops.mask_to_native(measured, sizes, ncls, want_out=True)
     masks = [ops.native_frames(native, sizes, T, b) for b in range(B)]
+    pictures = None
+    if overlay:
+        rgb = ops.overlay_native(flat_dev, native, sizes, T, ncls, **_overlay_args(cfg))
+        pictures = [ops.native_rgb_frames(rgb, sizes, T, b) for b in range(B)]
     r5 = lambda v: round(float(v), 5)
     per_clip = [{"native_hw": [h0, w0]} for h0, w0 in sizes]
     if vote:
@@ -138,7 +171,10 @@ def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, r
                                         "ef_mean": r5(bs[0]), "ef_min": r5(bs[1]), "ef_max": r5(bs[2]), "mean_cycle_frames": r5(bs[3])}
     report = {"clips": B, "frames": T, "grid": [H, W], "forward": {"graph_replays": runner.replays, "eager_calls": runner.eager_calls},
               "per_clip": per_clip}
-    return {"masks": masks, "grid_mask": measured, "frames": frames, "sizes": sizes, "report": report}
+    res = {"masks": masks, "grid_mask": measured, "frames": frames, "sizes": sizes, "report": report}
+    if overlay:
+        res["overlay"] = pictures
+    return res
 
 
 def _grey(path: str) -> np.ndarray:
@@ -224,6 +260,9 @@ def main(argv=None) -> dict:
     ap.add_argument("--weights", default="")
     ap.add_argument("--ema", action="store_true", help="use the checkpoint's EMA weights (optim.ema_decay > 0 runs)")
     ap.add_argument("--out", required=True, help="directory for <name>/mask_XXX.png and report.json")
+    ap.add_argument("--overlay", action="store_true",
+                    help="also write <name>/overlay_XXX.png: the frame in grey, the predicted classes tinted, their contours opaque "
+                         "(the configuration's overlay: section)")
     ap.add_argument("inputs", nargs="+", metavar="INPUT|key=value",
                     help=".npy / .npz clips or directories of PNG frames; arguments of the form key=value that name no file override the configuration")
     args = ap.parse_args(argv)
@@ -251,12 +290,15 @@ def main(argv=None) -> dict:
     for T, ks in by_T.items():
         for lo in range(0, len(ks), max(1, cfg.batch_size)):
             part = ks[lo:lo + max(1, cfg.batch_size)]
-            res = segment_native(model, cfg, [loaded[k][2] for k in part], [loaded[k][3] for k in part], runner=runner)
-            for k, m, rep in zip(part, res["masks"], res["report"]["per_clip"]):
+            res = segment_native(model, cfg, [loaded[k][2] for k in part], [loaded[k][3] for k in part], runner=runner, overlay=args.overlay)
+            for j, (k, m, rep) in enumerate(zip(part, res["masks"], res["report"]["per_clip"])):
                 name = loaded[k][0]
                 os.makedirs(os.path.join(args.out, name), exist_ok=True)
                 for t, fr in enumerate(m.cpu().numpy()):
                     Image.fromarray(fr).save(os.path.join(args.out, name, f"mask_{t:03d}.png"))
+                if args.overlay:
+                    for t, fr in enumerate(res["overlay"][j].cpu().numpy()):
+                        Image.fromarray(fr).save(os.path.join(args.out, name, f"overlay_{t:03d}.png"))
                 entries[k] = {"name": name, "input": loaded[k][1], "frames": T, **rep}
     report = {"clips": len(loaded), "grid": [cfg.data.size, cfg.data.size], "weights": args.weights, "ema": bool(args.ema),
               "forward": {"graph_replays": runner.replays, "eager_calls": runner.eager_calls}, "per_clip": entries}

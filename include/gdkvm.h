@@ -911,6 +911,53 @@ size_t gdkvm_frames_from_native_workspace_bytes(int clips, int T, int C, int H, 
 int gdkvm_frames_from_native(const uint8_t* native, const int32_t* sizes, void* out, size_t native_bytes, void* workspace,
                              size_t workspace_bytes, int clips, int T, int C, int H, int W, int out_dtype, void* stream);
 
+/* Draw a mask, its contour and optionally a second mask's contour over grey frames at each clip's NATIVE size: the picture a person looks at
+ * (predict.py --overlay, eval.py's eval_stage.vis_overlay; csrc/overlay_native.hip).  Every output byte is a function of integers that
+ * depends on neither the algorithm nor the schedule.
+ * Per native frame of clip b, (h0, w0) = sizes[b], each in 1..2048: grey [h0, w0] uint8, mask [h0, w0] uint8, optionally ref [h0, w0]
+ * uint8; ncls in 2..8, a contour width w in 1..3, alpha in 0..256, and two palettes pal [ncls][3], ref_pal [ncls][3] of bytes (R, G, B).
+ *   1. A byte k is a CLASS BYTE when 1 <= k < ncls.  Class 0, the bytes >= ncls and 255 are never drawn.
+ *   2. Pixel (y, x) with the class byte k is a CONTOUR PIXEL of a mask when some (dy, dx) with |dy| + |dx| <= w has (y + dy, x + dx)
+ *      outside the frame, or holding a byte != k (any other byte counts as different, 255 included).  That is the class minus its
+ *      4-neighbour erosion iterated w times with the outside of the frame as background; with w = 1 it is gdkvm_surface_distance's surface.
+ *   3. out [h0, w0, 3] uint8, interleaved RGB; the FIRST case that applies decides the pixel, with g = grey[y][x]:
+ *        a. a contour pixel of mask with the byte k:              pal[k]
+ *        b. with a ref, a contour pixel of ref with the byte k':  ref_pal[k']
+ *        c. mask holds a class byte k:                            channel c = (g (256 - alpha) + pal[k][c] alpha + 128) >> 8
+ *        d. otherwise:                                            (g, g, g)
+ * So alpha = 0 draws contours only, alpha = 256 paints the class solid, and a mask without class bytes returns the grey frame in three
+ * channels.
+ * grey, mask and ref are RAGGED, the layout of gdkvm_mask_to_native's out / target: clip b's T frames of h0 w0 bytes follow each other, and
+ * clip b + 1 follows clip b.  out is ragged the same way with three bytes per pixel: a frame's first byte is three times its pixel offset.
+ * Frames start at ANY byte address.  native_bytes = the pixel bytes each input holds (out holds 3 native_bytes); it must cover the sum over
+ * the clips of T h0 w0.  out overlaps no input.  ref is optional (NULL), ref_pal is required with it.
+ * sizes (int32 [clips, 2]), pal and ref_pal are HOST arrays: the entry validates every value, computes every clip's offset and band geometry
+ * itself and hands them and the packed palettes to the kernel by value in the kernel arguments, GDKVM_OVERLAY_NATIVE_CLIPS clips per
+ * launch, longer batches in several launches; nothing is copied to the device, nothing allocated, nothing synchronised (a capture holds
+ * the sizes and the colours).
+ * gdkvm_overlay_native_workspace_bytes is 0 for every shape and the workspace may be NULL; the pair is there so that a caller treats every
+ * kernel of this family alike.  Bit-reproducible: no atomics, no floating point, one writer per output byte.  Bad arguments (clips < 0,
+ * T < 1, null grey, mask, sizes, pal or out, ref without ref_pal, a size outside 1..2048, ncls outside 2..8, width outside 1..3, alpha
+ * outside 0..256, native_bytes short of the sum, out overlapping an input, clips * T > 2^30) are GDKVM_ERR_SHAPE before any device call;
+ * clips == 0 is GDKVM_OK without a launch.
+ * Launch geometry, for tests that want shapes on both sides of it: a workgroup owns a band of whole native rows of one (clip, frame):
+ * floor(GDKVM_OVERLAY_NATIVE_BAND_RUNS / (1 + ceil(w0 / GDKVM_OVERLAY_NATIVE_RUN))) rows -- the most whose
+ * run slots, a head and ceil(w0 / 16) runs per row, give a lane at most two -- at least 1, at most GDKVM_OVERLAY_NATIVE_BAND_ROWS, and keeps the band's rows of
+ * mask and ref with w rows above and below in LDS (rows outside the frame and the columns beside it are zeros there: class 0).  Every row
+ * is cut into runs of GDKVM_OVERLAY_NATIVE_RUN pixels on the 16-byte grid of the ADDRESSES of out (a head of up to 15 pixels, runs of three
+ * 16-byte stores, a ragged tail; heads, tails and misaligned inputs take byte accesses); a launch has at most
+ * GDKVM_OVERLAY_NATIVE_MAX_WG workgroups, which take further (clip, frame, band) items in a grid-stride loop; one kernel per width, with
+ * and without a ref. */
+#define GDKVM_OVERLAY_NATIVE_RUN 16
+#define GDKVM_OVERLAY_NATIVE_BAND_RUNS 512
+#define GDKVM_OVERLAY_NATIVE_BAND_ROWS 64
+#define GDKVM_OVERLAY_NATIVE_MAX_WG 4096
+#define GDKVM_OVERLAY_NATIVE_CLIPS 64
+size_t gdkvm_overlay_native_workspace_bytes(int clips, int T, int ncls, int width);
+int gdkvm_overlay_native(const uint8_t* grey, const uint8_t* mask, const uint8_t* ref, const int32_t* sizes, const uint8_t* pal,
+                         const uint8_t* ref_pal, uint8_t* out, size_t native_bytes, void* workspace, size_t workspace_bytes, int clips,
+                         int T, int ncls, int width, int alpha, void* stream);
+
 /* Surface distances between one class of a predicted mask and of its target (what HD, HD95 and ASSD are made of; csrc/surface_distance.hip).
  * Every output is an integer that depends on neither the algorithm nor the schedule; the three floating-point metrics are a few lines on top
  * (gdkvm_amd.ops.surface_metrics) and not part of this ABI.  Distances are in pixels of the masks' grid (isotropic pixels assumed).

@@ -6,9 +6,11 @@ columns) or a directory of native_frame_*.png / frame_*.png (tools/convert_camus
 native pixel).  The frames are area-averaged onto the network's grid on the GPU (ops.frames_from_native), segmented as eval.py segments,
 post-processed as the configuration says (data.temporal_vote, data.lv_keep_largest, data.lv_fill_holes), taken back to the native size
 (ops.mask_to_native) and, with data.lv_class >= 0, measured: ED / ES frames, volumes and EF per clip, beat by beat with data.lv_beats, in mL
-with a spacing.  Written: <out>/<name>/mask_XXX.png (class indices, native size) and <out>/report.json, which is also printed.
+with a spacing.  Written: <out>/<name>/mask_XXX.png (class indices, native size) and <out>/report.json, which is also printed; with --overlay also
+<out>/<name>/overlay_XXX.png, the picture to look at: the native frame in grey, the predicted classes tinted and their contours opaque
+(ops.overlay_native on the GPU; colours, tint and contour width: the configuration's overlay: section).
 
-    python predict.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] --out DIR INPUT... [key=value ...]"""
+    python predict.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [--overlay] --out DIR INPUT... [key=value ...]"""
 import os
 import sys
 

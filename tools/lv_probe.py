@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -47,6 +47,10 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     same rule at ratios that are no whole number (it averages the pixels a window touches with equal weights; the rule weighs them by
     their overlap) -- and the byte floor: native bytes read plus output bytes written over the HBM rate above
     (profiles/native_input_probe.txt; DESIGN.md).
+(o) --overlay (this part alone): gdkvm_overlay_native on 16 clips of 10 frames of 549 x 778 (and of mixed CAMUS-like sizes), ventricle-like
+    masks of 4 classes, with and without a reference mask, at contour widths 1 and 3, beside the torch expression of the same rule on the
+    same device tensors (padded shifts compared, palettes gathered, torch.where; the probe first checks that it draws the kernel's bytes)
+    and the byte floor: 2 or 3 bytes read and 3 written per pixel over the HBM rate above (profiles/overlay_probe.txt).
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
     data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
     instead, and with data.lv_class=-1, alternated, twice each."""
@@ -563,6 +567,113 @@ def part_i(dev, clips, T, S, reps, n_in=2):
         print(flush=True)
 
 
+def torch_overlay(grey, mask, ref, sizes, offsets, T, ncls, width, alpha, pal, rpal):
+    """ops.overlay_native as a plain torch expression on the device (the yardstick): per clip the 2 w (w + 1) shifted compares of the
+    zero-padded masks, the palettes gathered by class, the integer blend and three torch.where in the rule's order."""
+    out = torch.empty(3 * grey.numel(), dtype=torch.uint8, device=grey.device)
+
+    def contour(m):
+        h0, w0 = m.shape[1:]
+        p = torch.nn.functional.pad(m, (width, width, width, width))
+        same = torch.ones_like(m, dtype=torch.bool)
+        for dy in range(-width, width + 1):
+            r = width - abs(dy)
+            for dx in range(-r, r + 1):
+                if dy or dx:
+                    same &= p[:, width + dy:width + dy + h0, width + dx:width + dx + w0] == m
+        return (m >= 1) & (m < ncls) & ~same
+
+    for b, (h0, w0) in enumerate(sizes):
+        sl = slice(offsets[b], offsets[b] + T * h0 * w0)
+        g, m = grey[sl].view(T, h0, w0), mask[sl].view(T, h0, w0)
+        g3 = g.to(torch.int32)[..., None].expand(T, h0, w0, 3)
+        cls = (m >= 1) & (m < ncls)
+        colour = pal[torch.where(cls, m, torch.zeros_like(m)).long()]
+        o = torch.where(cls[..., None], (g3 * (256 - alpha) + colour * alpha + 128) >> 8, g3)
+        if ref is not None:
+            r = ref[sl].view(T, h0, w0)
+            on_r = contour(r)
+            o = torch.where(on_r[..., None], rpal[torch.where(on_r, r, torch.zeros_like(r)).long()], o)
+        o = torch.where(contour(m)[..., None], colour, o)
+        out[3 * sl.start:3 * sl.stop] = o.to(torch.uint8).reshape(-1)
+    return out
+
+
+def part_o(dev, clips, T, S, ncls, reps, n_in=2):
+    """(o) gdkvm_overlay_native: `clips` clips of T frames of 549 x 778 each, and of mixed CAMUS-like sizes -- random grey bytes under
+    ventricle-like masks (drifting ellipses drawn at S x S, voted and taken to the native size by ops.mask_to_native; the reference is the
+    next input's mask, so the two contours lie close) -- through the C symbol on a preallocated out, with and without the reference, at
+    contour widths 1 and 3, beside the torch expression of the same rule in the same alternated windows and the byte floor: grey, mask and
+    reference read and three bytes per pixel written once each over the HBM rate this probe quotes everywhere.  The kernel writes a
+    preallocated out; the torch expression allocates its result and its intermediates inside its timed window, as a plain torch expression
+    does, and `x torch` is the ratio to that."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    alpha = 96
+    pal_h = torch.tensor(ops.OVERLAY_PALETTE[:ncls], dtype=torch.uint8)
+    rpal_h = torch.tensor(ops.OVERLAY_REFERENCE_PALETTE[:ncls], dtype=torch.uint8)
+    pal_d, rpal_d = pal_h.to(dev).to(torch.int32), rpal_h.to(dev).to(torch.int32)
+    mixed = [(549, 778), (1181, 972), (843, 512), (300, 400), (487, 823), (708, 1050), (584, 439), (967, 601)]
+    for label, sizes in (("549 x 778", [(549, 778)] * clips), ("mixed sizes", [mixed[b % len(mixed)] for b in range(clips)])):
+        host = torch.tensor(sizes, dtype=torch.int32)
+        offsets, total = [], 0
+        for h0, w0 in sizes:
+            offsets.append(total)
+            total += T * h0 * w0
+        grid = [drifting_masks(clips, T, S, ncls, s, dev) for s in range(n_in)]
+        masks = [ops.mask_to_native(ops.temporal_vote(m, ncls, 2)[0], sizes, ncls)[0] for m in grid]
+        gen = torch.Generator(device=dev).manual_seed(11)
+        greys = [torch.randint(0, 256, (total,), dtype=torch.uint8, device=dev, generator=gen) for _ in range(n_in)]
+        out = torch.empty(3 * total, dtype=torch.uint8, device=dev)
+        drawn = sum(int(((m >= 1) & (m < ncls)).sum()) for m in masks) / (n_in * total)
+
+        def ov(i, width, ref):
+            rc = lib.gdkvm_overlay_native(greys[i].data_ptr(), masks[i].data_ptr(), masks[(i + 1) % n_in].data_ptr() if ref else None,
+                                          host.data_ptr(), pal_h.data_ptr(), rpal_h.data_ptr(), out.data_ptr(), total, None, 0, clips, T, ncls,
+                                          width, alpha, st)
+            assert rc == 0, lib.gdkvm_last_error()
+
+        def tov(i, width, ref):
+            return torch_overlay(greys[i], masks[i], masks[(i + 1) % n_in] if ref else None, sizes, offsets, T, ncls, width, alpha, pal_d, rpal_d)
+
+        for width, ref in ((1, False), (3, True)):
+            ov(0, width, ref)
+            differ = int((tov(0, width, ref) != out).sum())
+            torch.cuda.synchronize()
+            if differ:                                             # no table from a yardstick that draws something else
+                raise SystemExit(f"lv_probe --overlay: the torch expression differs from the kernel in {differ} of {3 * total} bytes "
+                                 f"({label}, width {width}, {'with' if ref else 'no'} reference)")
+            print(f"    ({label}, width {width}, {'with' if ref else 'no'} reference: the torch expression differs from the kernel in {differ} of "
+                  f"{3 * total} bytes)")
+        forms = {}
+        for ref in (False, True):
+            for width in (1, 3):
+                tag = f"width {width}, {'reference' if ref else 'no reference'}"
+                nbytes = (3 if ref else 2) * total + 3 * total
+                forms["overlay_native, " + tag] = (lambda i, w=width, r=ref: ov(i, w, r), CALLS, nbytes)
+                forms["torch expression, " + tag] = (lambda i, w=width, r=ref: tov(i, w, r), 1, nbytes)
+        times = {name: [] for name in forms}
+        for rep in range(reps + 3):
+            for name, (fn, calls, _) in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    fn(rep % n_in)
+                e1.record()
+                e1.synchronize()
+                if rep >= 3:
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / calls)
+        print(f"(o) overlay_native, {clips} clips of {T} frames of {label}, {ncls} classes, {total / 1e6:.1f} MB of native pixels, {100 * drawn:.1f} % "
+              f"of them of a drawn class: us per call, windows of device events, median / minimum of {reps} windows per form (alternated, "
+              f"{n_in} inputs in rotation)")
+        print(f"{'form':52s} {'median us':>10s} {'min us':>9s} {'MB':>8s} {'floor us':>9s} {'x floor':>8s} {'x torch':>8s}")
+        for name, (_, _, nbytes) in forms.items():
+            med, floor = statistics.median(times[name]), nbytes / HBM * 1e6
+            ref_t = statistics.median(times[name.replace("overlay_native", "torch expression")])
+            print(f"{name:52s} {med:10.1f} {min(times[name]):9.1f} {nbytes / 1e6:8.1f} {floor:9.2f} {med / floor:8.1f} {med / ref_t:8.3f}")
+        print(flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
@@ -592,6 +703,9 @@ def main():
         return
     if "--native-input" in sys.argv:
         part_i(dev, 2 if quick else 16, 3 if quick else 10, 256, 5 if quick else 40)
+        return
+    if "--overlay" in sys.argv:
+        part_o(dev, 2 if quick else 16, 3 if quick else 10, 256, 4, 5 if quick else 30)
         return
     if "--mm-only" in sys.argv:
         for S in (112, 256):
