@@ -53,8 +53,14 @@ network's grid against a nearest-neighbour down-sampled tracing, are not.  ops.m
 (half-pixel-centre bilinear on the one-hot planes, exact integers) and counts it against the native target in the same pass; a frame counts
 when its native target has a pixel of some class.  A `native` block holds `dice_per_class`, `mean_foreground_dice`, `iou_per_class`,
 `mean_foreground_iou` (the grid's formulas and rounding), `pixels` (the native pixels compared) and `frames`; with any of `temporal_vote`,
-`lv_keep_largest`, `lv_fill_holes` on, `native.post` holds the same keys for the post-processed mask.  The surface distances and the volumes
-stay on the grid.  Every other key keeps its value; with the key off nothing new runs.
+`lv_keep_largest`, `lv_fill_holes` on, `native.post` holds the same keys for the post-processed mask.  With `data.native_surface_class` >= 0
+(which needs `native_eval`) the RAW predicted mask at native size (ops.mask_to_native's out) is also measured against the native target with
+ops.surface_distance_native, and a `native.surface` block holds `class`, `unit`, `frames`, `frames_one_empty`, `hd_mean`, `hd95_mean`,
+`assd_mean` over the frames that count above (surface_metrics_mm / surface_summary, rounded like `surface_mm`): in mm (`unit`: "mm") with
+the spacing of the NATIVE pixel for every clip (gdkvm_amd.data.native_spacing_table: the dataset's own, e.g. the native_spacing.json of
+tools/convert_camus.py --native-spacing, else `data.native_spacing_um`), else in native pixels (`unit`: "px", measured at 1000 x 1000 um so
+that one pixel reads as 1.0).  Like the grid's `surface` block these are the distances of the unfiltered mask.  The volumes stay on the
+grid.  Every other key keeps its value; with the keys off nothing new runs.
 
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
@@ -83,7 +89,7 @@ def main(argv=None):
 
     from gdkvm_amd import ops
     from gdkvm_amd.config import beat_prominence_permille, load_config
-    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table, native_target_table, view_pair_table
+    from gdkvm_amd.data import build_dataset, clip_length_table, clip_spacing_table, native_spacing_table, native_target_table, view_pair_table
     from gdkvm_amd.distributed import init_from_env, shard_range
     from gdkvm_amd.model import GDKVM, GDKVMConfig
 
@@ -160,6 +166,7 @@ def main(argv=None):
                            for w, dt in ((12, torch.int64), (20, torch.int64), (6, torch.float64))]
         bp_pred, bp_tgt = bp_rows(), bp_rows()
     nat_on = cfg.data.native_eval                                 # off: no new call below
+    ns_cls = cfg.data.native_surface_class if nat_on else -1      # -1 = off: no new call below (config: >= 0 needs native_eval)
     if nat_on:
         nat_sizes = native_target_table(ds)                       # host int32 [clips, 2] = (h0, w0)
         if nat_sizes is None:
@@ -168,6 +175,13 @@ def main(argv=None):
         nat_post = bool(vote or keep or fillc)                    # a second set of sums for the post-processed mask
         nat_k = cfg.data.num_classes * 3 + 2                      # native counts [ncls, 3], then the pixels compared and the labelled frames
         nat_acc = torch.zeros((2 if nat_post else 1) * nat_k, dtype=torch.int64, device=dev)
+        if ns_cls >= 0:
+            # host int32 [clips, 2] micrometres per NATIVE pixel; without one for every clip the distances are in native pixels
+            nat_sp = native_spacing_table(ds, cfg)
+            ns_unit = "mm" if nat_sp is not None else "px"
+            if nat_sp is None:
+                nat_sp = torch.full((len(ds), 2), 1000, dtype=torch.int32)
+            ns_sums = torch.zeros(5, dtype=torch.float64, device=dev)     # ops.surface_summary, accumulated on the device
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -234,8 +248,11 @@ def main(argv=None):
             n_flat = n_flat.to(dev)
             n_px = torch.tensor([h0 * w0 for h0, w0 in n_sz], dtype=torch.int64, device=dev)
             for slot, pm in enumerate((mask, measured) if nat_post else (mask,)):
-                _, n_c, _ = ops.mask_to_native(pm, n_sz, cfg.data.num_classes, target=n_flat, want_out=False)
+                n_out, n_c, _ = ops.mask_to_native(pm, n_sz, cfg.data.num_classes, target=n_flat, want_out=slot == 0 and ns_cls >= 0)
                 n_lab = n_c[..., 2].sum(-1) > 0                   # [B, T]
+                if n_out is not None:                             # the raw mask's surface distances at native size, over the same frames
+                    n_surf = ops.surface_distance_native(n_out, n_flat, n_sz, mask.shape[1], nat_sp[i:i + nb], cls=ns_cls)
+                    ns_sums += ops.surface_summary(*ops.surface_metrics_mm(n_surf), n_surf, n_lab)
                 nat_acc[slot * nat_k:(slot + 1) * nat_k] += torch.cat([(n_c * n_lab[..., None, None]).sum((0, 1)).long().reshape(-1),
                                                                        torch.stack([(n_lab.sum(1) * n_px).sum(), n_lab.sum()])])
         if lv_cls >= 0:
@@ -307,6 +324,8 @@ def main(argv=None):
             torch.distributed.all_reduce(bt_acc)                  # ... and the beat-by-beat sums
         if nat_on:
             torch.distributed.all_reduce(nat_acc)                 # ... and the native counts, pixels and frames
+            if ns_cls >= 0:
+                torch.distributed.all_reduce(ns_sums)             # ... and the five native surface-distance sums
         if bp_on:
             for tab in bp_pred + bp_tgt:                          # ... and the record tables: every row was written by one rank and is 0 on
                 torch.distributed.all_reduce(tab)                 # the others, and integer and fp64 sums with zeros are exact
@@ -427,6 +446,10 @@ def main(argv=None):
             res["native"] = nat_block(acc[:nat_k])
             if nat_post:
                 res["native"]["post"] = nat_block(acc[nat_k:])
+            if ns_cls >= 0:
+                st = ops.surface_stats(ns_sums.cpu())
+                res["native"]["surface"] = {"class": ns_cls, "unit": ns_unit, "frames": st["frames"], "frames_one_empty": st["frames_one_empty"],
+                                            **{k: round(st[k], 5) for k in ("hd_mean", "hd95_mean", "assd_mean")}}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -45,6 +45,10 @@ class DataCfg:
                                      # block; needs lv_class >= 0, a spacing for every clip and a dataset with patient / view (camus_png)
     native_eval: bool = False        # eval.py: Dice / IoU at every clip's NATIVE frame size against the tracing as stored (ops.mask_to_native): a
                                      # `native` block; needs a dataset with a native target for every clip (data.native_target_table)
+    native_surface_class: int = -1   # eval.py: the class whose HD, HD95 and ASSD are also measured at every clip's NATIVE frame size
+                                     # (ops.surface_distance_native): a `surface` block inside `native`; -1 = off, >= 0 needs native_eval
+    native_spacing_um: Any = None    # eval.py: [row_um, col_um], the micrometres per NATIVE pixel (integers in 1..4095) for datasets that carry
+                                     # none of their own (data.native_spacing_table); without a spacing for every clip the block is in pixels
     synthetic_beats: float = 1.0     # the synthetic clips' heart beats per clip (> 0; 1.0: the clips of before, bit for bit)
     whole_video: bool = False        # echonet_npz only: a clip is the video's first `frames` frames (several beats), not the window around ED / ES
 
@@ -192,6 +196,16 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
         raise ValueError(f"data.native_eval = {d.native_eval!r}: true or false")
     if d.native_eval and not 2 <= d.num_classes <= 8:
         raise ValueError(f"data.native_eval: ops.mask_to_native votes over 2..8 classes, data.num_classes = {d.num_classes}")
+    nsc = d.native_surface_class
+    if isinstance(nsc, bool) or not isinstance(nsc, int) or not -1 <= nsc < d.num_classes:
+        raise ValueError(f"data.native_surface_class = {nsc!r}: -1 (off) or a class in 0..{d.num_classes - 1}")
+    if nsc >= 0 and not d.native_eval:
+        raise ValueError(f"data.native_surface_class = {nsc} needs data.native_eval: true (the surface distances at native size are part of "
+                         "the `native` block)")
+    nsp = d.native_spacing_um
+    if nsp is not None and (not isinstance(nsp, list) or len(nsp) != 2
+                            or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4095 for v in nsp)):
+        raise ValueError(f"data.native_spacing_um = {nsp!r}: null or [row_um, col_um], two integers in 1..4095 (micrometres per native pixel)")
     if d.whole_video and d.kind != "echonet_npz":
         raise ValueError(f"data.whole_video is for data.kind = echonet_npz, not {d.kind!r}")
     if isinstance(d.beat_distance, bool) or not isinstance(d.beat_distance, int) or not 1 <= d.beat_distance <= 4096:

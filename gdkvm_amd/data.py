@@ -22,7 +22,10 @@ ops.lv_beats.  A dataset's native_hw(i) / native_target(i), where it has them (n
 .npz; camus_png: the native_mask_XXX.png of tools/convert_camus.py --native-masks), are clip i's labels at the clip's OWN frame size, untouched
 by any resize; native_target_table gathers the sizes for eval.py's `native` block (data.native_eval).  native_frames(i) likewise hands out the
 clip's grey IMAGE frames at their own size (npy_clips: an optional `native_frames` array; camus_png: the native_frame_XXX.png of
-tools/convert_camus.py --native-frames), what ops.frames_from_native and predict.py take.  Samples stay (frames, target).
+tools/convert_camus.py --native-frames), what ops.frames_from_native and predict.py take.  native_spacing_um(i) is the spacing of the
+NATIVE pixel (npy_clips: an optional `native_spacing_um` array; camus_png: the native_spacing.json of tools/convert_camus.py
+--native-spacing), else None; native_spacing_table gathers them, with `data.native_spacing_um` as the fallback, for the surface distances at
+native size (ops.surface_distance_native, eval.py's native.surface block).  Samples stay (frames, target).
 """
 from __future__ import annotations
 
@@ -70,6 +73,9 @@ class SyntheticEchoClips(Dataset):
 
     def spacing_um(self, i):
         return None                                               # a drawing has no physical size
+
+    def native_spacing_um(self, i):
+        return None
 
     def __getitem__(self, i) -> Tuple[torch.Tensor, torch.Tensor]:
         rng = np.random.default_rng(self.seed * 1_000_003 + i)
@@ -256,6 +262,9 @@ class EchoNetNpz(Dataset):
     def spacing_um(self, i):
         return None                                               # EchoNet-Dynamic ships no pixel spacing
 
+    def native_spacing_um(self, i):
+        return None
+
     def _scalar(self, i, key) -> Optional[float]:
         with np.load(self.files[i]) as z:
             if key not in z.files:
@@ -306,6 +315,12 @@ class NpzClips(Dataset):
         """The clip's optional `spacing_um` array [row_um, col_um]; None without it or when it is no pair of integers in 1..4095."""
         with np.load(self.files[i]) as z:
             return _spacing_pair(z["spacing_um"]) if "spacing_um" in z.files else None
+
+    def native_spacing_um(self, i):
+        """The clip's optional `native_spacing_um` array [row_um, col_um], the micrometres per pixel of its native frames; None without it
+        or when it is no pair of integers in 1..4095."""
+        with np.load(self.files[i]) as z:
+            return _spacing_pair(z["native_spacing_um"]) if "native_spacing_um" in z.files else None
 
     def native_hw(self, i) -> Optional[Tuple[int, int]]:
         """(h0, w0) of the clip's optional `native_target` array [T, h0, w0]; None without it."""
@@ -396,6 +411,18 @@ class CamusPng(Dataset):
         except (ValueError, AttributeError):
             return None
 
+    def native_spacing_um(self, i):
+        """The sequence's native_spacing.json "spacing_um" [row_um, col_um] (tools/convert_camus.py --native-spacing: the NIfTI pixdim itself,
+        the micrometres per pixel of the native frames); None without the file or when it holds no pair of integers in 1..4095."""
+        p = os.path.join(self.seqs[i], "native_spacing.json")
+        if not os.path.exists(p):
+            return None
+        try:
+            with open(p) as f:
+                return _spacing_pair(json.load(f).get("spacing_um"))
+        except (ValueError, AttributeError):
+            return None
+
     def _picked(self, i):
         """The frame files of sequence i that make its clip, in order (one pick for __getitem__ and native_target)"""
         fr = sorted(glob.glob(os.path.join(self.seqs[i], "frame_*.png")))
@@ -469,6 +496,21 @@ def clip_spacing_table(ds, cfg) -> Optional[torch.Tensor]:
     one clip has neither (then nothing is measured in mm: a table with holes would average over a different set of clips)."""
     fallback = _spacing_pair(cfg.data.spacing_um) if cfg.data.spacing_um is not None else None
     own = getattr(ds, "spacing_um", None)
+    rows = []
+    for i in range(len(ds)):
+        sp = own(i) if own is not None else None
+        sp = sp if sp is not None else fallback
+        if sp is None:
+            return None
+        rows.append(sp)
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2)
+
+
+def native_spacing_table(ds, cfg) -> Optional[torch.Tensor]:
+    """int32 [len(ds), 2] (host) = every clip's (row_um, col_um) per NATIVE pixel: the dataset's own native_spacing_um(i), else
+    cfg.data.native_spacing_um; None as soon as one clip has neither (clip_spacing_table's rule, for the native frames)."""
+    fallback = _spacing_pair(cfg.data.native_spacing_um) if cfg.data.native_spacing_um is not None else None
+    own = getattr(ds, "native_spacing_um", None)
     rows = []
     for i in range(len(ds)):
         sp = own(i) if own is not None else None

@@ -145,6 +145,8 @@ SIGNATURES = {
     "gdkvm_surface_distance": (_i, [_vp] * 4 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_surface_distance_mm_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_surface_distance_mm": (_i, [_vp] * 5 + [_sz] + [_i] * 4 + [_vp]),
+    "gdkvm_surface_distance_native_workspace_bytes": (_sz, [_i, _i, ctypes.c_longlong, ctypes.c_longlong]),
+    "gdkvm_surface_distance_native": (_i, [_vp] * 5 + [_sz, _vp, _sz] + [_i] * 3 + [_vp]),
     "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
     "gdkvm_signed_distance": (_i, [_vp] * 3 + [_sz] + [_i] * 4 + [ctypes.c_uint, _vp]),
     "gdkvm_adamw_workspace_bytes": (_sz, [_i, ctypes.c_longlong]),
@@ -2803,6 +2805,115 @@ def _surface_distance(entry: str, mask, target, spacing_um, cls):
     surf = torch.empty(lead + (8,), dtype=torch.int64, device=dev)
     ws = _workspace(entry + "_workspace_bytes", dev, frames, H, W, floor=16)
     _call(entry, dev, mask, target, *sp, surf, _Ws(ws), frames, H, W, int(cls))
+    return surf
+
+
+# GDKVM_SURFACE_NATIVE_*: the launch geometry of surface_distance_native, for tests that want shapes on both sides of it
+SURFACE_NATIVE_BAND_ROWS, SURFACE_NATIVE_STRIP, SURFACE_NATIVE_MAX_WG, SURFACE_NATIVE_CLIPS = 32, 64, 4096, 64
+
+
+def _native_spacing(what: str, spacing_um, clips: int) -> list:
+    """[(ry, rx), ...] as Python integers from a sequence of pairs or a HOST integer tensor [clips, 2]; every value in 1..SPACING_UM_MAX.
+    A device tensor is refused like device sizes: the entry validates the spacings on the host and hands them over by value."""
+    if isinstance(spacing_um, torch.Tensor):
+        if spacing_um.device.type != "cpu":
+            raise GdkvmError(f"{what}: spacing_um must be host integers (a sequence of (ry, rx) or a CPU tensor [clips, 2]): they are validated "
+                             "and handed to the kernels by value before anything is launched, and a device tensor would have to be copied back first")
+        if spacing_um.dim() != 2 or spacing_um.shape[1] != 2 or torch.is_floating_point(spacing_um) or spacing_um.dtype == torch.bool:
+            raise GdkvmError(f"{what}: spacing_um must be an integer tensor [clips, 2] = (ry, rx), got {spacing_um.dtype} {tuple(spacing_um.shape)}")
+        rows = spacing_um.tolist()
+    else:
+        try:
+            rows = [tuple(r) for r in spacing_um]
+        except TypeError:
+            raise GdkvmError(f"{what}: spacing_um must be a sequence of (ry, rx) or a CPU tensor [clips, 2], got {type(spacing_um).__name__}") from None
+    out = []
+    for b, r in enumerate(rows):
+        if len(r) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in r):
+            raise GdkvmError(f"{what}: spacing_um[{b}] = {r!r} is no pair of integers (ry, rx)")
+        if not (1 <= r[0] <= SPACING_UM_MAX and 1 <= r[1] <= SPACING_UM_MAX):
+            raise GdkvmError(f"{what}: spacing_um[{b}] = {r[0]} x {r[1]} um outside 1..{SPACING_UM_MAX}")
+        out.append((r[0], r[1]))
+    if len(out) != clips:
+        raise GdkvmError(f"{what}: {len(out)} spacings for {clips} clips")
+    return out
+
+
+def _surface_bool(x: torch.Tensor) -> torch.Tensor:
+    """The surface of the boolean set x [h, w]: its pixels with a 4-neighbour outside the set or the frame"""
+    p = torch.nn.functional.pad(x, (1, 1, 1, 1))
+    return x & ~(p[:-2, 1:-1] & p[2:, 1:-1] & p[1:-1, :-2] & p[1:-1, 2:])
+
+
+def _directed_d2_host(pa: torch.Tensor, pb: torch.Tensor, ry: int, rx: int) -> torch.Tensor:
+    """int64 [len(pa)]: min over q in pb of (ry dy)^2 + (rx dx)^2, brute force over coordinates [n, 2] = (y, x), in chunks of pa"""
+    out = torch.empty(pa.shape[0], dtype=torch.int64)
+    step = max(1, (1 << 22) // max(1, pb.shape[0]))
+    for i in range(0, pa.shape[0], step):
+        d = pa[i:i + step, None, :] - pb[None, :, :]
+        out[i:i + step] = ((d[..., 0] * ry) ** 2 + (d[..., 1] * rx) ** 2).amin(1)
+    return out
+
+
+def _surface_native_host(m: torch.Tensor, t: torch.Tensor, ry: int, rx: int, cls: int) -> list:
+    """The record of gdkvm_surface_distance_native for one frame [h0, w0] (uint8, CPU) as 8 Python ints"""
+    pa, pb = _surface_bool(m == cls).nonzero(), _surface_bool(t == cls).nonzero()
+    nA, nB = pa.shape[0], pb.shape[0]
+    if nA == 0 or nB == 0:
+        return [nA, nB, 0, 0, 0, 0, 0, 0]
+    dab, dba = _directed_d2_host(pa, pb, ry, rx), _directed_d2_host(pb, pa, ry, rx)
+    fixed = lambda d: sum(math.isqrt(int(v) << 16) * int(c) for v, c in zip(*(u.tolist() for u in torch.unique(d, return_counts=True))))
+    pooled = torch.sort(torch.cat([dab, dba])).values
+    n = nA + nB
+    lo = (95 * (n - 1)) // 100
+    return [nA, nB, int(dab.max()), int(dba.max()), fixed(dab), fixed(dba), int(pooled[lo]), int(pooled[min(lo + 1, n - 1)])]
+
+
+def surface_distance_native(mask: torch.Tensor, target: torch.Tensor, sizes, T: int, spacing_um, cls: int = 1) -> torch.Tensor:
+    """gdkvm_surface_distance_native: surface_distance_mm at every clip's own frame size.  mask and target are RAGGED flat uint8 tensors,
+    clip b's T frames of h0 w0 bytes in turn (mask_to_native returns one, pack_native builds one); sizes the clips' native (h0, w0), each in
+    1..2048, and spacing_um the micrometres per NATIVE pixel (ry, rx) of every clip, each in 1..4095: both HOST integers, a sequence of
+    pairs or a CPU integer tensor [clips, 2] (a device tensor is refused).  Returns surf int64 [clips, T, 8] = nA, nB, hAB, hBA (um^2),
+    sAB, sBA (sums of the distances in units of 2^-8 um, each rounded down), q_lo, q_hi (um^2), surface_distance_mm's record (definition:
+    include/gdkvm.h): surface_metrics_mm, surface_summary and surface_stats apply unchanged.  mask and target may start at any byte
+    address.  CPU tensors take the same rule in torch (brute force over the surface pixels' coordinates in int64), so the wrapper works
+    without a GPU."""
+    what = "surface_distance_native"
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    if isinstance(cls, bool) or not isinstance(cls, int) or not 0 <= cls <= 254:
+        raise GdkvmError(f"{what}: cls = {cls!r} must be an integer in 0..254")
+    sz = _native_sizes(what, sizes)
+    clips = len(sz)
+    sp = _native_spacing(what, spacing_um, clips)
+    offsets, total = _native_offsets(sz, T)
+    if not isinstance(mask, torch.Tensor):
+        raise GdkvmError(f"{what}: mask must be a flat uint8 tensor, got {type(mask).__name__}")
+    for name, t in (("mask", mask), ("target", target)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < total:
+            raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {total} bytes (the clips' T h0 w0 in turn), got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != mask.device:
+            raise GdkvmError("tensors on different devices")
+        if not t.is_contiguous():
+            raise GdkvmError("GDKVM ops need contiguous tensors")
+    if not mask.is_cuda:
+        # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
+        surf = torch.zeros((clips, T, 8), dtype=torch.int64)
+        for b, (h0, w0) in enumerate(sz):
+            m = mask[offsets[b]:offsets[b] + T * h0 * w0].view(T, h0, w0)
+            t = target[offsets[b]:offsets[b] + T * h0 * w0].view(T, h0, w0)
+            for f in range(T):
+                surf[b, f] = torch.tensor(_surface_native_host(m[f], t[f], sp[b][0], sp[b][1], cls), dtype=torch.int64)
+        return surf
+    dev = _dev(mask, target)
+    surf = torch.empty((clips, T, 8), dtype=torch.int64, device=dev)
+    if clips == 0:
+        return surf
+    host_sz = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
+    host_sp = torch.tensor(sp, dtype=torch.int32).reshape(clips, 2)
+    ws = _workspace("gdkvm_surface_distance_native_workspace_bytes", dev, clips, T, total, T * sum(h0 for h0, _ in sz), floor=16)
+    _call("gdkvm_surface_distance_native", dev, mask, target, host_sz, host_sp, surf, total, _Ws(ws), clips, T, cls)
     return surf
 
 

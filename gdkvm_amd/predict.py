@@ -15,7 +15,8 @@ rint(col_um w0 / W)) -- tools/convert_camus.py's spacing_um formula; the mL keys
 1..4095.  With overlay=True it also draws what a person looks at, ops.overlay_native of the native frames under those native masks (the
 configuration's `overlay:` section); overlay_clip draws one clip with an optional reference mask, which is what eval.py's
 eval_stage.vis_overlay writes.  Everything after the copy runs on the device: there is no CPU path for the forward, and a CPU model is
-refused.
+refused.  ops.surface_distance_native, the native family's measurement against a tracing, has no place here: a prediction has no target
+(eval.py reports it as native.surface).
 
 load_input reads what predict.py's command line names: a .npy file ([T, h0, w0] uint8), a .npz file (`frames`, optional `spacing_um` =
 the NATIVE micrometres per pixel) or a directory of native_frame_*.png (else frame_*.png), where a spacing.json with "native_hw" (the

@@ -1002,6 +1002,47 @@ int gdkvm_surface_distance(const uint8_t* mask, const uint8_t* target, int64_t* 
 size_t gdkvm_surface_distance_mm_workspace_bytes(int frames, int H, int W);
 int gdkvm_surface_distance_mm(const uint8_t* mask, const uint8_t* target, const int32_t* spacing_um, int64_t* surf, void* workspace,
                               size_t workspace_bytes, int frames, int H, int W, int cls, void* stream);
+/* The same at every clip's NATIVE frame size: HD, HD95 and ASSD in mm against the tracing as the dataset stores it, with the spacing of the
+ * native pixel (eval.py's native.surface block; csrc/surface_native.hip).  Every output is an integer that depends on neither the algorithm
+ * nor the schedule.
+ * Per native frame of clip b: (h0, w0) = sizes[b], each side in 1..2048; (ry, rx) = spacing_um[b], micrometres per NATIVE pixel down the
+ * rows and along the columns, each in 1..4095; class cls in 0..254.  Rules 1, 2, 5 and 6 of gdkvm_surface_distance and rules 3 and 4 of
+ * gdkvm_surface_distance_mm apply unchanged: A and B are the pixels of mask and target equal to cls; the surface is the 4-neighbour erosion
+ * with the outside of the frame as background; adjacency is geometric, no wrap between rows and none between the frames of the ragged
+ * buffer; d2(p, q) = (ry dy)^2 + (rx dx)^2 in um^2.  surf [clips T, 8] int64 = nA, nB, hAB, hBA, sAB = sum over S(A) of
+ * isqrt(d2_AB(p) 2^16), sBA, q_lo, q_hi with the ranks lo = floor(95 (n - 1) / 100) and hi = min(lo + 1, n - 1) of the pooled multiset;
+ * nA == 0 or nB == 0: the six other fields are 0.  So gdkvm_amd.ops.surface_metrics_mm, surface_summary and surface_stats apply to the
+ * records unchanged, and on uniform clips the records are those of gdkvm_surface_distance_mm bit for bit.
+ * Bounds: d2 <= 2 (2047 * 4095)^2 < 2^47, so the isqrt's operand d2 2^16 is below 2^63 (the kernel's isqrt is exact for every operand
+ * below 2^63: its root is below 2^31.5, the fp64 estimate is off by at most one, and (r + 1)^2 < 2^64); a term of a sum is below 2^32 and
+ * a sum below 2^54.
+ * mask and target are RAGGED, exactly the layout of gdkvm_mask_to_native's out / target: clip b's T frames of h0 w0 bytes follow each other
+ * and clip b + 1 follows clip b.  Frames start at ANY byte address.  native_bytes = the bytes mask and target each hold; it must cover the
+ * sum over the clips of T h0 w0.  surf is 16-byte aligned.
+ * sizes and spacing_um are HOST int32 [clips, 2]: the entry validates every value (so this form has no -1 record), computes every clip's
+ * offsets itself and hands them with the sizes and the spacings to the kernels by value in the kernel arguments,
+ * GDKVM_SURFACE_NATIVE_CLIPS clips per launch, longer batches in several launches; nothing is copied to the device, nothing allocated,
+ * nothing synchronised (a capture holds the sizes and the spacings).
+ * The workspace (16-byte aligned, at least gdkvm_surface_distance_native_workspace_bytes(clips, T, native_bytes, native_rows) bytes with
+ * native_bytes = the sum of T h0 w0 and native_rows = the sum of T h0 over the clips) is scratch and need not be zeroed: per frame 512
+ * bytes of counts, per pixel 2 bits of surface bitmaps (rows padded to whole 32-bit words, hence native_rows), two 16-bit planes and two
+ * 32-bit list entries: about 12.1 bytes per pixel, an upper bound that depends on the four integers of the query only (0 for a bad query).
+ * Bad arguments (clips < 0, T < 1, cls, a size outside 1..2048, a spacing outside 1..4095, null mask, target, sizes, spacing_um or surf, a
+ * misaligned surf, native_bytes short of the sum, clips * T > 2^30, a null, short or misaligned workspace) are GDKVM_ERR_SHAPE before any
+ * device call; clips == 0 is GDKVM_OK without a launch.  Bit-reproducible.
+ * Launch geometry, for tests that want shapes on both sides of it: four kernels in stream order per launch, no workgroup waits for
+ * another.  The surfaces and the walks along the rows go by BANDS of GDKVM_SURFACE_NATIVE_BAND_ROWS native rows of one (clip, frame) (the
+ * surface kernel reads one halo row above and below its band); the sweeps down the columns by STRIPS of GDKVM_SURFACE_NATIVE_STRIP columns,
+ * one lane per column; a frame's maxima, sums and ranks by one workgroup.  A launch has at most GDKVM_SURFACE_NATIVE_MAX_WG workgroups per
+ * kernel, which take further items in a grid-stride loop. */
+#define GDKVM_SURFACE_NATIVE_BAND_ROWS 32
+#define GDKVM_SURFACE_NATIVE_STRIP 64
+#define GDKVM_SURFACE_NATIVE_MAX_WG 4096
+#define GDKVM_SURFACE_NATIVE_CLIPS 64
+size_t gdkvm_surface_distance_native_workspace_bytes(int clips, int T, long long native_bytes, long long native_rows);
+int gdkvm_surface_distance_native(const uint8_t* mask, const uint8_t* target, const int32_t* sizes, const int32_t* spacing_um,
+                                  int64_t* surf, size_t native_bytes, void* workspace, size_t workspace_bytes, int clips, int T, int cls,
+                                  void* stream);
 
 /* Signed squared distance maps of label frames (the operand of gdkvm_seg_loss_boundary_fwd / _bwd; csrc/signed_distance.hip).  Every output is
  * an integer that depends on neither the algorithm nor the schedule.  Distances are in pixels of the frame's grid (isotropic pixels assumed).

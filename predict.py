@@ -8,7 +8,9 @@ post-processed as the configuration says (data.temporal_vote, data.lv_keep_large
 (ops.mask_to_native) and, with data.lv_class >= 0, measured: ED / ES frames, volumes and EF per clip, beat by beat with data.lv_beats, in mL
 with a spacing.  Written: <out>/<name>/mask_XXX.png (class indices, native size) and <out>/report.json, which is also printed; with --overlay also
 <out>/<name>/overlay_XXX.png, the picture to look at: the native frame in grey, the predicted classes tinted and their contours opaque
-(ops.overlay_native on the GPU; colours, tint and contour width: the configuration's overlay: section).
+(ops.overlay_native on the GPU; colours, tint and contour width: the configuration's overlay: section).  The fourth member of the native
+family, ops.surface_distance_native (HD, HD95 and ASSD in mm at native size), measures a mask against a tracing: a prediction has none, so
+it adds nothing here and is eval.py's (data.native_surface_class).
 
     python predict.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [--overlay] --out DIR INPUT... [key=value ...]"""
 import os

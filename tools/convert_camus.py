@@ -32,10 +32,16 @@ With --resample area (the default is bilinear: the tree of before) frame_XXX.png
     byte frame (the rule of gdkvm_frames_from_native in include/gdkvm.h) instead of the point-sampled bilinear resize: a tree converted this
     way holds exactly the bytes ops.frames_from_native produces from native_frame_XXX.png, so a model trained on it sees at prediction
     time what it saw in training.  Labels stay nearest.
+With --native-spacing (off by default) every sequence also gets
+    <dst>/<split>/patientXXXX/<2CH|4CH>/native_spacing.json   {"spacing_um": [row_um, col_um]}: the micrometres per pixel of the NATIVE
+    frames, the header's pixdim itself: row_um = rint(1000 pixdim_y_mm), col_um = rint(1000 pixdim_x_mm) -- no resize rounds it.  What
+    eval.py's native.surface block measures HD, HD95 and ASSD in mm with (CamusPng.native_spacing_um, data.native_surface_class).
+    spacing.json stays as it is.  No file (and a log line) when a pixdim is not finite or not positive, or a value falls outside 1..4095.
 
 NIfTI-1 is read here directly (a 348-byte header + a raw array, gzip around it): no nibabel in this image.  Nothing touches a GPU.
 
     python tools/convert_camus.py <src> <dst> [--size 256] [--frames 10] [--split train] [--native-masks] [--native-frames] [--resample area]
+        [--native-spacing]
 """
 import argparse
 import glob
@@ -95,6 +101,17 @@ def spacing_um(dx_mm: float, dy_mm: float, native_h: int, native_w: int, size: i
     if not (math.isfinite(dx_mm) and math.isfinite(dy_mm) and dx_mm > 0 and dy_mm > 0):
         return None
     row, col = float(np.rint(1000.0 * dy_mm * native_h / size)), float(np.rint(1000.0 * dx_mm * native_w / size))
+    if not (1 <= row <= SPACING_UM_MAX and 1 <= col <= SPACING_UM_MAX):
+        return None
+    return [int(row), int(col)]
+
+
+def native_spacing_um(dx_mm: float, dy_mm: float):
+    """[row_um, col_um] of the native pixel of dy_mm x dx_mm, or None when a pixdim is not finite or not positive or a value falls outside
+    1..SPACING_UM_MAX."""
+    if not (math.isfinite(dx_mm) and math.isfinite(dy_mm) and dx_mm > 0 and dy_mm > 0):
+        return None
+    row, col = float(np.rint(1000.0 * dy_mm)), float(np.rint(1000.0 * dx_mm))
     if not (1 <= row <= SPACING_UM_MAX and 1 <= col <= SPACING_UM_MAX):
         return None
     return [int(row), int(col)]
@@ -213,7 +230,7 @@ class defaultdict_const(dict):
 
 
 def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = "train", log=print, native_masks: bool = False,
-            native_frames: bool = False, resample: str = "bilinear") -> dict:
+            native_frames: bool = False, resample: str = "bilinear", native_spacing: bool = False) -> dict:
     from PIL import Image
     if resample not in ("bilinear", "area"):
         raise ValueError(f"resample = {resample!r} is neither 'bilinear' nor 'area'")
@@ -255,6 +272,13 @@ def convert(src: str, dst: str, size: int = 256, frames: int = 10, split: str = 
             else:
                 with open(os.path.join(out, "spacing.json"), "w") as f:
                     json.dump({"spacing_um": sp, "native_hw": [int(img.shape[1]), int(img.shape[0])]}, f)
+            if native_spacing:                                                # the pixdim itself: the spacing of the native frames
+                nsp = native_spacing_um(dx_mm, dy_mm)
+                if nsp is None:
+                    log(f"  {pid} {view}: no usable native pixel spacing (pixdim {dx_mm} x {dy_mm} mm): no native_spacing.json")
+                else:
+                    with open(os.path.join(out, "native_spacing.json"), "w") as f:
+                        json.dump({"spacing_um": nsp}, f)
             cfg = os.path.join(pdir, f"Info_{view}.cfg")
             if os.path.exists(cfg):
                 with open(cfg, errors="replace") as f:
@@ -278,5 +302,8 @@ if __name__ == "__main__":
     ap.add_argument("--native-frames", action="store_true", help="also write every picked image frame at its own size as bytes (native_frame_XXX.png)")
     ap.add_argument("--resample", choices=("bilinear", "area"), default="bilinear",
                     help="how frame_XXX.png is made: point-sampled bilinear (the default), or the exact area average of ops.frames_from_native")
+    ap.add_argument("--native-spacing", action="store_true",
+                    help="also write the spacing of the native pixel, the header's pixdim in micrometres (native_spacing.json)")
     a = ap.parse_args()
-    convert(a.src, a.dst, a.size, a.frames, a.split, native_masks=a.native_masks, native_frames=a.native_frames, resample=a.resample)
+    convert(a.src, a.dst, a.size, a.frames, a.split, native_masks=a.native_masks, native_frames=a.native_frames, resample=a.resample,
+            native_spacing=a.native_spacing)

@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay] [--native-surface]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -51,6 +51,13 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     masks of 4 classes, with and without a reference mask, at contour widths 1 and 3, beside the torch expression of the same rule on the
     same device tensors (padded shifts compared, palettes gathered, torch.where; the probe first checks that it draws the kernel's bytes)
     and the byte floor: 2 or 3 bytes read and 3 written per pixel over the HBM rate above (profiles/overlay_probe.txt).
+(s) --native-surface (this part alone): gdkvm_surface_distance_native (class 1, 308 x 154 um per native pixel) on 16 clips of 10 frames of
+    549 x 778 and of the mixed CAMUS-like sizes of (n): ventricle-like ellipses against a shifted copy (a prediction close to its tracing),
+    the ellipses with islands against the ellipses, and an empty class (class 3); through the C symbol on a preallocated workspace, beside
+    two yardsticks in the same alternated windows: gdkvm_surface_distance_mm's workspace form on the uniform 549 x 778 batch (one workgroup
+    per frame; the only other way to these records, and the probe first checks that they are bit-equal there) and the byte floor, mask +
+    target bytes over the HBM rate above.  Then ONE moderate pathological frame, a 512^2 checkerboard against a single pixel, run once and
+    timed with a pair of events (profiles/native_surface_probe.txt).  --once: every form once, no windows (for a kernel trace).
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
     data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
     instead, and with data.lv_class=-1, alternated, twice each."""
@@ -674,6 +681,132 @@ def part_o(dev, clips, T, S, ncls, reps, n_in=2):
         print(flush=True)
 
 
+def native_ellipses(sizes, T, seed):
+    """Per clip uint8 [T, h0, w0]: one rotated ellipse of class 1 per frame covering about a tenth of it, with a ring of class 2 around it"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for h0, w0 in sizes:
+        yy, xx = np.mgrid[0:h0, 0:w0].astype(np.float32)
+        m = np.zeros((T, h0, w0), np.uint8)
+        for t in range(T):
+            th = rng.uniform(-0.5, 0.5)
+            la, sa = rng.uniform(0.22, 0.30), rng.uniform(0.10, 0.14)
+            dx, dy = xx / w0 - rng.uniform(0.45, 0.55), yy / h0 - rng.uniform(0.45, 0.55)
+            al, ac = dx * math.sin(th) + dy * math.cos(th), dx * math.cos(th) - dy * math.sin(th)
+            d = (al / la) ** 2 + (ac / sa) ** 2
+            m[t][d <= 1.5] = 2
+            m[t][d <= 1.0] = 1
+        out.append(m)
+    return out
+
+
+def native_islands(clips, seed):
+    """Three discs of class 1 per frame near the corners of every clip's frames (add_islands at native sizes)"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for m in clips:
+        T, h0, w0 = m.shape
+        yy, xx = np.mgrid[0:h0, 0:w0]
+        m = m.copy()
+        for t in range(T):
+            for _ in range(3):
+                cy, cx = ((rng.uniform(0.04, 0.16) if rng.random() < 0.5 else rng.uniform(0.84, 0.96)) * n for n in (h0, w0))
+                m[t][(yy - cy) ** 2 + (xx - cx) ** 2 <= (rng.uniform(0.01, 0.05) * min(h0, w0)) ** 2] = 1
+        out.append(m)
+    return out
+
+
+def part_s(dev, clips, T, reps, once=False):
+    """(s) gdkvm_surface_distance_native: `clips` clips of T native frames, through the C symbol on a preallocated workspace, beside
+    gdkvm_surface_distance_mm on the uniform batch and the byte floor (mask + target read once) in the same alternated windows."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ry, rx = 308, 154
+    mixed = [(549, 778), (1181, 972), (843, 512), (300, 400), (487, 823), (708, 1050), (584, 439), (967, 601)]
+    flat = lambda cl: torch.from_numpy(np.concatenate([c.reshape(-1) for c in cl])).to(dev)
+    for label, sizes in (("549 x 778", [(549, 778)] * clips), ("mixed sizes", [mixed[b % len(mixed)] for b in range(clips)])):
+        uniform = len(set(sizes)) == 1
+        base = native_ellipses(sizes, T, 1)
+        shifted = [np.roll(c, (7, -5), (1, 2)) for c in base]
+        pred, tgt, isl = flat(base), flat(shifted), flat(native_islands(base, 2))
+        total, rows = pred.numel(), T * sum(h0 for h0, _ in sizes)
+        host_sz = torch.tensor(sizes, dtype=torch.int32)
+        host_sp = torch.tensor([(ry, rx)] * clips, dtype=torch.int32)
+        need = lib.gdkvm_surface_distance_native_workspace_bytes(clips, T, total, rows)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        surf = torch.empty((clips, T, 8), dtype=torch.int64, device=dev)
+
+        def sn(m, g, cls=1):
+            rc = lib.gdkvm_surface_distance_native(m.data_ptr(), g.data_ptr(), host_sz.data_ptr(), host_sp.data_ptr(), surf.data_ptr(), total,
+                                                   ws.data_ptr(), need, clips, T, cls, st)
+            assert rc == 0, lib.gdkvm_last_error()
+
+        forms = {
+            "surface_distance_native, ellipse against a shifted copy": (lambda: sn(pred, tgt), 5),
+            "surface_distance_native, with islands against the ellipse": (lambda: sn(isl, pred), 5),
+            "surface_distance_native, empty class": (lambda: sn(pred, tgt, 3), 5),
+        }
+        if uniform:
+            h0, w0 = sizes[0]
+            need_mm = lib.gdkvm_surface_distance_mm_workspace_bytes(clips * T, h0, w0)
+            ws_mm = torch.empty(max(need_mm, 16), dtype=torch.uint8, device=dev)
+            sp_dev = torch.tensor([(ry, rx)] * (clips * T), dtype=torch.int32, device=dev)
+            surf_mm = torch.empty((clips, T, 8), dtype=torch.int64, device=dev)
+
+            def mm(m, g, cls=1):
+                rc = lib.gdkvm_surface_distance_mm(m.data_ptr(), g.data_ptr(), sp_dev.data_ptr(), surf_mm.data_ptr(), ws_mm.data_ptr(), need_mm,
+                                                   clips * T, h0, w0, cls, st)
+                assert rc == 0, lib.gdkvm_last_error()
+
+            sn(isl, pred); mm(isl, pred)
+            torch.cuda.synchronize()
+            print(f"    ({label}: the records of surface_distance_mm's workspace form are "
+                  f"{'bit-equal' if torch.equal(surf, surf_mm) else 'NOT EQUAL'} to surface_distance_native's)")
+            forms["surface_distance_mm (one workgroup per frame), shifted copy"] = (lambda: mm(pred, tgt), 2)
+            forms["surface_distance_mm (one workgroup per frame), islands"] = (lambda: mm(isl, pred), 2)
+        times = {name: [] for name in forms}
+        for rep_ in range(1 if once else reps + 3):
+            for name, (fn, calls) in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(1 if once else calls):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                if once or rep_ >= 3:
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / (1 if once else calls))
+        nbytes = 2 * total
+        floor = nbytes / HBM * 1e6
+        print(f"(s) surface_distance_native, {clips} clips of {T} native frames of {label}, class 1, {ry} x {rx} um, {total / 1e6:.1f} MB of labels "
+              f"each side, workspace {need / 1e6:.1f} MB: us per call, windows of device events, median / minimum of {len(next(iter(times.values())))} "
+              f"windows per form (alternated)")
+        print(f"{'form':62s} {'median us':>10s} {'min us':>9s} {'MB':>8s} {'floor us':>9s} {'x floor':>8s}")
+        for name in forms:
+            med = statistics.median(times[name])
+            print(f"{name:62s} {med:10.1f} {min(times[name]):9.1f} {nbytes / 1e6:8.1f} {floor:9.2f} {med / floor:8.1f}")
+        print(flush=True)
+    # one moderate pathological frame, once: every pixel of the checkerboard's class is surface, and every walk is as long as the pixel is far
+    S = 512
+    board = np.zeros((1, S, S), np.uint8)
+    board[0, (np.add.outer(np.arange(S), np.arange(S)) % 2) == 0] = 1
+    one = np.zeros((1, S, S), np.uint8)
+    one[0, S - 1, 0] = 1
+    bm, og = flat([board]), flat([one])
+    hs, hp = torch.tensor([(S, S)], dtype=torch.int32), torch.tensor([(ry, rx)], dtype=torch.int32)
+    need = lib.gdkvm_surface_distance_native_workspace_bytes(1, 1, S * S, S)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    surf = torch.empty((1, 1, 8), dtype=torch.int64, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = lib.gdkvm_surface_distance_native(bm.data_ptr(), og.data_ptr(), hs.data_ptr(), hp.data_ptr(), surf.data_ptr(), S * S, ws.data_ptr(), need,
+                                           1, 1, 1, st)
+    e1.record()
+    e1.synchronize()
+    assert rc == 0, lib.gdkvm_last_error()
+    print(f"(s) one frame of {S} x {S}, a checkerboard ({int(surf[0, 0, 0])} surface pixels) against a single pixel, ONE call (its first: code "
+          f"already loaded by the calls above): {e0.elapsed_time(e1) * 1e3:.1f} us; record {surf[0, 0].tolist()}", flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
@@ -703,6 +836,9 @@ def main():
         return
     if "--native-input" in sys.argv:
         part_i(dev, 2 if quick else 16, 3 if quick else 10, 256, 5 if quick else 40)
+        return
+    if "--native-surface" in sys.argv:
+        part_s(dev, 2 if quick else 16, 3 if quick else 10, 3 if quick else 20, once="--once" in sys.argv)
         return
     if "--overlay" in sys.argv:
         part_o(dev, 2 if quick else 16, 3 if quick else 10, 256, 4, 5 if quick else 30)
