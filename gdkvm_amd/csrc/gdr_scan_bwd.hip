@@ -391,7 +391,7 @@ static int scan_bwd_impl(const void* q, const void* k, const void* v, const floa
         return gdkvm_fail(GDKVM_ERR_ARG, "scan_bwd: q, d_r and d_q come together");
     WsView ws;
     if (int rc = carve("scan_bwd", const_cast<void*>(fwd_workspace), fwd_workspace_bytes, B, T, Hh, N, Dk, Dv, &ws)) return rc;
-    if (bwd_workspace_bytes < gdkvm_scan_bwd_workspace_bytes(B, T, Hh, N, Dk, Dv) - 16)
+    if (bwd_workspace_bytes < gdkvm_scan_bwd_workspace_bytes(B, T, Hh, N, Dk, Dv))
         return gdkvm_fail(GDKVM_ERR_WORKSPACE, "scan_bwd: backward workspace %zu < %zu bytes", bwd_workspace_bytes,
                           gdkvm_scan_bwd_workspace_bytes(B, T, Hh, N, Dk, Dv));
     if (int rc = gdkvm_check_device()) return rc;

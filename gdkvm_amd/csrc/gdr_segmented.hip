@@ -80,7 +80,8 @@ extern "C" int gdkvm_scan_fwd_segmented(const void* q, const void* k, const void
         return gdkvm_scan_fwd(q, k, v, alpha, beta, s_in, r_out, s_out, nullptr, workspace, workspace_bytes, B, T, Hh, N, Dk, Dv, io_dtype, rule, flags, stream);
     if (int rc = check_ptrs("scan_fwd_segmented", {q, k, v, alpha, beta, r_out, workspace}, {s_in, s_out})) return rc;
     const SegView sv = seg_carve(workspace, B, T, Hh, N, Dk, Dv, S);
-    if (workspace_bytes < sv.total) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "scan_fwd_segmented: workspace %zu < %zu bytes", workspace_bytes, sv.total);
+    if (workspace_bytes < sv.total + 256)               // what gdkvm_scan_segmented_workspace_bytes returns
+        return gdkvm_fail(GDKVM_ERR_WORKSPACE, "scan_fwd_segmented: workspace %zu < %zu bytes", workspace_bytes, sv.total + 256);
     if (rule == GDKVM_RULE_DELTA_PARALLEL) flags |= GDKVM_FLAG_WIDE_RANGE;      // as gdkvm_scan_fwd
     const int BS = B * S, Ts = T / S;                                              // [B, T, ...] viewed as [B*S, T/S, ...]
     if (int rc = gdkvm_scan_prep(q, k, v, beta, sv.ws, sv.ws_bytes, BS, Ts, Hh, N, Dk, Dv, io_dtype, rule, flags, stream)) return rc;

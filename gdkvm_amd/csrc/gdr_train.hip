@@ -116,11 +116,12 @@ int train_check(const char* fn, void* ws, size_t ws_bytes, int B, int T, int Hh,
     if (!ws || !gdkvm_aligned16(ws)) return gdkvm_fail(GDKVM_ERR_ARG, "%s: workspace null or misaligned", fn);
     if (wide) {                                       // (the wide-key workspace has a layout of its own: gdr_general.hpp)
         const size_t need = gdr_general_train_workspace_bytes(B, T, Hh, N, Dk, Dv);
-        if (ws_bytes < need) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+        if (ws_bytes < need + 256) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need + 256);
         return GDKVM_OK;
     }
     *out = train_carve(ws, B, T, Hh, N, Dk, Dv, io_dtype);
-    if (ws_bytes < out->total) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, out->total);
+    if (ws_bytes < out->total + 256)                  // what gdkvm_scan_train_workspace_bytes returns
+        return gdkvm_fail(GDKVM_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, out->total + 256);
     return GDKVM_OK;
 }
 

@@ -1054,8 +1054,8 @@ extern "C" size_t gdkvm_kpff_workspace_bytes(int Ck, int Cv, int Cp, int io_dtyp
 {
     if ((io_dtype != GDKVM_BF16 && io_dtype != GDKVM_F32) || Ck <= 0 || Cv <= 0 || Cp <= 0) return 16;
     const size_t pack = ((size_t)2 * Cp * (Cp + Ck + Cv) + (size_t)Cp * Ck + (size_t)Cp * Cv) * sizeof(bf16_t);
-    if (io_dtype == GDKVM_F32) return (Ck % 32 || Cv % 32 || Cp % 32) ? 16 : 2 * pack + 16;      // split arm: high and low packs
-    return pack + 16;
+    if (Ck % 32 || Cv % 32 || Cp % 32) return 16;                                                // the exact arm packs nothing
+    return (io_dtype == GDKVM_F32 ? 2 * pack : pack) + 16;                                       // split arm: high and low packs
 }
 
 static thread_local int g_kpff_skip_pack = 0;            // set by gdkvm_kpff_fwd_packed around its call
@@ -1097,7 +1097,7 @@ extern "C" int gdkvm_kpff_fwd_train(const void* local, const void* global, const
     if (io_dtype == GDKVM_BF16 && Ck % 32 == 0 && Cv % 32 == 0 && Cp % 32 == 0) {
         const size_t need = gdkvm_kpff_workspace_bytes(Ck, Cv, Cp, io_dtype) - 16;
         if (!workspace || !gdkvm_aligned16(workspace)) return gdkvm_fail(GDKVM_ERR_ARG, "kpff_fwd: workspace null or misaligned");
-        if (workspace_bytes < need) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "kpff_fwd: workspace %zu < %zu bytes", workspace_bytes, need + 16);
+        if (workspace_bytes < need + 16) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "kpff_fwd: workspace %zu < %zu bytes", workspace_bytes, need + 16);
         const size_t lds1 = (size_t)KPFF_TM * (Cin + KPFF_PAD16) * sizeof(bf16_t);
         if (lds1 > 160 * 1024) return gdkvm_fail(GDKVM_ERR_SHAPE, "kpff_fwd: Cp+Ck+Cv=%d exceeds the LDS tile", Cin);
         const int total_tiles = BT * tiles;
@@ -1138,7 +1138,7 @@ extern "C" int gdkvm_kpff_fwd_train(const void* local, const void* global, const
     if (io_dtype == GDKVM_F32 && Ck % 32 == 0 && Cv % 32 == 0 && Cp % 32 == 0 && workspace && lds_split <= 160 * 1024) {
         const size_t need = gdkvm_kpff_workspace_bytes(Ck, Cv, Cp, io_dtype) - 16;
         if (!gdkvm_aligned16(workspace)) return gdkvm_fail(GDKVM_ERR_ARG, "kpff_fwd: workspace misaligned");
-        if (workspace_bytes < need) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "kpff_fwd: workspace %zu < %zu bytes", workspace_bytes, need + 16);
+        if (workspace_bytes < need + 16) return gdkvm_fail(GDKVM_ERR_WORKSPACE, "kpff_fwd: workspace %zu < %zu bytes", workspace_bytes, need + 16);
         bf16_t* wpk = static_cast<bf16_t*>(workspace);
         const size_t lo_off = need / (2 * sizeof(bf16_t));
         if (!g_kpff_skip_pack) {

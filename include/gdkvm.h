@@ -287,7 +287,9 @@ int gdkvm_gemm_tn_colsum(const void* a, const void* b, float* c, float* colsum, 
  * otherwise -- other channel counts, or workspace == NULL, which is how a caller asks for it -> exact fp32 MFMA (3x slower).
  * io_dtype bf16 with channel counts that are multiples of 32 -> bf16 MFMA with fp32 accumulation (weights and the pooled
  * feature are rounded to bf16, i.e. bf16-autocast accuracy); other bf16 shapes use the exact fp32 arm.  `workspace`
- * (gdkvm_kpff_workspace_bytes) holds the bf16 copies of the weights (high and low terms for f32), rebuilt on every call.
+ * (gdkvm_kpff_workspace_bytes) holds the bf16 copies of the weights (high and low terms for f32), rebuilt on every call; the
+ * exact arm packs nothing, and for its channel counts the size is the 16-byte floor in both I/O types.  A workspace of
+ * fewer bytes than the size entry returns is refused (GDKVM_ERR_WORKSPACE) by every arm that uses it.
  * Supported: Ck, Cv, Cp multiples of 16; h*w <= 4096 (grids wider than 16 columns are processed as 4-row x 16-column tiles). */
 size_t gdkvm_kpff_workspace_bytes(int Ck, int Cv, int Cp, int io_dtype);
 int gdkvm_kpff_fwd(const void* local, const void* global, const void* pixel,

@@ -24,6 +24,22 @@ def _reference(x, w, b, res, relu, dy, mask, eps=1e-5):
     return y.detach(), x64.grad, w64.grad, b64.grad, (None if r64 is None else r64.grad), rm, rv
 
 
+def _bn_act_close(dtype, y, rm, rv, dx, dgamma, dbeta, dres, ref):
+    """The bounds of test_bn_act_forward_backward against `ref` = _reference(...) (also applied by tests/poisoned_buffers.py)."""
+    y_ref, dx_ref, dw_ref, db_ref, dr_ref, rm_ref, rv_ref = ref
+    # forward: fp32 arithmetic on the same inputs, one rounding to the io dtype
+    eps_io = 2.0 ** -8 if dtype == torch.bfloat16 else 1e-5
+    assert (y.double().cpu() - y_ref).abs().max() <= eps_io * max(1.0, y_ref.abs().max().item())
+    assert (rm.double().cpu() - rm_ref).abs().max() <= 1e-5 and (rv.double().cpu() - rv_ref).abs().max() <= 1e-4
+    tol = 3e-2 if dtype == torch.bfloat16 else 2e-4
+    scale = max(dx_ref.abs().max().item(), 1e-6)
+    assert (dx.double().cpu() - dx_ref).abs().max() <= tol * scale
+    assert (dgamma.double().cpu() - dw_ref).abs().max() <= tol * max(dw_ref.abs().max().item(), 1.0)
+    assert (dbeta.double().cpu() - db_ref).abs().max() <= tol * max(db_ref.abs().max().item(), 1.0)
+    if dres is not None:
+        assert (dres.double().cpu() - dr_ref).abs().max() <= tol * max(dr_ref.abs().max().item(), 1.0)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("mode", ["relu", "plain", "res_relu", "res"])
@@ -46,17 +62,8 @@ def test_bn_act_forward_backward(hip, dtype, shape, mode):
     assert y.dtype == dtype and y.is_contiguous(**cl)
     y.backward(dy)
     y_ref, dx_ref, dw_ref, db_ref, dr_ref, rm_ref, rv_ref = _reference(x, w, b, res, relu, dy, y.detach() > 0)
-    # forward: fp32 arithmetic on the same inputs, one rounding to the io dtype
-    eps_io = 2.0 ** -8 if dtype == torch.bfloat16 else 1e-5
-    assert (y.double().cpu() - y_ref).abs().max() <= eps_io * max(1.0, y_ref.abs().max().item())
-    assert (rm.double().cpu() - rm_ref).abs().max() <= 1e-5 and (rv.double().cpu() - rv_ref).abs().max() <= 1e-4
-    tol = 3e-2 if dtype == torch.bfloat16 else 2e-4
-    scale = max(dx_ref.abs().max().item(), 1e-6)
-    assert (xg.grad.double().cpu() - dx_ref).abs().max() <= tol * scale
-    assert (wg.grad.double().cpu() - dw_ref).abs().max() <= tol * max(dw_ref.abs().max().item(), 1.0)
-    assert (bg.grad.double().cpu() - db_ref).abs().max() <= tol * max(db_ref.abs().max().item(), 1.0)
-    if has_res:
-        assert (rg.grad.double().cpu() - dr_ref).abs().max() <= tol * max(dr_ref.abs().max().item(), 1.0)
+    _bn_act_close(dtype, y, rm, rv, xg.grad, wg.grad, bg.grad, rg.grad if has_res else None,
+                  (y_ref, dx_ref, dw_ref, db_ref, dr_ref, rm_ref, rv_ref))
 
 
 def test_bn_variance_of_a_far_from_zero_signal(hip):
@@ -193,6 +200,16 @@ def test_batchnorm_relu_maxpool_as_one_op(hip, shape):
     assert hip.bn_relu_pool_served(x) and not hip.bn_relu_pool_served(x.float())
 
 
+def _wgrad_close(d, ref, rows):
+    """gdkvm_gemm_tn over `rows` rows against the fp64 product `ref` (test_hand_written_products_of_the_training_backward)."""
+    assert d.dtype == torch.float32 and ((d.double() - ref).abs() <= 1e-5 * (rows ** 0.5) * (1.0 + ref.abs() / rows ** 0.5)).all()
+
+
+def _colsum_close(db, ref, rows):
+    """gdkvm_gemm_tn_colsum's column sums over `rows` rows against fp64 (test_token_linear_and_split_k_weight_gradient)."""
+    assert (db.double().cpu() - ref.cpu()).abs().max() <= 1e-4 * rows ** 0.5
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_token_linear_and_split_k_weight_gradient(hip, dtype):
     torch.manual_seed(5)
@@ -223,8 +240,17 @@ def test_token_linear_and_split_k_weight_gradient(hip, dtype):
     # the bias gradient from the same launch (gdkvm_gemm_tn_colsum): column sums of dy, fp32 accumulation, the same bits on every run
     dw2, db2 = hip.wgrad(dy[:1001], x[:1001], colsum=True)
     assert torch.equal(dw2, hip.wgrad(dy[:1001], x[:1001]))
-    assert (db2.double().cpu() - dy[:1001].double().cpu().sum(0)).abs().max() <= 1e-4 * 1001 ** 0.5
+    _colsum_close(db2, dy[:1001].double().cpu().sum(0), 1001)
     assert torch.equal(db2, hip.wgrad(dy[:1001], x[:1001], colsum=True)[1])
+
+
+def _head_close(dtype, z, dx, dw, db, z64, dx64, dw64, db64):
+    """ops.head's logits and gradients against conv2d in fp64 on the same operands (test_head_forward_and_one_pass_backward)."""
+    tol = 2.0 ** -7 if dtype == torch.bfloat16 else 1e-5
+    assert (z.double() - z64).abs().max() <= tol * max(1.0, z64.abs().max().item())
+    assert (dx.double() - dx64).abs().max() <= tol * max(1.0, dx64.abs().max().item())
+    assert dw.dtype == torch.float32 and (dw.double() - dw64).abs().max() <= 1e-5 * max(1.0, dw64.abs().max().item())
+    assert (db.double() - db64).abs().max() <= 1e-5 * max(1.0, db64.abs().max().item())
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -246,11 +272,7 @@ def test_head_forward_and_one_pass_backward(hip, case, dtype):
     w64, b64 = conv.weight.detach().double().requires_grad_(True), conv.bias.detach().double().requires_grad_(True)
     z64 = F.conv2d(x64, w64, b64)
     z64.backward(gz.double())
-    tol = 2.0 ** -7 if dtype == torch.bfloat16 else 1e-5
-    assert (z.double() - z64).abs().max() <= tol * max(1.0, z64.abs().max().item())
-    assert (x.grad.double() - x64.grad).abs().max() <= tol * max(1.0, x64.grad.abs().max().item())
-    assert conv.weight.grad.dtype == torch.float32 and (conv.weight.grad.double() - w64.grad).abs().max() <= 1e-5 * max(1.0, w64.grad.abs().max().item())
-    assert (conv.bias.grad.double() - b64.grad).abs().max() <= 1e-5 * max(1.0, b64.grad.abs().max().item())
+    _head_close(dtype, z, x.grad, conv.weight.grad, conv.bias.grad, z64, x64.grad, w64.grad, b64.grad)
     g1 = (x.grad.clone(), conv.weight.grad.clone(), conv.bias.grad.clone())
     x.grad = None; conv.zero_grad(set_to_none=True)
     hip.head(x, conv.weight, conv.bias).backward(gz)
@@ -312,7 +334,7 @@ def test_hand_written_products_of_the_training_backward(hip, dtype, shape):
     a2 = a[:, :(K // 8) * 8]
     d = hip.wgrad(a2, b2)                                               # [K, N] fp32 = a^T b2 over the M rows
     ref2 = a2.double().t() @ b2.double()
-    assert d.dtype == torch.float32 and ((d.double() - ref2).abs() <= 1e-5 * (M ** 0.5) * (1.0 + ref2.abs() / M ** 0.5)).all()
+    _wgrad_close(d, ref2, M)
     assert torch.equal(d, hip.wgrad(a2, b2))                            # fixed summation order
 
 
@@ -371,6 +393,11 @@ def test_training_convolution_forward_and_data_gradient(hip, case):
     assert not hip.conv3x3_train_served(x, wt, (2, 2), (1, 1), (1, 1), 1)
 
 
+def conv3x3_wgrad_bound(ref, npix):
+    """The largest |gdkvm_conv3x3_wgrad - fp64| allowed over `npix` pixels (test_convolution_weight_gradient)."""
+    return 1e-5 * npix ** 0.5 * max(1.0, ref.abs().max().item() / npix ** 0.5)
+
+
 @pytest.mark.parametrize("case", [(6, 64, 64, 28, 28), (3, 128, 128, 14, 14), (9, 256, 256, 7, 7), (2, 384, 128, 14, 14), (2, 192, 64, 28, 28),
                                   (3, 64, 192, 9, 13), (1, 128, 64, 64, 64), (5, 64, 64, 3, 2)])
 def test_convolution_weight_gradient(hip, case):
@@ -383,7 +410,7 @@ def test_convolution_weight_gradient(hip, case):
     w64 = torch.zeros(k, c, 3, 3, device="cuda", dtype=torch.float64, requires_grad=True)
     F.conv2d(x.double(), w64, None, 1, 1).backward(dy.double())
     assert dw.dtype == torch.float32 and dw.shape == w64.shape and dw.is_contiguous()
-    assert (dw.double() - w64.grad).abs().max() <= 1e-5 * (n * h * w) ** 0.5 * max(1.0, w64.grad.abs().max().item() / (n * h * w) ** 0.5)
+    assert (dw.double() - w64.grad).abs().max() <= conv3x3_wgrad_bound(w64.grad, n * h * w)
     assert torch.equal(dw, hip.conv3x3_wgrad(x, dy))
     # the same numbers in the memory order of a channels_last parameter (no re-layout copy when they become its .grad)
     dwc = hip.conv3x3_wgrad(x, dy, channels_last=True)
@@ -641,6 +668,19 @@ def test_training_weight_packs_in_one_launch(hip):
     assert all("_gdkvm_train_packs" not in w.__dict__ for w in ws)
 
 
+def _stem_forward_close(y, ref):
+    assert y.shape == ref.shape and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
+    assert (y.double() - ref).abs().max() <= 2.0 ** -8 * max(1.0, ref.abs().max().item())
+
+
+def _stem_wgrad_close(dw, dref, w, n, hh, ww):
+    # the weight gradient is gdkvm_stem_wgrad_nchw: fp32 accumulation over the exact bf16 products, fixed order -> a few fp32 roundings of
+    # the sum's magnitude away from fp64, and the same bits on every run
+    assert dw.dtype == torch.float32 and dw.shape == w.shape
+    scale = max(1.0, dref.abs().max().item())
+    assert (dw.double() - dref).abs().max() <= 2e-5 * scale * max(1.0, (n * hh * ww / 4) ** 0.5 / 64)
+
+
 @pytest.mark.parametrize("case", [(3, 3, 112, 112), (2, 1, 64, 48), (1, 4, 130, 118), (9, 3, 20, 256)])
 def test_training_stem_convolution_on_the_stem_kernel(hip, case):
     """ops.stem_conv (gdkvm_stem_pack_s2d + gdkvm_stem_conv_nchw: the inference stem kernel in its convolution-only form) == conv2d(x, w,
@@ -654,16 +694,11 @@ def test_training_stem_convolution_on_the_stem_kernel(hip, case):
     y = ops.stem_conv(x, w)
     w64 = w.detach().bfloat16().double().requires_grad_()
     ref = F.conv2d(x.double(), w64, None, 2, 3)
-    assert y.shape == ref.shape and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
-    assert (y.double() - ref).abs().max() <= 2.0 ** -8 * max(1.0, ref.abs().max().item())
+    _stem_forward_close(y, ref)
     gy = torch.randn_like(y)
     (dw,) = torch.autograd.grad(y, w, gy)
     (dref,) = torch.autograd.grad(ref, w64, gy.double())
-    # the weight gradient is gdkvm_stem_wgrad_nchw: fp32 accumulation over the exact bf16 products, fixed order -> a few fp32 roundings of
-    # the sum's magnitude away from fp64, and the same bits on every run
-    assert dw.dtype == torch.float32 and dw.shape == w.shape
-    scale = max(1.0, dref.abs().max().item())
-    assert (dw.double() - dref).abs().max() <= 2e-5 * scale * max(1.0, (n * hh * ww / 4) ** 0.5 / 64)
+    _stem_wgrad_close(dw, dref, w, n, hh, ww)
     (dw2,) = torch.autograd.grad(ops.stem_conv(x, w), w, gy)
     assert torch.equal(dw, dw2)
     wcl = torch.nn.Parameter(w.detach().clone().contiguous(memory_format=torch.channels_last))      # the gradient takes the parameter's memory format
@@ -722,7 +757,15 @@ def test_strided_block_convolutions_forward_and_backward(hip, case):
     assert lib.gdkvm_conv_s2_dgrad(gyb.data_ptr(), zeros.data_ptr(), dg.data_ptr(), dx_zero.data_ptr(), n, c, hh, ww, k, 0, ops.BF16, st) == -6   # GDKVM_ERR_ARG
 
 
-@pytest.mark.parametrize("case", [(2, 64, 64, 12, 10, 3, 1, 1), (3, 128, 40, 9, 9, 1, 2, 0), (1, 64, 72, 16, 16, 5, 2, 2), (2, 64, 64, 8, 8, 3, 3, 0)])
+STRIDED_WINDOW_CASES = [(2, 64, 64, 12, 10, 3, 1, 1), (3, 128, 40, 9, 9, 1, 2, 0), (1, 64, 72, 16, 16, 5, 2, 2), (2, 64, 64, 8, 8, 3, 3, 0)]
+
+
+def _strided_wgrad_close(dw, rdw, like):
+    assert dw.stride() == like.stride()
+    assert (dw.double() - rdw).abs().max() <= 2e-5 * max(1.0, rdw.abs().max().item())
+
+
+@pytest.mark.parametrize("case", STRIDED_WINDOW_CASES)
 def test_strided_weight_gradient_any_window(hip, case):
     """ops.conv_wgrad_strided (gdkvm_conv_wgrad_strided) for windows / strides / paddings beyond the block's: against fp64 autograd."""
     from gdkvm_amd import ops
@@ -735,8 +778,7 @@ def test_strided_weight_gradient_any_window(hip, case):
     (rdw,) = torch.autograd.grad(ry, w64, gy.double())
     for like in (torch.empty(k, c, r, r, device="cuda"), torch.empty(k, c, r, r, device="cuda").contiguous(memory_format=torch.channels_last)):
         dw = ops.conv_wgrad_strided(x, gy, like, stride, pad)
-        assert dw.stride() == like.stride()
-        assert (dw.double() - rdw).abs().max() <= 2e-5 * max(1.0, rdw.abs().max().item())
+        _strided_wgrad_close(dw, rdw, like)
 
 
 def test_training_step_is_deterministic(hip):
