@@ -62,6 +62,15 @@ tools/convert_camus.py --native-spacing, else `data.native_spacing_um`), else in
 that one pixel reads as 1.0).  Like the grid's `surface` block these are the distances of the unfiltered mask.  The volumes stay on the
 grid.  Every other key keeps its value; with the keys off nothing new runs.
 
+With `data.lv_strain` (and `lv_class` >= 0) the contour of the class is measured as well (ops.lv_contour on the post-processed prediction and on
+the target: its border with `data.lv_wall_classes` is the endocardium, its border with `data.lv_base_classes` the mitral plane): a `strain`
+block holds the `unit` of the lengths ("mm" with a spacing for every clip, and then ED / ES are the `lv_mm` block's frames, else "px" and the
+`lv` block's frames), `clips_with_strain`, `gls_mae`, `gls_bias`, `gls_pearson_r`, `mean_ref_gls`, `mean_pred_gls` of the global longitudinal
+strain (L_ES - L_ED) / L_ED of the endocardial contour (ops.contour_lengths / lv_strain), and a `long_axis` block with the same statistics of
+the apex-to-annulus shortening over the clips whose ED and ES frames have a base interface on both sides, and `clips_without_landmarks`.
+With an empty `lv_base_classes` (a binary dataset: `lv_wall_classes: [0]`) the strain is that of the whole outline and there are no
+landmarks; the block says so.  Every other key keeps its value; with the key off nothing new runs.
+
 --ema evaluates the checkpoint's averaged weights (its "ema" entry, written by runs with optim.ema_decay > 0) instead of the trained ones.
 
     python eval.py --config config/config_gdkvm_01.yaml --weights outputs/gdkvm_step3000.pth [--ema] [key=value ...]"""
@@ -165,6 +174,11 @@ def main(argv=None):
         bp_rows = lambda: [torch.zeros(len(ds), cfg.data.frames, w, dtype=dt, device=dev)
                            for w, dt in ((12, torch.int64), (20, torch.int64), (6, torch.float64))]
         bp_pred, bp_tgt = bp_rows(), bp_rows()
+    st_on = cfg.data.lv_strain                                    # off: no new call below (config: on needs lv_class >= 0)
+    if st_on:
+        st_args = dict(cls=lv_cls, wall=cfg.data.lv_wall_classes, base=cfg.data.lv_base_classes)
+        # ops.ef_summary of the GLS [8], of the long-axis shortening [8], then the clips with a strain and without landmarks
+        st_sums = torch.zeros(17, dtype=torch.float64, device=dev)
     nat_on = cfg.data.native_eval                                 # off: no new call below
     ns_cls = cfg.data.native_surface_class if nat_on else -1      # -1 = off: no new call below (config: >= 0 needs native_eval)
     if nat_on:
@@ -197,7 +211,7 @@ def main(argv=None):
         consumer asks for the next batch, so nothing may read it later -- the temporal vote of the prediction, its largest-component filter, its
         hole filling and its surface distances, one batch behind, want the target and get a copy made here.  The last element is the
         target's volumes in mL (with a spacing and lv_class >= 0): the loader is unshuffled, so the clips of a submission are the next rows
-        of the spacing table."""
+        of the spacing table; behind it, with data.lv_strain, the target's contour lengths."""
         pending = None
         sub = lo                                                  # the first clip of the batch being submitted
         for frames, target in DevicePrefetcher(dl, dev, slots=3, frames_dtype=fdt, target_dtype=torch.uint8):
@@ -210,9 +224,13 @@ def main(argv=None):
                 if bp_on:                                         # the target's records at the clips' own rows
                     for tab, rec in zip(bp_tgt, t_rec):
                         tab[sub:sub + target.shape[0]] = rec
-                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy, t_ml)
+                t_len = None
+                if st_on:                                         # the target's contour lengths [B, T, 3], mm with a spacing
+                    t_sp = spacing[sub:sub + target.shape[0], None] if mm else None
+                    t_len = ops.contour_lengths(ops.lv_contour(target, spacing_um=t_sp, **st_args), t_sp)
+                nxt = (nxt, t_geom[..., 1].contiguous(), t_stats[..., 0].contiguous(), t_copy, t_ml, t_len)
             else:
-                nxt = (nxt, None, None, t_copy, None)
+                nxt = (nxt, None, None, t_copy, None, None)
             sub += target.shape[0]
             if pending is not None:
                 yield pending[0].get() + pending[1:]
@@ -220,7 +238,7 @@ def main(argv=None):
         if pending is not None:
             yield pending[0].get() + pending[1:]
 
-    for mask, c, t_vol, t_npix, t_copy, t_ml in batches():
+    for mask, c, t_vol, t_npix, t_copy, t_ml, t_len in batches():
         sp = spacing[i:i + mask.shape[0], None] if mm else None   # [B, 1, 2]: results arrive one batch behind, in order, and i counts them
         # only frames that carry labels count (EchoNet-Dynamic: the two traced frames of a clip -- gdkvm_amd.data.IGNORE_LABEL everywhere
         # else, where a predicted pixel must not enter |A|): a labelled frame has a non-empty target in some class
@@ -272,6 +290,20 @@ def main(argv=None):
                 _, q_val = ops.lv_ef(q_geom[..., 1], q_stats[..., 0], pick_vol=t_ml, pick_npix=t_npix)
                 ok = (m_idx[:, 0] >= 0) & (m_val[:, 0] > 0)
                 ef_sums[8:] += torch.cat([ops.ef_summary(q_val[:, k], m_val[:, k], ok) for k in (2, 0, 1)])
+            if st_on:
+                # the contour of the same post-processed mask, read at the target's ED / ES frames as picked above (mm: on the mL curve);
+                # a clip counts when the block above counts it and both sides have a contour at both frames
+                s_rec = ops.lv_contour(measured, spacing_um=sp, **st_args)
+                s_len = ops.contour_lengths(s_rec, sp)
+                s_npix = s_rec[..., 0].contiguous()
+                picks, use = (m_idx, ok) if mm else (r_idx, (r_idx[:, 0] >= 0) & (r_val[:, 0] > 0))
+                parts = []
+                for k in (0, 2):                                  # the endocardial contour, then the apex-to-annulus axis
+                    _, g_ref, _, g_ok = ops.lv_strain(t_len[..., k].contiguous(), t_npix, picks)
+                    _, g_pred, _, p_ok = ops.lv_strain(s_len[..., k].contiguous(), s_npix, picks)
+                    parts.append(use & g_ok & p_ok & (parts[0] if parts else True))
+                    st_sums[4 * k:4 * k + 8] += ops.ef_summary(g_pred[:, 0], g_ref[:, 0], parts[-1])
+                st_sums[16] += (parts[0] & ~parts[1]).sum()
         if beats_on:
             # beat by beat, on the curves of the same post-processed mask: the prediction's, and the target's where it labels every valid frame
             ln = bt_len[i:i + mask.shape[0]]
@@ -312,6 +344,8 @@ def main(argv=None):
         torch.distributed.all_reduce(counts)                      # the only exchanges: 3 integers per class ...
         if lv_cls >= 0:
             torch.distributed.all_reduce(ef_sums)                 # ... and the eight EF sums
+        if st_on:
+            torch.distributed.all_reduce(st_sums)                 # ... and the strain sums
         if vote:
             torch.distributed.all_reduce(tv_acc)                  # ... and the voted mask's counts and change totals
         if keep:
@@ -346,6 +380,20 @@ def main(argv=None):
                     cnt = max(float(sums[0]), 1.0)
                     lv_mm[f"{name}_mae_ml"], lv_mm[f"{name}_bias_ml"] = float(sums[2]) / cnt, float(sums[1]) / cnt
                 res["lv_mm"] = {k: (v if isinstance(v, int) else round(v, 5)) for k, v in lv_mm.items()}
+            if st_on:
+                acc = st_sums.cpu()
+                names = {"clips_with_ef": "clips_with_strain", "ef_mae": "gls_mae", "ef_bias": "gls_bias", "ef_pearson_r": "gls_pearson_r",
+                         "mean_ref_ef": "mean_ref_gls", "mean_pred_ef": "mean_pred_gls"}
+                axis = {"clips_with_ef": "clips_with_landmarks", "ef_mae": "shortening_mae", "ef_bias": "shortening_bias",
+                        "ef_pearson_r": "shortening_pearson_r", "mean_ref_ef": "mean_ref_shortening", "mean_pred_ef": "mean_pred_shortening"}
+                rnd5 = lambda v: v if isinstance(v, int) else round(v, 5)
+                blk = {"unit": "mm" if mm else "px", "wall_classes": list(cfg.data.lv_wall_classes), "base_classes": list(cfg.data.lv_base_classes),
+                       **{names[k]: rnd5(v) for k, v in ops.ef_stats(acc[:8]).items()}}
+                if cfg.data.lv_base_classes:
+                    blk["long_axis"] = {**{axis[k]: rnd5(v) for k, v in ops.ef_stats(acc[8:16]).items()}, "clips_without_landmarks": int(acc[16])}
+                else:
+                    blk["long_axis"] = "none: data.lv_base_classes is empty, the strain is that of the whole outline and there are no landmarks"
+                res["strain"] = blk
         if vote:
             acc = tv_acc.cpu()
             tv_dice = ops.dice_from_counts(acc[:-5].view(cfg.data.num_classes, 3)).tolist()

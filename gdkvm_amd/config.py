@@ -49,6 +49,11 @@ class DataCfg:
                                      # (ops.surface_distance_native): a `surface` block inside `native`; -1 = off, >= 0 needs native_eval
     native_spacing_um: Any = None    # eval.py: [row_um, col_um], the micrometres per NATIVE pixel (integers in 1..4095) for datasets that carry
                                      # none of their own (data.native_spacing_table); without a spacing for every clip the block is in pixels
+    lv_strain: bool = False          # eval.py: global longitudinal strain of lv_class from its contour's length at ED and ES (ops.lv_contour /
+                                     # contour_lengths / lv_strain): a `strain` block; needs lv_class >= 0
+    lv_wall_classes: Any = field(default_factory=lambda: [2])    # ... the classes whose border with lv_class is the endocardium (non-empty)
+    lv_base_classes: Any = field(default_factory=lambda: [3])    # ... the classes whose border with lv_class is the mitral plane: apex, long
+                                     # axis and its shortening come from it.  A binary dataset sets [0] / []: the whole outline's strain, no landmarks
     synthetic_beats: float = 1.0     # the synthetic clips' heart beats per clip (> 0; 1.0: the clips of before, bit for bit)
     whole_video: bool = False        # echonet_npz only: a clip is the video's first `frames` frames (several beats), not the window around ED / ES
 
@@ -206,6 +211,27 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     if nsp is not None and (not isinstance(nsp, list) or len(nsp) != 2
                             or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4095 for v in nsp)):
         raise ValueError(f"data.native_spacing_um = {nsp!r}: null or [row_um, col_um], two integers in 1..4095 (micrometres per native pixel)")
+    if not isinstance(d.lv_strain, bool):
+        raise ValueError(f"data.lv_strain = {d.lv_strain!r}: true or false")
+    for key in ("lv_wall_classes", "lv_base_classes"):
+        cl = getattr(d, key)
+        if not isinstance(cl, list) or any(isinstance(c, bool) or not isinstance(c, int) for c in cl) or len(set(cl)) != len(cl):
+            raise ValueError(f"data.{key} = {cl!r}: a list of distinct class numbers")
+    if d.lv_strain:                  # (the class lists are only read with the switch on: a binary dataset keeps the defaults while it is off)
+        if d.lv_class < 0:
+            raise ValueError("data.lv_strain needs data.lv_class >= 0 (the class whose contour is measured)")
+        top = min(d.num_classes, 32) - 1
+        for key in ("lv_wall_classes", "lv_base_classes"):
+            cl = getattr(d, key)
+            if any(not 0 <= c <= top for c in cl) or d.lv_class in cl:
+                raise ValueError(f"data.{key} = {cl!r}: classes in 0..{top} other than data.lv_class = {d.lv_class}")
+        if d.lv_class > top:
+            raise ValueError(f"data.lv_strain: data.lv_class = {d.lv_class} outside 0..{top}")
+        if not d.lv_wall_classes:
+            raise ValueError("data.lv_wall_classes is empty: the contour needs at least one class on the other side "
+                             "(a binary dataset: lv_wall_classes: [0], lv_base_classes: [])")
+        if set(d.lv_wall_classes) & set(d.lv_base_classes):
+            raise ValueError(f"data.lv_wall_classes = {d.lv_wall_classes!r} and data.lv_base_classes = {d.lv_base_classes!r} overlap")
     if d.whole_video and d.kind != "echonet_npz":
         raise ValueError(f"data.whole_video is for data.kind = echonet_npz, not {d.kind!r}")
     if isinstance(d.beat_distance, bool) or not isinstance(d.beat_distance, int) or not 1 <= d.beat_distance <= 4096:

@@ -129,6 +129,7 @@ SIGNATURES = {
     "gdkvm_lv_ef": (_i, [_vp] * 6 + [_i, _i, ctypes.c_int64, _vp]),
     "gdkvm_lv_beats": (_i, [_vp] * 7 + [_i] * 5 + [ctypes.c_int64, _vp]),
     "gdkvm_lv_biplane": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
+    "gdkvm_lv_contour": (_i, [_vp] * 3 + [_i] * 4 + [ctypes.c_uint] * 2 + [_vp]),
     "gdkvm_largest_component_workspace_bytes": (_sz, [_i] * 3),
     "gdkvm_largest_component": (_i, [_vp] * 5 + [_sz] + [_i] * 6 + [_vp]),
     "gdkvm_fill_holes_workspace_bytes": (_sz, [_i] * 3),
@@ -2218,6 +2219,162 @@ def lv_biplane(stats: torch.Tensor, disks: torch.Tensor, geom: torch.Tensor, spa
     npix = torch.empty((P, T), dtype=torch.int64, device=dev)
     _call("gdkvm_lv_biplane", dev, stats, disks, geom, sp, pr, out, npix, C, T, D, P)
     return out, npix
+
+
+LV_CONTOUR_BAND_ROWS, LV_CONTOUR_WORD_BITS = 64, 64      # GDKVM_LV_CONTOUR_BAND_ROWS, GDKVM_LV_CONTOUR_WORD_BITS
+LV_CONTOUR_MAX_BYTE = 31                                 # cls and the members of the sets are bytes in 0..31
+
+# (dy, dx) of a class pixel's 8 neighbours under the direction their pair counts for: E, S, SE, SW
+_CONTOUR_NEIGHBOURS = (((0, 1), (0, -1)), ((1, 0), (-1, 0)), ((1, 1), (-1, -1)), ((1, -1), (-1, 1)))
+
+
+def _byte_set(what: str, name: str, members) -> int:
+    ms = [members] if isinstance(members, int) and not isinstance(members, bool) else list(members)
+    if any(isinstance(c, bool) or int(c) != c or not 0 <= int(c) <= LV_CONTOUR_MAX_BYTE for c in ms) or len({int(c) for c in ms}) != len(ms):
+        raise GdkvmError(f"{what}: {name} = {ms} must be distinct integers in 0..{LV_CONTOUR_MAX_BYTE}")
+    bits = 0
+    for c in ms:
+        bits |= 1 << int(c)
+    return bits
+
+
+def _lv_contour_host(m: torch.Tensor, sp: Optional[torch.Tensor], cls: int, wall: int, base: int) -> torch.Tensor:
+    """The rule of gdkvm_lv_contour for the frames m [F, H, W] (uint8, CPU) in int64: rec [F, 16].  sp: int32 [F, 2] or None."""
+    F, H, W = m.shape
+    rec = torch.zeros((F, 16), dtype=torch.int64)
+    if F == 0:
+        return rec
+    pad = torch.nn.functional.pad(m.to(torch.int64), (1, 1, 1, 1), value=0)      # a position outside the frame reads as byte 0
+    inside = torch.zeros((H + 2, W + 2), dtype=torch.bool)
+    inside[1:-1, 1:-1] = True
+    lut = torch.zeros((256, 3), dtype=torch.bool)
+    for b in range(LV_CONTOUR_MAX_BYTE + 1):
+        lut[b] = torch.tensor([b == cls, bool((wall >> b) & 1), bool((base >> b) & 1)])
+    planes = lut[pad]                                                             # [F, H + 2, W + 2, 3]
+    C = (planes[..., 0] & inside)[:, 1:-1, 1:-1]
+    ys = torch.arange(H, dtype=torch.int64)[None, :, None]
+    xs = torch.arange(W, dtype=torch.int64)[None, None, :]
+    rec[:, 0] = C.sum((1, 2))
+    for s in (0, 1):
+        X = planes[..., 1 + s]
+        for d, pair in enumerate(_CONTOUR_NEIGHBOURS):
+            for dy, dx in pair:
+                hit = C & X[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+                rec[:, 1 + 4 * s + d] += hit.sum((1, 2))
+                if s == 1 and d < 2:
+                    rec[:, 9] += (hit * (2 * xs + dx)).sum((1, 2))
+                    rec[:, 10] += (hit * (2 * ys + dy)).sum((1, 2))
+    nb = rec[:, 5] + rec[:, 6]
+    has = nb > 0
+    den = torch.where(has, 2 * nb, torch.ones_like(nb))
+    bx2 = torch.div(2 * rec[:, 9] + nb, den, rounding_mode="floor")
+    by2 = torch.div(2 * rec[:, 10] + nb, den, rounding_mode="floor")
+    ry = torch.ones(F, dtype=torch.int64) if sp is None else sp[:, 0].to(torch.int64)
+    rx = torch.ones(F, dtype=torch.int64) if sp is None else sp[:, 1].to(torch.int64)
+    d2 = (ry[:, None, None] * (2 * ys - by2[:, None, None])) ** 2 + (rx[:, None, None] * (2 * xs - bx2[:, None, None])) ** 2
+    d2 = torch.where(C, d2, torch.full_like(d2, -1)).reshape(F, -1)
+    best = d2.amax(1)
+    idx = torch.arange(H * W, dtype=torch.int64)[None, :].expand(F, -1)
+    apex = torch.where(d2 == best[:, None], idx, torch.full_like(idx, H * W)).amin(1)                # ties: the smallest y W + x
+    minus = torch.full_like(nb, -1)
+    rec[:, 11], rec[:, 12], rec[:, 13] = torch.where(has, bx2, minus), torch.where(has, by2, minus), torch.where(has, apex, minus)
+    rec[:, 14] = torch.where(has, best, torch.zeros_like(best))
+    if sp is not None:
+        bad = ((sp < 1) | (sp > SPACING_UM_MAX)).any(1)
+        rec[bad] = -1
+    return rec
+
+
+def lv_contour(mask: torch.Tensor, cls: int = 1, wall=(2,), base=(3,), spacing_um: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gdkvm_lv_contour: per frame of mask [..., H, W] uint8 the contour record of class `cls` (0..31) against the byte sets `wall` and `base`
+    (sequences of distinct bytes in 0..31, disjoint, without cls; wall non-empty, base may be empty): rec int64 [..., 16] = n, N_E N_S N_SE
+    N_SW of the wall interface, the same of the base interface, SX2 SY2, the base point bx2 by2 in half pixels, the apex's y W + x, D2 at the
+    apex, 0 (definition: include/gdkvm.h; every word an exact integer; without a base interface words 11-13 are -1).  CAMUS: cls = cavity,
+    wall = myocardium, base = atrium; a binary mask takes wall = (0,), base = () and has no landmarks.  spacing_um int32 [..., 2] = (row_um,
+    col_um), broadcast over the leading dimensions, only moves the apex (D2 in um^2 x 4); None: pixels.  contour_lengths turns the record
+    into lengths.  The mask may start at any byte address.  CPU tensors take the same rule in torch, so the wrapper works without a GPU."""
+    what = "lv_contour"
+    lead, frames, H, W = _mask_frames(what, mask, cls)
+    if isinstance(cls, bool) or int(cls) != cls or not 0 <= int(cls) <= LV_CONTOUR_MAX_BYTE:
+        raise GdkvmError(f"{what}: cls = {cls} outside 0..{LV_CONTOUR_MAX_BYTE}")
+    cls = int(cls)
+    wall_set, base_set = _byte_set(what, "wall", wall), _byte_set(what, "base", base)
+    if wall_set == 0:
+        raise GdkvmError(f"{what}: wall is empty")
+    if wall_set & base_set:
+        raise GdkvmError(f"{what}: wall and base overlap")
+    if (wall_set | base_set) >> cls & 1:
+        raise GdkvmError(f"{what}: wall / base holds cls = {cls}")
+    if not mask.is_cuda:
+        if not mask.is_contiguous():
+            raise GdkvmError("GDKVM ops need contiguous tensors")
+        sp = None if spacing_um is None else _spacing_frames(what, spacing_um, lead, mask.device).reshape(frames, 2)
+        return _lv_contour_host(mask.reshape(frames, H, W), sp, cls, wall_set, base_set).reshape(lead + (16,))
+    dev = _dev(mask)
+    sp = None if spacing_um is None else _spacing_frames(what, spacing_um, lead, dev)
+    rec = torch.empty(lead + (16,), dtype=torch.int64, device=dev)
+    _call("gdkvm_lv_contour", dev, mask, sp, rec, frames, H, W, cls, wall_set, base_set)
+    return rec
+
+
+def contour_lengths(rec: torch.Tensor, spacing_um: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The three lengths of lv_contour's records, float64 [..., 3] = L_wall (the endocardial contour), L_base (the annulus width), L_axis
+    (apex to base point), on rec's device: the Cauchy-Crofton length over the four lattice directions, weighted by their angular sectors
+    (include/gdkvm.h), fp64 with one rounding per operation.  spacing_um int32 [..., 2] as lv_contour took it: mm; None: pixels.  L_axis is
+    0 without a base interface; a -1 record (spacing out of range) gives -1."""
+    if rec.dtype != torch.int64 or rec.dim() < 1 or rec.shape[-1] != 16:
+        raise GdkvmError(f"contour_lengths: rec must be int64 [..., 16], got {rec.dtype} {tuple(rec.shape)}")
+    lead = tuple(rec.shape[:-1])
+    r = rec.to(torch.float64)
+    if spacing_um is None:
+        ry = rx = torch.ones(lead, dtype=torch.float64, device=rec.device)
+        unit = 1.0
+    else:
+        sp = _spacing_frames("contour_lengths", spacing_um, lead, rec.device).to(torch.float64)
+        ry, rx = sp[..., 0], sp[..., 1]
+        unit = 1000.0
+    phi = torch.atan2(ry, rx)
+    delta = (ry * rx) / torch.sqrt(ry * ry + rx * rx)
+    out = []
+    for s in (0, 1):
+        ne, ns, nd = r[..., 1 + 4 * s], r[..., 2 + 4 * s], r[..., 3 + 4 * s] + r[..., 4 + 4 * s]
+        out.append(0.5 * (phi * (ne * ry) + (math.pi / 2 - phi) * (ns * rx) + (math.pi / 4) * (nd * delta)))
+    out.append(torch.sqrt(r[..., 14].clamp(min=0.0)) / 2.0)
+    res = torch.stack(out, -1) / unit
+    return torch.where((rec[..., 0] < 0)[..., None], torch.full_like(res, -1.0), res)
+
+
+def lv_strain(length: torch.Tensor, npix: torch.Tensor, ed_es: torch.Tensor, min_pixels: int = 1):
+    """Longitudinal strain of clips from a length curve, torch fp64 on the inputs' device (a few operations on [B, T]: no kernel).  length
+    float64 [B, T] (contour_lengths' L_wall, or L_axis for the long-axis shortening), npix int64 [B, T] (rec[..., 0]), ed_es = lv_ef's
+    ed_es_nvalid int32 [B, 3].  Frame t is valid when npix >= min_pixels and length > 0.  The strain curve is e_t = (L_t - L_ED) / L_ED, GLS
+    = e_ES; the peak strain is the minimum of e_t over the valid frames, ties to the lowest t.  ok holds when ed >= 0 and both picked frames
+    are valid.  Returns (curve float64 [B, T], 0 at invalid frames; gls_peak float64 [B, 3] = GLS, peak strain, L_ED; peak_frame int64 [B];
+    ok bool [B]); a clip that is not ok has curve = gls_peak = 0 and peak_frame = -1."""
+    if length.dim() != 2 or length.dtype != torch.float64:
+        raise GdkvmError(f"lv_strain: length must be float64 [B, T], got {length.dtype} {tuple(length.shape)}")
+    B, T = length.shape
+    if npix.dtype != torch.int64 or tuple(npix.shape) != (B, T):
+        raise GdkvmError(f"lv_strain: npix must be int64 {(B, T)}, got {npix.dtype} {tuple(npix.shape)}")
+    if ed_es.dim() != 2 or tuple(ed_es.shape) != (B, 3) or torch.is_floating_point(ed_es):
+        raise GdkvmError(f"lv_strain: ed_es must be an integer tensor {(B, 3)}, got {ed_es.dtype} {tuple(ed_es.shape)}")
+    if T < 1:
+        raise GdkvmError("lv_strain: T = 0")
+    valid = (npix >= int(min_pixels)) & (length > 0)
+    ed, es = ed_es[:, 0].to(torch.int64), ed_es[:, 1].to(torch.int64)
+    picked = (ed >= 0) & (es >= 0) & (ed < T) & (es < T)
+    ed_c, es_c = ed.clamp(0, T - 1)[:, None], es.clamp(0, T - 1)[:, None]
+    ok = picked & valid.gather(1, ed_c)[:, 0] & valid.gather(1, es_c)[:, 0]
+    l_ed = torch.where(ok, length.gather(1, ed_c)[:, 0], torch.ones_like(length[:, 0]))
+    use = valid & ok[:, None]
+    curve = torch.where(use, (length - l_ed[:, None]) / l_ed[:, None], torch.zeros_like(length))
+    gls = curve.gather(1, es_c)[:, 0]
+    peak = torch.where(use, curve, torch.full_like(curve, float("inf"))).amin(1)
+    t = torch.arange(T, dtype=torch.int64, device=length.device)[None, :].expand(B, -1)
+    frame = torch.where(use & (curve == peak[:, None]), t, torch.full_like(t, T)).amin(1)
+    zero = torch.zeros_like(gls)
+    gls_peak = torch.stack([torch.where(ok, gls, zero), torch.where(ok, peak, zero), torch.where(ok, l_ed, zero)], -1)
+    return curve, gls_peak, torch.where(ok, frame, torch.full_like(frame, -1)), ok
 
 
 def beats_summary(pred_summ: torch.Tensor, pred_info: torch.Tensor, ref_summ: torch.Tensor, ref_info: torch.Tensor,

@@ -12,7 +12,9 @@ size) through
 and, with data.lv_class >= 0, measures the class on the grid per clip: ops.lv_measure / lv_ef (pixel^3; EF is a ratio), ops.lv_beats with
 data.lv_beats, and with a native pixel spacing (row_um, col_um) ops.lv_measure_mm at the grid spacing (rint(row_um h0 / H),
 rint(col_um w0 / W)) -- tools/convert_camus.py's spacing_um formula; the mL keys are left out, with the reason, when that falls outside
-1..4095.  With overlay=True it also draws what a person looks at, ops.overlay_native of the native frames under those native masks (the
+1..4095.  With data.lv_strain a `strain` entry per clip holds the global longitudinal strain of the class's endocardial contour between
+those ED / ES frames, the peak strain and its frame, and the contour and apex-to-annulus lengths at ED and ES (ops.lv_contour /
+contour_lengths / lv_strain; mm for a clip with a grid spacing, else px).  With overlay=True it also draws what a person looks at, ops.overlay_native of the native frames under those native masks (the
 configuration's `overlay:` section); overlay_clip draws one clip with an optional reference mask, which is what eval.py's
 eval_stage.vis_overlay writes.  Everything after the copy runs on the device: there is no CPU path for the forward, and a CPU model is
 refused.  ops.surface_distance_native, the native family's measurement against a tracing, has no place here: a prediction has no target
@@ -151,8 +153,8 @@ def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, r
                 sp = torch.tensor([g or (1, 1) for g in grid_sp], dtype=torch.int32).reshape(B, 1, 2).to(dev)
                 q_stats, _, q_geom = ops.lv_measure_mm(measured, sp, cls=lv_cls)
                 q_vol = q_geom[..., 1].contiguous()
-                m_idx, m_val = ops.lv_ef(q_vol, q_stats[..., 0].contiguous())
-                m_idx, m_val = m_idx.tolist(), m_val.tolist()
+                m_picks, m_val = ops.lv_ef(q_vol, q_stats[..., 0].contiguous())
+                m_idx, m_val = m_picks.tolist(), m_val.tolist()
             for b, g in enumerate(grid_sp):
                 if g is not None:
                     per_clip[b]["lv_mm"] = {"grid_spacing_um": list(g), "ed_frame": m_idx[b][0], "es_frame": m_idx[b][1],
@@ -170,6 +172,28 @@ def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, r
             for b, (bi, bs) in enumerate(zip(b_info.tolist(), b_summ.tolist())):
                 per_clip[b]["beats"] = {"volume_unit": unit, "beats": bi[0], "end_systoles": bi[1], "frames_below_min": bi[2],
                                         "ef_mean": r5(bs[0]), "ef_min": r5(bs[1]), "ef_max": r5(bs[2]), "mean_cycle_frames": r5(bs[3])}
+        if d.lv_strain:
+            # the contour of the same post-processed mask: in mm at the lv_mm block's ED / ES for a clip with a grid spacing, else in pixels
+            # at the lv block's
+            c_args = dict(cls=lv_cls, wall=d.lv_wall_classes, base=d.lv_base_classes)
+            forms = {"px": (ops.lv_contour(measured, **c_args), None, idx)}
+            if q_vol is not None:
+                forms["mm"] = (ops.lv_contour(measured, spacing_um=sp, **c_args), sp, m_picks)
+            rows = {}
+            for unit, (rec, usp, picks) in forms.items():
+                lens = ops.contour_lengths(rec, usp)
+                npx = rec[..., 0].contiguous()
+                _, gp, pf, ok = ops.lv_strain(lens[..., 0].contiguous(), npx, picks)
+                _, ga, _, oka = ops.lv_strain(lens[..., 2].contiguous(), npx, picks)
+                rows[unit] = [t.tolist() for t in (lens, gp, pf, ok, ga, oka, picks)]
+            for b in range(B):
+                unit = "mm" if "mm" in rows and grid_sp[b] is not None else "px"
+                lens, gp, pf, ok, ga, oka, picks = (r[b] for r in rows[unit])
+                ed, es = picks[0], picks[1]
+                at = lambda t, k: r5(lens[t][k]) if t >= 0 else 0.0
+                per_clip[b]["strain"] = {"unit": unit, "ok": bool(ok), "gls": r5(gp[0]), "peak_strain": r5(gp[1]), "peak_frame": pf,
+                                         "wall_ed": at(ed, 0), "wall_es": at(es, 0), "landmarks": bool(oka), "axis_ed": at(ed, 2),
+                                         "axis_es": at(es, 2), "axis_shortening": r5(ga[0])}
     report = {"clips": B, "frames": T, "grid": [H, W], "forward": {"graph_replays": runner.replays, "eager_calls": runner.eager_calls},
               "per_clip": per_clip}
     res = {"masks": masks, "grid_mask": measured, "frames": frames, "sizes": sizes, "report": report}

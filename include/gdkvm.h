@@ -730,6 +730,48 @@ int gdkvm_lv_beats(const int64_t* area, const double* vol, const int32_t* length
  * in ascending j; no allocation, no atomics, no synchronisation with the host: capturable; bit-reproducible. */
 int gdkvm_lv_biplane(const int64_t* stats, const int64_t* disks, const double* geom, const int32_t* spacing_um, const int32_t* pairs,
                      double* out, int64_t* npix, int C, int T, int D, int P, void* stream);
+/* Contour length and landmarks of one class of label masks (csrc/lv_contour.hip): what global longitudinal strain needs -- the length of the
+ * endocardial contour, the width of the mitral annulus, the apex and the apex-to-annulus long axis.  CAMUS class 1 (cavity) borders class 2
+ * (myocardium) along the endocardium and class 3 (atrium) along the mitral plane.  Per frame the inputs are:
+ *   - mask [H, W] uint8, H, W in 1..1024.
+ *   - class cls in 0..31.
+ *   - two sets of bytes given as 32-bit masks over the bytes 0..31: wall_set and base_set.  The two sets are disjoint, and neither holds
+ *     cls.  wall_set must be non-zero.  base_set may be 0.
+ *   - Bytes >= 32 (255 included) belong to no set.
+ *   - A position outside the frame reads as byte 0.  This is the background rule the surface kernels already use.
+ *   - The spacing is (ry, rx) um per pixel down the rows and along the columns, each in 1..4095.  A NULL spacing pointer means ry = rx = 1.
+ *   1. Pair counts.  The four directions are d in {E = (0,+1), S = (+1,0), SE = (+1,+1), SW = (+1,-1)}, written (dy, dx).  For a set X,
+ *      N_d[X] is the number of unordered position pairs {p, p+d} where one member is an in-frame pixel holding cls and the other member's
+ *      byte (outside the frame: 0) is in X.  Equivalently: over every cls pixel and each of its 8 neighbours, count the neighbours whose
+ *      byte is in X, sorted by direction.  These are the intersection counts of the interface curve between the class and X with the four
+ *      families of lattice lines.
+ *   2. Base point.  Over the E and S pairs of base_set only:  n_b = N_E + N_S,  SX2 = sum (p.x + q.x),  SY2 = sum (p.y + q.y).  These are
+ *      twice the crack midpoints, so they are integers.  An outside neighbour contributes -1 or W / H.
+ *      bx2 = floor((2 SX2 + n_b) / (2 n_b)), with the floor taken towards -infinity, and by2 likewise.  This is the interface's centroid in
+ *      half-pixel units, rounded half up.
+ *   3. Apex.  The apex is the cls pixel p that maximises D2(p) = (ry (2 p.y - by2))^2 + (rx (2 p.x - bx2))^2.  This is below 2^48, so it
+ *      is exact in int64.  Ties go to the smallest p.y W + p.x.
+ *   4. Record rec [frames, 16] int64, 16-byte aligned:
+ *        word 0: n, the pixels of cls.   words 1-4: N_E, N_S, N_SE, N_SW of wall_set.   words 5-8: the same four counts of base_set.
+ *        words 9-10: SX2, SY2.   words 11-12: bx2, by2.   word 13: the apex's y W + x.   word 14: D2 at the apex.   word 15: 0.
+ *      With n_b == 0 (which covers n == 0): words 9, 10 and 14 are 0 and words 11-13 are -1.
+ *      For a frame whose spacing lies outside 1..4095, every word is -1, as in gdkvm_lv_measure_mm.
+ *   5. Every word is an integer that depends on neither the algorithm nor the schedule.
+ * From the record, three lengths in fp64 with one rounding per operation (gdkvm_amd.ops.contour_lengths, on the host or the device):
+ *   phi = atan2(ry, rx),  delta = (ry rx) / sqrt(ry^2 + rx^2);
+ *   for a set's four counts:  L = 0.5 (phi (N_E ry) + (pi/2 - phi) (N_S rx) + (pi/4) ((N_SE + N_SW) delta))
+ *   (the Cauchy-Crofton length with the four lattice directions, weighted by their angular sectors; with ry = rx it reduces to
+ *   (pi/8) (N_E + N_S + (N_SE + N_SW) / sqrt 2));  L_wall is the endocardial contour, L_base the annulus width, L_axis = sqrt(D2) / 2 the
+ *   apex-to-base-point distance.  Units are um, then mm (/ 1000); without a spacing the units are pixels.
+ * mask [frames, H, W] contiguous, ANY byte alignment; spacing_um [frames, 2] int32 on the device (4-byte aligned) or NULL.  A bad shape is
+ * GDKVM_ERR_SHAPE; cls outside 0..31, sets that overlap or hold cls, wall_set == 0, a null mask, a null or misaligned rec and a misaligned
+ * spacing_um are GDKVM_ERR_ARG; both before any device call.  frames == 0 is GDKVM_OK without a launch.  One 256-lane workgroup per frame
+ * walks it in bands of GDKVM_LV_CONTOUR_BAND_ROWS rows held as bit planes of GDKVM_LV_CONTOUR_WORD_BITS-bit words in LDS; no workspace, no
+ * allocation, no global atomics, no fences: capturable; bit-reproducible. */
+#define GDKVM_LV_CONTOUR_BAND_ROWS 64
+#define GDKVM_LV_CONTOUR_WORD_BITS 64
+int gdkvm_lv_contour(const uint8_t* mask, const int32_t* spacing_um, int64_t* rec,
+                     int frames, int H, int W, int cls, unsigned wall_set, unsigned base_set, void* stream);
 
 /* Keep the largest connected component of one class of label masks (the clean-up in front of gdkvm_lv_measure: an argmax mask is no tracing,
  * and a false-positive island far from the ventricle enters tmin / tmax, the long axis and the disks; csrc/largest_component.hip).  Every

@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay] [--native-surface]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay] [--native-surface] [--contour]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -58,6 +58,10 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     per frame; the only other way to these records, and the probe first checks that they are bit-equal there) and the byte floor, mask +
     target bytes over the HBM rate above.  Then ONE moderate pathological frame, a 512^2 checkerboard against a single pixel, run once and
     timed with a pair of events (profiles/native_surface_probe.txt).  --once: every form once, no windows (for a kernel trace).
+(c) --contour (this part alone): gdkvm_lv_contour (class 1 against the wall {2} and the base {3}) on 512 frames of 112^2 and of 256^2, the
+    ellipses of (a) inside a ring of class 2 with class 3 over their lower quarter: without and with a spacing, without a base set, on every
+    pixel of the class and on none, beside gdkvm_lv_measure on the same masks, the torch expression of the same eight counts (the padded
+    mask compared, eight shifted ANDs and sums per set; the probe first checks that it counts what the kernel counts) and the byte floor.
 (b) eval.py's wall time (a fresh process each: start-up, captures and the split) on the synthetic split with data.lv_class=1, with
     data.lv_keep_largest=4 on top of it, with data.lv_fill_holes=4 instead, with data.temporal_vote=1 instead, with data.surface_class=1
     instead, and with data.lv_class=-1, alternated, twice each."""
@@ -807,6 +811,100 @@ def part_s(dev, clips, T, reps, once=False):
           f"already loaded by the calls above): {e0.elapsed_time(e1) * 1e3:.1f} us; record {surf[0, 0].tolist()}", flush=True)
 
 
+def contour_masks(F, S, seed):
+    """ellipse_masks with what the contour needs around the cavity: a ring of class 2 (the wall), and class 3 (the atrium) over the lower
+    quarter of ellipse and ring, so that the cavity ends in a straight mitral plane"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
+    out = np.zeros((F, S, S), np.uint8)
+    for f in range(F):
+        th = rng.uniform(-0.5, 0.5)
+        la, sa = S * rng.uniform(0.22, 0.30), S * rng.uniform(0.10, 0.14)
+        dx, dy = xx - S * rng.uniform(0.45, 0.55), yy - S * rng.uniform(0.45, 0.55)
+        al, ac = dx * math.sin(th) + dy * math.cos(th), dx * math.cos(th) - dy * math.sin(th)
+        d = (al / la) ** 2 + (ac / sa) ** 2
+        out[f][d <= 1.5] = 2
+        out[f][d <= 1.0] = 1
+        out[f][(d <= 1.5) & (al > 0.6 * la)] = 3
+    return out
+
+
+def torch_contour_counts(mask, cls, wall, base):
+    """Words 1 .. 8 of ops.lv_contour's record as a plain torch expression (the yardstick): the zero-padded mask compared with the class and
+    with the one class of each set, and per set eight shifted ANDs and sums, two per direction"""
+    H, W = mask.shape[-2:]
+    p = torch.nn.functional.pad(mask, (1, 1, 1, 1))
+    c = mask == cls
+    out = []
+    for other in (wall, base):
+        x = p == other
+        for (dy, dx) in ((0, 1), (1, 0), (1, 1), (1, -1)):
+            a = (c & x[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]).sum((1, 2))
+            b = (c & x[:, 1 - dy:1 - dy + H, 1 - dx:1 - dx + W]).sum((1, 2))
+            out.append(a + b)
+    return torch.stack(out, 1)
+
+
+def part_c(dev, F, S, reps, n_in=4):
+    """(c) gdkvm_lv_contour (class 1 against the wall {2} and the base {3}) beside gdkvm_lv_measure on the same masks, the torch expression
+    of its eight counts, and the byte floor (every mask byte once over the HBM rate above), in the same alternated windows."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    masks = [torch.from_numpy(contour_masks(F, S, s)).to(dev) for s in range(n_in)]
+    full = torch.ones((F, S, S), dtype=torch.uint8, device=dev)
+    rec = torch.empty((F, 16), dtype=torch.int64, device=dev)
+    stats = torch.empty((F, 12), dtype=torch.int64, device=dev)
+    disks = torch.empty((F, 20), dtype=torch.int64, device=dev)
+    geom = torch.empty((F, 4), dtype=torch.float64, device=dev)
+    spacing = torch.tensor([330, 468], dtype=torch.int32, device=dev).expand(F, 2).contiguous()
+
+    def contour(mask, cls, sp=None, wall=1 << 2, base=1 << 3):
+        rc = lib.gdkvm_lv_contour(mask.data_ptr(), None if sp is None else sp.data_ptr(), rec.data_ptr(), F, S, S, cls, wall, base, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    def lv(mask, cls):
+        rc = lib.gdkvm_lv_measure(mask.data_ptr(), stats.data_ptr(), disks.data_ptr(), geom.data_ptr(), F, S, S, cls, 20, st)
+        assert rc == 0, lib.gdkvm_last_error()
+
+    contour(masks[0], 1)
+    want = torch_contour_counts(masks[0], 1, 2, 3)
+    torch.cuda.synchronize()
+    if not torch.equal(rec[:, 1:9], want):                         # no table from a yardstick that counts something else
+        raise SystemExit("lv_probe --contour: the torch expression differs from the kernel's counts")
+    lens = ops.contour_lengths(rec)
+    print(f"    (contour: {float(rec[:, 0].float().mean()):.0f} pixels of the class, wall {float(lens[:, 0].mean()):.1f}, base {float(lens[:, 1].mean()):.1f}, "
+          f"axis {float(lens[:, 2].mean()):.1f} pixels long on average; the torch expression counts the same)")
+    forms = {
+        "lv_contour, ventricle": (lambda i: contour(masks[i], 1), CALLS),
+        "lv_contour, the same with a spacing": (lambda i: contour(masks[i], 1, spacing), CALLS),
+        "lv_contour, no base set": (lambda i: contour(masks[i], 1, None, 1 << 2, 0), CALLS),
+        "lv_contour, every pixel of the class": (lambda i: contour(full, 1, None, 1 << 2, 1), CALLS),
+        "lv_contour, no pixel of the class": (lambda i: contour(full, 2, None, 1 << 3, 1), CALLS),
+        "lv_measure, the same ventricle": (lambda i: lv(masks[i], 1), CALLS),
+        "torch expression of the 8 counts": (lambda i: torch_contour_counts(masks[i], 1, 2, 3), 2),
+    }
+    times = {name: [] for name in forms}
+    for r in range(reps + 3):
+        for name, (fn, calls) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn(r % n_in)
+            e1.record()
+            e1.synchronize()
+            if r >= 3:
+                times[name].append(e0.elapsed_time(e1) * 1e3 / calls)
+    nbytes = F * S * S
+    print(f"(c) {F} frames of {S}x{S}: us per launch, windows of device events, median / minimum of {reps} windows per form (alternated, {n_in} "
+          f"inputs in rotation); floor = {nbytes / 1e6:.1f} MB over the HBM rate = {nbytes / HBM * 1e6:.2f} us")
+    print(f"{'form':48s} {'median us':>10s} {'min us':>9s} {'x floor':>9s} {'x torch':>9s}")
+    ref = statistics.median(times["torch expression of the 8 counts"])
+    for name in forms:
+        med = statistics.median(times[name])
+        print(f"{name:48s} {med:10.1f} {min(times[name]):9.1f} {med / (nbytes / HBM * 1e6):9.1f} {med / ref:9.3f}")
+    print(flush=True)
+
+
 def part_b(runs, overrides):
     print(f"(b) eval.py wall time, synthetic split, a fresh process per run ({' '.join(overrides) or 'the shipped configuration'})")
     for run in range(runs):
@@ -842,6 +940,10 @@ def main():
         return
     if "--overlay" in sys.argv:
         part_o(dev, 2 if quick else 16, 3 if quick else 10, 256, 4, 5 if quick else 30)
+        return
+    if "--contour" in sys.argv:
+        for S in (112, 256):
+            part_c(dev, 8 if quick else 512, S, 5 if quick else 40)
         return
     if "--mm-only" in sys.argv:
         for S in (112, 256):
