@@ -59,8 +59,12 @@ ops.surface_distance_native, and a `native.surface` block holds `class`, `unit`,
 `assd_mean` over the frames that count above (surface_metrics_mm / surface_summary, rounded like `surface_mm`): in mm (`unit`: "mm") with
 the spacing of the NATIVE pixel for every clip (gdkvm_amd.data.native_spacing_table: the dataset's own, e.g. the native_spacing.json of
 tools/convert_camus.py --native-spacing, else `data.native_spacing_um`), else in native pixels (`unit`: "px", measured at 1000 x 1000 um so
-that one pixel reads as 1.0).  Like the grid's `surface` block these are the distances of the unfiltered mask.  The volumes stay on the
-grid.  Every other key keeps its value; with the keys off nothing new runs.
+that one pixel reads as 1.0).  Like the grid's `surface` block these are the distances of the unfiltered mask.  With `data.native_lv`
+(which needs `native_eval` and `lv_class` >= 0) the volumes are measured there too: ops.lv_measure_native on the POST-PROCESSED predicted
+mask at native size (the raw one when no post-processing is on) and on the native target, ED / ES picked on the target's curve with
+ops.lv_ef as for `lv_mm`, and a `native.lv` block holds the `lv_mm` keys (EF statistics, EDV / ESV `_mae_ml` / `_bias_ml`), `unit`: "mL" and
+`frames` with a native spacing for every clip, else the EF statistics, `unit`: "px3" (measured at 1000 x 1000 um) and `frames`.  Every
+other key keeps its value; with the keys off nothing new runs.
 
 With `data.lv_strain` (and `lv_class` >= 0) the contour of the class is measured as well (ops.lv_contour on the post-processed prediction and on
 the target: its border with `data.lv_wall_classes` is the endocardium, its border with `data.lv_base_classes` the mitral plane): a `strain`
@@ -196,6 +200,15 @@ def main(argv=None):
             if nat_sp is None:
                 nat_sp = torch.full((len(ds), 2), 1000, dtype=torch.int32)
             ns_sums = torch.zeros(5, dtype=torch.float64, device=dev)     # ops.surface_summary, accumulated on the device
+    nlv_on = cfg.data.native_lv                                   # off: no new call below (config: on needs native_eval and lv_class >= 0)
+    if nlv_on:
+        # host int32 [clips, 2] micrometres per NATIVE pixel; without one for every clip the volumes are in native pixel^3
+        nlv_sp = native_spacing_table(ds, cfg)
+        nlv_unit = "mL" if nlv_sp is not None else "px3"
+        if nlv_sp is None:
+            nlv_sp = torch.full((len(ds), 2), 1000, dtype=torch.int32)
+        # ops.ef_summary of the EF, the EDV and the ESV measured at native size [24], then the frames measured
+        nlv_sums = torch.zeros(25, dtype=torch.float64, device=dev)
     vis_left = cfg.eval_stage.num_vis if rank == 0 else 0
     # this rank's shard through a prefetching loader (worker processes decode, pinned staging, host-to-device copies on a side stream) into
     # ONE captured forward per batch shape (SegmentRunner -> GraphedSegment: a hipGraph replay per batch; the short last batch runs eagerly)
@@ -266,9 +279,23 @@ def main(argv=None):
             n_flat = n_flat.to(dev)
             n_px = torch.tensor([h0 * w0 for h0, w0 in n_sz], dtype=torch.int64, device=dev)
             for slot, pm in enumerate((mask, measured) if nat_post else (mask,)):
-                n_out, n_c, _ = ops.mask_to_native(pm, n_sz, cfg.data.num_classes, target=n_flat, want_out=slot == 0 and ns_cls >= 0)
+                lv_slot = nlv_on and slot == int(nat_post)        # the post-processed mask's slot (the raw one's without post-processing)
+                n_out, n_c, _ = ops.mask_to_native(pm, n_sz, cfg.data.num_classes, target=n_flat,
+                                                   want_out=(slot == 0 and ns_cls >= 0) or lv_slot)
                 n_lab = n_c[..., 2].sum(-1) > 0                   # [B, T]
-                if n_out is not None:                             # the raw mask's surface distances at native size, over the same frames
+                if lv_slot:
+                    # the volumes of that native mask and of the native target at every clip's own size; ED / ES are the target's frames,
+                    # picked on the target's curve, and a clip counts when its target has two such frames and a volume, as for lv_mm
+                    l_sp = nlv_sp[i:i + nb]
+                    g_stats, _, g_geom = ops.lv_measure_native(n_flat, n_sz, mask.shape[1], l_sp, cls=lv_cls)
+                    q_stats, _, q_geom = ops.lv_measure_native(n_out, n_sz, mask.shape[1], l_sp, cls=lv_cls)
+                    g_vol, g_npix = g_geom[..., 1].contiguous(), g_stats[..., 0].contiguous()
+                    g_idx, g_val = ops.lv_ef(g_vol, g_npix)
+                    _, q_val = ops.lv_ef(q_geom[..., 1].contiguous(), q_stats[..., 0].contiguous(), pick_vol=g_vol, pick_npix=g_npix)
+                    ok = (g_idx[:, 0] >= 0) & (g_val[:, 0] > 0)
+                    nlv_sums += torch.cat([ops.ef_summary(q_val[:, k], g_val[:, k], ok) for k in (2, 0, 1)]
+                                          + [torch.tensor([g_npix.numel()], dtype=torch.float64, device=dev)])
+                if n_out is not None and slot == 0 and ns_cls >= 0:    # the raw mask's surface distances at native size, over the same frames
                     n_surf = ops.surface_distance_native(n_out, n_flat, n_sz, mask.shape[1], nat_sp[i:i + nb], cls=ns_cls)
                     ns_sums += ops.surface_summary(*ops.surface_metrics_mm(n_surf), n_surf, n_lab)
                 nat_acc[slot * nat_k:(slot + 1) * nat_k] += torch.cat([(n_c * n_lab[..., None, None]).sum((0, 1)).long().reshape(-1),
@@ -360,6 +387,8 @@ def main(argv=None):
             torch.distributed.all_reduce(nat_acc)                 # ... and the native counts, pixels and frames
             if ns_cls >= 0:
                 torch.distributed.all_reduce(ns_sums)             # ... and the five native surface-distance sums
+            if nlv_on:
+                torch.distributed.all_reduce(nlv_sums)            # ... and the native volume sums
         if bp_on:
             for tab in bp_pred + bp_tgt:                          # ... and the record tables: every row was written by one rank and is 0 on
                 torch.distributed.all_reduce(tab)                 # the others, and integer and fp64 sums with zeros are exact
@@ -498,6 +527,15 @@ def main(argv=None):
                 st = ops.surface_stats(ns_sums.cpu())
                 res["native"]["surface"] = {"class": ns_cls, "unit": ns_unit, "frames": st["frames"], "frames_one_empty": st["frames_one_empty"],
                                             **{k: round(st[k], 5) for k in ("hd_mean", "hd95_mean", "assd_mean")}}
+            if nlv_on:
+                acc = nlv_sums.cpu()
+                blk = ops.ef_stats(acc[:8])
+                if nlv_unit == "mL":                              # (in pixel^3 the EF, a ratio, is all there is to report)
+                    for name, sums in (("edv", acc[8:16]), ("esv", acc[16:24])):
+                        cnt = max(float(sums[0]), 1.0)
+                        blk[f"{name}_mae_ml"], blk[f"{name}_bias_ml"] = float(sums[2]) / cnt, float(sums[1]) / cnt
+                res["native"]["lv"] = {**{k: (v if isinstance(v, int) else round(v, 5)) for k, v in blk.items()}, "unit": nlv_unit,
+                                       "frames": int(acc[24])}
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -47,6 +47,9 @@ class DataCfg:
                                      # `native` block; needs a dataset with a native target for every clip (data.native_target_table)
     native_surface_class: int = -1   # eval.py: the class whose HD, HD95 and ASSD are also measured at every clip's NATIVE frame size
                                      # (ops.surface_distance_native): a `surface` block inside `native`; -1 = off, >= 0 needs native_eval
+    native_lv: bool = False          # eval.py, predict.py: EDV, ESV and EF of lv_class measured at every clip's NATIVE frame size
+                                     # (ops.lv_measure_native): an `lv` block inside `native` / an `lv_native` entry per clip; needs native_eval
+                                     # (eval.py) and lv_class >= 0
     native_spacing_um: Any = None    # eval.py: [row_um, col_um], the micrometres per NATIVE pixel (integers in 1..4095) for datasets that carry
                                      # none of their own (data.native_spacing_table); without a spacing for every clip the block is in pixels
     lv_strain: bool = False          # eval.py: global longitudinal strain of lv_class from its contour's length at ED and ES (ops.lv_contour /
@@ -207,6 +210,11 @@ def load_config(path: str | None = None, overrides: list[str] | None = None) -> 
     if nsc >= 0 and not d.native_eval:
         raise ValueError(f"data.native_surface_class = {nsc} needs data.native_eval: true (the surface distances at native size are part of "
                          "the `native` block)")
+    if not isinstance(d.native_lv, bool):
+        raise ValueError(f"data.native_lv = {d.native_lv!r}: true or false")
+    if d.native_lv and not (d.native_eval and d.lv_class >= 0):
+        raise ValueError(f"data.native_lv needs data.native_eval: true and data.lv_class >= 0 (the volumes at native size are part of the "
+                         f"`native` block and are those of lv_class), got native_eval = {d.native_eval}, lv_class = {d.lv_class}")
     nsp = d.native_spacing_um
     if nsp is not None and (not isinstance(nsp, list) or len(nsp) != 2
                             or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4095 for v in nsp)):

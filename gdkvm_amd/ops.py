@@ -148,6 +148,7 @@ SIGNATURES = {
     "gdkvm_surface_distance_mm": (_i, [_vp] * 5 + [_sz] + [_i] * 4 + [_vp]),
     "gdkvm_surface_distance_native_workspace_bytes": (_sz, [_i, _i, ctypes.c_longlong, ctypes.c_longlong]),
     "gdkvm_surface_distance_native": (_i, [_vp] * 5 + [_sz, _vp, _sz] + [_i] * 3 + [_vp]),
+    "gdkvm_lv_measure_native": (_i, [_vp] * 7 + [_sz, ctypes.c_longlong] + [_i] * 4 + [_vp]),
     "gdkvm_signed_distance_workspace_bytes": (_sz, [_i] * 4),
     "gdkvm_signed_distance": (_i, [_vp] * 3 + [_sz] + [_i] * 4 + [ctypes.c_uint, _vp]),
     "gdkvm_adamw_workspace_bytes": (_sz, [_i, ctypes.c_longlong]),
@@ -3072,6 +3073,140 @@ def surface_distance_native(mask: torch.Tensor, target: torch.Tensor, sizes, T: 
     ws = _workspace("gdkvm_surface_distance_native_workspace_bytes", dev, clips, T, total, T * sum(h0 for h0, _ in sz), floor=16)
     _call("gdkvm_surface_distance_native", dev, mask, target, host_sz, host_sp, surf, total, _Ws(ws), clips, T, cls)
     return surf
+
+
+# GDKVM_LV_NATIVE_*: the launch geometry of lv_measure_native, for tests that want shapes on both sides of it
+LV_NATIVE_BAND_ROWS, LV_NATIVE_MAX_WG, LV_NATIVE_CLIPS = 32, 4096, 64
+_LV_Q = 1 << 16
+_I64_MAX, _I64_MIN = (1 << 63) - 1, -(1 << 63)
+
+
+def _lv_native_axis(n: int, sx: int, sy: int, sxx: int, sxy: int, syy: int, ry: int, rx: int):
+    """Steps 2 and 3' of gdkvm_lv_measure_mm in Python integers and floats (IEEE fp64, one rounding per operation, sqrt and division correctly
+    rounded; round() is half to even, as rint): (Vx, Vy, E, k)"""
+    g = math.gcd(ry, rx)
+    py, px = ry // g, rx // g
+    pm = max(px, py)
+    A, B, C = n * sxx - sx * sx, n * sxy - sx * sy, n * syy - sy * sy
+    a = float(px * px) * float(A) - float(py * py) * float(C)
+    b = 2.0 * (float(px * py) * float(B))
+    r = math.sqrt(a * a + b * b)
+    if r == 0.0:
+        vx, vy = 0.0, 1.0
+    elif a >= 0.0:
+        vx, vy = a + r, b
+    else:
+        vx, vy = b, r - a
+    nrm = math.sqrt(vx * vx + vy * vy)
+    ux, uy = vx / nrm, vy / nrm
+    if uy < 0.0 or (uy == 0.0 and ux < 0.0):
+        ux, uy = -ux, -uy
+    ex, ey = ux * float(px), uy * float(py)
+    e = math.sqrt(ex * ex + ey * ey)
+    return (int(round((ux * float(px * _LV_Q)) / float(pm))), int(round((uy * float(py * _LV_Q)) / float(pm))),
+            int(round((e * float(_LV_Q)) / float(pm))), e * float(g))
+
+
+def _lv_native_host(m: torch.Tensor, ry: int, rx: int, cls: int, D: int):
+    """The records of gdkvm_lv_measure_native for one frame [h0, w0] (uint8, CPU): (stats 12 ints, disks D ints, geom 6 floats, band rows
+    [ceil(h0 / LV_NATIVE_BAND_ROWS)][8 + D] ints).  int64 tensors for what the header bounds below 2^63, Python integers for A, B and C."""
+    nbands = (m.shape[0] + LV_NATIVE_BAND_ROWS - 1) // LV_NATIVE_BAND_ROWS
+    ys, xs = (m == cls).nonzero(as_tuple=True)
+    n = int(xs.numel())
+    if n == 0:
+        return [0] * 12, [0] * D, [0.0] * 6, [[0] * (8 + D) for _ in range(nbands)]
+    band = torch.div(ys, LV_NATIVE_BAND_ROWS, rounding_mode="floor")
+    per_band = lambda v: torch.zeros(nbands, dtype=torch.int64).index_add_(0, band, v)
+    mom = [per_band(v) for v in (torch.ones_like(xs), xs, ys, xs * xs, xs * ys, ys * ys)]
+    tot = [int(v.sum()) for v in mom]
+    sx, sy = tot[1], tot[2]
+    Vx, Vy, E, k = _lv_native_axis(*tot, ry, rx)
+    t = (n * xs - sx) * Vx + (n * ys - sy) * Vy               # |.| < 2^50
+    b_min = torch.full((nbands,), _I64_MAX, dtype=torch.int64).scatter_reduce_(0, band, t, "amin")
+    b_max = torch.full((nbands,), _I64_MIN, dtype=torch.int64).scatter_reduce_(0, band, t, "amax")
+    tmin, tmax = int(t.min()), int(t.max())
+    P1 = n * E
+    Lt = tmax - tmin + P1
+    lo = D * (t - tmin)
+    hi = lo + D * P1
+    w_band = [per_band((torch.clamp(hi, max=(j + 1) * Lt) - torch.clamp(lo, min=j * Lt)).clamp_(min=0)) for j in range(D)]
+    disks = [int(w.sum()) for w in w_band]
+    L = ((float(Lt) / float(P1)) * k) / 1000.0
+    pix = float(ry * rx) / 1e6
+    s = 0.0
+    for w in disks:
+        aj = (float(w) / float(D * P1)) * pix
+        s = s + aj * aj
+    geom = [L, ((math.pi * D) * s) / (4.0 * L) / 1000.0, ((float(sx) / float(n)) * float(rx)) / 1000.0,
+            ((float(sy) / float(n)) * float(ry)) / 1000.0, k, float(n * ry * rx) / 1e6]
+    rows = torch.stack(mom + [b_min, b_max] + w_band, 1).tolist()
+    return tot + [Vx, Vy, tmin, tmax, Lt, E], disks, geom, rows
+
+
+def lv_measure_native(mask: torch.Tensor, sizes, T: int, spacing_um, cls: int = 1, disks: int = 20, want_bands: bool = False):
+    """gdkvm_lv_measure_native: lv_measure_mm at every clip's own frame size.  mask is a RAGGED flat uint8 tensor, clip b's T frames of
+    h0 w0 bytes in turn (mask_to_native returns one, pack_native builds one); sizes the clips' native (h0, w0), each in 1..2048, and
+    spacing_um the micrometres per NATIVE pixel (ry, rx) of every clip, each in 1..4095: both HOST integers, a sequence of pairs or a CPU
+    integer tensor [clips, 2] (a device tensor is refused).  Returns (stats int64 [clips, T, 12] = n sx sy sxx sxy syy Vx Vy tmin tmax Lt E,
+    disks int64 [clips, T, D], geom float64 [clips, T, 6] = L in mm, V in mL, cx, cy in mm, k, area in mm^2), lv_measure_mm's records
+    (definition: include/gdkvm.h): lv_ef, lv_beats and lv_biplane (with native_spacing_frames) apply unchanged.  want_bands: also the
+    per-band partials, int64 [bands, 8 + D] in clip, frame, band order with ceil(h0 / LV_NATIVE_BAND_ROWS) bands per frame = n sx sy sxx
+    sxy syy tmin tmax W_0 .. W_(D-1) of the band's rows.  mask may start at any byte address.  CPU tensors take the same rule in torch
+    and Python integers, so the wrapper works without a GPU."""
+    what = "lv_measure_native"
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    if isinstance(cls, bool) or not isinstance(cls, int) or not 0 <= cls <= 254:
+        raise GdkvmError(f"{what}: cls = {cls!r} must be an integer in 0..254")
+    if isinstance(disks, bool) or not isinstance(disks, int) or not 1 <= disks <= LV_MAX_DISKS:
+        raise GdkvmError(f"{what}: disks = {disks!r} must be an integer in 1..{LV_MAX_DISKS}")
+    sz = _native_sizes(what, sizes)
+    clips = len(sz)
+    sp = _native_spacing(what, spacing_um, clips)
+    offsets, total = _native_offsets(sz, T)
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 1 or mask.numel() < total:
+        raise GdkvmError(f"{what}: mask must be a flat uint8 tensor of at least {total} bytes (the clips' T h0 w0 in turn), got "
+                         f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    if not mask.is_contiguous():
+        raise GdkvmError("GDKVM ops need contiguous tensors")
+    nbands = T * sum((h0 + LV_NATIVE_BAND_ROWS - 1) // LV_NATIVE_BAND_ROWS for h0, _ in sz)
+    if not mask.is_cuda:
+        # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
+        stats = torch.zeros((clips, T, 12), dtype=torch.int64)
+        dk = torch.zeros((clips, T, disks), dtype=torch.int64)
+        geom = torch.zeros((clips, T, 6), dtype=torch.float64)
+        rows = []
+        for b, (h0, w0) in enumerate(sz):
+            m = mask[offsets[b]:offsets[b] + T * h0 * w0].view(T, h0, w0)
+            for f in range(T):
+                s, d, g, r = _lv_native_host(m[f], sp[b][0], sp[b][1], cls, disks)
+                stats[b, f], dk[b, f] = torch.tensor(s, dtype=torch.int64), torch.tensor(d, dtype=torch.int64)
+                geom[b, f] = torch.tensor(g, dtype=torch.float64)
+                rows += r
+        bands = torch.tensor(rows, dtype=torch.int64).reshape(nbands, 8 + disks)
+        return (stats, dk, geom, bands) if want_bands else (stats, dk, geom)
+    dev = _dev(mask)
+    stats = torch.empty((clips, T, 12), dtype=torch.int64, device=dev)
+    dk = torch.empty((clips, T, disks), dtype=torch.int64, device=dev)
+    geom = torch.empty((clips, T, 6), dtype=torch.float64, device=dev)
+    bands = torch.empty((nbands, 8 + disks), dtype=torch.int64, device=dev)
+    if clips:
+        host_sz = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
+        host_sp = torch.tensor(sp, dtype=torch.int32).reshape(clips, 2)
+        _call("gdkvm_lv_measure_native", dev, mask, host_sz, host_sp, stats, dk, geom, bands, total, nbands, clips, T, cls, disks)
+    return (stats, dk, geom, bands) if want_bands else (stats, dk, geom)
+
+
+def native_spacing_frames(spacing_um, T: int, device) -> torch.Tensor:
+    """int32 [clips, T, 2] on `device`: every clip's native (ry, rx) for each of its T frames, the table lv_biplane reads beside the
+    records of lv_measure_native.  spacing_um as there: HOST integers, validated here before anything is copied."""
+    what = "native_spacing_frames"
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    if not isinstance(spacing_um, torch.Tensor):
+        spacing_um = list(spacing_um) if hasattr(spacing_um, "__iter__") else spacing_um
+    sp = _native_spacing(what, spacing_um, len(spacing_um) if hasattr(spacing_um, "__len__") else 0)
+    return torch.tensor(sp, dtype=torch.int32).reshape(len(sp), 1, 2).expand(len(sp), T, 2).contiguous().to(device)
 
 
 def surface_metrics_mm(surf: torch.Tensor):

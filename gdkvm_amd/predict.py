@@ -12,7 +12,10 @@ size) through
 and, with data.lv_class >= 0, measures the class on the grid per clip: ops.lv_measure / lv_ef (pixel^3; EF is a ratio), ops.lv_beats with
 data.lv_beats, and with a native pixel spacing (row_um, col_um) ops.lv_measure_mm at the grid spacing (rint(row_um h0 / H),
 rint(col_um w0 / W)) -- tools/convert_camus.py's spacing_um formula; the mL keys are left out, with the reason, when that falls outside
-1..4095.  With data.lv_strain a `strain` entry per clip holds the global longitudinal strain of the class's endocardial contour between
+1..4095.  With data.native_lv an `lv_native` entry per clip holds the same class measured on the NATIVE post-processed masks of step 5
+(ops.lv_measure_native / lv_ef: ed_frame, es_frame, valid_frames, ef, and with a native spacing -- each component rint-ed to integer um and
+recorded -- edv_ml and esv_ml; a clip without a usable spacing is measured at 1 x 1 um and reports the EF, with the reason under
+lv_native_ml_omitted).  With data.lv_strain a `strain` entry per clip holds the global longitudinal strain of the class's endocardial contour between
 those ED / ES frames, the peak strain and its frame, and the contour and apex-to-annulus lengths at ED and ES (ops.lv_contour /
 contour_lengths / lv_strain; mm for a clip with a grid spacing, else px).  With overlay=True it also draws what a person looks at, ops.overlay_native of the native frames under those native masks (the
 configuration's `overlay:` section); overlay_clip draws one clip with an optional reference mask, which is what eval.py's
@@ -50,6 +53,12 @@ def grid_spacing_um(spacing_um, h0: int, w0: int, H: int, W: int) -> Optional[Tu
     if not (1 <= row <= ops.SPACING_UM_MAX and 1 <= col <= ops.SPACING_UM_MAX):
         return None
     return int(row), int(col)
+
+
+def native_spacing_um(spacing_um) -> Optional[Tuple[int, int]]:
+    """The native pixel's (row_um, col_um) as the integers ops.lv_measure_native takes: each component rint-ed; None when a value is not
+    finite or a result falls outside 1..SPACING_UM_MAX."""
+    return grid_spacing_um(spacing_um, 1, 1, 1, 1)
 
 
 def make_runner(model):
@@ -163,6 +172,19 @@ def segment_native(model, cfg, clips: Sequence[torch.Tensor], spacing_um=None, r
                     why = "no spacing" if spacing_um[b] is None else \
                         f"the grid spacing of {spacing_um[b][0]} x {spacing_um[b][1]} um pixels falls outside 1..{ops.SPACING_UM_MAX} um"
                     per_clip[b]["lv_mm_omitted"] = why
+        if d.native_lv:
+            # the same class on the native post-processed masks above, at every clip's own size with the spacing of the native pixel (each
+            # component rint-ed to integer um); a clip without a usable spacing is measured at 1 x 1 um: its EF is a ratio, its mL keys are left out
+            nat_sp = [None if s is None else native_spacing_um(s) for s in (spacing_um if spacing_um is not None else [None] * B)]
+            n_stats, _, n_geom = ops.lv_measure_native(native, sizes, T, [s or (1, 1) for s in nat_sp], cls=lv_cls)
+            n_idx, n_val = ops.lv_ef(n_geom[..., 1].contiguous(), n_stats[..., 0].contiguous())
+            for b, (i3, v3) in enumerate(zip(n_idx.tolist(), n_val.tolist())):
+                per_clip[b]["lv_native"] = {"ed_frame": i3[0], "es_frame": i3[1], "valid_frames": i3[2], "ef": r5(v3[2])}
+                if nat_sp[b] is not None:
+                    per_clip[b]["lv_native"].update(spacing_um=list(nat_sp[b]), edv_ml=r5(v3[0]), esv_ml=r5(v3[1]))
+                else:
+                    per_clip[b]["lv_native_ml_omitted"] = "no spacing" if spacing_um is None or spacing_um[b] is None else \
+                        f"the native spacing of {spacing_um[b][0]} x {spacing_um[b][1]} um falls outside 1..{ops.SPACING_UM_MAX} um"
         if d.lv_beats:
             if q_vol is not None and all(g is not None for g in grid_sp):
                 b_vol, unit = q_vol, "ml"

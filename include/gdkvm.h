@@ -1087,6 +1087,55 @@ size_t gdkvm_surface_distance_native_workspace_bytes(int clips, int T, long long
 int gdkvm_surface_distance_native(const uint8_t* mask, const uint8_t* target, const int32_t* sizes, const int32_t* spacing_um,
                                   int64_t* surf, size_t native_bytes, void* workspace, size_t workspace_bytes, int clips, int T, int cls,
                                   void* stream);
+/* gdkvm_lv_measure_mm at every clip's NATIVE frame size: EDV, ESV and EF in mL from the tracing as the dataset stores it, with the spacing
+ * of the native pixel (eval.py's native.lv block; csrc/lv_native.hip).
+ * Per native frame of clip b: (h0, w0) = sizes[b], each side in 1..2048; (ry, rx) = spacing_um[b], micrometres per NATIVE pixel down the
+ * rows and along the columns, each in 1..4095; class cls in 0..254; D disks in 1..64; Q = 2^16.  Steps 1, 2, 3', 4, 5 and 6' of
+ * gdkvm_lv_measure_mm apply to every native frame, integer for integer and fp64 operation for fp64 operation (contraction off, each
+ * operation rounded once).  The records are stats [clips, T, 12] = n, sx, sy, sxx, sxy, syy, Vx, Vy, tmin, tmax, Lt, E, disks [clips, T, D]
+ * = W_j and geom [clips, T, 6] = L mm, V mL, cx mm, cy mm, k um, area mm^2, that entry's layout: gdkvm_lv_ef, gdkvm_lv_beats and
+ * gdkvm_lv_biplane apply to them unchanged, and on uniform clips with sides <= 1024 the three records equal gdkvm_lv_measure_mm's bit for
+ * bit, doubles included.  An empty frame (n = 0) gives all 0; the entry validates every size and spacing, so this form has no -1 record.
+ * The bounds the integer widths rest on, for sides up to 2048 (x, y <= 2047):
+ *   - n <= 2^22;  sx, sy < 2^33;  sxx, sxy, syy < 2^44.
+ *   - A = n sxx - sx^2 equals the sum over pixel pairs of (x_i - x_j)^2, which only grows with the set: its largest value is the full
+ *     2048^2 frame's, 2^44 (2048^2 - 1) / 12 < 2^62.5; the same holds for C, and |B| <= sqrt(A C).  So A, B and C fit int64, but the two
+ *     products n sxx and sx^2 reach 2^66: A, B and C are formed in unsigned 64-bit wrap-around arithmetic, whose difference is the exact
+ *     value, never in a double.
+ *   - |n x - sx| < 2^33 and |Vx|, |Vy| <= 2^16, so the projection takes 64-bit products and |t_p| < 2^50.
+ *   - P1 = n E <= 2^38;  Lt = tmax - tmin + P1 < 2^51 + 2^38;  D (t_p - tmin) + D P1 and (j + 1) Lt are both below 2^58.
+ *   - W_j: a pixel meets disk j only inside a slab of (L / D + 1) pixel extents along the axis, which is at most sqrt(2) (L / D + 1) + 1
+ *     pixels per row or column along the frame's dominant direction, over at most 2048 of them, with L <= 4095 pixel extents; an overlap
+ *     is at most D P1.  So W_j <= 2048 (sqrt(2) (4095 / D + 1) + 1) D 2^38 < 2^61.6, and sum_j W_j = n D P1 <= 2^44 D exactly.
+ * mask is RAGGED, exactly the layout of gdkvm_mask_to_native's out / target: clip b's T frames of h0 w0 bytes follow each other and clip
+ * b + 1 follows clip b.  Frames start at ANY byte address.  native_bytes = the bytes mask holds; it must cover the sum over the clips of
+ * T h0 w0.  stats, disks, geom and bands are 16-byte aligned.
+ * sizes and spacing_um are HOST int32 [clips, 2], handled as gdkvm_surface_distance_native handles them: the entry validates every value,
+ * computes every clip's offsets itself and hands them with the sizes and the spacings to the kernels by value in the kernel arguments,
+ * GDKVM_LV_NATIVE_CLIPS clips per launch, longer batches in several launches; nothing is copied to the device, nothing allocated, nothing
+ * synchronised (a capture holds the sizes and the spacings).
+ * A frame's work is spread over many workgroups: four kernels in stream order per launch over BANDS of GDKVM_LV_NATIVE_BAND_ROWS native
+ * rows of one (clip, frame) -- per band the six moments; per band tmin / tmax (every workgroup adds its frame's band moments and evaluates
+ * step 3' itself: the same operations on the same totals give every workgroup of a frame the same axis); per band the partial W_j (64-bit
+ * integer atomics in LDS, then stored); per frame one workgroup that adds the bands and writes the records.  No workgroup waits for
+ * another, no global atomics, no fences.  A launch has at most GDKVM_LV_NATIVE_MAX_WG workgroups per kernel, which take further items in a
+ * grid-stride loop.
+ * The per-band partials are an OUTPUT, not scratch: bands int64 [native_bands, 8 + D] with native_bands = the sum over the clips of
+ * T ceil(h0 / GDKVM_LV_NATIVE_BAND_ROWS), in clip, frame, band order.  One row holds n, sx, sy, sxx, sxy, syy, tmin, tmax and W_0 ..
+ * W_(D-1) restricted to the band's rows (tmin, tmax over the band's pixels with the FRAME's n, sx, sy and axis; W_j against the frame's
+ * tmin and Lt).  A band without a pixel of the class in a frame that has some holds 0 moments, tmin = INT64_MAX, tmax = INT64_MIN and
+ * W = 0; every band of an empty frame holds all 0.  Every word is an exact integer that depends on no schedule.  (No workspace, hence no
+ * size query.)
+ * clips < 0, T < 1, D outside 1..64, a size outside 1..2048, a spacing outside 1..4095, native_bytes short of the sum, native_bands not
+ * equal to the sum and clips * T > 2^30 are GDKVM_ERR_SHAPE; cls outside 0..254, a null mask, sizes, spacing_um, stats, disks, geom or
+ * bands and a misaligned output are GDKVM_ERR_ARG (the codes of gdkvm_lv_measure_mm); all of them before any device call.  clips == 0 is
+ * GDKVM_OK without a launch.  Bit-reproducible. */
+#define GDKVM_LV_NATIVE_BAND_ROWS 32
+#define GDKVM_LV_NATIVE_MAX_WG 4096
+#define GDKVM_LV_NATIVE_CLIPS 64
+int gdkvm_lv_measure_native(const uint8_t* mask, const int32_t* sizes, const int32_t* spacing_um, int64_t* stats, int64_t* disks,
+                            double* geom, int64_t* bands, size_t native_bytes, long long native_bands, int clips, int T, int cls, int D,
+                            void* stream);
 
 /* Signed squared distance maps of label frames (the operand of gdkvm_seg_loss_boundary_fwd / _bwd; csrc/signed_distance.hip).  Every output is
  * an integer that depends on neither the algorithm nor the schedule.  Distances are in pixels of the frame's grid (isotropic pixels assumed).

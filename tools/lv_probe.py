@@ -2,7 +2,7 @@
 """What the LV measurement, the temporal vote, the largest-component filter and the hole filling in front of it and the surface distances
 cost (profiles/r10_a_lv_probe.txt, profiles/r12_a_cc_probe.txt, profiles/r13_a_surface_probe.txt, profiles/r16_a_fill_holes_probe.txt; the
 vote's figures are in DESIGN.md).
-python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay] [--native-surface] [--contour]
+python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--beats] [--native] [--native-input] [--overlay] [--native-surface] [--native-lv] [--contour]
 
 (a) gdkvm_lv_measure (class 1, 20 disks) on 512 frames of 112^2 (the cfg2 mask) and of 256^2, beside the kernel that writes those very masks,
     gdkvm_upsample_argmax_dice (bf16 stride-4 logits of 2 classes + uint8 target -> mask + counts), in the same run.  Both are called through the
@@ -58,6 +58,11 @@ python3 tools/lv_probe.py [--quick] [--no-eval] [--vote-only] [--mm-only] [--bea
     per frame; the only other way to these records, and the probe first checks that they are bit-equal there) and the byte floor, mask +
     target bytes over the HBM rate above.  Then ONE moderate pathological frame, a 512^2 checkerboard against a single pixel, run once and
     timed with a pair of events (profiles/native_surface_probe.txt).  --once: every form once, no windows (for a kernel trace).
+(l) --native-lv (this part alone): gdkvm_lv_measure_native (class 1, 20 disks, 308 x 154 um per native pixel) on a CAMUS-like ragged batch,
+    16 clips of 10 frames with sizes drawn between 584 x 323 and 1945 x 1181: ventricle-like ellipses, every pixel of the class, and an
+    empty class, beside the byte floor -- every mask byte read once per pass (three passes) over the HBM rate above.  Then the largest shape
+    gdkvm_lv_measure_mm runs too, 160 frames of 1024 x 1024, beside that entry (one workgroup per frame; the probe first checks that the
+    records are bit-equal) in the same alternated windows, with the ratio (profiles/native_lv_probe.txt).  --once as for (s).
 (c) --contour (this part alone): gdkvm_lv_contour (class 1 against the wall {2} and the base {3}) on 512 frames of 112^2 and of 256^2, the
     ellipses of (a) inside a ring of class 2 with class 3 over their lower quarter: without and with a spacing, without a base set, on every
     pixel of the class and on none, beside gdkvm_lv_measure on the same masks, the torch expression of the same eight counts (the padded
@@ -811,6 +816,94 @@ def part_s(dev, clips, T, reps, once=False):
           f"already loaded by the calls above): {e0.elapsed_time(e1) * 1e3:.1f} us; record {surf[0, 0].tolist()}", flush=True)
 
 
+def part_l(dev, clips, T, reps, frames_1024, once=False):
+    """(l) gdkvm_lv_measure_native (class 1, 20 disks): a CAMUS-like ragged batch beside the byte floor, then the largest shape that
+    gdkvm_lv_measure_mm runs too, frames of 1024 x 1024, beside that entry (one workgroup per frame) in the same alternated windows."""
+    lib = ops.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ry, rx, D = 308, 154, 20
+    rng = np.random.default_rng(3)
+    camus = [(int(rng.integers(584, 1946)), int(rng.integers(323, 1182))) for _ in range(clips)]
+    flat = lambda cl: torch.from_numpy(np.concatenate([c.reshape(-1) for c in cl])).to(dev)
+
+    def windows(forms):
+        times = {name: [] for name in forms}
+        for rep_ in range(1 if once else reps + 3):
+            for name, (fn, calls) in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(1 if once else calls):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                if once or rep_ >= 3:
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / (1 if once else calls))
+        return times
+
+    for label, sizes, frames in ((f"{clips} clips of {T} frames, sizes drawn between 584 x 323 and 1945 x 1181", camus, T),
+                                 (f"{frames_1024} frames of 1024 x 1024", [(1024, 1024)], frames_1024)):
+        uniform = len(sizes) == 1
+        nclips = len(sizes)
+        masks = [flat(native_ellipses(sizes, frames, s)) for s in (1, 2)]
+        total = masks[0].numel()
+        nbands = frames * sum((h0 + ops.LV_NATIVE_BAND_ROWS - 1) // ops.LV_NATIVE_BAND_ROWS for h0, _ in sizes)
+        full = torch.ones(total, dtype=torch.uint8, device=dev)
+        host_sz = torch.tensor(sizes, dtype=torch.int32)
+        host_sp = torch.tensor([(ry, rx)] * nclips, dtype=torch.int32)
+        stats = torch.empty((nclips, frames, 12), dtype=torch.int64, device=dev)
+        disks = torch.empty((nclips, frames, D), dtype=torch.int64, device=dev)
+        geom = torch.empty((nclips, frames, 6), dtype=torch.float64, device=dev)
+        bands = torch.empty((nbands, 8 + D), dtype=torch.int64, device=dev)
+        turn = [0]
+
+        def ln(m, cls=1):
+            rc = lib.gdkvm_lv_measure_native(m.data_ptr(), host_sz.data_ptr(), host_sp.data_ptr(), stats.data_ptr(), disks.data_ptr(),
+                                             geom.data_ptr(), bands.data_ptr(), total, nbands, nclips, frames, cls, D, st)
+            assert rc == 0, lib.gdkvm_last_error()
+
+        def rotate(fn):
+            def go():
+                turn[0] += 1
+                fn(masks[turn[0] % 2])
+            return go
+
+        forms = {
+            "lv_measure_native, ellipse (a tenth of the frame)": (rotate(ln), 5),
+            "lv_measure_native, every pixel of the class": (lambda: ln(full), 2),
+            "lv_measure_native, no pixel of the class": (lambda: ln(masks[0], 3), 5),
+        }
+        if uniform:
+            sp_dev = torch.tensor([(ry, rx)] * frames, dtype=torch.int32, device=dev)
+            s_mm, d_mm, g_mm = torch.empty_like(stats), torch.empty_like(disks), torch.empty_like(geom)
+
+            def mm(m, cls=1):
+                rc = lib.gdkvm_lv_measure_mm(m.data_ptr(), sp_dev.data_ptr(), s_mm.data_ptr(), d_mm.data_ptr(), g_mm.data_ptr(), frames, 1024, 1024,
+                                             cls, D, st)
+                assert rc == 0, lib.gdkvm_last_error()
+
+            ln(masks[0]); mm(masks[0])
+            torch.cuda.synchronize()
+            same = all(torch.equal(a.view(torch.int64), b.view(torch.int64)) for a, b in ((stats, s_mm), (disks, d_mm), (geom, g_mm)))
+            print(f"    ({label}: the records of lv_measure_mm are {'bit-equal' if same else 'NOT EQUAL'} to lv_measure_native's)")
+            forms["lv_measure_mm (one workgroup per frame), ellipse"] = (rotate(mm), 2)
+            forms["lv_measure_mm (one workgroup per frame), every pixel"] = (lambda: mm(full), 1)
+        times = windows(forms)
+        floor = total / HBM * 1e6
+        print(f"(l) lv_measure_native, {label}, class 1, {D} disks, {ry} x {rx} um, {total / 1e6:.1f} MB of labels, {nbands} bands of "
+              f"{ops.LV_NATIVE_BAND_ROWS} rows: us per call, windows of device events, median / minimum of {len(next(iter(times.values())))} windows "
+              f"per form (alternated); floor = the mask read once per pass over the HBM rate: {floor:.2f} us a pass, three passes {3 * floor:.2f} us")
+        print(f"{'form':62s} {'median us':>10s} {'min us':>9s} {'MB':>8s} {'x 3 passes':>11s}")
+        for name in forms:
+            med = statistics.median(times[name])
+            print(f"{name:62s} {med:10.1f} {min(times[name]):9.1f} {total / 1e6:8.1f} {med / (3 * floor):11.1f}")
+        if uniform:
+            for tag in ("ellipse", "every pixel"):
+                a = statistics.median(times[[n for n in forms if n.startswith("lv_measure_native") and tag in n][0]])
+                b = statistics.median(times[[n for n in forms if n.startswith("lv_measure_mm") and tag in n][0]])
+                print(f"    ({tag}: lv_measure_mm / lv_measure_native = {b / a:.2f})")
+        print(flush=True)
+
+
 def contour_masks(F, S, seed):
     """ellipse_masks with what the contour needs around the cavity: a ring of class 2 (the wall), and class 3 (the atrium) over the lower
     quarter of ellipse and ring, so that the cavity ends in a straight mitral plane"""
@@ -937,6 +1030,9 @@ def main():
         return
     if "--native-surface" in sys.argv:
         part_s(dev, 2 if quick else 16, 3 if quick else 10, 3 if quick else 20, once="--once" in sys.argv)
+        return
+    if "--native-lv" in sys.argv:
+        part_l(dev, 2 if quick else 16, 3 if quick else 10, 3 if quick else 20, 4 if quick else 160, once="--once" in sys.argv)
         return
     if "--overlay" in sys.argv:
         part_o(dev, 2 if quick else 16, 3 if quick else 10, 256, 4, 5 if quick else 30)
