@@ -4,9 +4,8 @@
 // two pixel lattices, q = floor((2 N + h0 w0) / (2 h0 w0)), and every plane of the output holds q, float(q) * (1 / 255) or that rounded
 // once to bf16.  out depends on neither the schedule nor the path taken.  No floating-point code in front of the final cast, no atomics.
 //
-// The native sizes differ from clip to clip: the launcher gets them as HOST integers, validates them, computes every clip's byte offset and
-// its band geometry and hands them to the kernel BY VALUE in the kernel arguments, at most FN_CLIPS clips per launch (2.5 KB of the 4 KB an
-// argument block may have), longer batches in several launches -- as mask_to_native.hip does: nothing copied, nothing allocated.
+// The native sizes differ from clip to clip, so the native frames are ragged: native_clips.hpp holds the launcher's side of that; a clip's
+// entry here is its offset and its band geometry, FN_CLIPS of them 2.5 KB of the 4 KB an argument block may have.
 //
 // A workgroup of 256 lanes owns a BAND of grid rows of one (clip, frame): as many as one CHUNK of native rows covers, a chunk being the
 // native rows whose bytes fit FN_CHUNK_BYTES of LDS and whose column sums fit FN_HS_WORDS (8 grid rows of a 549 x 778 frame on a 256 x 256
@@ -37,7 +36,7 @@
 // The grid follows the clip with the most bands of the launch: item = (clip, frame, band) over clips x T x maxbands, and a workgroup whose
 // band lies past its clip's last leaves at once.  More than FN_MAX_WG items are taken grid-stride.
 
-#include "mask_frame.hpp"
+#include "native_clips.hpp"
 
 namespace {
 
@@ -49,10 +48,10 @@ constexpr int FN_PART = GDKVM_FRAMES_FROM_NATIVE_PART;                 // native
 constexpr int FN_MAX_WG = GDKVM_FRAMES_FROM_NATIVE_MAX_WG;             // workgroups per launch; more items than that are walked grid-stride
 constexpr int FN_CLIPS = GDKVM_FRAMES_FROM_NATIVE_CLIPS;               // clips per launch
 constexpr int FN_BAND_ROWS = GDKVM_FRAMES_FROM_NATIVE_BAND_ROWS;       // grid rows of a band at most
-constexpr int FN_MAX_NATIVE = 2048, FN_MAX_GRID = 1024, FN_MAX_WP = 1024;
+constexpr int FN_MAX_GRID = 1024, FN_MAX_WP = 1024;
 constexpr int FN_BATCH = 8, FN_ROWS = 4;                               // native bytes, and folds, a lane reads from LDS before it uses the first
 constexpr int FN_U8 = 0, FN_F32 = 1, FN_BF16 = 2;                      // out_dtype (gdkvm.h)
-static_assert(FN_CHUNK_BYTES >= FN_MAX_NATIVE && FN_CHUNK_BYTES % 16 == 0, "a chunk holds at least one native row");
+static_assert(FN_CHUNK_BYTES >= NATIVE_MAX_SIDE && FN_CHUNK_BYTES % 16 == 0, "a chunk holds at least one native row");
 static_assert(FN_CHUNK_BYTES / 16 + 1 <= 4 * FN_NT, "a lane carries a chunk's vectors in four registers of 16 bytes");
 static_assert(FN_HS_WORDS >= FN_MAX_WP && FN_ACC_WORDS >= FN_MAX_WP && FN_ACC_WORDS <= FN_HS_WORDS, "one row of parts fits both; the sums fit the fold words");
 
@@ -146,9 +145,8 @@ __global__ __launch_bounds__(FN_NT) void frames_from_native_kernel(FnArgs a)
             const unsigned rem = it - (unsigned)clip * pc;
             t = (int)(rem / mb); band = (int)(rem - (unsigned)t * mb);
         } else {
-            clip = (int)(item / per_clip);
-            const long long rem = item - clip * per_clip;
-            t = (int)(rem / a.maxbands); band = (int)(rem - (long long)t * a.maxbands);
+            const NativeItem it64 = native_item(item, per_clip, a.maxbands);
+            clip = it64.clip; t = it64.t; band = it64.band;
         }
         const FnClip c = a.c[clip];
         if (band >= c.nbands) continue;                    // (uniform: a smaller clip of the launch has fewer bands)
@@ -305,7 +303,6 @@ inline bool fn_shape_ok(int clips, int T, int C, int H, int W)
     return clips >= 0 && T >= 1 && C >= 1 && C <= 4 && H >= 1 && H <= FN_MAX_GRID && W >= 1 && W <= FN_MAX_GRID;
 }
 inline size_t fn_elem(int out_dtype) { return out_dtype == FN_U8 ? 1 : out_dtype == FN_F32 ? 4 : 2; }
-inline bool fn_overlap(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) { return a < b + nb && b < a + na; }
 
 // The band geometry of one clip (the file's head): P = 2^pl parts per column and PV = 2^pvl per grid row while one has more than FN_PART
 // native pixels and the words allow, the native rows per chunk, and as many grid rows per band as one chunk covers.
@@ -347,45 +344,30 @@ extern "C" int gdkvm_frames_from_native(const uint8_t* native, const int32_t* si
     if (clips == 0) return GDKVM_OK;
     if (!native || !sizes || !out) return gdkvm_fail(GDKVM_ERR_SHAPE, "frames_from_native: null pointer (native, the host sizes and out are required)");
     if (int rc = mask_check_aligned16("frames_from_native", GDKVM_ERR_SHAPE, "out", {out})) return rc;
+    size_t total;
+    if (int rc = native_check_clips("frames_from_native", "frames", sizes, nullptr, native_bytes, clips, T, total)) return rc;
     const size_t frames = (size_t)clips * (size_t)T;
-    if (frames > ((size_t)1 << 30)) return gdkvm_fail(GDKVM_ERR_SHAPE, "frames_from_native: clips * T = %zu frames exceed 2^30", frames);
-    size_t total = 0;
-    for (int b = 0; b < clips; ++b) {
-        const int h0 = sizes[2 * b], w0 = sizes[2 * b + 1];
-        if (h0 < 1 || h0 > FN_MAX_NATIVE || w0 < 1 || w0 > FN_MAX_NATIVE)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "frames_from_native: clip %d has the native size %d x %d (h0, w0 in 1..%d)", b, h0, w0, FN_MAX_NATIVE);
-        total += (size_t)T * (size_t)h0 * (size_t)w0;      // (< 2^30 * 2^22)
-    }
-    if (native_bytes < total)
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "frames_from_native: the native frames of these sizes take %zu bytes, native_bytes = %zu", total,
-                          native_bytes);
-    if (fn_overlap(static_cast<const uint8_t*>(out), frames * (size_t)C * (size_t)H * (size_t)W * fn_elem(out_dtype), native, total))
+    if (native_overlap(out, frames * (size_t)C * (size_t)H * (size_t)W * fn_elem(out_dtype), native, total))
         return gdkvm_fail(GDKVM_ERR_SHAPE, "frames_from_native: out must not overlap native");
     const size_t need = gdkvm_frames_from_native_workspace_bytes(clips, T, C, H, W, out_dtype);
     if (int rc = mask_check_workspace("frames_from_native", H, W, need, workspace, workspace_bytes)) return rc;
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    size_t off = 0;                                        // carried from launch to launch
-    for (int b0 = 0; b0 < clips; b0 += FN_CLIPS) {
-        const int nb = clips - b0 < FN_CLIPS ? clips - b0 : FN_CLIPS;
-        FnArgs a{};
+    return native_launches<FnArgs, FN_CLIPS>(sizes, clips, T, [&](FnArgs& a, int k, int, int h0, int w0, size_t off) {
+        a.c[k] = fn_geometry(off, h0, w0, H, W);
+        return a.c[k].nbands;
+    }, [&](FnArgs& a, int b0, int nb) -> int {
         a.native = native;
         a.out = out;
-        a.T = T; a.C = C; a.H = H; a.W = W; a.maxbands = 1; a.clip0 = b0;
-        for (int k = 0; k < nb; ++k) {
-            const int h0 = sizes[2 * (b0 + k)], w0 = sizes[2 * (b0 + k) + 1];
-            a.c[k] = fn_geometry(off, h0, w0, H, W);
-            if (a.c[k].nbands > a.maxbands) a.maxbands = a.c[k].nbands;
-            off += (size_t)T * (size_t)h0 * (size_t)w0;
-        }
+        a.T = T; a.C = C; a.H = H; a.W = W; a.clip0 = b0;
         a.items = (long long)nb * (long long)T * (long long)a.maxbands;
-        const unsigned grid = (unsigned)(a.items < FN_MAX_WG ? a.items : FN_MAX_WG);
+        const dim3 grid = native_grid(a.items, FN_MAX_WG);
         switch (out_dtype) {
-            case FN_U8: hipLaunchKernelGGL(frames_from_native_kernel<FN_U8>, dim3(grid), dim3(FN_NT), 0, st, a); break;
-            case FN_F32: hipLaunchKernelGGL(frames_from_native_kernel<FN_F32>, dim3(grid), dim3(FN_NT), 0, st, a); break;
-            default: hipLaunchKernelGGL(frames_from_native_kernel<FN_BF16>, dim3(grid), dim3(FN_NT), 0, st, a);
+            case FN_U8: hipLaunchKernelGGL(frames_from_native_kernel<FN_U8>, grid, dim3(FN_NT), 0, st, a); break;
+            case FN_F32: hipLaunchKernelGGL(frames_from_native_kernel<FN_F32>, grid, dim3(FN_NT), 0, st, a); break;
+            default: hipLaunchKernelGGL(frames_from_native_kernel<FN_BF16>, grid, dim3(FN_NT), 0, st, a);
         }
         GDKVM_LAUNCH_CHECK("frames_from_native_kernel");
-    }
-    return GDKVM_OK;
+        return GDKVM_OK;
+    });
 }

@@ -4,9 +4,8 @@
 // operation, for sides up to 2048 -- so the index and product widths are this file's own (the header restates the bounds they rest on) and
 // lv_measure.hip's kernel is neither instantiated nor touched.
 //
-// The mask is ragged as in mask_to_native.hip and surface_native.hip, and the launcher does what those do: sizes and spacings are HOST
-// integers, it validates them, computes every clip's byte offset and band-row offset and hands (offsets, h0, w0, ry, rx) to the kernels BY
-// VALUE in the kernel arguments, at most LN_CLIPS clips per launch.  Nothing copied, nothing allocated, nothing synchronised.
+// The mask is ragged: native_clips.hpp holds the launcher's side of that; a clip's entry here is (byte offset, band-row offset, h0, w0, ry,
+// rx).  Nothing copied, nothing allocated, nothing synchronised.
 //
 // A frame's work is spread over many workgroups by FOUR kernels in stream order over BANDS of LN_BAND_ROWS native rows of one (clip,
 // frame); a kernel reads what an earlier KERNEL wrote and nothing that another workgroup of its own launch writes: no flag, no spinning, no
@@ -24,7 +23,7 @@
 // Every kernel takes further items grid-stride past LN_MAX_WG workgroups.  Loop bounds: a band's vectors count to LN_BAND_ROWS w0 / 16 /
 // 256 = 16 per lane, a pixel meets at most D disks, the gcd takes at most 18 turns, a frame has at most 64 bands.
 
-#include "mask_frame.hpp"
+#include "native_clips.hpp"
 
 // No fused multiply-add in this file's own arithmetic (see lv_measure.hip): the fp64 steps are the definition's operations, one rounding each
 #pragma clang fp contract(off)
@@ -44,11 +43,10 @@ constexpr int LN_MAX_D = 64;                                   // disks
 constexpr int LN_BAND_ROWS = GDKVM_LV_NATIVE_BAND_ROWS;        // rows of a band (gdkvm.h)
 constexpr int LN_MAX_WG = GDKVM_LV_NATIVE_MAX_WG;              // workgroups per launch; more items than that are walked grid-stride
 constexpr int LN_CLIPS = GDKVM_LV_NATIVE_CLIPS;                // clips per launch
-constexpr int LN_MAX_NATIVE = 2048, LN_UM_MAX = 4095;
-constexpr int LN_MAX_BANDS = LN_MAX_NATIVE / LN_BAND_ROWS;     // 64: lane l of a wave holds band l of the frame
+constexpr int LN_MAX_BANDS = NATIVE_MAX_SIDE / LN_BAND_ROWS;   // 64: lane l of a wave holds band l of the frame
 constexpr i64 LN_I64_MAX = 0x7fffffffffffffffLL, LN_I64_MIN = -0x7fffffffffffffffLL - 1;
 static_assert(LN_MAX_BANDS <= 64, "one wave adds a frame's bands");
-static_assert(LN_BAND_ROWS * LN_MAX_NATIVE <= (1 << 16), "a lane of 256 meets at most 256 + 2 pixels of a band: its n, sx, sy fit 32 bits");
+static_assert(LN_BAND_ROWS * NATIVE_MAX_SIDE <= (1 << 16), "a lane of 256 meets at most 256 + 2 pixels of a band: its n, sx, sy fit 32 bits");
 
 struct LnClip {
     u64 off, brow;                                         // the clip's first byte in mask, its first row in bands
@@ -334,52 +332,35 @@ extern "C" int gdkvm_lv_measure_native(const uint8_t* mask, const int32_t* sizes
         return gdkvm_fail(GDKVM_ERR_ARG, "%s: null pointer (mask, the host sizes, the host spacing_um, stats, disks, geom and bands are required)",
                           name);
     if (int rc = mask_check_aligned16(name, GDKVM_ERR_ARG, "outputs", {stats, disks, geom, bands})) return rc;
-    const size_t frames = (size_t)clips * (size_t)T;
-    if (frames > ((size_t)1 << 30)) return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: clips * T = %zu frames exceed 2^30", name, frames);
-    size_t total = 0, rows = 0;
-    for (int b = 0; b < clips; ++b) {
-        const int h0 = sizes[2 * b], w0 = sizes[2 * b + 1], ry = spacing_um[2 * b], rx = spacing_um[2 * b + 1];
-        if (h0 < 1 || h0 > LN_MAX_NATIVE || w0 < 1 || w0 > LN_MAX_NATIVE)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: clip %d has the native size %d x %d (h0, w0 in 1..%d)", name, b, h0, w0, LN_MAX_NATIVE);
-        if (ry < 1 || ry > LN_UM_MAX || rx < 1 || rx > LN_UM_MAX)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: clip %d has the spacing %d x %d um (ry, rx in 1..%d)", name, b, ry, rx, LN_UM_MAX);
-        total += (size_t)T * (size_t)h0 * (size_t)w0;      // (< 2^30 * 2^22)
-        rows += (size_t)T * (size_t)((h0 + LN_BAND_ROWS - 1) / LN_BAND_ROWS);
-    }
-    if (native_bytes < total)
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: the native frames of these sizes take %zu bytes, native_bytes = %zu", name, total, native_bytes);
+    size_t total, rows = 0;
+    if (int rc = native_check_clips(name, "frames", sizes, spacing_um, native_bytes, clips, T, total)) return rc;
+    for (int b = 0; b < clips; ++b) rows += (size_t)T * (size_t)((sizes[2 * b] + LN_BAND_ROWS - 1) / LN_BAND_ROWS);
     if (native_bands < 0 || (size_t)native_bands != rows)
         return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: the native frames of these sizes have %zu bands of %d rows, native_bands = %lld", name, rows,
                           LN_BAND_ROWS, native_bands);
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    size_t off = 0, brow = 0;                              // carried from launch to launch
-    for (int b0 = 0; b0 < clips; b0 += LN_CLIPS) {
-        const int nb = clips - b0 < LN_CLIPS ? clips - b0 : LN_CLIPS;
-        LnArgs a{};
+    size_t brow = 0;                                       // carried from launch to launch, as the walk carries off
+    return native_launches<LnArgs, LN_CLIPS>(sizes, clips, T, [&](LnArgs& a, int k, int b, int h0, int w0, size_t off) {
+        a.c[k] = LnClip{(u64)off, (u64)brow, (unsigned short)h0, (unsigned short)w0, (unsigned short)spacing_um[2 * b],
+                        (unsigned short)spacing_um[2 * b + 1]};
+        const int nbands = (h0 + LN_BAND_ROWS - 1) / LN_BAND_ROWS;
+        brow += (size_t)T * (size_t)nbands;
+        return nbands;
+    }, [&](LnArgs& a, int b0, int nb) -> int {
         a.mask = mask; a.stats = reinterpret_cast<i64*>(stats); a.disks = reinterpret_cast<i64*>(disks); a.geom = geom;
         a.bands = reinterpret_cast<i64*>(bands);
         a.frame0 = (long long)b0 * T;
-        a.nclips = nb; a.T = T; a.cls = cls; a.D = D; a.maxbands = 1;
-        for (int k = 0; k < nb; ++k) {
-            const int h0 = sizes[2 * (b0 + k)], w0 = sizes[2 * (b0 + k) + 1];
-            a.c[k] = LnClip{(u64)off, (u64)brow, (unsigned short)h0, (unsigned short)w0, (unsigned short)spacing_um[2 * (b0 + k)],
-                            (unsigned short)spacing_um[2 * (b0 + k) + 1]};
-            const int nbands = (h0 + LN_BAND_ROWS - 1) / LN_BAND_ROWS;
-            if (nbands > a.maxbands) a.maxbands = nbands;
-            off += (size_t)T * (size_t)h0 * (size_t)w0;
-            brow += (size_t)T * (size_t)nbands;
-        }
-        auto grid = [](long long items) { return dim3((unsigned)(items < LN_MAX_WG ? items : LN_MAX_WG)); };
+        a.nclips = nb; a.T = T; a.cls = cls; a.D = D;
         const long long fr = (long long)nb * T;
-        hipLaunchKernelGGL(ln_moments_kernel, grid(fr * a.maxbands), dim3(LN_NT), 0, st, a);
+        hipLaunchKernelGGL(ln_moments_kernel, native_grid(fr * a.maxbands, LN_MAX_WG), dim3(LN_NT), 0, st, a);
         GDKVM_LAUNCH_CHECK("ln_moments_kernel");
-        hipLaunchKernelGGL(ln_extent_kernel, grid(fr * a.maxbands), dim3(LN_NT), 0, st, a);
+        hipLaunchKernelGGL(ln_extent_kernel, native_grid(fr * a.maxbands, LN_MAX_WG), dim3(LN_NT), 0, st, a);
         GDKVM_LAUNCH_CHECK("ln_extent_kernel");
-        hipLaunchKernelGGL(ln_disks_kernel, grid(fr * a.maxbands), dim3(LN_NT), 0, st, a);
+        hipLaunchKernelGGL(ln_disks_kernel, native_grid(fr * a.maxbands, LN_MAX_WG), dim3(LN_NT), 0, st, a);
         GDKVM_LAUNCH_CHECK("ln_disks_kernel");
-        hipLaunchKernelGGL(ln_finish_kernel, grid(fr), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(ln_finish_kernel, native_grid(fr, LN_MAX_WG), dim3(64), 0, st, a);
         GDKVM_LAUNCH_CHECK("ln_finish_kernel");
-    }
-    return GDKVM_OK;
+        return GDKVM_OK;
+    });
 }

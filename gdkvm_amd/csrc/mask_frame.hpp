@@ -1,14 +1,37 @@
 // mask_frame.hpp -- what the per-frame kernels over uint8 label masks share (lv_measure.hip, largest_component.hip, surface_distance.hip, fill_holes.hip):
 // ONE workgroup walks one frame [H, W] of bytes at any byte address.  The frame split and its sweeps, the walk over the set bits of a match
-// word, integer wave reductions and the workgroup fold of their per-wave partials, the accessors of a frame's 32-, 16- and 64-bit words, and the
-// launchers' shared argument checks.  A new per-frame mask kernel starts here (one that labels connected components: from mask_labels.hpp,
-// which builds on this).  No floating-point code: a file may include this ahead of
-// an fp-contract pragma of its own.  Like gdkvm_device.hpp, every device helper is __forceinline__ and written with the exact expression the
-// kernels used before they shared it (tools/isa_equal.py).
+// word, integer wave reductions and the workgroup fold of their per-wave partials, the accessors of a frame's 32-, 16- and 64-bit words, the
+// byte-parallel compares of packed label bytes (temporal_vote.hip and mask_to_native.hip count with them) and the launchers' shared
+// argument checks.  A new per-frame mask kernel starts here (one that labels connected components: from mask_labels.hpp, one over clips at
+// their native size: from native_clips.hpp; both build on this).  No floating-point code: a file may include this ahead of an fp-contract
+// pragma of its own.  Like gdkvm_device.hpp, every device helper is __forceinline__ and written with the exact expression the kernels used
+// before they shared it (tools/isa_equal.py).
 #pragma once
 #include <initializer_list>
 
 #include "gdkvm_device.hpp"
+
+// gdkvm_common.hpp's gdkvm_aligned16 for device code (an overload: that header is one of the sources build.source_hash() pins)
+__device__ __forceinline__ bool gdkvm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// the bytes from address a up to the 16-byte grid: 0..15, the head of a run of bytes that is then read or written 16 bytes at a time
+__device__ __forceinline__ int head16(uintptr_t a) { return (int)((16u - (unsigned)(a & 15u)) & 15u); }
+
+// Four label bytes to a word, compared byte-parallel: each answer is 0x80 in every byte for which it is yes.
+constexpr unsigned BYTES_HI = 0x80808080u, BYTES_LO = 0x7f7f7f7fu, BYTES_ONE = 0x01010101u;
+// ... in every byte of x that equals c (exact for every byte value: the low seven bits are tested without a carry into the next byte)
+__device__ __forceinline__ unsigned eq80(unsigned x, unsigned c)
+{
+    const unsigned y = x ^ (c * BYTES_ONE);
+    return ~(((y & BYTES_LO) + BYTES_LO) | y) & BYTES_HI;
+}
+// ... where a and b differ
+__device__ __forceinline__ unsigned ne80(unsigned a, unsigned b)
+{
+    const unsigned y = a ^ b;
+    return (((y & BYTES_LO) + BYTES_LO) | y) & BYTES_HI;
+}
+// ... where a > b, for bytes below 128: (b + 128) - a borrows from no neighbour and keeps its top bit iff b >= a
+__device__ __forceinline__ unsigned gt80(unsigned a, unsigned b) { return ~((b | BYTES_HI) - a) & BYTES_HI; }
 
 // bit e = byte e of the vector equals cls
 __device__ __forceinline__ unsigned match16(const uint4& v, unsigned cls)
@@ -60,7 +83,7 @@ struct MaskFrame {
     // (HW - head) & 15 as in the kernels that had the split inline.
     __device__ __forceinline__ MaskFrame(const uint8_t* base_, int HW, int W_, unsigned cls_) : base(base_), W(W_), cls(cls_)
     {
-        int h = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base_) & 15u)) & 15u);
+        int h = head16(reinterpret_cast<uintptr_t>(base_));
         if (h > HW) h = HW;
         const int nv = (HW - h) >> 4;
         head = h; nvec = nv; nbody = 16 * nv; tail = HW - h - 16 * nv;

@@ -4,10 +4,8 @@
 // pixels around a native pixel vote their weights wy wx for their classes, the class with the most votes wins, the smallest class among
 // equals, 255 when nothing votes.  out and counts depend on neither the schedule nor the path taken.  No floating-point code in this file.
 //
-// The native sizes differ from clip to clip, so the native masks are ragged: the launcher gets the sizes as HOST integers, validates them,
-// computes every clip's byte offset and hands (offset, h0, w0, rows per band, bands) to the kernel BY VALUE in the kernel arguments, at most
-// MN_CLIPS clips per launch (1.6 KB of the 4 KB an argument block may have), longer batches in several launches -- as adamw.hip does with
-// its addresses: no table in device memory whose contents the kernel would have to trust, nothing copied, nothing allocated.
+// The native sizes differ from clip to clip, so the native masks are ragged: native_clips.hpp holds the launcher's side of that; a clip's
+// entry here is (offset, h0, w0, rows per band, bands), MN_CLIPS of them 1.6 KB of the 4 KB an argument block may have.
 //
 // A workgroup of 256 lanes owns a BAND of native rows of one (clip, frame): as many whole rows as come nearest above MN_BAND_PIXELS pixels,
 // so that a band of a 549 x 778 frame (6 rows) and one of a 2048 x 3 frame (1366 rows) both keep the lanes busy.  The rows of a band follow each
@@ -40,7 +38,7 @@
 // The grid follows the clip with the most bands of the launch: item = (clip, frame, band) over clips x T x maxbands, and a workgroup whose
 // band lies past its clip's last leaves at once.  More than MN_MAX_WG items are taken grid-stride.
 
-#include "mask_frame.hpp"
+#include "native_clips.hpp"
 
 namespace {
 
@@ -49,10 +47,8 @@ constexpr int MN_RUN = GDKVM_MASK_TO_NATIVE_RUN;               // native pixels 
 constexpr int MN_BAND_PIXELS = GDKVM_MASK_TO_NATIVE_BAND_PIXELS;       // a band is the fewest whole rows with at least this many pixels
 constexpr int MN_MAX_WG = GDKVM_MASK_TO_NATIVE_MAX_WG;         // workgroups per launch; more items than that are walked grid-stride
 constexpr int MN_CLIPS = GDKVM_MASK_TO_NATIVE_CLIPS;           // clips per launch
-constexpr int MN_MAX_NATIVE = 2048;
 static_assert(MN_RUN == 16, "a run is one 16-byte vector");
 static_assert(MN_BAND_PIXELS == MN_NT * MN_RUN, "a band gives every lane one run");
-constexpr unsigned MN_HI = 0x80808080u, MN_LO = 0x7f7f7f7fu, MN_ONE = 0x01010101u;
 
 struct MnClip {
     unsigned long long off;                                // the clip's first byte in out / target
@@ -68,14 +64,7 @@ struct MnArgs {
 };
 static_assert(sizeof(MnArgs) <= 2048, "the clip table travels in the kernel arguments");
 
-// 0x80 in every byte of x that equals c (exact for every byte value; temporal_vote.hip's tv_eq80)
-__device__ __forceinline__ unsigned mn_eq80(unsigned x, unsigned c)
-{
-    const unsigned y = x ^ (c * MN_ONE);
-    return ~(((y & MN_LO) + MN_LO) | y) & MN_HI;
-}
 __device__ __forceinline__ int mn_clamp(int i, int hi) { return i < 0 ? 0 : (i > hi ? hi : i); }
-__device__ __forceinline__ bool mn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <int NC>
 __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
@@ -86,9 +75,7 @@ __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
     const bool dice = a.target != nullptr;
     const long long per_clip = (long long)a.T * a.maxbands;
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
-        const int clip = (int)(item / per_clip);           // (< MN_CLIPS)
-        const long long rem = item - clip * per_clip;
-        const int t = (int)(rem / a.maxbands), band = (int)(rem - (long long)t * a.maxbands);
+        const auto [clip, t, band] = native_item(item, per_clip, a.maxbands);      // (clip < MN_CLIPS)
         const MnClip c = a.c[clip];
         if (band >= c.nbands) continue;                    // (uniform: a smaller clip of the launch has fewer bands)
         const int h0 = c.h0, w0 = c.w0, row0 = band * c.rpb;
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
         const uint8_t* tp = dice ? a.target + fpos : nullptr;
         // the 16-byte grid of out's addresses (target's without an out): run 0 is the head, run j >= 1 starts at s + head + 16 (j - 1)
         const uintptr_t ga = reinterpret_cast<uintptr_t>(op ? (const uint8_t*)op : tp) + (uintptr_t)s;
-        int head = (int)((16u - (unsigned)(ga & 15u)) & 15u);
+        int head = head16(ga);
         if (head > e - s) head = e - s;
         const int nrun = 1 + (e - s - head + MN_RUN - 1) / MN_RUN;
         // nx(x + 1) = nx(x) + 2 W = nx(x) + qx dx + rx with 0 <= rx < dx, and the same down the rows; column 0 starts from (ix00, fx00)
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
             }
             if (op) {
                 uint8_t* o = op + ps;
-                if (n == MN_RUN && mn_aligned16(o)) {
+                if (n == MN_RUN && gdkvm_aligned16(o)) {
                     *reinterpret_cast<uint4*>(o) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
                 } else {
 #pragma unroll
@@ -176,7 +163,7 @@ __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
             if (dice) {
                 const uint8_t* g = tp + ps;
                 unsigned tw[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-                if (n == MN_RUN && mn_aligned16(g)) {
+                if (n == MN_RUN && gdkvm_aligned16(g)) {
                     const uint4 v = *reinterpret_cast<const uint4*>(g);
                     tw[0] = v.x; tw[1] = v.y; tw[2] = v.z; tw[3] = v.w;
                 } else {
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
                 for (int cl = 0; cl < NC; ++cl)
 #pragma unroll
                     for (int w = 0; w < 4; ++w) {
-                        const unsigned eo = mn_eq80(ow[w], (unsigned)cl), et = mn_eq80(tw[w], (unsigned)cl);
+                        const unsigned eo = eq80(ow[w], (unsigned)cl), et = eq80(tw[w], (unsigned)cl);
                         cnt[3 * cl + 0] += __builtin_popcount(eo & et);
                         cnt[3 * cl + 1] += __builtin_popcount(eo);
                         cnt[3 * cl + 2] += __builtin_popcount(et);
@@ -216,8 +203,6 @@ __global__ __launch_bounds__(MN_NT) void mask_to_native_kernel(MnArgs a)
 
 inline bool mn_shape_ok(int clips, int T, int H, int W, int ncls) { return mask_shape_ok(clips, H, W) && T >= 1 && ncls >= 2 && ncls <= 8; }
 
-inline bool mn_overlap(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) { return a < b + nb && b < a + na; }
-
 }  // namespace
 
 // The kernel keeps its state in registers and adds its sums into the zeroed counts: no workspace for any shape.
@@ -239,19 +224,10 @@ extern "C" int gdkvm_mask_to_native(const uint8_t* mask, const int32_t* sizes, c
     if (!out && !target) return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_to_native: neither out nor target: nothing to do");
     if (target && !counts) return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_to_native: counts required with a target");
     if (int rc = mask_check_aligned16("mask_to_native", GDKVM_ERR_SHAPE, "counts", {target ? counts : nullptr})) return rc;
-    const size_t frames = (size_t)clips * (size_t)T;
-    if (frames > ((size_t)1 << 30)) return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_to_native: clips * T = %zu frames exceed 2^30", frames);
-    size_t total = 0;
-    for (int b = 0; b < clips; ++b) {
-        const int h0 = sizes[2 * b], w0 = sizes[2 * b + 1];
-        if (h0 < 1 || h0 > MN_MAX_NATIVE || w0 < 1 || w0 > MN_MAX_NATIVE)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_to_native: clip %d has the native size %d x %d (h0, w0 in 1..%d)", b, h0, w0, MN_MAX_NATIVE);
-        total += (size_t)T * (size_t)h0 * (size_t)w0;      // (< 2^30 * 2^22)
-    }
-    if (native_bytes < total)
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_to_native: the native masks of these sizes take %zu bytes, native_bytes = %zu", total, native_bytes);
-    const size_t src_bytes = frames * (size_t)H * (size_t)W;
-    if (out && (mn_overlap(out, total, mask, src_bytes) || (target && mn_overlap(out, total, target, total))))
+    size_t total;
+    if (int rc = native_check_clips("mask_to_native", "masks", sizes, nullptr, native_bytes, clips, T, total)) return rc;
+    const size_t frames = (size_t)clips * (size_t)T, src_bytes = frames * (size_t)H * (size_t)W;
+    if (out && (native_overlap(out, total, mask, src_bytes) || (target && native_overlap(out, total, target, total))))
         return gdkvm_fail(GDKVM_ERR_SHAPE, "mask_to_native: out must overlap neither mask nor target");
     const size_t need = gdkvm_mask_to_native_workspace_bytes(clips, T, H, W, ncls);
     if (int rc = mask_check_workspace("mask_to_native", H, W, need, workspace, workspace_bytes)) return rc;
@@ -259,35 +235,29 @@ extern "C" int gdkvm_mask_to_native(const uint8_t* mask, const int32_t* sizes, c
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (target)
         if (int rc = gdkvm_zero_async(counts, frames * (size_t)ncls * 3 * sizeof(int32_t), st)) return rc;
-    size_t off = 0;                                        // carried from launch to launch
-    for (int b0 = 0; b0 < clips; b0 += MN_CLIPS) {
-        const int nb = clips - b0 < MN_CLIPS ? clips - b0 : MN_CLIPS;
-        MnArgs a{};
+    return native_launches<MnArgs, MN_CLIPS>(sizes, clips, T, [&](MnArgs& a, int k, int, int h0, int w0, size_t off) {
+        int rpb = (MN_BAND_PIXELS + w0 - 1) / w0;          // the fewest whole rows with at least MN_BAND_PIXELS pixels
+        if (rpb > h0) rpb = h0;
+        const int nbands = (h0 + rpb - 1) / rpb;
+        a.c[k] = MnClip{(unsigned long long)off, h0, w0, rpb, nbands};
+        return nbands;
+    }, [&](MnArgs& a, int b0, int nb) -> int {
         a.mask = mask + (size_t)b0 * (size_t)T * (size_t)H * (size_t)W;
         a.target = target; a.out = out;
         a.counts = target ? counts + (size_t)b0 * (size_t)T * (size_t)ncls * 3 : nullptr;
-        a.T = T; a.H = H; a.W = W; a.maxbands = 1;
-        for (int k = 0; k < nb; ++k) {
-            const int h0 = sizes[2 * (b0 + k)], w0 = sizes[2 * (b0 + k) + 1];
-            int rpb = (MN_BAND_PIXELS + w0 - 1) / w0;      // the fewest whole rows with at least MN_BAND_PIXELS pixels
-            if (rpb > h0) rpb = h0;
-            const int nbands = (h0 + rpb - 1) / rpb;
-            a.c[k] = MnClip{(unsigned long long)off, h0, w0, rpb, nbands};
-            if (nbands > a.maxbands) a.maxbands = nbands;
-            off += (size_t)T * (size_t)h0 * (size_t)w0;
-        }
+        a.T = T; a.H = H; a.W = W;
         a.items = (long long)nb * (long long)T * (long long)a.maxbands;
-        const unsigned grid = (unsigned)(a.items < MN_MAX_WG ? a.items : MN_MAX_WG);
+        const dim3 grid = native_grid(a.items, MN_MAX_WG);
         switch (ncls) {
-            case 2: hipLaunchKernelGGL(mask_to_native_kernel<2>, dim3(grid), dim3(MN_NT), 0, st, a); break;
-            case 3: hipLaunchKernelGGL(mask_to_native_kernel<3>, dim3(grid), dim3(MN_NT), 0, st, a); break;
-            case 4: hipLaunchKernelGGL(mask_to_native_kernel<4>, dim3(grid), dim3(MN_NT), 0, st, a); break;
-            case 5: hipLaunchKernelGGL(mask_to_native_kernel<5>, dim3(grid), dim3(MN_NT), 0, st, a); break;
-            case 6: hipLaunchKernelGGL(mask_to_native_kernel<6>, dim3(grid), dim3(MN_NT), 0, st, a); break;
-            case 7: hipLaunchKernelGGL(mask_to_native_kernel<7>, dim3(grid), dim3(MN_NT), 0, st, a); break;
-            default: hipLaunchKernelGGL(mask_to_native_kernel<8>, dim3(grid), dim3(MN_NT), 0, st, a);
+            case 2: hipLaunchKernelGGL(mask_to_native_kernel<2>, grid, dim3(MN_NT), 0, st, a); break;
+            case 3: hipLaunchKernelGGL(mask_to_native_kernel<3>, grid, dim3(MN_NT), 0, st, a); break;
+            case 4: hipLaunchKernelGGL(mask_to_native_kernel<4>, grid, dim3(MN_NT), 0, st, a); break;
+            case 5: hipLaunchKernelGGL(mask_to_native_kernel<5>, grid, dim3(MN_NT), 0, st, a); break;
+            case 6: hipLaunchKernelGGL(mask_to_native_kernel<6>, grid, dim3(MN_NT), 0, st, a); break;
+            case 7: hipLaunchKernelGGL(mask_to_native_kernel<7>, grid, dim3(MN_NT), 0, st, a); break;
+            default: hipLaunchKernelGGL(mask_to_native_kernel<8>, grid, dim3(MN_NT), 0, st, a);
         }
         GDKVM_LAUNCH_CHECK("mask_to_native_kernel");
-    }
-    return GDKVM_OK;
+        return GDKVM_OK;
+    });
 }

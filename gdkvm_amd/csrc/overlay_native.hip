@@ -4,9 +4,8 @@
 // frame; contour of the mask > contour of the ref > tinted class > grey.  Exact integers, one writer per output byte, no atomics: out depends
 // on neither the schedule nor the path taken.  No floating-point code in this file.
 //
-// The buffers are ragged as in mask_to_native.hip, and the launcher does what that one does: the sizes are HOST integers, it validates
-// them, computes every clip's pixel offset and hands (offset, h0, w0, rows per band, bands) to the kernel BY VALUE in the kernel arguments,
-// at most OV_CLIPS clips per launch, beside the two palettes packed one colour to a word.  Nothing copied, nothing allocated.
+// The buffers are ragged: native_clips.hpp holds the launcher's side of that; a clip's entry here is (pixel offset, h0, w0, rows per band,
+// bands), and the two palettes travel beside the clips, packed one colour to a word.
 //
 // A workgroup of 256 lanes owns a BAND of native rows of one (clip, frame): the most whole rows whose run slots (below: 1 + ceil(w0 / 16)
 // per row) number at most OV_BAND_RUNS = 512, two to a lane -- 10 rows of a 549 x 778 frame -- at least one row and at most
@@ -48,7 +47,7 @@
 // band lies past its clip's last leaves at once.  More than OV_MAX_WG items are taken grid-stride.  Dynamic LDS: the 192 bytes of the
 // colour table and one or two tiles of the launch's largest (rows + 2 w) P, at most 192 + 2 * 9 * 2112 bytes (a 2048-wide frame).
 
-#include "mask_frame.hpp"
+#include "native_clips.hpp"
 
 namespace {
 
@@ -58,12 +57,11 @@ constexpr int OV_BAND_RUNS = GDKVM_OVERLAY_NATIVE_BAND_RUNS;   // a band is the 
 constexpr int OV_BAND_ROWS = GDKVM_OVERLAY_NATIVE_BAND_ROWS;   // ... and at most this many rows
 constexpr int OV_MAX_WG = GDKVM_OVERLAY_NATIVE_MAX_WG;         // workgroups per launch; more items than that are walked grid-stride
 constexpr int OV_CLIPS = GDKVM_OVERLAY_NATIVE_CLIPS;           // clips per launch
-constexpr int OV_MAX_NATIVE = 2048, OV_MAX_WIDTH = 3;
+constexpr int OV_MAX_WIDTH = 3;
 constexpr int OV_TAB = 24;                                     // entries of the colour table: [0] grey, [k] tint, [8 + k] contour, [16 + k] ref contour
 constexpr int OV_PAL_BYTES = OV_TAB * 8;                       // the table in front of the tiles
 static_assert(OV_RUN == 16, "a run is three 16-byte vectors of out");
 static_assert(OV_BAND_RUNS == 2 * OV_NT, "a band gives every lane at most two runs");
-constexpr unsigned OV_HI = 0x80808080u, OV_LO = 0x7f7f7f7fu, OV_ONE = 0x01010101u;
 
 // bytes of a native row's LDS row: 16 + 15 in front of the pixels, and a window's seven words may end 25 bytes behind the last pixel
 __host__ __device__ constexpr int ov_pitch(int w0) { return (w0 + 71) & ~15; }
@@ -81,13 +79,12 @@ struct OvArgs {
 };
 static_assert(sizeof(OvArgs) <= 2048, "the clip table travels in the kernel arguments");
 
-__device__ __forceinline__ bool ov_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // 0x80 in every byte of d that is not zero
-__device__ __forceinline__ unsigned ov_nz80(unsigned d) { return (((d & OV_LO) + OV_LO) | d) & OV_HI; }
+__device__ __forceinline__ unsigned ov_nz80(unsigned d) { return (((d & BYTES_LO) + BYTES_LO) | d) & BYTES_HI; }
 // 0x80 in every byte of c that is a class byte: not zero and below ncls (<= 8)
 __device__ __forceinline__ unsigned ov_cls80(unsigned c, unsigned ncls)
 {
-    const unsigned ge = (((c & OV_LO) + (0x80u - ncls) * OV_ONE) | c) & OV_HI;
+    const unsigned ge = (((c & BYTES_LO) + (0x80u - ncls) * BYTES_ONE) | c) & BYTES_HI;
     return ov_nz80(c) & ~ge;
 }
 // 0xff in every byte of x that holds 0x80 (x has no other bits)
@@ -201,9 +198,7 @@ __global__ __launch_bounds__(OV_NT) void overlay_native_kernel(OvArgs a)
     }
     const long long per_clip = (long long)a.T * a.maxbands;
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
-        const int clip = (int)(item / per_clip);           // (< OV_CLIPS)
-        const long long rem = item - clip * per_clip;
-        const int t = (int)(rem / a.maxbands), band = (int)(rem - (long long)t * a.maxbands);
+        const auto [clip, t, band] = native_item(item, per_clip, a.maxbands);      // (clip < OV_CLIPS)
         const OvClip c = a.c[clip];
         if (band >= c.nbands) continue;                    // (uniform: a smaller clip of the launch has fewer bands)
         const int h0 = c.h0, w0 = c.w0, row0 = band * c.rpb;
@@ -247,7 +242,7 @@ __global__ __launch_bounds__(OV_NT) void overlay_native_kernel(OvArgs a)
             // the grey bytes, four pixels to a word; a byte past the run's end is neither loaded nor used
             unsigned gw[4] = {0u, 0u, 0u, 0u};
             const uint8_t* gp = gf + q + x;
-            if (full && ov_aligned16(gp)) {
+            if (full && gdkvm_aligned16(gp)) {
                 const uint4 v = *reinterpret_cast<const uint4*>(gp);
                 gw[0] = v.x; gw[1] = v.y; gw[2] = v.z; gw[3] = v.w;
             } else {
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(OV_NT) void overlay_native_kernel(OvArgs a)
                 }
             }
             uint8_t* o = of + 3 * (q + x);
-            if (full && ov_aligned16(o)) {                 // (every full run behind the head is)
+            if (full && gdkvm_aligned16(o)) {                 // (every full run behind the head is)
                 uint4* o4 = reinterpret_cast<uint4*>(o);
                 o4[0] = make_uint4(ow[0], ow[1], ow[2], ow[3]);
                 o4[1] = make_uint4(ow[4], ow[5], ow[6], ow[7]);
@@ -312,8 +307,6 @@ __global__ __launch_bounds__(OV_NT) void overlay_native_kernel(OvArgs a)
     }
 }
 
-inline bool ov_overlap(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) { return a < b + nb && b < a + na; }
-
 inline int ov_rows_per_band(int h0, int w0)
 {
     int rpb = OV_BAND_RUNS / (1 + (w0 + OV_RUN - 1) / OV_RUN);   // the most whole rows whose run slots are at most OV_BAND_RUNS
@@ -323,10 +316,10 @@ inline int ov_rows_per_band(int h0, int w0)
 }
 
 template <int WD>
-void ov_launch(bool ref, unsigned grid, size_t lds, hipStream_t st, const OvArgs& a)
+void ov_launch(bool ref, dim3 grid, size_t lds, hipStream_t st, const OvArgs& a)
 {
-    if (ref) hipLaunchKernelGGL((overlay_native_kernel<WD, true>), dim3(grid), dim3(OV_NT), lds, st, a);
-    else hipLaunchKernelGGL((overlay_native_kernel<WD, false>), dim3(grid), dim3(OV_NT), lds, st, a);
+    if (ref) hipLaunchKernelGGL((overlay_native_kernel<WD, true>), grid, dim3(OV_NT), lds, st, a);
+    else hipLaunchKernelGGL((overlay_native_kernel<WD, false>), grid, dim3(OV_NT), lds, st, a);
 }
 
 }  // namespace
@@ -349,52 +342,39 @@ extern "C" int gdkvm_overlay_native(const uint8_t* grey, const uint8_t* mask, co
     if (!grey || !mask || !sizes || !pal || !out)
         return gdkvm_fail(GDKVM_ERR_SHAPE, "overlay_native: null pointer (grey, mask, the host sizes, the host palette and out are required)");
     if (ref && !ref_pal) return gdkvm_fail(GDKVM_ERR_SHAPE, "overlay_native: ref_pal required with a ref");
-    const size_t frames = (size_t)clips * (size_t)T;
-    if (frames > ((size_t)1 << 30)) return gdkvm_fail(GDKVM_ERR_SHAPE, "overlay_native: clips * T = %zu frames exceed 2^30", frames);
-    size_t total = 0;
-    for (int b = 0; b < clips; ++b) {
-        const int h0 = sizes[2 * b], w0 = sizes[2 * b + 1];
-        if (h0 < 1 || h0 > OV_MAX_NATIVE || w0 < 1 || w0 > OV_MAX_NATIVE)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "overlay_native: clip %d has the native size %d x %d (h0, w0 in 1..%d)", b, h0, w0, OV_MAX_NATIVE);
-        total += (size_t)T * (size_t)h0 * (size_t)w0;      // (< 2^30 * 2^22)
-    }
-    if (native_bytes < total)
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "overlay_native: the native frames of these sizes take %zu bytes, native_bytes = %zu", total, native_bytes);
-    if (ov_overlap(out, 3 * total, grey, total) || ov_overlap(out, 3 * total, mask, total) || (ref && ov_overlap(out, 3 * total, ref, total)))
+    size_t total;
+    if (int rc = native_check_clips("overlay_native", "frames", sizes, nullptr, native_bytes, clips, T, total)) return rc;
+    if (native_overlap(out, 3 * total, grey, total) || native_overlap(out, 3 * total, mask, total) ||
+        (ref && native_overlap(out, 3 * total, ref, total)))
         return gdkvm_fail(GDKVM_ERR_SHAPE, "overlay_native: out must overlap none of grey, mask and ref");
     const size_t need = gdkvm_overlay_native_workspace_bytes(clips, T, ncls, width);
     if (int rc = mask_check_workspace("overlay_native", 0, 0, need, workspace, workspace_bytes)) return rc;
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    size_t off = 0;                                        // carried from launch to launch
-    for (int b0 = 0; b0 < clips; b0 += OV_CLIPS) {
-        const int nb = clips - b0 < OV_CLIPS ? clips - b0 : OV_CLIPS;
-        OvArgs a{};
+    size_t tile = 0;                                       // the current launch's largest tile: the launch callable clears it for the next
+    return native_launches<OvArgs, OV_CLIPS>(sizes, clips, T, [&](OvArgs& a, int k, int, int h0, int w0, size_t off) {
+        const int rpb = ov_rows_per_band(h0, w0), nbands = (h0 + rpb - 1) / rpb;
+        a.c[k] = OvClip{(unsigned long long)off, h0, w0, rpb, nbands};
+        const size_t tb = (size_t)(rpb + 2 * width) * (size_t)ov_pitch(w0);
+        if (tb > tile) tile = tb;
+        return nbands;
+    }, [&](OvArgs& a, int, int nb) -> int {
         a.grey = grey; a.mask = mask; a.ref = ref; a.out = out;
-        a.T = T; a.maxbands = 1; a.ncls = ncls; a.alpha = alpha;
+        a.T = T; a.ncls = ncls; a.alpha = alpha;
         for (int k = 1; k < ncls; ++k) {                   // (class 0 is never drawn)
             a.pal[k] = (unsigned)pal[3 * k] | (unsigned)pal[3 * k + 1] << 8 | (unsigned)pal[3 * k + 2] << 16;
             if (ref) a.pal[8 + k] = (unsigned)ref_pal[3 * k] | (unsigned)ref_pal[3 * k + 1] << 8 | (unsigned)ref_pal[3 * k + 2] << 16;
         }
-        size_t tile = 0;                                   // the launch's largest tile
-        for (int k = 0; k < nb; ++k) {
-            const int h0 = sizes[2 * (b0 + k)], w0 = sizes[2 * (b0 + k) + 1];
-            const int rpb = ov_rows_per_band(h0, w0), nbands = (h0 + rpb - 1) / rpb;
-            a.c[k] = OvClip{(unsigned long long)off, h0, w0, rpb, nbands};
-            if (nbands > a.maxbands) a.maxbands = nbands;
-            const size_t tb = (size_t)(rpb + 2 * width) * (size_t)ov_pitch(w0);
-            if (tb > tile) tile = tb;
-            off += (size_t)T * (size_t)h0 * (size_t)w0;
-        }
         a.items = (long long)nb * (long long)T * (long long)a.maxbands;
-        const unsigned grid = (unsigned)(a.items < OV_MAX_WG ? a.items : OV_MAX_WG);
+        const dim3 grid = native_grid(a.items, OV_MAX_WG);
         const size_t lds = OV_PAL_BYTES + (ref ? 2 : 1) * tile;   // (<= 192 + 2 * 9 * 2112: below the 64 KiB a launch may ask for)
+        tile = 0;
         switch (width) {
             case 1: ov_launch<1>(ref != nullptr, grid, lds, st, a); break;
             case 2: ov_launch<2>(ref != nullptr, grid, lds, st, a); break;
             default: ov_launch<3>(ref != nullptr, grid, lds, st, a);
         }
         GDKVM_LAUNCH_CHECK("overlay_native_kernel");
-    }
-    return GDKVM_OK;
+        return GDKVM_OK;
+    });
 }

@@ -2,9 +2,8 @@
 // size (h0, w0) (what HD, HD95 and ASSD in mm at native resolution are made of; eval.py's native.surface block).  include/gdkvm.h holds the
 // definition (gdkvm_surface_distance_native); every output is an integer that depends on neither the algorithm nor the schedule.
 //
-// The buffers are ragged as in mask_to_native.hip, and the launcher does what that one does: sizes and spacings are HOST integers, it
-// validates them, computes every clip's pixel offset and bitmap offset and hands (offsets, h0, w0, ry, rx) to the kernels BY VALUE in the
-// kernel arguments, at most SN_CLIPS clips per launch.  Nothing copied, nothing allocated, nothing synchronised.
+// The buffers are ragged: native_clips.hpp holds the launcher's side of that; a clip's entry here is (pixel offset, bitmap offset, h0, w0,
+// ry, rx).  Nothing copied, nothing allocated, nothing synchronised.
 //
 // A frame's work is spread over many workgroups by FOUR kernels in stream order; a kernel reads what an earlier KERNEL wrote and nothing
 // that another workgroup of its own launch writes: no flag, no spinning, no fence anybody polls.
@@ -39,7 +38,7 @@
 // of two 16-bit loads: 2^21 * 2047 * 2 = 8.6 G loads, over 64 bands x 256 lanes.  (d): n = 2^21 + 1 values, 49 passes of n / 256 = 8193
 // trips per lane, in ONE workgroup per frame.  Slow, bounded, and only (d) is not spread.
 
-#include "mask_frame.hpp"
+#include "native_clips.hpp"
 
 namespace {
 
@@ -51,9 +50,8 @@ constexpr int SN_BAND_ROWS = GDKVM_SURFACE_NATIVE_BAND_ROWS;   // rows of a band
 constexpr int SN_STRIP = GDKVM_SURFACE_NATIVE_STRIP;           // columns of a strip: one wave
 constexpr int SN_MAX_WG = GDKVM_SURFACE_NATIVE_MAX_WG;         // workgroups per launch; more items than that are walked grid-stride
 constexpr int SN_CLIPS = GDKVM_SURFACE_NATIVE_CLIPS;           // clips per launch
-constexpr int SN_MAX_NATIVE = 2048, SN_UM_MAX = 4095;
-constexpr int SN_MAX_BANDS = SN_MAX_NATIVE / SN_BAND_ROWS;     // 64: a frame's count slots, and one wave sums them
-constexpr int SN_MAX_WPR = SN_MAX_NATIVE / 32;                 // words of a bitmap row
+constexpr int SN_MAX_BANDS = NATIVE_MAX_SIDE / SN_BAND_ROWS;   // 64: a frame's count slots, and one wave sums them
+constexpr int SN_MAX_WPR = NATIVE_MAX_SIDE / 32;               // words of a bitmap row
 constexpr unsigned SN_NONE = 0xffffu;                          // g of a column without a pixel of the other surface
 constexpr int SN_SWEEP = 8;                                    // rows of a column sweep whose loads are in flight together
 constexpr int SN_WALK = 4;                                     // steps of a row walk whose loads are in flight together
@@ -112,9 +110,7 @@ __global__ __launch_bounds__(SN_NT) void sn_surfaces_kernel(SnArgs a)
     const unsigned cls = (unsigned)a.cls;
     const long long per_clip = (long long)a.T * a.maxbands, items = per_clip * a.nclips;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
-        const int clip = (int)(item / per_clip);
-        const long long rem = item - clip * per_clip;
-        const int t = (int)(rem / a.maxbands), band = (int)(rem - (long long)t * a.maxbands);
+        const auto [clip, t, band] = native_item(item, per_clip, a.maxbands);
         const SnClip c = a.c[clip];
         const int h0 = c.h0, w0 = c.w0, wpr = (w0 + 31) >> 5, nbands = (h0 + SN_BAND_ROWS - 1) / SN_BAND_ROWS;
         if (band >= nbands) continue;                      // (uniform: a smaller clip of the launch has fewer bands)
@@ -408,20 +404,10 @@ extern "C" int gdkvm_surface_distance_native(const uint8_t* mask, const uint8_t*
     if (!mask || !target || !sizes || !spacing_um || !surf)
         return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: null pointer (mask, target, the host sizes, the host spacing_um and surf are required)", name);
     if (int rc = mask_check_aligned16(name, GDKVM_ERR_SHAPE, "surf", {surf})) return rc;
+    size_t total, rows = 0;
+    if (int rc = native_check_clips(name, "frames", sizes, spacing_um, native_bytes, clips, T, total)) return rc;
+    for (int b = 0; b < clips; ++b) rows += (size_t)T * (size_t)sizes[2 * b];
     const size_t frames = (size_t)clips * (size_t)T;
-    if (frames > ((size_t)1 << 30)) return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: clips * T = %zu frames exceed 2^30", name, frames);
-    size_t total = 0, rows = 0;
-    for (int b = 0; b < clips; ++b) {
-        const int h0 = sizes[2 * b], w0 = sizes[2 * b + 1], ry = spacing_um[2 * b], rx = spacing_um[2 * b + 1];
-        if (h0 < 1 || h0 > SN_MAX_NATIVE || w0 < 1 || w0 > SN_MAX_NATIVE)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: clip %d has the native size %d x %d (h0, w0 in 1..%d)", name, b, h0, w0, SN_MAX_NATIVE);
-        if (ry < 1 || ry > SN_UM_MAX || rx < 1 || rx > SN_UM_MAX)
-            return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: clip %d has the spacing %d x %d um (ry, rx in 1..%d)", name, b, ry, rx, SN_UM_MAX);
-        total += (size_t)T * (size_t)h0 * (size_t)w0;      // (< 2^30 * 2^22)
-        rows += (size_t)T * (size_t)h0;
-    }
-    if (native_bytes < total)
-        return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: the native frames of these sizes take %zu bytes, native_bytes = %zu", name, total, native_bytes);
     const SnCarve cv = sn_carve(frames, total, rows);
     if (!workspace || workspace_bytes < cv.total || !gdkvm_aligned16(workspace))
         return gdkvm_fail(GDKVM_ERR_SHAPE, "%s: %zu frames of %zu pixels need a 16-byte aligned workspace of %zu bytes, got %zu", name, frames,
@@ -429,37 +415,31 @@ extern "C" int gdkvm_surface_distance_native(const uint8_t* mask, const uint8_t*
     if (int rc = gdkvm_check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint8_t* ws = static_cast<uint8_t*>(workspace);
-    size_t off = 0, woff = 0;                              // carried from launch to launch
-    for (int b0 = 0; b0 < clips; b0 += SN_CLIPS) {
-        const int nb = clips - b0 < SN_CLIPS ? clips - b0 : SN_CLIPS;
-        SnArgs a{};
+    size_t woff = 0;                                       // carried from launch to launch, as the walk carries off
+    return native_launches<SnArgs, SN_CLIPS>(sizes, clips, T, [&](SnArgs& a, int k, int b, int h0, int w0, size_t off) {
+        a.c[k] = SnClip{(u64)off, (u64)woff, (unsigned short)h0, (unsigned short)w0, (unsigned short)spacing_um[2 * b],
+                        (unsigned short)spacing_um[2 * b + 1]};
+        const int nstrips = (w0 + SN_STRIP - 1) / SN_STRIP;
+        if (nstrips > a.maxstrips) a.maxstrips = nstrips;  // (from 0: at least 1)
+        woff += (size_t)T * (size_t)h0 * (size_t)((w0 + 31) >> 5);
+        return (h0 + SN_BAND_ROWS - 1) / SN_BAND_ROWS;
+    }, [&](SnArgs& a, int b0, int nb) -> int {
         a.mask = mask; a.target = target; a.surf = reinterpret_cast<i64*>(surf);
         a.counts = reinterpret_cast<unsigned*>(ws + cv.counts);
         a.bm[0] = reinterpret_cast<unsigned*>(ws + cv.bm); a.bm[1] = reinterpret_cast<unsigned*>(ws + cv.bm + cv.bm_bytes);
         a.g[0] = reinterpret_cast<unsigned short*>(ws + cv.g); a.g[1] = reinterpret_cast<unsigned short*>(ws + cv.g + cv.g_bytes);
         a.list = reinterpret_cast<unsigned*>(ws + cv.list);
         a.frame0 = (long long)b0 * T;
-        a.nclips = nb; a.T = T; a.cls = cls; a.maxbands = 1; a.maxstrips = 1;
-        for (int k = 0; k < nb; ++k) {
-            const int h0 = sizes[2 * (b0 + k)], w0 = sizes[2 * (b0 + k) + 1];
-            a.c[k] = SnClip{(u64)off, (u64)woff, (unsigned short)h0, (unsigned short)w0, (unsigned short)spacing_um[2 * (b0 + k)],
-                            (unsigned short)spacing_um[2 * (b0 + k) + 1]};
-            const int nbands = (h0 + SN_BAND_ROWS - 1) / SN_BAND_ROWS, nstrips = (w0 + SN_STRIP - 1) / SN_STRIP;
-            if (nbands > a.maxbands) a.maxbands = nbands;
-            if (nstrips > a.maxstrips) a.maxstrips = nstrips;
-            off += (size_t)T * (size_t)h0 * (size_t)w0;
-            woff += (size_t)T * (size_t)h0 * (size_t)((w0 + 31) >> 5);
-        }
-        auto grid = [](long long items) { return dim3((unsigned)(items < SN_MAX_WG ? items : SN_MAX_WG)); };
+        a.nclips = nb; a.T = T; a.cls = cls;
         const long long fr = (long long)nb * T;
-        hipLaunchKernelGGL(sn_surfaces_kernel, grid(fr * a.maxbands), dim3(SN_NT), 0, st, a);
+        hipLaunchKernelGGL(sn_surfaces_kernel, native_grid(fr * a.maxbands, SN_MAX_WG), dim3(SN_NT), 0, st, a);
         GDKVM_LAUNCH_CHECK("sn_surfaces_kernel");
-        hipLaunchKernelGGL(sn_columns_kernel, grid(fr * 2 * a.maxstrips), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(sn_columns_kernel, native_grid(fr * 2 * a.maxstrips, SN_MAX_WG), dim3(64), 0, st, a);
         GDKVM_LAUNCH_CHECK("sn_columns_kernel");
-        hipLaunchKernelGGL(sn_rows_kernel, grid(fr * 2 * a.maxbands), dim3(SN_NT), 0, st, a);
+        hipLaunchKernelGGL(sn_rows_kernel, native_grid(fr * 2 * a.maxbands, SN_MAX_WG), dim3(SN_NT), 0, st, a);
         GDKVM_LAUNCH_CHECK("sn_rows_kernel");
-        hipLaunchKernelGGL(sn_finish_kernel, grid(fr), dim3(SN_NT), 0, st, a);
+        hipLaunchKernelGGL(sn_finish_kernel, native_grid(fr, SN_MAX_WG), dim3(SN_NT), 0, st, a);
         GDKVM_LAUNCH_CHECK("sn_finish_kernel");
-    }
-    return GDKVM_OK;
+        return GDKVM_OK;
+    });
 }

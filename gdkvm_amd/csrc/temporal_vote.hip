@@ -49,7 +49,6 @@ constexpr int TV_NARROW_BELOW = GDKVM_TEMPORAL_VOTE_NARROW_BELOW;      // ... th
 constexpr int TV_MAX_WG = GDKVM_TEMPORAL_VOTE_MAX_WG;          // workgroups per launch; more items than that are walked grid-stride
 static_assert(TV_RUN == TV_LANES * 16 && TV_NARROW_RUN == TV_LANES * 4, "a lane owns 16 or 4 positions");
 constexpr int TV_FLUSH = 32;                                   // frames whose sums a wave parks in LDS before it adds them to info / counts
-constexpr unsigned TV_HI = 0x80808080u, TV_LO = 0x7f7f7f7fu, TV_ONE = 0x01010101u;
 
 struct TvArgs {
     const uint8_t* mask; const uint8_t* target; uint8_t* out; int32_t* info; int32_t* counts;
@@ -57,20 +56,6 @@ struct TvArgs {
     int nrun, T, HW, radius;
 };
 
-// 0x80 in every byte of x that equals c (exact for every byte value: the low seven bits are tested without a carry into the next byte)
-__device__ __forceinline__ unsigned tv_eq80(unsigned x, unsigned c)
-{
-    const unsigned y = x ^ (c * TV_ONE);
-    return ~(((y & TV_LO) + TV_LO) | y) & TV_HI;
-}
-// 0x80 in every byte where a and b differ
-__device__ __forceinline__ unsigned tv_ne80(unsigned a, unsigned b)
-{
-    const unsigned y = a ^ b;
-    return (((y & TV_LO) + TV_LO) | y) & TV_HI;
-}
-// 0x80 in every byte where a > b, for bytes below 128: (b + 128) - a borrows from no neighbour and keeps its top bit iff b >= a
-__device__ __forceinline__ unsigned tv_gt80(unsigned a, unsigned b) { return ~((b | TV_HI) - a) & TV_HI; }
 // 0x80 -> 0xff per byte
 __device__ __forceinline__ unsigned tv_bytes(unsigned m80) { return m80 | (m80 - (m80 >> 7)); }
 
@@ -162,7 +147,7 @@ __global__ __launch_bounds__(TV_LANES) void temporal_vote_kernel(TvArgs a)
             for (int c = 0; c < NC; ++c)
 #pragma unroll
                 for (int w = 0; w < VW; ++w) {
-                    const unsigned e1 = tv_eq80(v.w[w], (unsigned)c) >> 7;
+                    const unsigned e1 = eq80(v.w[w], (unsigned)c) >> 7;
                     cnt[c][w] = enter ? cnt[c][w] + e1 : cnt[c][w] - e1;
                 }
         };
@@ -205,28 +190,28 @@ __global__ __launch_bounds__(TV_LANES) void temporal_vote_kernel(TvArgs a)
                     unsigned valid = 0, best = 0, arg = 0;
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
-                        const unsigned e80 = tv_eq80(o, (unsigned)c);
+                        const unsigned e80 = eq80(o, (unsigned)c);
                         valid |= e80;
                         const unsigned key = (cnt[c][w] << 1) + (e80 >> 7);
                         if (c == 0) {
                             best = key;
                         } else {
-                            const unsigned m = tv_bytes(tv_gt80(key, best));     // strictly more: the smallest class keeps an equal key
+                            const unsigned m = tv_bytes(gt80(key, best));     // strictly more: the smallest class keeps an equal key
                             best = (key & m) | (best & ~m);
-                            arg = (((unsigned)c * TV_ONE) & m) | (arg & ~m);
+                            arg = (((unsigned)c * BYTES_ONE) & m) | (arg & ~m);
                         }
                     }
                     const unsigned vm = tv_bytes(valid);
                     const unsigned res = (arg & vm) | (o & ~vm);              // a byte >= ncls passes through
                     out.w[w] = res;
-                    v[0] += __builtin_popcount(tv_ne80(res, o));
-                    v[1] += __builtin_popcount(tv_ne80(o, prev_own.w[w]));
-                    v[2] += __builtin_popcount(tv_ne80(res, prev_out.w[w]));
+                    v[0] += __builtin_popcount(ne80(res, o));
+                    v[1] += __builtin_popcount(ne80(o, prev_own.w[w]));
+                    v[2] += __builtin_popcount(ne80(res, prev_out.w[w]));
                     if (dice) {
                         const unsigned g = cur.tgt[k].w[w];
 #pragma unroll
                         for (int c = 0; c < NC; ++c) {
-                            const unsigned eo = tv_eq80(res, (unsigned)c), et = tv_eq80(g, (unsigned)c);
+                            const unsigned eo = eq80(res, (unsigned)c), et = eq80(g, (unsigned)c);
                             v[3 + 3 * c + 0] += __builtin_popcount(eo & et);
                             v[3 + 3 * c + 1] += __builtin_popcount(eo);
                             v[3 + 3 * c + 2] += __builtin_popcount(et);

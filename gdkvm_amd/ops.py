@@ -2541,31 +2541,44 @@ MASK_TO_NATIVE_MAX_SIDE = 2048
 MASK_TO_NATIVE_RUN, MASK_TO_NATIVE_BAND_PIXELS, MASK_TO_NATIVE_MAX_WG, MASK_TO_NATIVE_CLIPS = 16, 4096, 4096, 64
 
 
-def _native_sizes(what: str, sizes, clips: Optional[int] = None) -> list:
-    """[(h0, w0), ...] as Python integers from a sequence of pairs or a HOST integer tensor [clips, 2]; every side in
-    1..MASK_TO_NATIVE_MAX_SIDE.  A device tensor is refused: the sizes decide where every byte goes, so they are validated on the host."""
-    if isinstance(sizes, torch.Tensor):
-        if sizes.device.type != "cpu":
-            raise GdkvmError(f"{what}: sizes must be host integers (a sequence of (h0, w0) or a CPU tensor [clips, 2]): they are validated and "
-                             "turned into byte offsets before anything is launched, and a device tensor would have to be copied back first")
-        if sizes.dim() != 2 or sizes.shape[1] != 2 or torch.is_floating_point(sizes) or sizes.dtype == torch.bool:
-            raise GdkvmError(f"{what}: sizes must be an integer tensor [clips, 2] = (h0, w0), got {sizes.dtype} {tuple(sizes.shape)}")
-        rows = sizes.tolist()
+# The two per-clip tables of a ragged call: the argument's name, the pair's names, the upper bound, the unit behind a value, the noun of
+# "N ... for M clips", and what becomes of the values
+_SIZE_PAIRS = ("sizes", "(h0, w0)", MASK_TO_NATIVE_MAX_SIDE, "", "sizes", "turned into byte offsets")
+_SPACING_PAIRS = ("spacing_um", "(ry, rx)", SPACING_UM_MAX, " um", "spacings", "handed to the kernels by value")
+
+
+def _native_pairs(what: str, table, rows, clips: Optional[int] = None) -> list:
+    """[(h0, w0), ...] (table = _SIZE_PAIRS) or [(ry, rx), ...] (_SPACING_PAIRS) as Python integers from a sequence of pairs or a HOST
+    integer tensor [clips, 2]; every value in 1..the table's bound.  A device tensor is refused: the sizes decide where every byte goes and
+    the spacings travel by value, so both are validated on the host."""
+    arg, pair, hi, unit, noun, use = table
+    if isinstance(rows, torch.Tensor):
+        if rows.device.type != "cpu":
+            raise GdkvmError(f"{what}: {arg} must be host integers (a sequence of {pair} or a CPU tensor [clips, 2]): they are validated and "
+                             f"{use} before anything is launched, and a device tensor would have to be copied back first")
+        if rows.dim() != 2 or rows.shape[1] != 2 or torch.is_floating_point(rows) or rows.dtype == torch.bool:
+            raise GdkvmError(f"{what}: {arg} must be an integer tensor [clips, 2] = {pair}, got {rows.dtype} {tuple(rows.shape)}")
+        rows = rows.tolist()
     else:
         try:
-            rows = [tuple(r) for r in sizes]
+            rows = [tuple(r) for r in rows]
         except TypeError:
-            raise GdkvmError(f"{what}: sizes must be a sequence of (h0, w0) or a CPU tensor [clips, 2], got {type(sizes).__name__}") from None
+            raise GdkvmError(f"{what}: {arg} must be a sequence of {pair} or a CPU tensor [clips, 2], got {type(rows).__name__}") from None
     out = []
     for b, r in enumerate(rows):
         if len(r) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in r):
-            raise GdkvmError(f"{what}: sizes[{b}] = {r!r} is no pair of integers (h0, w0)")
-        if not (1 <= r[0] <= MASK_TO_NATIVE_MAX_SIDE and 1 <= r[1] <= MASK_TO_NATIVE_MAX_SIDE):
-            raise GdkvmError(f"{what}: sizes[{b}] = {r[0]} x {r[1]} outside 1..{MASK_TO_NATIVE_MAX_SIDE}")
+            raise GdkvmError(f"{what}: {arg}[{b}] = {r!r} is no pair of integers {pair}")
+        if not (1 <= r[0] <= hi and 1 <= r[1] <= hi):
+            raise GdkvmError(f"{what}: {arg}[{b}] = {r[0]} x {r[1]}{unit} outside 1..{hi}")
         out.append((r[0], r[1]))
     if clips is not None and len(out) != clips:
-        raise GdkvmError(f"{what}: {len(out)} sizes for {clips} clips")
+        raise GdkvmError(f"{what}: {len(out)} {noun} for {clips} clips")
     return out
+
+
+def _frames_per_clip(what: str, T, words: str = " frames per clip") -> None:
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise GdkvmError(f"{what}: T = {T!r}{words} must be an integer >= 1")
 
 
 def _native_offsets(sizes, T: int):
@@ -2575,6 +2588,33 @@ def _native_offsets(sizes, T: int):
         offs.append(total)
         total += T * h0 * w0
     return offs, total
+
+
+_NO_SPACING = object()          # _native_clips' spacing_um of an entry that takes no spacing table (None is a caller's bad table, and refused)
+
+
+def _native_clips(what: str, sizes, T: int, spacing_um=_NO_SPACING, clips: Optional[int] = None):
+    """The tables of a ragged call, validated: (sz = [(h0, w0), ...], sp = [(ry, rx), ...] or None for an entry without a spacing table,
+    every clip's first byte, the bytes of all).  T is an integer >= 1 by now (_frames_per_clip)."""
+    sz = _native_pairs(what, _SIZE_PAIRS, sizes, clips)
+    sp = None if spacing_um is _NO_SPACING else _native_pairs(what, _SPACING_PAIRS, spacing_um, len(sz))
+    return (sz, sp) + _native_offsets(sz, T)
+
+
+def _host_table(pairs) -> torch.Tensor:
+    """The host int32 [clips, 2] table of validated pairs that a native entry reads before it launches"""
+    return torch.tensor(pairs, dtype=torch.int32).reshape(len(pairs), 2)
+
+
+def _flat_u8(what: str, name: str, t, n: int, like: Optional[torch.Tensor] = None, note: str = "", contiguous: bool = True) -> None:
+    """t is a ragged native buffer: a flat uint8 tensor of at least n bytes, on the device of `like`, contiguous"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < n:
+        raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {n} bytes (the clips' T h0 w0 in turn{note}), got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if like is not None and t.device != like.device:
+        raise GdkvmError("tensors on different devices")
+    if contiguous and not t.is_contiguous():
+        raise GdkvmError("GDKVM ops need contiguous tensors")
 
 
 def _native_axis(n_out: int, n_in: int):
@@ -2624,18 +2664,14 @@ def mask_to_native(mask: torch.Tensor, sizes, num_classes: int, target: Optional
     if T < 1:
         raise GdkvmError(f"{what}: T = {T} frames per clip, at least 1")
     clips = frames // T
-    sz = _native_sizes(what, sizes, clips)
-    offsets, total = _native_offsets(sz, T)
+    sz, _, offsets, total = _native_clips(what, sizes, T, clips=clips)
     if target is None and not want_out:
         raise GdkvmError(f"{what}: neither out (want_out=False) nor a target: nothing to do")
     if out is not None and not want_out:
         raise GdkvmError(f"{what}: an out tensor with want_out=False")
     for name, t in (("target", target), ("out", out)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < total):
-            raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {total} bytes (the clips' T h0 w0 in turn), got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t is not None and t.device != mask.device:
-            raise GdkvmError("tensors on different devices")
+        if t is not None:
+            _flat_u8(what, name, t, total, mask, contiguous=False)     # (contiguity: behind mask's, below or in _dev)
     if not mask.is_cuda:
         # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
         if not mask.is_contiguous() or any(t is not None and not t.is_contiguous() for t in (target, out)):
@@ -2664,25 +2700,28 @@ def mask_to_native(mask: torch.Tensor, sizes, num_classes: int, target: Optional
     counts = torch.empty(lead + (num_classes, 3), dtype=torch.int32, device=dev) if target is not None else None
     if clips == 0:
         return out, counts, offsets
-    host = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
     # (allocated per call like every workspace of this module; the kernel asks for none today)
     ws = _workspace("gdkvm_mask_to_native_workspace_bytes", dev, clips, T, H, W, num_classes, floor=16)
-    _call("gdkvm_mask_to_native", dev, mask, host, target, out, counts, total, _Ws(ws), clips, T, H, W, num_classes)
+    _call("gdkvm_mask_to_native", dev, mask, _host_table(sz), target, out, counts, total, _Ws(ws), clips, T, H, W, num_classes)
     return out, counts, offsets
+
+
+def _native_view(what: str, flat, sizes, T, b, bpp: int) -> torch.Tensor:
+    """Clip b of a ragged native buffer of bpp bytes per pixel as a view: [T, h0, w0], with bpp > 1 [T, h0, w0, bpp]"""
+    sz = _native_pairs(what, _SIZE_PAIRS, sizes)
+    _frames_per_clip(what, T, "")
+    if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < len(sz):
+        raise GdkvmError(f"{what}: clip {b!r} is none of the {len(sz)} clips")
+    offsets, total = _native_offsets(sz, T)
+    if not isinstance(flat, torch.Tensor) or flat.dim() != 1 or flat.numel() < bpp * total:
+        raise GdkvmError(f"{what}: flat must be a 1-D tensor of at least {bpp * total} elements, got {tuple(getattr(flat, 'shape', ()))}")
+    h0, w0 = sz[b]
+    return flat[bpp * offsets[b]:bpp * (offsets[b] + T * h0 * w0)].view((T, h0, w0) if bpp == 1 else (T, h0, w0, bpp))
 
 
 def native_frames(flat: torch.Tensor, sizes, T: int, b: int) -> torch.Tensor:
     """Clip b of a ragged native buffer (mask_to_native's out, pack_native's flat) as a [T, h0, w0] view."""
-    sz = _native_sizes("native_frames", sizes)
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"native_frames: T = {T!r} must be an integer >= 1")
-    if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < len(sz):
-        raise GdkvmError(f"native_frames: clip {b!r} is none of the {len(sz)} clips")
-    offsets, total = _native_offsets(sz, T)
-    if not isinstance(flat, torch.Tensor) or flat.dim() != 1 or flat.numel() < total:
-        raise GdkvmError(f"native_frames: flat must be a 1-D tensor of at least {total} elements, got {tuple(getattr(flat, 'shape', ()))}")
-    h0, w0 = sz[b]
-    return flat[offsets[b]:offsets[b] + T * h0 * w0].view(T, h0, w0)
+    return _native_view("native_frames", flat, sizes, T, b, 1)
 
 
 def pack_native(clips) -> Tuple[torch.Tensor, list]:
@@ -2698,7 +2737,7 @@ def pack_native(clips) -> Tuple[torch.Tensor, list]:
                              f"{tuple(getattr(c, 'shape', ()))}")
         if c.device != clips[0].device:
             raise GdkvmError("tensors on different devices")
-    sizes = _native_sizes("pack_native", [(int(c.shape[1]), int(c.shape[2])) for c in clips])
+    sizes = _native_pairs("pack_native", _SIZE_PAIRS, [(int(c.shape[1]), int(c.shape[2])) for c in clips])
     return torch.cat([c.reshape(-1) for c in clips]), sizes
 
 
@@ -2736,8 +2775,7 @@ def frames_from_native(flat: torch.Tensor, sizes, T: int, grid=None, channels: i
     if not isinstance(flat, torch.Tensor) or flat.dtype != torch.uint8 or flat.dim() != 1:
         raise GdkvmError(f"{what}: flat must be a flat uint8 tensor (the clips' T h0 w0 bytes in turn), got {getattr(flat, 'dtype', type(flat))} "
                          f"{tuple(getattr(flat, 'shape', ()))}")
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    _frames_per_clip(what, T)
     try:
         H, W = grid
     except (TypeError, ValueError):
@@ -2748,9 +2786,8 @@ def frames_from_native(flat: torch.Tensor, sizes, T: int, grid=None, channels: i
         raise GdkvmError(f"{what}: channels = {channels!r} must be an integer in 1..4")
     if dtype not in _FRAMES_DTYPES:
         raise GdkvmError(f"{what}: dtype {dtype} is none of uint8, float32, bfloat16")
-    sz = _native_sizes(what, sizes)
+    sz, _, offsets, total = _native_clips(what, sizes, T)
     clips = len(sz)
-    offsets, total = _native_offsets(sz, T)
     if flat.numel() < total:
         raise GdkvmError(f"{what}: the native frames of these sizes take {total} bytes, flat holds {flat.numel()}")
     shape = (clips, T, channels, H, W)
@@ -2780,10 +2817,9 @@ def frames_from_native(flat: torch.Tensor, sizes, T: int, grid=None, channels: i
         raise GdkvmError(f"{what}: out must not overlap flat")
     if clips == 0:
         return out, offsets
-    host = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
     # (allocated per call like every workspace of this module; the kernel asks for none today)
     ws = _workspace("gdkvm_frames_from_native_workspace_bytes", dev, clips, T, channels, H, W, _FRAMES_DTYPES[dtype], floor=16)
-    _call("gdkvm_frames_from_native", dev, flat, host, out, total, _Ws(ws), clips, T, channels, H, W, _FRAMES_DTYPES[dtype])
+    _call("gdkvm_frames_from_native", dev, flat, _host_table(sz), out, total, _Ws(ws), clips, T, channels, H, W, _FRAMES_DTYPES[dtype])
     return out, offsets
 
 
@@ -2863,33 +2899,26 @@ def overlay_native(grey: torch.Tensor, mask: torch.Tensor, sizes, T: int, num_cl
     (native_rgb_frames views one clip of it as [T, h0, w0, 3]); `out`: a flat uint8 tensor of at least three times the pixels to write
     into, overlapping no input.  CPU tensors take the same rule in torch integers, so the wrapper works without a GPU."""
     what = "overlay_native"
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    _frames_per_clip(what, T)
     if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 8:
         raise GdkvmError(f"{what}: num_classes = {num_classes!r} must be an integer in 2..8")
     if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= OVERLAY_MAX_WIDTH:
         raise GdkvmError(f"{what}: width = {width!r} must be an integer in 1..{OVERLAY_MAX_WIDTH}")
     if isinstance(alpha, bool) or not isinstance(alpha, int) or not 0 <= alpha <= 256:
         raise GdkvmError(f"{what}: alpha = {alpha!r} must be an integer in 0..256")
-    sz = _native_sizes(what, sizes)
+    sz, _, offsets, total = _native_clips(what, sizes, T)
     clips = len(sz)
-    offsets, total = _native_offsets(sz, T)
     pal = _overlay_palette(what, "palette", palette, num_classes, OVERLAY_PALETTE)
     rpal = _overlay_palette(what, "reference_palette", reference_palette, num_classes, OVERLAY_REFERENCE_PALETTE)
     if not isinstance(grey, torch.Tensor):
         raise GdkvmError(f"{what}: grey must be a flat uint8 tensor, got {type(grey).__name__}")
-    for name, t, n in (("grey", grey, total), ("mask", mask, total), ("reference", reference, total), ("out", out, 3 * total)):
-        if name in ("reference", "out") and t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < n:
-            raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {n} bytes (the clips' T h0 w0 in turn"
-                             f"{', three bytes per pixel' if name == 'out' else ''}), got {getattr(t, 'dtype', type(t))} "
-                             f"{tuple(getattr(t, 'shape', ()))}")
-        if t.device != grey.device:
-            raise GdkvmError("tensors on different devices")
-        if not t.is_contiguous():
-            raise GdkvmError("GDKVM ops need contiguous tensors")
-    if out is None:
+    _flat_u8(what, "grey", grey, total)
+    _flat_u8(what, "mask", mask, total, grey)
+    if reference is not None:
+        _flat_u8(what, "reference", reference, total, grey)
+    if out is not None:
+        _flat_u8(what, "out", out, 3 * total, grey, note=", three bytes per pixel")
+    else:
         out = torch.empty(3 * total, dtype=torch.uint8, device=grey.device)
     for name, t in (("grey", grey), ("mask", mask), ("reference", reference)):
         if t is not None and total and out.data_ptr() < t.data_ptr() + total and t.data_ptr() < out.data_ptr() + 3 * total:
@@ -2905,27 +2934,16 @@ def overlay_native(grey: torch.Tensor, mask: torch.Tensor, sizes, T: int, num_cl
             out[3 * lo:3 * hi] = o.reshape(-1)
         return out
     dev = _dev(grey, mask, reference, out)
-    host = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
     # (allocated per call like every workspace of this module; the kernel asks for none today)
     ws = _workspace("gdkvm_overlay_native_workspace_bytes", dev, clips, T, num_classes, width, floor=16)
-    _call("gdkvm_overlay_native", dev, grey, mask, reference, host, pal, rpal if reference is not None else None, out, total, _Ws(ws),
+    _call("gdkvm_overlay_native", dev, grey, mask, reference, _host_table(sz), pal, rpal if reference is not None else None, out, total, _Ws(ws),
           clips, T, num_classes, width, alpha)
     return out
 
 
 def native_rgb_frames(flat: torch.Tensor, sizes, T: int, b: int) -> torch.Tensor:
     """Clip b of a ragged native RGB buffer (overlay_native's result) as a [T, h0, w0, 3] view: native_frames with three bytes per pixel."""
-    sz = _native_sizes("native_rgb_frames", sizes)
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"native_rgb_frames: T = {T!r} must be an integer >= 1")
-    if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < len(sz):
-        raise GdkvmError(f"native_rgb_frames: clip {b!r} is none of the {len(sz)} clips")
-    offsets, total = _native_offsets(sz, T)
-    if not isinstance(flat, torch.Tensor) or flat.dim() != 1 or flat.numel() < 3 * total:
-        raise GdkvmError(f"native_rgb_frames: flat must be a 1-D tensor of at least {3 * total} elements, got "
-                         f"{tuple(getattr(flat, 'shape', ()))}")
-    h0, w0 = sz[b]
-    return flat[3 * offsets[b]:3 * (offsets[b] + T * h0 * w0)].view(T, h0, w0, 3)
+    return _native_view("native_rgb_frames", flat, sizes, T, b, 3)
 
 
 def surface_distance(mask: torch.Tensor, target: torch.Tensor, cls: int = 1) -> torch.Tensor:
@@ -2970,33 +2988,6 @@ def _surface_distance(entry: str, mask, target, spacing_um, cls):
 SURFACE_NATIVE_BAND_ROWS, SURFACE_NATIVE_STRIP, SURFACE_NATIVE_MAX_WG, SURFACE_NATIVE_CLIPS = 32, 64, 4096, 64
 
 
-def _native_spacing(what: str, spacing_um, clips: int) -> list:
-    """[(ry, rx), ...] as Python integers from a sequence of pairs or a HOST integer tensor [clips, 2]; every value in 1..SPACING_UM_MAX.
-    A device tensor is refused like device sizes: the entry validates the spacings on the host and hands them over by value."""
-    if isinstance(spacing_um, torch.Tensor):
-        if spacing_um.device.type != "cpu":
-            raise GdkvmError(f"{what}: spacing_um must be host integers (a sequence of (ry, rx) or a CPU tensor [clips, 2]): they are validated "
-                             "and handed to the kernels by value before anything is launched, and a device tensor would have to be copied back first")
-        if spacing_um.dim() != 2 or spacing_um.shape[1] != 2 or torch.is_floating_point(spacing_um) or spacing_um.dtype == torch.bool:
-            raise GdkvmError(f"{what}: spacing_um must be an integer tensor [clips, 2] = (ry, rx), got {spacing_um.dtype} {tuple(spacing_um.shape)}")
-        rows = spacing_um.tolist()
-    else:
-        try:
-            rows = [tuple(r) for r in spacing_um]
-        except TypeError:
-            raise GdkvmError(f"{what}: spacing_um must be a sequence of (ry, rx) or a CPU tensor [clips, 2], got {type(spacing_um).__name__}") from None
-    out = []
-    for b, r in enumerate(rows):
-        if len(r) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in r):
-            raise GdkvmError(f"{what}: spacing_um[{b}] = {r!r} is no pair of integers (ry, rx)")
-        if not (1 <= r[0] <= SPACING_UM_MAX and 1 <= r[1] <= SPACING_UM_MAX):
-            raise GdkvmError(f"{what}: spacing_um[{b}] = {r[0]} x {r[1]} um outside 1..{SPACING_UM_MAX}")
-        out.append((r[0], r[1]))
-    if len(out) != clips:
-        raise GdkvmError(f"{what}: {len(out)} spacings for {clips} clips")
-    return out
-
-
 def _surface_bool(x: torch.Tensor) -> torch.Tensor:
     """The surface of the boolean set x [h, w]: its pixels with a 4-neighbour outside the set or the frame"""
     p = torch.nn.functional.pad(x, (1, 1, 1, 1))
@@ -3037,24 +3028,15 @@ def surface_distance_native(mask: torch.Tensor, target: torch.Tensor, sizes, T: 
     address.  CPU tensors take the same rule in torch (brute force over the surface pixels' coordinates in int64), so the wrapper works
     without a GPU."""
     what = "surface_distance_native"
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    _frames_per_clip(what, T)
     if isinstance(cls, bool) or not isinstance(cls, int) or not 0 <= cls <= 254:
         raise GdkvmError(f"{what}: cls = {cls!r} must be an integer in 0..254")
-    sz = _native_sizes(what, sizes)
+    sz, sp, offsets, total = _native_clips(what, sizes, T, spacing_um)
     clips = len(sz)
-    sp = _native_spacing(what, spacing_um, clips)
-    offsets, total = _native_offsets(sz, T)
     if not isinstance(mask, torch.Tensor):
         raise GdkvmError(f"{what}: mask must be a flat uint8 tensor, got {type(mask).__name__}")
-    for name, t in (("mask", mask), ("target", target)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < total:
-            raise GdkvmError(f"{what}: {name} must be a flat uint8 tensor of at least {total} bytes (the clips' T h0 w0 in turn), got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != mask.device:
-            raise GdkvmError("tensors on different devices")
-        if not t.is_contiguous():
-            raise GdkvmError("GDKVM ops need contiguous tensors")
+    _flat_u8(what, "mask", mask, total)
+    _flat_u8(what, "target", target, total, mask)
     if not mask.is_cuda:
         # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
         surf = torch.zeros((clips, T, 8), dtype=torch.int64)
@@ -3068,10 +3050,8 @@ def surface_distance_native(mask: torch.Tensor, target: torch.Tensor, sizes, T: 
     surf = torch.empty((clips, T, 8), dtype=torch.int64, device=dev)
     if clips == 0:
         return surf
-    host_sz = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
-    host_sp = torch.tensor(sp, dtype=torch.int32).reshape(clips, 2)
     ws = _workspace("gdkvm_surface_distance_native_workspace_bytes", dev, clips, T, total, T * sum(h0 for h0, _ in sz), floor=16)
-    _call("gdkvm_surface_distance_native", dev, mask, target, host_sz, host_sp, surf, total, _Ws(ws), clips, T, cls)
+    _call("gdkvm_surface_distance_native", dev, mask, target, _host_table(sz), _host_table(sp), surf, total, _Ws(ws), clips, T, cls)
     return surf
 
 
@@ -3154,21 +3134,14 @@ def lv_measure_native(mask: torch.Tensor, sizes, T: int, spacing_um, cls: int = 
     sxy syy tmin tmax W_0 .. W_(D-1) of the band's rows.  mask may start at any byte address.  CPU tensors take the same rule in torch
     and Python integers, so the wrapper works without a GPU."""
     what = "lv_measure_native"
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    _frames_per_clip(what, T)
     if isinstance(cls, bool) or not isinstance(cls, int) or not 0 <= cls <= 254:
         raise GdkvmError(f"{what}: cls = {cls!r} must be an integer in 0..254")
     if isinstance(disks, bool) or not isinstance(disks, int) or not 1 <= disks <= LV_MAX_DISKS:
         raise GdkvmError(f"{what}: disks = {disks!r} must be an integer in 1..{LV_MAX_DISKS}")
-    sz = _native_sizes(what, sizes)
+    sz, sp, offsets, total = _native_clips(what, sizes, T, spacing_um)
     clips = len(sz)
-    sp = _native_spacing(what, spacing_um, clips)
-    offsets, total = _native_offsets(sz, T)
-    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 1 or mask.numel() < total:
-        raise GdkvmError(f"{what}: mask must be a flat uint8 tensor of at least {total} bytes (the clips' T h0 w0 in turn), got "
-                         f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
-    if not mask.is_contiguous():
-        raise GdkvmError("GDKVM ops need contiguous tensors")
+    _flat_u8(what, "mask", mask, total)
     nbands = T * sum((h0 + LV_NATIVE_BAND_ROWS - 1) // LV_NATIVE_BAND_ROWS for h0, _ in sz)
     if not mask.is_cuda:
         # the same rule in torch on the host (no launch; the wrapper's checks and layout are the GPU path's)
@@ -3191,9 +3164,7 @@ def lv_measure_native(mask: torch.Tensor, sizes, T: int, spacing_um, cls: int = 
     geom = torch.empty((clips, T, 6), dtype=torch.float64, device=dev)
     bands = torch.empty((nbands, 8 + disks), dtype=torch.int64, device=dev)
     if clips:
-        host_sz = torch.tensor(sz, dtype=torch.int32).reshape(clips, 2)
-        host_sp = torch.tensor(sp, dtype=torch.int32).reshape(clips, 2)
-        _call("gdkvm_lv_measure_native", dev, mask, host_sz, host_sp, stats, dk, geom, bands, total, nbands, clips, T, cls, disks)
+        _call("gdkvm_lv_measure_native", dev, mask, _host_table(sz), _host_table(sp), stats, dk, geom, bands, total, nbands, clips, T, cls, disks)
     return (stats, dk, geom, bands) if want_bands else (stats, dk, geom)
 
 
@@ -3201,11 +3172,10 @@ def native_spacing_frames(spacing_um, T: int, device) -> torch.Tensor:
     """int32 [clips, T, 2] on `device`: every clip's native (ry, rx) for each of its T frames, the table lv_biplane reads beside the
     records of lv_measure_native.  spacing_um as there: HOST integers, validated here before anything is copied."""
     what = "native_spacing_frames"
-    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
-        raise GdkvmError(f"{what}: T = {T!r} frames per clip must be an integer >= 1")
+    _frames_per_clip(what, T)
     if not isinstance(spacing_um, torch.Tensor):
         spacing_um = list(spacing_um) if hasattr(spacing_um, "__iter__") else spacing_um
-    sp = _native_spacing(what, spacing_um, len(spacing_um) if hasattr(spacing_um, "__len__") else 0)
+    sp = _native_pairs(what, _SPACING_PAIRS, spacing_um, len(spacing_um) if hasattr(spacing_um, "__len__") else 0)
     return torch.tensor(sp, dtype=torch.int32).reshape(len(sp), 1, 2).expand(len(sp), T, 2).contiguous().to(device)
 
 

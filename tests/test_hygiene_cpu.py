@@ -1,7 +1,8 @@
 """CPU checks of round 6's host-side rules: pack / graph invalidation is per model and only on real changes, a convolution that leaves the
 hand-written path says so (and raises under GDKVM_STRICT=1), the launcher honours the reference guide's CUDA_VISIBLE_DEVICES, the
 flat-gradient exchange refuses a parameter without a gradient, stream groups of a captured segment must keep 16-byte output slabs.  And one rule of the kernel sources: the shared device idioms are
-written once, in csrc/gdkvm_device.hpp, and those of the per-frame mask kernels in csrc/mask_frame.hpp and csrc/mask_labels.hpp."""
+written once, in csrc/gdkvm_device.hpp, those of the per-frame mask kernels in csrc/mask_frame.hpp and csrc/mask_labels.hpp, and those of the
+kernels over clips at their native size in csrc/native_clips.hpp."""
 import glob
 import os
 import re
@@ -257,3 +258,46 @@ def test_mask_frame_idioms_live_in_one_header():
     missing += [idiom for idiom, rx in _LABEL_IDIOMS.items() if not re.search(rx, labels)]
     assert not missing, f"the patterns do not match the headers' own idioms: {missing}"
     assert all(re.search(r"\b" + d + r"\s*\(", header) for d in ("match16", "wave_sum", "wave_min", "wave_max", "visit_xy", "visit_p"))
+
+
+# The kernels over ragged batches of clips at their own frame size share the clip table's check, the walk over a call's launches and the
+# item decode through csrc/native_clips.hpp, which builds on mask_frame.hpp; that one holds the packed-byte compares temporal_vote.hip shares
+# with them.
+_NATIVE_KERNELS = ("mask_to_native.hip", "frames_from_native.hip", "overlay_native.hip", "surface_native.hip", "lv_native.hip")
+_NATIVE_IDIOMS = {
+    "item decode": r"\bitem\s*/\s*per_clip\b[^;]*;[^;]*;[^;]*\brem\s*/",
+    "shared helper definition": r"\b\w*(eq80|_overlap|_aligned16)\s*\([^()]*\)\s*\{",
+    "native bound": r"\b(h0|w0|ry|rx)\s*>\s*(\d+|[A-Z][A-Z0-9_]*)\b",
+    "head split": _MASK_IDIOMS["head split"],
+}
+# Sites left as they were because the helper changed the file's gfx950 assembly, with the number of differing lines: (file, idiom) ->
+# (the number of such sites in the file, reason), so that one more written-out copy in an allowed file fails too
+_NATIVE_IDIOM_ALLOWED = {
+    ("lv_native.hip", "item decode"): (1, "ln_item is a function that the compiler simplifies on its own before it inlines it: with native_item "
+                                          "inside it the file's code moves (338 assembly lines)"),
+    ("surface_native.hip", "item decode"): (2, "sn_columns_kernel and sn_rows_kernel decode a direction beside the strip or band: with their three "
+                                               "lines replaced by native_item taking per_frame as a long long, tools/isa_equal.py counts 4 assembly "
+                                               "lines, one sign extension that changes places in each; sn_surfaces_kernel uses the helper"),
+}
+
+
+def test_native_clip_idioms_live_in_one_header():
+    csrc = os.path.join(ROOT, "gdkvm_amd", "csrc")
+    with open(os.path.join(csrc, "native_clips.hpp")) as f:
+        native = f.read()
+    with open(os.path.join(csrc, "mask_frame.hpp")) as f:
+        frame = f.read()
+    assert '#include "mask_frame.hpp"' in native
+    found = {}
+    for name in _NATIVE_KERNELS + ("temporal_vote.hip",):
+        with open(os.path.join(csrc, name)) as f:
+            text = f.read()
+        assert ('#include "native_clips.hpp"' if name in _NATIVE_KERNELS else '#include "mask_frame.hpp"') in text
+        found.update({(name, idiom): len(re.findall(rx, text)) for idiom, rx in _NATIVE_IDIOMS.items() if re.search(rx, text)})
+    allowed = {site: n for site, (n, _) in _NATIVE_IDIOM_ALLOWED.items()}
+    assert found == allowed, (f"native-clip idioms outside native_clips.hpp / mask_frame.hpp, (file, idiom): sites -- found {sorted(found.items())}, "
+                              f"allowed {sorted(allowed.items())}")
+    missing = [idiom for idiom, rx in _NATIVE_IDIOMS.items() if not re.search(rx, native + frame)]
+    assert not missing, f"the patterns do not match the headers' own idioms: {missing}"
+    assert all(re.search(r"\b" + d + r"\s*\(", native) for d in ("native_check_clips", "native_launches", "native_grid", "native_overlap", "native_item"))
+    assert all(re.search(r"\b" + d + r"\s*\(", frame) for d in ("eq80", "head16", "gdkvm_aligned16"))
